@@ -2,7 +2,13 @@
 """bench.py — headline benchmark of the MI355X linemodLevelup hot path (BASELINE.json metric:
 templates·Mpixels matched/sec on 640x480 RGB-D).
 
-    python bench.py --gpus N --steps K --warmup W [--scaling weak|strong]
+    python bench.py --gpus N --steps K --warmup W [--scaling weak|strong] [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times exactly K steps once, writes the match records of the last timed step
+under --dump-outputs DIR (DIR/match_<field>.npy, float64; the inputs are seeded, identical from run to run)
+and prints the line.  --full adds everything else below: the parity gates, the roofline leg and its PMC
+passes, 9 repeats of the timed region (`ms_per_step` = their median), the extras legs, the CPU baseline
+and the strong-scaling reference.
 
 A *step* is one `Detector.match` of the reference driver loop (linemod_and_levelup_test.py:314-327,
 linemod_ros/detect.py:83-138) on a NEW host frame: the frame is handed over in host memory
@@ -28,10 +34,10 @@ rank; started plainly (`python bench.py --gpus N`) it re-executes itself under
 `python -m torch.distributed.run --standalone --nproc-per-node N`, one rank per GPU (on a box with
 fewer GPUs than ranks: LM_BENCH_BACKEND=gloo LM_BENCH_DEVICE=0 rehearses the path on one device).
 
-Before anything is timed (N=1) the GPU's results must equal the CPU oracle's — the synchronous call on two
+--full: before anything is timed (N=1) the GPU's results must equal the CPU oracle's — the synchronous call on two
 frames AND the streamed path with shared launches on four steps — or the bench exits without a number.
 
-One JSON line on stdout (rank 0).  `roofline` is for the dominant kernel (k_local_bits): `achieved` /
+One JSON line on stdout (rank 0).  --full: `roofline` is for the dominant kernel (k_local_bits): `achieved` /
 `frac` = ALGORITHMIC response bytes per launch (sum nfeat*256 per 16x16 evaluation) / the
 kernel's mean duration from HIP events on its stream, against the HBM peak — the convention BASELINE.json
 asks for, labelled as NOT a physical fraction (the bit-plane kernels load 16 bytes where the reference
@@ -63,6 +69,7 @@ STRONG_OBJECTS = 8            # --scaling strong: configs[3], 8 objects x 2000 t
 THRESHOLD = 75.0
 N_FRAMES = 16                 # distinct host frames in the pool the stream cycles through
 N_PARKED = 4                  # frames parked in HBM for the resident legs (roofline, extras)
+SETTLE_STEPS = 192            # untimed stream steps of the one-time set-up before the first warm-up (timed() below)
 PIPELINE_DEPTH = int(os.environ.get("LM_BENCH_DEPTH", "0"))   # frames in flight (<= lm_detector_max_in_flight() = 16): upload, front end, coarse pass, refinement, duplicate removal of
                                                               # neighbouring BATCHES of frames side by side while the host collects the oldest frame.  Default (0): three batches
                                                               # (lm_detector_get_batch() = 4 frames share their kernel launches: 12 frames); the timed region starts and ends
@@ -137,7 +144,13 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--repeats", type=int, default=9, help="timed regions of exactly --steps steps each; ms_per_step is their median")
+    ap.add_argument("--full", action="store_true", help="besides the headline: the parity gates against the CPU oracle, the roofline leg and its PMC passes, "
+                                                        "9 repeats of the timed region, the extras legs, the CPU baseline and the strong-scaling reference "
+                                                        "(a plain run sets up, warms up, times --steps steps once and prints the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write the match records of the last timed step "
+                                                                         "(what Detector.match returns) to DIR/<field>.npy as float64")
+    ap.add_argument("--repeats", type=int, default=None, help="timed regions of exactly --steps steps each; ms_per_step is their median "
+                                                               "(default: 1, with --full 9)")
     ap.add_argument("--templates", type=int, default=N_TEMPLATES, help="template pyramids per object")
     ap.add_argument("--scaling", choices=["weak", "strong"], default=os.environ.get("LM_BENCH_SCALING", "weak"),
                     help="N>1: weak = one object x --templates per GPU (configs[1] scaled up); strong = a fixed bank of 8 objects x "
@@ -157,6 +170,8 @@ def main():
     ap.add_argument("--exchange", choices=["auto", "host", "device"], default="auto",
                     help="multi-GPU exchange of the match records: on the device (sharded.DeviceExchange; auto = when world > 1) or through the host")
     args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 9 if args.full else 1
     if args.dry_ranks > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(dry_ranks(args))
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -280,7 +295,7 @@ def main():
     # against the CPU oracle (quantisation in numpy, match loops = the SSE C port pinned to the reference's lines) - bit-exact
     # (x, y, similarity, template_id) in the canonical order, or the bench aborts without a number.
     parity = None
-    if world == 1 and not strong and not args.no_parity_gate:
+    if args.full and world == 1 and not strong and not args.no_parity_gate:
         parity = parity_gate(det, frames, banks[classes[0]], classes, args.templates)
 
     host_t = {"submit": 0.0, "collect": 0.0, "gather": 0.0, "merge": 0.0}
@@ -341,7 +356,7 @@ def main():
         if tlog["n"] < len(tlog["buf"]):                        # the frame's lm_timings, read out after the timed region (one ctypes call here)
             det.lastTimingsInto(tlog["buf"][tlog["n"]])
             tlog["n"] += 1
-        last["n"] = len(out)
+        last["n"], last["k"], last["out"] = len(out), k, out
 
     # ... and the gate on the streamed path itself (world 1: the timed loop's submit / collect with the same number of frames in flight)
     if parity is not None:
@@ -363,8 +378,11 @@ def main():
             ex.grow_if_needed()
             if res:
                 det.selectFrame(k % N_PARKED)
-            last["n"] = len(sharded.match_sharded(det, None if res else list(host_frame(k)), THRESHOLD, classes, device=dev, resident=res,
-                                                  shard=not by_class))
+            out = sharded.match_sharded(det, None if res else list(host_frame(k)), THRESHOLD, classes, device=dev, resident=res,
+                                        shard=not by_class)
+            last["n"] = len(out)
+            if k == last["k"]:
+                last["out"] = out
 
     def fence():
         if use_dist:
@@ -378,9 +396,13 @@ def main():
         # one-time set-up, before the W warm-up steps: every slot of the result ring (lm_detector_max_in_flight() = 16) allocates its
         # pinned staging buffer and device buffers the first time a frame lands in it - with W < 16 that would happen inside the
         # timed region (~0.5 ms per slot at the driver's --steps 20 --warmup 5)
+        # ... and then SETTLE_STEPS frames of the same stream, untimed: the library chooses how many frames share a launch from moving averages
+        # of the gap between submits and of the cost of a launch, which the slow first-use submits above leave far from the loop's own pace
+        # (measured, plain run at --steps 20 --warmup 5 without it: 3.8 frames per launch and 0.127 ms per step, against 6.9 and 0.081 once settled)
         key = "resident" if resident else "live"
         if not primed[key]:
             run(lm.load_library().lm_detector_max_in_flight(), resident)
+            run(SETTLE_STEPS, resident)
             primed[key] = True
         run(warmup, resident)
         fence()
@@ -412,20 +434,21 @@ def main():
     # in the timed region.  HIP events on the kernels' streams, recorded by the library around each launch.
     excl = {"coarse_ms": 0.0, "local_ms": 0.0, "coarse_bytes": 0.0, "local_bytes": 0.0, "frontend_ms": 0.0}
     EXCL = 20
-    det.setBatchQueue(0)                                  # full batches only in this leg (the stream's default launches early while the GPU's queue is short)
-    for rep in range(3 + EXCL):
-        for b in range(BATCH):
-            det.submitFrame(frames[(rep * BATCH + b) % N_FRAMES], THRESHOLD, classes)
-        for b in range(BATCH):
-            det.collect(sort_unique=False, distinct=True)
-            if rep >= 3:
-                tm = det.lastTimings()
-                assert tm["batch_frames"] == BATCH, tm
-                for q in ("coarse_bytes", "local_bytes"):             # algorithmic bytes: per frame -> summed over the launch
-                    excl[q] += tm[q] / EXCL
-                if b == 0:                                              # the stage times are per launch (identical for the frames of a batch)
-                    for q in ("coarse_ms", "local_ms", "frontend_ms"):
+    if args.full or args.roofline_only:
+        det.setBatchQueue(0)                                  # full batches only in this leg (the stream's default launches early while the GPU's queue is short)
+        for rep in range(3 + EXCL):
+            for b in range(BATCH):
+                det.submitFrame(frames[(rep * BATCH + b) % N_FRAMES], THRESHOLD, classes)
+            for b in range(BATCH):
+                det.collect(sort_unique=False, distinct=True)
+                if rep >= 3:
+                    tm = det.lastTimings()
+                    assert tm["batch_frames"] == BATCH, tm
+                    for q in ("coarse_bytes", "local_bytes"):             # algorithmic bytes: per frame -> summed over the launch
                         excl[q] += tm[q] / EXCL
+                    if b == 0:                                              # the stage times are per launch (identical for the frames of a batch)
+                        for q in ("coarse_ms", "local_ms", "frontend_ms"):
+                            excl[q] += tm[q] / EXCL
     det.setBatchQueue(args.batch_queue)
     if args.roofline_only:
         if rank == 0:
@@ -440,14 +463,17 @@ def main():
         import cProfile, io, pstats
         pr = cProfile.Profile(); pr.enable(); timed(args.steps, args.warmup); pr.disable()
         st = io.StringIO(); pstats.Stats(pr, stream=st).sort_stats("tottime").print_stats(14); sys.stderr.write(st.getvalue())
-    # THE timed region: exactly K steps (a new host frame per step, H2D included) between two fences — repeated, because at the driver's
-    # flags it is ~1.7 ms long and its run-to-run spread was as large as most optimisations: `ms_per_step` is the MEDIAN of the
-    # repeats (each: W warm-up steps, fence, K timed steps, fence; N > 1: the MAX over the ranks of each repeat), min / max / all in `repeats`
+    # THE timed region: exactly K steps (a new host frame per step, H2D included) between two fences.  A plain run times it once; --full
+    # repeats it (--repeats, 9), because at the driver's flags it is ~1.7 ms long and its run-to-run spread was as large as most optimisations
+    # (VERDICT r05): `ms_per_step` is the MEDIAN of the repeats (each: W warm-up steps, fence, K timed steps, fence; N > 1: the MAX over the
+    # ranks of each repeat), min / max / all in `repeats`
     reps = max(1, args.repeats)
     dts = [timed(args.steps, args.warmup) for _ in range(reps)]
     dt = sorted(dts)[len(dts) // 2]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last["out"])
     steady = None
-    if world == 1 and not args.no_extras and args.steps < 200:     # the same loop at 200 steps: the fill and drain of the frame pipeline amortised
+    if args.full and world == 1 and not args.no_extras and args.steps < 200:     # the same loop at 200 steps: the fill and drain of the frame pipeline amortised
         steady = timed(200, args.warmup) / 200.0 * 1e3
         timed(args.steps, args.warmup)                             # (leaves the per-step accumulators of a K-step region behind, as the fields below expect)
     n_final = last["n"]
@@ -457,21 +483,22 @@ def main():
     total_templates = args.templates * n_obj
     value = total_templates * (W * H / 1e6) * K / dt
     replay = None
-    if not args.no_extras:
+    if args.full and not args.no_extras:
         dtr = timed(args.steps, args.warmup, resident=True)
         replay = {"ms_per_step": dtr / K * 1e3, "value": total_templates * (W * H / 1e6) * K / dtr, "unit": "templates*Mpx/s",
                   "note": "round-1 headline definition: %d frames parked in HBM and replayed with a device-to-device copy, no H2D in the timed region" % N_PARKED}
 
     if rank == 0:
-        # dominant kernel of this rank, timed alone (see the roofline leg above)
-        if excl["local_ms"] >= excl["coarse_ms"]:
-            # (local_ms brackets the refinement launches: k_local_bits + a k_local launch for the candidates it leaves — oversized templates —,
-            # or k_local alone when the bank / geometry keeps the byte planes)
-            kname, kms, kbytes, kpipe = ("k_local_bits" if det.refinesOnBitPlanes() else "k_local"), excl["local_ms"], excl["local_bytes"], mean["local_ms"]
-        else:
-            kname, kms, kbytes, kpipe = ("k_coarse_bits" if det.getPaths()[1] == "bits" else "k_coarse"), excl["coarse_ms"], excl["coarse_bytes"], mean["coarse_ms"]
-        achieved = kbytes / (kms * 1e-3) / 1e9 if kms > 0 else 0.0
-        gbps = lambda b, ms: (b / (ms * 1e-3) / 1e9) if ms > 0 else 0.0
+        if args.full:
+            # dominant kernel of this rank, timed alone (see the roofline leg above)
+            if excl["local_ms"] >= excl["coarse_ms"]:
+                # (local_ms brackets the refinement launches: k_local_bits + a k_local launch for the candidates it leaves — oversized templates —,
+                # or k_local alone when the bank / geometry keeps the byte planes)
+                kname, kms, kbytes, kpipe = ("k_local_bits" if det.refinesOnBitPlanes() else "k_local"), excl["local_ms"], excl["local_bytes"], mean["local_ms"]
+            else:
+                kname, kms, kbytes, kpipe = ("k_coarse_bits" if det.getPaths()[1] == "bits" else "k_coarse"), excl["coarse_ms"], excl["coarse_bytes"], mean["coarse_ms"]
+            achieved = kbytes / (kms * 1e-3) / 1e9 if kms > 0 else 0.0
+            gbps = lambda b, ms: (b / (ms * 1e-3) / 1e9) if ms > 0 else 0.0
         if world == 1 and not strong:
             workload = "configs[1]: 1 object x %d templates, 640x480 RGB-D, Detector(150,[4,8]), threshold 75, planted synthetic bank" % args.templates
         elif strong:
@@ -488,8 +515,6 @@ def main():
             "repeats": {"n": reps, "ms_per_step_min": min(dts) / K * 1e3, "ms_per_step_max": max(dts) / K * 1e3, "ms_per_step_all": [t / K * 1e3 for t in dts],
                         "ms_per_step_is": "the median of n timed regions of exactly `steps` steps each"},
             "ms_per_step_steady_200": steady,
-            "kernel_us_per_frame": (excl["frontend_ms"] + excl["coarse_ms"] + excl["local_ms"]) / BATCH * 1e3,
-            "kernel_us_per_frame_is": "front end + coarse pass + refinement kernels of one %d-frame launch set, each timed alone on the GPU (roofline leg), per frame" % BATCH,
             "dtype": "u8", "data": "synthetic",
             "parity_checked": bool(parity and parity["ok"]), "parity": parity,
             "config": {"workload": workload, "host_cpus": host_cpus,
@@ -506,34 +531,40 @@ def main():
                        "pipeline_depth": PIPELINE_DEPTH, "frames_per_launch_max": BATCH, "batches_kept_queued": args.batch_queue,
                        "frames_per_launch_mean_timed": mean["batch_frames"],
                        "setup_before_warmup": "16 frames through the ingest ring (each of the library's 16 result slots allocates its pinned staging "
-                                              "buffer and device buffers on first use); the timed region starts and ends with an empty pipeline, "
-                                              "so at K = 20 it carries one frame latency (~0.45 ms) of fill and drain",
+                                              "buffer and device buffers on first use), then %d untimed steps of the stream; the timed region starts and ends with an empty pipeline, "
+                                              "so at K = 20 it carries one frame latency (~0.45 ms) of fill and drain" % SETTLE_STEPS,
                        "coarse_candidates_per_step": mean["coarse_candidates"], "matches_pre_unique_per_step": mean["matches_pre_unique"],
                        "matches_final_last_step": n_final, "templates_per_sec": total_templates * K / dt},
             "stages_ms": dict({k: mean[k] for k in ("h2d_ms", "frontend_ms", "coarse_ms", "local_ms", "d2h_ms", "total_ms")},
                               note="device time per LAUNCH in the pipelined region; a launch serves frames_per_launch = %d frames (h2d_ms: per frame)" % BATCH),
             "host_wall_ms": dict(host_mean, **{q: mean[q] for q in ("host_submit_ms", "host_wait_ms", "host_collect_ms", "host_merge_ms")}),
-            "roofline": {"bound": "hbm", "kernel": kname, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "traffic": None,
-                         "algorithmic_bytes_per_launch": kbytes, "kernel_ms": kms, "frames_per_launch": BATCH,
-                         "kernel_ms_covers": ("the events bracket the refinement of a batch: k_local_bits (and, for banks whose candidates can leave their planes, the k_local "
-                                              "launch that takes those; none at this workload)" if kname == "k_local_bits" else "one launch of the kernel"),
-                         "convention": "ALGORITHMIC bytes (SURVEY 8d: one byte per response read the reference performs) per launch / kernel time, "
-                                       "against the HBM peak as BASELINE.json's metric asks.  The linear memories are cache-resident, so this is not "
-                                       "physical HBM traffic (see `traffic`); the ceilings that physically bound the kernel are below",
-                         "vs_cache_ceilings": {"l2_peak_GBps": L2_PEAK_GBS, "frac_of_l2": achieved / L2_PEAK_GBS,
-                                               "lds_peak_GBps": LDS_PEAK_GBS, "frac_of_lds": achieved / LDS_PEAK_GBS},
-                         "duration_source": "HIP events around the kernel on its stream, %d launches of %d frames each, one launch set at a time inside bench.py (the kernel alone on the GPU)" % (EXCL, BATCH),
-                         "in_pipelined_region": {"kernel_ms": kpipe, "GBps": gbps(kbytes, kpipe),
-                                                 "note": "same launches in the timed region, sharing the GPU with the next frame's coarse pass and front end; "
-                                                         "frame-level: (coarse + local algorithmic bytes) / ms_per_step = %.0f GB/s"
-                                                         % gbps(mean["coarse_bytes"] + mean["local_bytes"], dt / K * 1e3)},
-                         "other": {"k_coarse_GBps": gbps(excl["coarse_bytes"], excl["coarse_ms"]), "k_local_GBps": gbps(excl["local_bytes"], excl["local_ms"]),
-                                   "k_coarse_ms": excl["coarse_ms"], "k_local_ms": excl["local_ms"]}},
+            "full": bool(args.full),
         }
+        if args.full:
+            out.update({
+                "kernel_us_per_frame": (excl["frontend_ms"] + excl["coarse_ms"] + excl["local_ms"]) / BATCH * 1e3,
+                "kernel_us_per_frame_is": "front end + coarse pass + refinement kernels of one %d-frame launch set, each timed alone on the GPU (roofline leg), per frame" % BATCH,
+                "roofline": {"bound": "hbm", "kernel": kname, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                             "frac": achieved / HBM_PEAK_GBS, "traffic": None,
+                             "algorithmic_bytes_per_launch": kbytes, "kernel_ms": kms, "frames_per_launch": BATCH,
+                             "kernel_ms_covers": ("the events bracket the refinement of a batch: k_local_bits (and, for banks whose candidates can leave their planes, the k_local "
+                                                  "launch that takes those; none at this workload)" if kname == "k_local_bits" else "one launch of the kernel"),
+                             "convention": "ALGORITHMIC bytes (SURVEY 8d: one byte per response read the reference performs) per launch / kernel time, "
+                                           "against the HBM peak as BASELINE.json's metric asks.  The linear memories are cache-resident, so this is not "
+                                           "physical HBM traffic (see `traffic`); the ceilings that physically bound the kernel are below",
+                             "vs_cache_ceilings": {"l2_peak_GBps": L2_PEAK_GBS, "frac_of_l2": achieved / L2_PEAK_GBS,
+                                                   "lds_peak_GBps": LDS_PEAK_GBS, "frac_of_lds": achieved / LDS_PEAK_GBS},
+                             "duration_source": "HIP events around the kernel on its stream, %d launches of %d frames each, one launch set at a time inside bench.py (the kernel alone on the GPU)" % (EXCL, BATCH),
+                             "in_pipelined_region": {"kernel_ms": kpipe, "GBps": gbps(kbytes, kpipe),
+                                                     "note": "same launches in the timed region, sharing the GPU with the next frame's coarse pass and front end; "
+                                                             "frame-level: (coarse + local algorithmic bytes) / ms_per_step = %.0f GB/s"
+                                                             % gbps(mean["coarse_bytes"] + mean["local_bytes"], dt / K * 1e3)},
+                             "other": {"k_coarse_GBps": gbps(excl["coarse_bytes"], excl["coarse_ms"]), "k_local_GBps": gbps(excl["local_bytes"], excl["local_ms"]),
+                                       "k_coarse_ms": excl["coarse_ms"], "k_local_ms": excl["local_ms"]}},
+            })
         if replay is not None:
             out["extras"] = {"resident_replay": replay}
-        if world == 1 and not strong and not args.no_extras:
+        if args.full and world == 1 and not strong and not args.no_extras:
             cls0 = classes[0]
             out["extras"].update({"synchronous_call": sync_latency(det, classes, args.templates),
                                   "pcie_inclusive": pcie_inclusive(det, frames, classes, args.templates),
@@ -565,88 +596,89 @@ def main():
                 "pipeline_leg": {"icp_ms": pl["icp_ms"], "iterations": pl["icp_iterations"],
                                  "achieved": (sum(i * (a * 24 + b * 48) for i, a, b in zip(pl["iterations"], pl["points_source"], pl["points_target"])) / (pl["icp_ms"] * 1e-3) / 1e9) if pl["icp_ms"] > 0 else 0.0,
                                  "unit": "GB/s"}}
-        # PMC counters of the dominant kernel, measured NOW: separate rocprofv3 --pmc passes over `bench.py --roofline-only` (the
-        # same launches as the roofline leg above), corrected as MI355X_MICROARCH.md (HBM) prescribes.  Without rocprofv3 (or with
-        # --no-pmc) the numbers of the last committed pass (profiles/roofline_traffic.json) are quoted and labelled as such.
-        paths = det.getPaths()
-        k_refine = "k_local_bits" if paths[0] == "bits" else "k_local"
-        k_coarse_name = "k_coarse_bits" if paths[1] == "bits" else "k_coarse"
-        pm_all = None if (args.no_pmc or args.no_extras or world != 1 or strong) else pmc_live((k_refine, k_coarse_name, "k_fe_stage", "k_fe_bits", "k_pack_bits", "k_pack_top", "k_dedupe"), args)
-        pm = pm_all.get(kname) if pm_all else None
-        rf = out["roofline"]
-        rf["frac_is"] = ("ALGORITHMIC bytes over the HBM peak (SURVEY 8d's convention): NOT a physical fraction - the bit-plane kernels load 16 bytes where the "
-                         "reference reads 256, from L1 / L2 - and it exceeds 1.  What the kernel reaches of the ceilings that can bind it is `binding` (<= 1), "
-                         "per stage under `stages`")
-        if pm is not None:
-            cz = ceilings_of(pm)
-            hbm = cz["hbm_bytes_per_dispatch"]      # FETCH_SIZE / WRITE_SIZE are in KB; gfx950: FETCH_SIZE tallies 128-B requests at 64 B (MI355X_MICROARCH.md, HBM)
-            pairs = kbytes / 256.0                   # (candidate, feature) pairs per launch: 256 algorithmic bytes each
-            lane_features = pairs / 8.0              # a wave instruction of k_local_bits serves 8 pairs (8 lanes per candidate)
-            rf.update({
-                "traffic": hbm,
-                "traffic_source": "live: rocprofv3 --kernel-trace --pmc passes of `bench.py --roofline-only` run by this bench.py (FETCH_SIZE x2 + WRITE_SIZE, "
-                                  "mean per %s dispatch of %d frames); memory-side (fabric) bytes, Infinity-Cache hits included" % (kname, BATCH),
-                "binding": cz["binding"], "ceilings": cz["fractions"], "tcp_accesses_per_cu_cycle_raw": cz["tcp_accesses_per_cu_cycle_raw"],
-                "tcp_miss_stall_cycles_per_cu_cycle": cz["tcp_miss_stall_cycles_per_cu_cycle"],
-                "hbm_frac_physical": cz["fractions"]["hbm"],
-                "kernel_us_profiled": cz["kernel_us_profiled"], "l2_hit_rate": cz["l2_hit_rate"],
-                "cu_cycles_per_wave_load": cz["cu_cycles_per_wave_load"], "l1_accesses_per_wave_load": cz["l1_accesses_per_wave_load"],
-                "insts_per_launch": {"salu": pm["SQ_INSTS_SALU"], "valu": pm["SQ_INSTS_VALU"], "vmem_rd": pm["SQ_INSTS_VMEM_RD"], "waves": pm["SQ_WAVES"]}})
-            if kname == "k_local_bits" and lane_features > 0:
-                per = pm["SQ_INSTS_VALU"] / lane_features
+        if args.full:
+            # PMC counters of the dominant kernel, measured NOW: separate rocprofv3 --pmc passes over `bench.py --roofline-only` (the
+            # same launches as the roofline leg above), corrected as MI355X_MICROARCH.md (HBM) prescribes.  Without rocprofv3 (or with
+            # --no-pmc) the numbers of the last committed pass (profiles/roofline_traffic.json) are quoted and labelled as such.
+            paths = det.getPaths()
+            k_refine = "k_local_bits" if paths[0] == "bits" else "k_local"
+            k_coarse_name = "k_coarse_bits" if paths[1] == "bits" else "k_coarse"
+            pm_all = None if (args.no_pmc or args.no_extras or world != 1 or strong) else pmc_live((k_refine, k_coarse_name, "k_fe_stage", "k_fe_bits", "k_pack_bits", "k_pack_top", "k_dedupe"), args)
+            pm = pm_all.get(kname) if pm_all else None
+            rf = out["roofline"]
+            rf["frac_is"] = ("ALGORITHMIC bytes over the HBM peak (SURVEY 8d's convention): NOT a physical fraction - the bit-plane kernels load 16 bytes where the "
+                             "reference reads 256, from L1 / L2 - and it exceeds 1.  What the kernel reaches of the ceilings that can bind it is `binding` (<= 1), "
+                             "per stage under `stages`")
+            if pm is not None:
+                cz = ceilings_of(pm)
+                hbm = cz["hbm_bytes_per_dispatch"]      # FETCH_SIZE / WRITE_SIZE are in KB; gfx950: FETCH_SIZE tallies 128-B requests at 64 B (MI355X_MICROARCH.md, HBM)
+                pairs = kbytes / 256.0                   # (candidate, feature) pairs per launch: 256 algorithmic bytes each
+                lane_features = pairs / 8.0              # a wave instruction of k_local_bits serves 8 pairs (8 lanes per candidate)
                 rf.update({
-                    "valu_per_lane_feature": per,
-                    "useful_valu_frac": USEFUL_ADDER_OPS_PER_LANE_FEATURE / per,
-                    "useful_valu_frac_with_window_shifts": (USEFUL_ADDER_OPS_PER_LANE_FEATURE + ALIGN_OPS_PER_LANE_FEATURE) / per,
-                    "useful_valu_note": "adder operations the bit-sliced sums need per lane and feature (5.0: ISA of the 16-feature loop body, DESIGN.md 3.1) over the "
-                                        "wave-level VALU instructions measured per lane and feature (SQ_INSTS_VALU / (pairs / 8)); round 3's kernel: 10 of 33",
-                    "what_bounds_it": "the number of wave loads: a wave load of k_local_bits (8 candidates x 128 contiguous bytes = 1 KB) takes 20-23 CU cycles whatever "
-                                      "the lanes or addresses (`cu_cycles_per_wave_load`; 16 = the 64 B per cycle of the L1 -> register path, `ceilings.l1_data`), with "
-                                      "the L2 -> L1 fills behind it (`ceilings.l2`, the miss-stall share).  Three schemes that share loads between neighbouring candidates "
-                                      "were built in round 5 — bit-exact, fewer wave loads, more L2 requests, none faster: profiles/r05_local_sharing/README.txt"})
-        # every stage of a frame with the ceiling that binds it, from the same PMC passes (one fraction <= 1 per stage, recomputable from profiles/r04_pmc.txt)
-        if pm_all:
-            B_FRONT = W * H * 3 + W * H * 2 + 8 * 2 * (W * H + (W // 2) * (H // 2))      # 1.54 MB in + 6.14 MB of linear memories (8 labels x 2 modalities x 2 levels) out per VGA frame
-            stages = {}
-            fe_us, fe_bytes = 0.0, 0.0
-            fe_parts = {}
-            for k in ("k_fe_stage", "k_fe_bits", "k_pack_bits", "k_pack_top"):
-                if k in pm_all:
-                    cz = ceilings_of(pm_all[k], wide_loads=False)
-                    n = pm_all[k]["dispatches"] / max(1, pm_all[k_refine]["dispatches"] if k_refine in pm_all else 1)     # dispatches of this kernel per batch
-                    fe_us += cz["kernel_us_profiled"] * n
-                    fe_bytes += cz["hbm_bytes_per_dispatch"] * n
-                    fe_parts[k] = {"dispatches_per_batch": n, "us_per_dispatch": cz["kernel_us_profiled"], "binding": cz["binding"], "ceilings": cz["fractions"],
-                                   "tcp_miss_stall_cycles_per_cu_cycle": cz["tcp_miss_stall_cycles_per_cu_cycle"]}
-            if fe_us > 0:
-                stages["frontend"] = {"kernels": fe_parts, "us_per_batch_profiled": fe_us, "ms_per_batch_events": excl["frontend_ms"],
-                                      "algorithmic_bytes_per_frame": B_FRONT,
-                                      "hbm_frac_algorithmic": B_FRONT * BATCH / (excl["frontend_ms"] * 1e-3) / 1e9 / HBM_PEAK_GBS if excl["frontend_ms"] > 0 else None,
-                                      "traffic_bytes_per_batch": fe_bytes, "traffic_over_algorithmic": fe_bytes / (B_FRONT * BATCH),
-                                      "note": "the one stage that streams: a frame in, its response maps out.  With bit planes for both passes the maps leave as 2 bits per "
-                                              "cell (2.8 MB per frame) instead of bytes in two layouts (11 MB), so the traffic can fall below SURVEY 8(d)'s algorithmic figure"}
-            for stage, k, ms in (("coarse", k_coarse_name, excl["coarse_ms"]), ("refine", k_refine, excl["local_ms"])):
-                if k in pm_all:
-                    cz = ceilings_of(pm_all[k])
-                    stages[stage] = {"kernel": k, "ms_per_batch_events": ms, "us_per_dispatch_profiled": cz["kernel_us_profiled"], "binding": cz["binding"],
-                                     "ceilings": cz["fractions"], "tcp_accesses_per_cu_cycle_raw": cz["tcp_accesses_per_cu_cycle_raw"],
-                                     "tcp_miss_stall_cycles_per_cu_cycle": cz["tcp_miss_stall_cycles_per_cu_cycle"], "l2_hit_rate": cz["l2_hit_rate"], "cu_cycles_per_wave_load": cz["cu_cycles_per_wave_load"],
-                                     "l1_accesses_per_wave_load": cz["l1_accesses_per_wave_load"]}
-            rf["stages"] = stages
-        if pm is None:
-            traffic = os.path.join(ROOT, "profiles", "roofline_traffic.json")   # last committed PMC pass (profiles/pmc_run.sh)
-            if os.path.exists(traffic):
-                try:
-                    tj = json.load(open(traffic))
-                    if tj.get("kernel") == kname:
-                        rf["traffic"] = tj.get("hbm_bytes_per_launch")
-                        rf["traffic_source"] = "NOT measured by this run - committed pass: " + str(tj.get("source"))
-                        for q in ("binding", "ceilings", "hbm_frac_physical", "frames_per_launch"):
-                            if q in tj:
-                                rf.setdefault(q if q != "frames_per_launch" else "traffic_frames_per_launch", tj[q])
-                except (OSError, ValueError):
-                    pass
-        if world == 1 and not strong and not args.no_cpu_baseline:
+                    "traffic": hbm,
+                    "traffic_source": "live: rocprofv3 --kernel-trace --pmc passes of `bench.py --roofline-only` run by this bench.py (FETCH_SIZE x2 + WRITE_SIZE, "
+                                      "mean per %s dispatch of %d frames); memory-side (fabric) bytes, Infinity-Cache hits included" % (kname, BATCH),
+                    "binding": cz["binding"], "ceilings": cz["fractions"], "tcp_accesses_per_cu_cycle_raw": cz["tcp_accesses_per_cu_cycle_raw"],
+                    "tcp_miss_stall_cycles_per_cu_cycle": cz["tcp_miss_stall_cycles_per_cu_cycle"],
+                    "hbm_frac_physical": cz["fractions"]["hbm"],
+                    "kernel_us_profiled": cz["kernel_us_profiled"], "l2_hit_rate": cz["l2_hit_rate"],
+                    "cu_cycles_per_wave_load": cz["cu_cycles_per_wave_load"], "l1_accesses_per_wave_load": cz["l1_accesses_per_wave_load"],
+                    "insts_per_launch": {"salu": pm["SQ_INSTS_SALU"], "valu": pm["SQ_INSTS_VALU"], "vmem_rd": pm["SQ_INSTS_VMEM_RD"], "waves": pm["SQ_WAVES"]}})
+                if kname == "k_local_bits" and lane_features > 0:
+                    per = pm["SQ_INSTS_VALU"] / lane_features
+                    rf.update({
+                        "valu_per_lane_feature": per,
+                        "useful_valu_frac": USEFUL_ADDER_OPS_PER_LANE_FEATURE / per,
+                        "useful_valu_frac_with_window_shifts": (USEFUL_ADDER_OPS_PER_LANE_FEATURE + ALIGN_OPS_PER_LANE_FEATURE) / per,
+                        "useful_valu_note": "adder operations the bit-sliced sums need per lane and feature (5.0: ISA of the 16-feature loop body, DESIGN.md 3.1) over the "
+                                            "wave-level VALU instructions measured per lane and feature (SQ_INSTS_VALU / (pairs / 8)); round 3's kernel: 10 of 33",
+                        "what_bounds_it": "the number of wave loads: a wave load of k_local_bits (8 candidates x 128 contiguous bytes = 1 KB) takes 20-23 CU cycles whatever "
+                                          "the lanes or addresses (`cu_cycles_per_wave_load`; 16 = the 64 B per cycle of the L1 -> register path, `ceilings.l1_data`), with "
+                                          "the L2 -> L1 fills behind it (`ceilings.l2`, the miss-stall share).  Three schemes that share loads between neighbouring candidates "
+                                          "were built in round 5 — bit-exact, fewer wave loads, more L2 requests, none faster: profiles/r05_local_sharing/README.txt"})
+            # every stage of a frame with the ceiling that binds it, from the same PMC passes (one fraction <= 1 per stage, recomputable from profiles/r04_pmc.txt)
+            if pm_all:
+                B_FRONT = W * H * 3 + W * H * 2 + 8 * 2 * (W * H + (W // 2) * (H // 2))      # 1.54 MB in + 6.14 MB of linear memories (8 labels x 2 modalities x 2 levels) out per VGA frame
+                stages = {}
+                fe_us, fe_bytes = 0.0, 0.0
+                fe_parts = {}
+                for k in ("k_fe_stage", "k_fe_bits", "k_pack_bits", "k_pack_top"):
+                    if k in pm_all:
+                        cz = ceilings_of(pm_all[k], wide_loads=False)
+                        n = pm_all[k]["dispatches"] / max(1, pm_all[k_refine]["dispatches"] if k_refine in pm_all else 1)     # dispatches of this kernel per batch
+                        fe_us += cz["kernel_us_profiled"] * n
+                        fe_bytes += cz["hbm_bytes_per_dispatch"] * n
+                        fe_parts[k] = {"dispatches_per_batch": n, "us_per_dispatch": cz["kernel_us_profiled"], "binding": cz["binding"], "ceilings": cz["fractions"],
+                                       "tcp_miss_stall_cycles_per_cu_cycle": cz["tcp_miss_stall_cycles_per_cu_cycle"]}
+                if fe_us > 0:
+                    stages["frontend"] = {"kernels": fe_parts, "us_per_batch_profiled": fe_us, "ms_per_batch_events": excl["frontend_ms"],
+                                          "algorithmic_bytes_per_frame": B_FRONT,
+                                          "hbm_frac_algorithmic": B_FRONT * BATCH / (excl["frontend_ms"] * 1e-3) / 1e9 / HBM_PEAK_GBS if excl["frontend_ms"] > 0 else None,
+                                          "traffic_bytes_per_batch": fe_bytes, "traffic_over_algorithmic": fe_bytes / (B_FRONT * BATCH),
+                                          "note": "the one stage that streams: a frame in, its response maps out.  With bit planes for both passes the maps leave as 2 bits per "
+                                                  "cell (2.8 MB per frame) instead of bytes in two layouts (11 MB), so the traffic can fall below SURVEY 8(d)'s algorithmic figure"}
+                for stage, k, ms in (("coarse", k_coarse_name, excl["coarse_ms"]), ("refine", k_refine, excl["local_ms"])):
+                    if k in pm_all:
+                        cz = ceilings_of(pm_all[k])
+                        stages[stage] = {"kernel": k, "ms_per_batch_events": ms, "us_per_dispatch_profiled": cz["kernel_us_profiled"], "binding": cz["binding"],
+                                         "ceilings": cz["fractions"], "tcp_accesses_per_cu_cycle_raw": cz["tcp_accesses_per_cu_cycle_raw"],
+                                         "tcp_miss_stall_cycles_per_cu_cycle": cz["tcp_miss_stall_cycles_per_cu_cycle"], "l2_hit_rate": cz["l2_hit_rate"], "cu_cycles_per_wave_load": cz["cu_cycles_per_wave_load"],
+                                         "l1_accesses_per_wave_load": cz["l1_accesses_per_wave_load"]}
+                rf["stages"] = stages
+            if pm is None:
+                traffic = os.path.join(ROOT, "profiles", "roofline_traffic.json")   # last committed PMC pass (profiles/pmc_run.sh)
+                if os.path.exists(traffic):
+                    try:
+                        tj = json.load(open(traffic))
+                        if tj.get("kernel") == kname:
+                            rf["traffic"] = tj.get("hbm_bytes_per_launch")
+                            rf["traffic_source"] = "NOT measured by this run - committed pass: " + str(tj.get("source"))
+                            for q in ("binding", "ceilings", "hbm_frac_physical", "frames_per_launch"):
+                                if q in tj:
+                                    rf.setdefault(q if q != "frames_per_launch" else "traffic_frames_per_launch", tj[q])
+                    except (OSError, ValueError):
+                        pass
+        if args.full and world == 1 and not strong and not args.no_cpu_baseline:
             os.sched_setaffinity(0, all_cpus)          # the CPU baseline (its all-cores variant) gets every core the process started with
             out["cpu_baseline"] = cpu_baseline(noisy_frames(N_FRAMES), banks[classes[0]], args.templates)
             out["speedup_vs_cpu_1thread"] = value / out["cpu_baseline"]["value"] if out["cpu_baseline"]["value"] else None
@@ -654,7 +686,7 @@ def main():
                                                 "maps on: OpenCV, which the reference's quantisation needs, is not in this image)")
             iq = out["cpu_baseline"].get("incl_quantisation", {}).get("value")
             out["speedup_vs_cpu_1thread_incl_quantisation"] = value / iq if iq else None
-        if world == 1 and not strong and not args.no_extras:
+        if args.full and world == 1 and not strong and not args.no_extras:
             sr = strong_reference(det, quant, frames, args.templates, steps=args.steps, depth=PIPELINE_DEPTH)
             out["extras"]["strong_scaling_reference"] = sr
             # One-GPU proxy of BASELINE's strong-scaling target (>= 6 x at 8 GPUs when sharding 16k templates): the 16k bank on this GPU against an
@@ -672,6 +704,22 @@ def main():
     if use_dist:
         dist.barrier()
         dist.destroy_process_group()
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path, recs):
+    """--dump-outputs: the match records of the last timed step, one float64 array per field of MATCH_DTYPE (x, y, similarity,
+    class_index, template_id) as DIR/match_<field>.npy, in the order Detector.match returns them.  A list larger than 64 MB in all
+    is cut to a fixed, seeded sample of records (kept in their order)."""
+    os.makedirs(path, exist_ok=True)
+    recs = np.array(recs, copy=True)
+    n_max = DUMP_MAX_BYTES // (8 * len(recs.dtype.names))
+    if len(recs) > n_max:
+        recs = recs[np.sort(np.random.default_rng(0).choice(len(recs), n_max, replace=False))]
+    for f in recs.dtype.names:
+        np.save(os.path.join(path, "match_%s.npy" % f), recs[f].astype(np.float64))
 
 
 def oracle_matches(od, lo, pb, rgb, dep, threshold):

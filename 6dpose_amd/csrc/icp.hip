@@ -364,10 +364,12 @@ k_icp_model_boxes(const uint16_t* __restrict__ models, int* __restrict__ model_b
     if (blockIdx.x == 0 && threadIdx.x == 0) known[4] = 1;        // (read by the kernels of a later launch)
 }
 
-void launch_icp_model_boxes(const uint16_t* models, int* model_bbox, int first_slot, int count, int W, int H, hipStream_t s) {
-    if (count <= 0) return;
-    (void)hipMemsetAsync(model_bbox + (size_t)first_slot * 8, 0, (size_t)count * 8 * sizeof(int), s);
+hipError_t launch_icp_model_boxes(const uint16_t* models, int* model_bbox, int first_slot, int count, int W, int H, hipStream_t s) {
+    if (count <= 0) return hipSuccess;
+    const hipError_t e = hipMemsetAsync(model_bbox + (size_t)first_slot * 8, 0, (size_t)count * 8 * sizeof(int), s);
+    if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_icp_model_boxes, dim3(32, count), dim3(256), 0, s, models, model_bbox, first_slot, W, H);
+    return hipGetLastError();
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2513,8 +2515,8 @@ k_icp_eval(IcpBuffers B, int it, int prev_slices, int max_shift, double max_dist
 // Searching points go through a queue in LDS (ordered by cost class, 2^class lanes per point, one grid column per lane: the
 // sweep of k_icp_eval); the queue is worked off in windows when more points search than it holds.
 // A hypothesis whose clouds do not fit (slice > 3520 points, or target records + normals + table + a minimal queue > the LDS) is
-// left alone (stop stays 0): the host then runs the sliced launches for it.  So is one whose team waited kTeamTimeout for a
-// member (the GPU is shared and the grid was not resident at once).
+// left alone (stop stays 0): the later stages of the ICP driver take it (pose_refine.cpp).  So is one whose team waited kTeamTimeout for
+// a member (the GPU is shared and the grid was not resident at once; team_note 4).
 constexpr int kSoloWG = 768;                // 12 waves = 3 per SIMD: 168 VGPRs each (1024 threads: 128, and the points' state went to scratch; 512: no more lanes than a search needs)
 constexpr int kSoloOwners = kSoloWG - 64;   // threads that own source points (waves 1-11)
 constexpr int kSoloRaw = 160 * 1024 - 5120; // bytes of the carve-out (the rest: partial sums, update matrix, counters)
@@ -2704,12 +2706,13 @@ k_icp_team(IcpBuffers B, unsigned int run, int shift_floor, double max_dist, int
     if (gridDim.y == 1 && B.count <= 64) {
         // One-dimensional grid (up to 64 hypotheses): the workgroups are dealt out to the hypotheses still to do in proportion to their source
         // points — a cloud of 10000 points next to one of 1500 gets seven times the members; with equal teams the large one sets the length
-        // of the launch while the CUs of the small ones idle.  Every wave of every workgroup computes the same table (lane = hypothesis).
+        // of the launch while the CUs of the small ones idle.  Every wave of every workgroup computes the same table (lane = hypothesis),
+        // whenever it starts: a hypothesis a team of this launch has finished (stop == run) still counts as at work.
         int w = 0;
         bool big = false;                                       // a cloud that needs the slab build
         if (lane < B.count) {
             const IcpState& T = B.st[lane];
-            if (T.status == 0 && T.stop == 0) {
+            if (T.status == 0 && (T.stop == 0 || T.stop == (int)run)) {
                 w = T.n_src > 0 ? T.n_src : 1;
                 big = team_needs_slab(T.n_tgt, T.gx, T.gy);
             }
@@ -2741,7 +2744,7 @@ k_icp_team(IcpBuffers B, unsigned int run, int shift_floor, double max_dist, int
         G = __shfl(members, h, 64);
     }
     IcpState& S = B.st[h];
-    if (S.status != 0 || S.stop != 0) return;
+    if (S.status != 0 || (S.stop != 0 && S.stop != (int)run)) return;
     const int ns = S.n_src, nt = S.n_tgt;
     const int gx = S.gx, gy = S.gy, zq_max = S.zq_max, ncell = gx * gy;
     const int it0 = S.resume_it;                                 // > 0: suspended by an earlier launch of the round after the finish stage of this evaluation index
@@ -3425,7 +3428,8 @@ k_icp_team(IcpBuffers B, unsigned int run, int shift_floor, double max_dist, int
         }
         return;
     }
-    if (tid == 0 && g == 0 && s_stop != 2) {                    // (a team that timed out leaves stop == 0: the host runs the sliced launches)
+    if (tid == 0 && g == 0 && s_stop == 2) S.team_note[0] = 4;  // (a team that timed out leaves stop == 0: the later stages of the ICP driver take it)
+    if (tid == 0 && g == 0 && s_stop != 2) {
         for (int a = 0; a < 12; ++a) S.T[a] = s_T[a];
         S.T[12] = 0.0; S.T[13] = 0.0; S.T[14] = 0.0; S.T[15] = 1.0;
         S.fitness = s_fin[0]; S.rmse = s_fin[1]; S.n_corr = s_fin_i[0]; S.iterations = s_fin_i[1];
@@ -3433,7 +3437,7 @@ k_icp_team(IcpBuffers B, unsigned int run, int shift_floor, double max_dist, int
         // diagnostics (shader cycles of wave 0 of member 0, which waits at the barriers for the other waves): exchange + finish, transform + queue, whole kernel, search, sums, evaluations, own searches, exchange alone
         S.clk[0] += s_clk[0]; S.clk[1] += s_clk[1]; S.clk[2] += (long long)__builtin_amdgcn_s_memtime() - t_begin; S.clk[3] += s_clk[2]; S.clk[4] += s_clk[3];
         S.clk[5] += s_clk[5]; S.clk[6] += s_clk[4]; S.clk[7] += s_clk[6];
-        S.stop = 1;
+        S.stop = (int)run;                                      // (the deal of a later workgroup of this launch still counts the hypothesis)
     }
 }
 
@@ -3511,28 +3515,31 @@ void launch_icp_evals(const IcpBuffers& B, int count, int it_from, int it_to, do
 //   8  five points per thread — batches so large that a team is one or two workgroups.
 // A launch with nothing to take is not free (measured on the icp leg: the idle build 2 costs 3 us, the idle build 4 another 6-8), so up
 // to 64 hypotheses — where the kernel deals the workgroups out by cloud size and a member holds more than 704 points only when the batch
-// has more than ~170k source points — the first call launches builds 1 and 2 only; the caller tries `large` (4 and 8) on what is left
-// before it goes to the sliced launches.
-void launch_icp_team(const IcpBuffers& B, int count, int large, double max_dist, int max_iter, double rel_tol, hipStream_t s) {
+// has more than ~170k source points — the first stage launches builds 1 and 2 only; the driver tries kIcpStageLarge (4 and 8) on what is
+// left before it goes to the sliced launches.
+void launch_icp_team(const IcpBuffers& B, int count, IcpStage stage, int cus, double max_dist, int max_iter, double rel_tol, hipStream_t s) {
     if (count <= 0) return;
     const Knobs& kn = knobs();
 #ifdef LM_DIAG
     if (kn.icp_maxiter_diag >= 0) max_iter = kn.icp_maxiter_diag;
 #endif
-    static const int cus = [] {
-        int dev = 0, n = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 64;
-        return n;
-    }();
+    const bool large = stage == kIcpStageLarge;
     int team = kn.icp_team > 0 ? kn.icp_team : 16;
     if (team > cus / count) team = cus / count;
     if (team > kIcpMaxSplit) team = kIcpMaxSplit;
     if (team < 1) team = 1;
-    static std::atomic<unsigned int> runs{0};                         // tags of the team's granules (see k_icp_team): unique per launch of the process, 0 = never published
     const bool dealt = count <= 64 && kn.icp_team == 0;              // (<= 64 hypotheses: the kernel deals the workgroups out itself, by cloud size)
     const dim3 grid = dealt ? dim3(cus) : dim3(team, count);
     int builds = kn.icp_builds > 0 ? kn.icp_builds : (dealt ? (large ? 4 | 8 : 1 | 2) : (large ? 0 : 1 | 2 | 4 | (team < 4 ? 8 : 0)));
     if (kn.icp_builds > 0 && large) builds = 0;
+    // Every launch draws its own run tag: the tag of the granules it publishes (k_icp_team) and what it writes into IcpState::stop.  Unique per
+    // launch of the process; 0 = never published, 1 = what k_icp_eval writes into stop.
+    static std::atomic<unsigned int> runs{0};
+    auto launch = [&](void (*kernel)(IcpBuffers, unsigned int, int, double, int, double, int, int), int allow) {
+        unsigned int run;
+        do run = (runs.fetch_add(1) + 1) & 0x3FFFFFFu; while (run < 2);
+        hipLaunchKernelGGL(kernel, grid, dim3(kSoloWG), 0, s, B, run, kn.icp_maxshift, max_dist, max_iter, rel_tol, allow, kn.icp_team_min_points);
+    };
     // A SECOND LAUNCH for a cramped batch (dealt grids): most hypotheses of a batch converge within a couple of evaluations and their
     // workgroups then idle while the ones that go on for all 30 keep the team they were dealt at the start (the pipeline's 16 detections: 12
     // done after two evaluations, the launch as long as 31 evaluations of a hypothesis on 8 workgroups).  When the clouds of a batch could
@@ -3542,27 +3549,17 @@ void launch_icp_team(const IcpBuffers& B, int count, int large, double max_dist,
     // grouped by the new team size (rounding); the rule looks at cloud sizes and evaluation indices only, so a run repeats itself bit for bit.
     const int relaunch = dealt && !large && kn.icp_builds == 0 ? kn.icp_relaunch : 0;
     for (int ph = 0; ph <= relaunch; ++ph) {
-        unsigned int run = (runs.fetch_add(1) + 1) & 0x3FFFFFFu;
-        if (run == 0) run = (runs.fetch_add(1) + 1) & 0x3FFFFFFu;
         const int allow = ph < relaunch ? kn.icp_cut_index * (ph + 1) * (ph + 1) : 0, b = ph == 0 ? builds : 2;   // (cut indices 3, 12, 27 ...)
-        if ((b & 3) == 3) {
-            hipLaunchKernelGGL((k_icp_team<1, false>), grid, dim3(kSoloWG), 0, s, B, run, kn.icp_maxshift, max_dist, max_iter, rel_tol, allow, kn.icp_team_min_points);
-            hipLaunchKernelGGL((k_icp_team<1, true>), grid, dim3(kSoloWG), 0, s, B, run, kn.icp_maxshift, max_dist, max_iter, rel_tol, allow, kn.icp_team_min_points);
-        }
-        else if (b & 1) hipLaunchKernelGGL((k_icp_team<1, false>), grid, dim3(kSoloWG), 0, s, B, run, kn.icp_maxshift, max_dist, max_iter, rel_tol, allow, kn.icp_team_min_points);
-        else if (b & 2) hipLaunchKernelGGL((k_icp_team<1, true>), grid, dim3(kSoloWG), 0, s, B, run, kn.icp_maxshift, max_dist, max_iter, rel_tol, allow, kn.icp_team_min_points);
-        if (b & 4) hipLaunchKernelGGL((k_icp_team<2, true>), grid, dim3(kSoloWG), 0, s, B, run, kn.icp_maxshift, max_dist, max_iter, rel_tol, allow, kn.icp_team_min_points);
-        if (b & 8) hipLaunchKernelGGL((k_icp_team<5, true>), grid, dim3(kSoloWG), 0, s, B, run, kn.icp_maxshift, max_dist, max_iter, rel_tol, allow, kn.icp_team_min_points);
+        if (b & 1) launch(k_icp_team<1, false>, allow);
+        if (b & 2) launch(k_icp_team<1, true>, allow);
+        if (b & 4) launch(k_icp_team<2, true>, allow);
+        if (b & 8) launch(k_icp_team<5, true>, allow);
     }
 }
 
-void launch_icp_pipeline(const IcpBuffers& B, int count, int W, int H, int flags, double voxel, double max_dist, int max_iter,
-                         double rel_tol, int knn, int solo_from, hipStream_t s) {
+void launch_icp_prepare(const IcpBuffers& B, int count, int W, int H, int flags, double voxel, int knn, hipStream_t s) {
     if (count <= 0) return;
     const Knobs& kn = knobs();
-#ifdef LM_DIAG
-    if (kn.icp_maxiter_diag >= 0) max_iter = kn.icp_maxiter_diag;            // diagnostics only (profiles/): stop after a few evaluations
-#endif
     const int scene_mode = flags & 1;
     if (!(flags & 0x100) || !kn.icp_wide_sort) hipLaunchKernelGGL(k_icp_bbox, dim3(32, count), dim3(256), 0, s, B, W, H);   // (0x100: every slot's box is in model_bbox)
     if (kn.icp_wide_sort) hipLaunchKernelGGL(k_icp_points_fused, dim3(kIcpStrips, count), dim3(kPtsWG), 0, s, B, W, H, flags);
@@ -3579,11 +3576,6 @@ void launch_icp_pipeline(const IcpBuffers& B, int count, int W, int H, int flags
     hipLaunchKernelGGL(k_icp_knn, dim3(kn.knn_blocks > 0 ? kn.knn_blocks : (count <= 32 ? 64 : 32), count), dim3(kKnnWG), 0, s, B, knn);
     hipLaunchKernelGGL(k_icp_knn_far, dim3(kKnnFarBlocks, count), dim3(512), 0, s, B, knn);
     hipLaunchKernelGGL(k_icp_normals, dim3(count <= 32 ? 64 : 16, count), dim3(256), 0, s, B);
-    if (solo_from != 0) {                                            // sliced launches only
-        launch_icp_evals(B, count, 0, max_iter + 1, max_dist, max_iter, rel_tol, s);
-        return;
-    }
-    launch_icp_team(B, count, 0, max_dist, max_iter, rel_tol, s);
 }
 
 }  // namespace lm

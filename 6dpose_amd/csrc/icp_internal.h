@@ -31,13 +31,20 @@ struct lm_icp {
     IcpState* h_st = nullptr;      // pinned: the states uploaded before / read after a run
     IcpState* h_st2 = nullptr;     // pinned: read-back of lm_icp_run (h_st keeps the initial states for a repeated run)
     int h_cap = 0;
-    int solo_from = 0;             // 0: RegistrationICP as one launch (k_icp_team), the sliced launches only for hypotheses it leaves unfinished;
-                                   // -1 (LM_ICP_SLICED=1): one launch per evaluation (k_icp_eval, rounds 1-5)
+    int cus = 0;                   // compute units of the device: the grid of k_icp_team
+    bool sliced_only = false;      // LM_ICP_SLICED=1: RegistrationICP as one launch per evaluation (k_icp_eval, rounds 1-5), no k_icp_team
+    std::vector<int> stage;        // per hypothesis of the last run: the lm::IcpStage that finished it
 };
 
 
 // pose_refine.cpp
-bool lm_icp_unfinished(const lm::IcpState* st, int count);   // a hypothesis k_icp_solo left to the sliced launches (status 0, stop 0)
+// The ICP ladder of one run of B.count hypotheses on stream s, in two halves around the caller's synchronisation of s:
+//   enqueue: the preparation of the clouds and the first stage (k_icp_team, or the sliced launches under LM_ICP_SLICED=1), e1, then the
+//            read-back of the states into the pinned h_st;
+//   finish:  for what the first stage left unfinished the large team builds, then the sliced launches, each followed by e1, the read-back
+//            and a synchronisation; a hypothesis still unfinished after those is an error.  Fills c->stage.
+int lm_icp_enqueue(lm_icp* c, const lm::IcpBuffers& B, int flags, lm::IcpState* h_st, hipStream_t s);
+int lm_icp_finish(lm_icp* c, const lm::IcpBuffers& B, lm::IcpState* h_st, hipStream_t s);
 int lm_icp_set_geometry(lm_icp* c, int W, int H);      // (re)allocates for a frame size; drops the slots when it changes
 int lm_icp_ensure_arenas(lm_icp* c, int count);        // arenas for `count` hypotheses
 int lm_icp_ensure_slots(lm_icp* c, int slots);         // resident model depth images

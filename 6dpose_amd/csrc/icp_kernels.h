@@ -48,7 +48,7 @@ struct IcpState {            // one pose hypothesis (device-written, downloaded 
     double gminx, gminy, gminz, cell, inv_cell, inv_z;
     double T[16];            // final transformation_ (row-major)
     double fitness, rmse;    // fitness_, inlier_rmse_
-    int stop;                // RegistrationICP finished (converged or max_iteration)
+    int stop;                // RegistrationICP finished (converged or max_iteration): 0 not yet, 1 by k_icp_eval, else the run tag of the k_icp_team launch
     int n_far;               // target points k_icp_knn left to k_icp_knn_far (their k nearest are more than 8 rings away)
     double fit_hist[2], rmse_hist[2];   // fitness / rmse of the last two evaluations, slot = evaluation parity
     int vox_done[2];         // groups of k_icp_voxel_wide that finished the model / scene cloud (kIcpSortGroups: k_icp_voxel has nothing to do)
@@ -59,7 +59,7 @@ struct IcpState {            // one pose hypothesis (device-written, downloaded 
     long long vox_clk[4];    // k_icp_voxel diagnostics (model cloud): cycles for the extent, the keys, the sort, the voxel means
     long long sort_clk[16];  // k_icp_voxel_wide (0-7, model cloud) / k_icp_grid_wide (8-15) diagnostics, slowest group per phase: cycles for picking its points, the sort, (voxels: count + wait for the groups before), writing, (grid: the column table); 6 / 13: largest group
     long long knn_clk[4];    // k_icp_knn diagnostics: slowest workgroup's cycles staging, in the 8-lane trips, in the whole-wave pass; points handed to whole waves
-    long long clk[8];        // k_icp_loop shader cycles (thread 0): A1 certainty test, reduction, solve, transform, A2 search, accumulate, queued points, -
+    long long clk[8];        // k_icp_eval shader cycles (thread 0): A1 certainty test, reduction, solve, transform, A2 search, accumulate, queued points, - (k_icp_team: see its end)
 };
 
 struct IcpBuffers {
@@ -99,15 +99,19 @@ struct IcpBuffers {
 struct TopkSel;
 void launch_icp_bind(const TopkSel* sel, const int32_t* nsel_status, const int32_t* class_base, const float* view_K,
                      const int32_t* view_valid, int num_views, IcpIn* in, IcpState* st, int top_k, hipStream_t s);
-// solo_from == 0: RegistrationICP as one launch (k_icp_team: a team of workgroups per hypothesis, all evaluations inside); a hypothesis whose
-// clouds it cannot hold comes back with stop == 0 and the caller runs launch_icp_evals(0 .. max_iter + 1) for it.  Otherwise: sliced launches only.
-void launch_icp_pipeline(const IcpBuffers& B, int count, int W, int H, int flags, double voxel, double max_dist, int max_iter,
-                         double rel_tol, int knn, int solo_from, hipStream_t s);
-// bit 0x100 of launch_icp_pipeline's flags: every model slot the hypotheses use had its box worked out at upload (launch_icp_model_boxes)
-void launch_icp_model_boxes(const uint16_t* models, int* model_bbox, int first_slot, int count, int W, int H, hipStream_t s);
+// The preparation of the clouds (box, dilated mask, back-projection, voxel down-sampling, search grid, kNN normals); bit 0x100 of flags:
+// every model slot the hypotheses use had its box worked out at upload (launch_icp_model_boxes).  RegistrationICP comes after it.
+void launch_icp_prepare(const IcpBuffers& B, int count, int W, int H, int flags, double voxel, int knn, hipStream_t s);
+hipError_t launch_icp_model_boxes(const uint16_t* models, int* model_bbox, int first_slot, int count, int W, int H, hipStream_t s);
+// The sliced launches of evaluations [it_from, it_to] (k_icp_eval); a hypothesis they finish gets stop == 1.
 void launch_icp_evals(const IcpBuffers& B, int count, int it_from, int it_to, double max_dist, int max_iter, double rel_tol, hipStream_t s);
-// the team kernel alone: large == 0 what launch_icp_pipeline launches at its end; large == 1 the builds for more than 704 source points per
-// workgroup, which the caller tries on unfinished hypotheses (stop == 0) before launch_icp_evals
-void launch_icp_team(const IcpBuffers& B, int count, int large, double max_dist, int max_iter, double rel_tol, hipStream_t s);
+
+// The stage of the ICP ladder that finished a hypothesis (lm_pose_result::stage); 0: not registered (status != 0).
+enum IcpStage { kIcpStageNone = 0, kIcpStageTeam = 1, kIcpStageLarge = 2, kIcpStageSliced = 3 };
+// RegistrationICP as one launch (k_icp_team: a team of workgroups per hypothesis, all evaluations inside) for the hypotheses with stop == 0.
+// stage kIcpStageTeam: the first builds, cut and relaunch included; kIcpStageLarge: the builds for more than 704 source points per workgroup.
+// A hypothesis the launch cannot hold comes back with stop == 0; one it finishes carries the run tag of its launch in stop (>= 2).
+// cus: compute units of the device the stream belongs to.
+void launch_icp_team(const IcpBuffers& B, int count, IcpStage stage, int cus, double max_dist, int max_iter, double rel_tol, hipStream_t s);
 
 }  // namespace lm

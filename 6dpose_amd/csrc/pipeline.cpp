@@ -15,11 +15,6 @@
 #include "icp_internal.h"
 #include "render_internal.h"
 
-namespace {
-constexpr double kVoxel = 0.0025, kMaxDist = 0.01, kRelTol = 1e-6;   // as pose_refine.cpp (LL.cpp:106, :31; Open3D defaults)
-constexpr int kMaxIter = 30, kKnn = 30;
-}
-
 struct lm_pipeline {
     lm_detector* det = nullptr;
     lm_icp* icp = nullptr;
@@ -161,7 +156,7 @@ extern "C" int lm_pipeline_set_views_rendered(lm_pipeline* p, lm_mesh* m, const 
             return rc;
         HIP_TRY(hipMemcpyAsync(p->icp->d_models + ((size_t)slot0 + c0) * npx, m->d_depth, (size_t)n * npx * sizeof(uint16_t),
                                hipMemcpyDeviceToDevice, m->s));
-        lm::launch_icp_model_boxes(p->icp->d_models, p->icp->d_model_bbox, slot0 + c0, n, p->W, p->H, m->s);   // the boxes of the new views, once (LL.cpp:43-50)
+        HIP_TRY(lm::launch_icp_model_boxes(p->icp->d_models, p->icp->d_model_bbox, slot0 + c0, n, p->W, p->H, m->s));   // the boxes of the new views, once (LL.cpp:43-50)
         for (int i = 0; i < n; ++i) p->icp->slot_boxed[(size_t)slot0 + c0 + i] = 1;
         HIP_TRY(hipStreamSynchronize(m->s));
     }
@@ -271,9 +266,7 @@ extern "C" int lm_pipeline_run(lm_pipeline* p, float threshold, const char* cons
         B.count = top_k;
         memcpy(B.sK, scene_K, sizeof(B.sK));
         // (k_icp_bind only binds views that were uploaded, and both upload paths work out the boxes: 0x100 = no k_icp_bbox)
-        launch_icp_pipeline(B, top_k, p->W, p->H, (flags & 0xFF) | 0x100, kVoxel, kMaxDist, kMaxIter, kRelTol, kKnn, c->solo_from, s);
-        HIP_TRY(hipEventRecord(c->e1, s));
-        HIP_TRY(hipMemcpyAsync(c->h_st, c->d_st, (size_t)top_k * sizeof(IcpState), hipMemcpyDeviceToHost, s));
+        if ((rc = lm_icp_enqueue(c, B, (flags & 0xFF) | 0x100, c->h_st, s))) return rc;
         HIP_TRY(hipMemcpyAsync(p->h_sel, p->d_sel, (size_t)top_k * sizeof(TopkSel), hipMemcpyDeviceToHost, s));
         HIP_TRY(hipMemcpyAsync(p->h_nsel, p->d_nsel, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
@@ -284,18 +277,7 @@ extern "C" int lm_pipeline_run(lm_pipeline* p, float threshold, const char* cons
             continue;
         }
         if (rc) return rc;
-        for (int pass = 0; pass < 2 && lm_icp_unfinished(c->h_st, top_k); ++pass) {
-            // clouds the first team builds do not hold (more than 704 source points per workgroup): the builds with more points per thread;
-            // what those leave too, or a team that timed out: the sliced launches
-            if (c->solo_from != 0) return lm_set_error(LM_ERR_HIP, "ICP: a hypothesis was left unfinished");
-            if (pass == 0) launch_icp_team(B, top_k, 1, kMaxDist, kMaxIter, kRelTol, s);
-            else launch_icp_evals(B, top_k, 0, kMaxIter + 1, kMaxDist, kMaxIter, kRelTol, s);
-            HIP_TRY(hipEventRecord(c->e1, s));
-            HIP_TRY(hipMemcpyAsync(c->h_st, c->d_st, (size_t)top_k * sizeof(IcpState), hipMemcpyDeviceToHost, s));
-            HIP_TRY(hipStreamSynchronize(s));
-            HIP_TRY(hipGetLastError());
-        }
-        if (lm_icp_unfinished(c->h_st, top_k)) return lm_set_error(LM_ERR_HIP, "ICP: a hypothesis was left unfinished");
+        if ((rc = lm_icp_finish(c, B, c->h_st, s))) return rc;
         break;
     }
     if (p->h_nsel[1] != 0)
@@ -319,6 +301,7 @@ extern "C" int lm_pipeline_run(lm_pipeline* p, float threshold, const char* cons
         const int base = p->h_class_base[sl.class_index];
         const size_t v = (size_t)base + sl.template_id;
         lm_icp_compose_result(st, &p->view_R[v * 9], &p->view_t[v * 3], &o.pose);
+        o.pose.stage = c->stage[(size_t)i];
     }
     *n_out = n;
     if (tm) {

@@ -182,10 +182,35 @@ void lm_icp_compose_result(const IcpState& st, const float* model_R, const float
     o.n_target = st.n_tgt;
 }
 
-bool lm_icp_unfinished(const IcpState* st, int count) {
-    for (int i = 0; i < count; ++i)
-        if (st[i].status == 0 && st[i].stop == 0) return true;
-    return false;
+int lm_icp_enqueue(lm_icp* c, const IcpBuffers& B, int flags, IcpState* h_st, hipStream_t s) {
+    launch_icp_prepare(B, B.count, c->W, c->H, flags, kVoxel, kKnn, s);
+    if (c->sliced_only) launch_icp_evals(B, B.count, 0, kMaxIter + 1, kMaxDist, kMaxIter, kRelTol, s);
+    else launch_icp_team(B, B.count, kIcpStageTeam, c->cus, kMaxDist, kMaxIter, kRelTol, s);
+    HIP_TRY(hipEventRecord(c->e1, s));
+    HIP_TRY(hipMemcpyAsync(h_st, c->d_st, (size_t)B.count * sizeof(IcpState), hipMemcpyDeviceToHost, s));
+    return LM_OK;
+}
+
+int lm_icp_finish(lm_icp* c, const IcpBuffers& B, IcpState* h_st, hipStream_t s) {
+    c->stage.assign((size_t)B.count, kIcpStageNone);
+    for (int stage = c->sliced_only ? kIcpStageSliced : kIcpStageTeam;; ++stage) {
+        bool unfinished = false;                                     // (status 0, stop 0)
+        for (int i = 0; i < B.count; ++i) {
+            if (h_st[i].status != 0) continue;
+            if (h_st[i].stop == 0) unfinished = true;
+            else if (c->stage[i] == kIcpStageNone) c->stage[i] = stage;
+        }
+        if (!unfinished) return LM_OK;
+        // clouds the first team builds do not hold (more than 704 source points per workgroup): the builds with more points per thread;
+        // what those leave too, or a team that timed out: the sliced launches
+        if (stage == kIcpStageSliced) return lm_set_error(LM_ERR_HIP, "ICP: a hypothesis was left unfinished");
+        if (stage == kIcpStageTeam) launch_icp_team(B, B.count, kIcpStageLarge, c->cus, kMaxDist, kMaxIter, kRelTol, s);
+        else launch_icp_evals(B, B.count, 0, kMaxIter + 1, kMaxDist, kMaxIter, kRelTol, s);
+        HIP_TRY(hipEventRecord(c->e1, s));
+        HIP_TRY(hipMemcpyAsync(h_st, c->d_st, (size_t)B.count * sizeof(IcpState), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        HIP_TRY(hipGetLastError());
+    }
 }
 
 extern "C" int lm_icp_create(int device, lm_icp** out) {
@@ -196,9 +221,12 @@ extern "C" int lm_icp_create(int device, lm_icp** out) {
         return lm_set_error(LM_ERR_NO_DEVICE, "no HIP device visible; libamdlinemod has no CPU fallback");
     if (device < 0 || device >= ndev) return lm_set_error(LM_ERR_INVALID, "device %d out of range", device);
     HIP_TRY(hipSetDevice(device));
+    int cus = 0;
+    HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
     lm_icp* c = new lm_icp();
     c->device = device;
-    if (const char* e = getenv("LM_ICP_SLICED")) c->solo_from = e[0] && e[0] != '0' ? -1 : 0;
+    c->cus = cus;
+    if (const char* e = getenv("LM_ICP_SLICED")) c->sliced_only = e[0] && e[0] != '0';
     if (hipStreamCreateWithFlags(&c->s, hipStreamNonBlocking) != hipSuccess || hipEventCreate(&c->e0) != hipSuccess ||
         hipEventCreate(&c->e1) != hipSuccess) {
         delete c;
@@ -254,7 +282,7 @@ extern "C" int lm_icp_set_models(lm_icp* c, int first_slot, int count, const uin
     uint8_t* stage = (uint8_t*)c->pinned + img;
     for (int i = 0; i < count; ++i) memcpy(stage + (size_t)i * img, model_depths[i], img);
     HIP_TRY(hipMemcpyAsync(c->d_models + (size_t)first_slot * c->W * c->H, stage, img * (size_t)count, hipMemcpyHostToDevice, c->s));
-    lm::launch_icp_model_boxes(c->d_models, c->d_model_bbox, first_slot, count, c->W, c->H, c->s);   // the boxes of the new images, once (LL.cpp:43-50)
+    HIP_TRY(lm::launch_icp_model_boxes(c->d_models, c->d_model_bbox, first_slot, count, c->W, c->H, c->s));   // the boxes of the new images, once (LL.cpp:43-50)
     for (int i = 0; i < count; ++i) c->slot_boxed[(size_t)first_slot + i] = 1;
     return LM_OK;
 }
@@ -292,19 +320,10 @@ extern "C" int lm_icp_run(lm_icp* c, int count, const int32_t* model_slots, cons
     HIP_TRY(hipEventRecord(c->e0, c->s));
     bool boxed = true;                                               // every slot's box was worked out when its image was uploaded: no k_icp_bbox
     for (int i = 0; i < count; ++i) boxed = boxed && c->slot_boxed[(size_t)(model_slots ? model_slots[i] : i)] != 0;
-    launch_icp_pipeline(B, count, c->W, c->H, (flags & 0xFF) | (boxed ? 0x100 : 0), kVoxel, kMaxDist, kMaxIter, kRelTol, kKnn, c->solo_from, c->s);
-    for (int pass = 0; pass < 3; ++pass) {
-        HIP_TRY(hipEventRecord(c->e1, c->s));
-        HIP_TRY(hipMemcpyAsync(c->h_st2, c->d_st, (size_t)count * sizeof(IcpState), hipMemcpyDeviceToHost, c->s));
-        HIP_TRY(hipStreamSynchronize(c->s));
-        HIP_TRY(hipGetLastError());
-        if (!lm_icp_unfinished(c->h_st2, count)) break;
-        // clouds the first team builds do not hold (more than 704 source points per workgroup): the builds with more points per thread;
-        // what those leave too, or a team that timed out: the sliced launches
-        if (pass == 2 || c->solo_from != 0) return lm_set_error(LM_ERR_HIP, "ICP: a hypothesis was left unfinished");
-        if (pass == 0) launch_icp_team(B, count, 1, kMaxDist, kMaxIter, kRelTol, c->s);
-        else launch_icp_evals(B, count, 0, kMaxIter + 1, kMaxDist, kMaxIter, kRelTol, c->s);
-    }
+    if ((rc = lm_icp_enqueue(c, B, (flags & 0xFF) | (boxed ? 0x100 : 0), c->h_st2, c->s))) return rc;
+    HIP_TRY(hipStreamSynchronize(c->s));
+    HIP_TRY(hipGetLastError());
+    if ((rc = lm_icp_finish(c, B, c->h_st2, c->s))) return rc;
     memcpy(c->h_st, c->h_st2, (size_t)count * sizeof(IcpState));
     c->last_count = count; c->last_flags = flags;
     if (device_ms) (void)hipEventElapsedTime(device_ms, c->e0, c->e1);
@@ -321,6 +340,7 @@ extern "C" int lm_icp_run(lm_icp* c, int count, const int32_t* model_slots, cons
         memset(&o, 0, sizeof(o));
         if (st.status == 1) { o.residual = -1.f; continue; }        // LL.cpp:52-55
         lm_icp_compose_result(st, model_Rs + 9 * i, model_ts + 3 * i, &o);
+        o.stage = c->stage[(size_t)i];
     }
     return LM_OK;
 }

@@ -77,7 +77,7 @@ class Timings(ctypes.Structure):
 class _CPoseResult(ctypes.Structure):
     _fields_ = [("R", ctypes.c_double * 9), ("t", ctypes.c_double * 3), ("residual", ctypes.c_float),
                 ("inlier_rmse", ctypes.c_float), ("iterations", ctypes.c_int32), ("n_source", ctypes.c_int32),
-                ("n_target", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+                ("n_target", ctypes.c_int32), ("stage", ctypes.c_int32)]
 
 
 class _CDetection(ctypes.Structure):
@@ -855,7 +855,7 @@ class poseRefine:
         self._R = np.array(res.R, np.float64).reshape(3, 3)
         self._t = np.array(res.t, np.float64).reshape(3, 1)
         self.info = {"inlier_rmse": float(res.inlier_rmse), "iterations": int(res.iterations),
-                     "n_source": int(res.n_source), "n_target": int(res.n_target)}
+                     "n_source": int(res.n_source), "n_target": int(res.n_target), "stage": int(res.stage)}
 
     def getResidual(self) -> float:
         return self.residual
@@ -884,21 +884,14 @@ def pose_refine_batch(scene_depth, scene_K, model_depths, model_Ks, model_Rs, mo
     ms = ctypes.c_float()
     _check(lib.lm_pose_refine_batch(device, _ptr(sd), sd.shape[1], sd.shape[0], _ptr(sK), n, ptrs, _ptr(Ks), _ptr(Rs), _ptr(ts),
                                     _ptr(xy), LM_ICP_SCENE_FROM_SCENE if scene_from_scene else 0, res, ctypes.byref(ms)))
-    out = []
-    for r in res:
-        out.append({"R": np.array(r.R).reshape(3, 3), "t": np.array(r.t), "residual": float(r.residual),
-                    "rmse": float(r.inlier_rmse), "iterations": int(r.iterations), "n_source": int(r.n_source),
-                    "n_target": int(r.n_target)})
-    return out, float(ms.value)
+    return [_pose_dict(r) for r in res], float(ms.value)
 
 
-def _pose_results(res):
-    out = []
-    for r in res:
-        out.append({"R": np.array(r.R).reshape(3, 3), "t": np.array(r.t), "residual": float(r.residual),
-                    "rmse": float(r.inlier_rmse), "iterations": int(r.iterations), "n_source": int(r.n_source),
-                    "n_target": int(r.n_target)})
-    return out
+def _pose_dict(r):
+    """One lm_pose_result as the result dict; stage: the ICP stage that finished the hypothesis (1 first team launch, 2 large team builds,
+    3 sliced launches; 0 not registered)."""
+    return {"R": np.array(r.R).reshape(3, 3), "t": np.array(r.t), "residual": float(r.residual), "rmse": float(r.inlier_rmse),
+            "iterations": int(r.iterations), "n_source": int(r.n_source), "n_target": int(r.n_target), "stage": int(r.stage)}
 
 
 class IcpContext:
@@ -947,7 +940,7 @@ class IcpContext:
         ms = ctypes.c_float()
         _check(self._lib.lm_icp_run(self._h, n, None if slots is None else _ptr(slots), _ptr(Ks), _ptr(Rs), _ptr(ts), _ptr(xy),
                                     self.flags, res, ctypes.byref(ms)))
-        return _pose_results(res), float(ms.value)
+        return [_pose_dict(r) for r in res], float(ms.value)
 
     def read_debug(self, hypothesis: int, kind: int):
         n = self._lib.lm_icp_read_debug(self._h, int(hypothesis), int(kind), None, 0)
@@ -1036,10 +1029,7 @@ class Pipeline:
             o = out[i]
             res.append({"x": int(o.match.x), "y": int(o.match.y), "similarity": float(o.match.similarity),
                         "class_index": int(o.match.class_index), "template_id": int(o.match.template_id),
-                        "width": int(o.width), "height": int(o.height), "status": int(o.status),
-                        "R": np.array(o.pose.R).reshape(3, 3), "t": np.array(o.pose.t), "residual": float(o.pose.residual),
-                        "rmse": float(o.pose.inlier_rmse), "iterations": int(o.pose.iterations),
-                        "n_source": int(o.pose.n_source), "n_target": int(o.pose.n_target)})
+                        "width": int(o.width), "height": int(o.height), "status": int(o.status), **_pose_dict(o.pose)})
         if norms_thresh is not None:
             posed = [r for r in res if r["status"] == 0]
             keep = nms_norms(np.array([r["t"] for r in posed], np.float64).reshape(-1, 3), np.array([-r["residual"] for r in posed], np.float64),

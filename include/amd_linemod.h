@@ -354,7 +354,8 @@ typedef struct lm_pose_result {
     int32_t iterations;
     int32_t n_source;    /* points after voxel down-sampling */
     int32_t n_target;
-    int32_t reserved;
+    int32_t stage;       /* the ICP stage that finished it: 1 first team launch (relaunch included), 2 large team builds,
+                            3 sliced launches (LM_ICP_SLICED=1: all); 0 not registered */
 } lm_pose_result;
 
 int lm_pose_refine(int device, const uint16_t *scene_depth, const uint16_t *model_depth, int width, int height,

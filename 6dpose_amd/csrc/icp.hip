@@ -2142,7 +2142,7 @@ static __device__ __forceinline__ bool icp_eval_body(const IcpBuffers& B, IcpSta
             if (g == 0) { fit_hist[(it - 1) & 1] = fit; rmse_hist[(it - 1) & 1] = rmse; }
             if (g == 0) {
                 S.fitness = fit; S.rmse = rmse; S.n_corr = ncorr;
-                if (stop) S.stop = 1;
+                if (stop) { S.stop = 1; S.build = 0; }
             }
             s_stop = stop ? 1 : 0;
             if (!stop) {
@@ -3437,6 +3437,7 @@ k_icp_team(IcpBuffers B, unsigned int run, int shift_floor, double max_dist, int
         // diagnostics (shader cycles of wave 0 of member 0, which waits at the barriers for the other waves): exchange + finish, transform + queue, whole kernel, search, sums, evaluations, own searches, exchange alone
         S.clk[0] += s_clk[0]; S.clk[1] += s_clk[1]; S.clk[2] += (long long)__builtin_amdgcn_s_memtime() - t_begin; S.clk[3] += s_clk[2]; S.clk[4] += s_clk[3];
         S.clk[5] += s_clk[5]; S.clk[6] += s_clk[4]; S.clk[7] += s_clk[6];
+        S.build = KP * 4 + (SLAB ? 2 : 0) + (slabbed ? 1 : 0);       // (which build served it: lm_icp_read_debug kind 3)
         S.stop = (int)run;                                      // (the deal of a later workgroup of this launch still counts the hypothesis)
     }
 }

@@ -56,6 +56,7 @@ struct IcpState {            // one pose hypothesis (device-written, downloaded 
     int team_size;           // k_icp_team: workgroups at work on the hypothesis in the current launch
     int resume_it;           // k_icp_team: > 0 = the hypothesis was suspended after the finish stage of this evaluation index (T, fit_hist, rmse_hist hold what the next launch goes on from)
     int team_note[4];        // k_icp_team left the hypothesis to the sliced launches: reason (1 source slice too large, 2 grid, 3 slab overflow: + member, targets needed, capacity; 4 time-out), else 0
+    int build;               // the build that finished the hypothesis: k_icp_team<KP, SLAB> writes KP * 4 + SLAB * 2 + (the cloud was slabbed) — 4 <1,false>, 6 / 7 <1,true>, 10 / 11 <2,true>, 22 / 23 <5,true> —; k_icp_eval 0
     long long vox_clk[4];    // k_icp_voxel diagnostics (model cloud): cycles for the extent, the keys, the sort, the voxel means
     long long sort_clk[16];  // k_icp_voxel_wide (0-7, model cloud) / k_icp_grid_wide (8-15) diagnostics, slowest group per phase: cycles for picking its points, the sort, (voxels: count + wait for the groups before), writing, (grid: the column table); 6 / 13: largest group
     long long knn_clk[4];    // k_icp_knn diagnostics: slowest workgroup's cycles staging, in the 8-lane trips, in the whole-wave pass; points handed to whole waves

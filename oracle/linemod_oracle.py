@@ -884,16 +884,74 @@ def voxel_down_sample(pts: np.ndarray, voxel: float = VOXEL_SIZE) -> np.ndarray:
     return out
 
 
-def estimate_normals(pts: np.ndarray, knn: int = KNN) -> np.ndarray:
+_ROWS = 256                  # rows of a brute-force distance block: n x m x 3 at once is ~0.9 GB at 6k points
+
+
+def _sqdist(p: np.ndarray, q: np.ndarray) -> np.ndarray:
+    """Squared distances of the points p (r, 3) to q (m, 3): (dx^2 + dy^2) + dz^2, the one formula of every mode."""
+    d = (p[:, None, :] - q[None, :, :]) ** 2
+    return d[..., 0] + d[..., 1] + d[..., 2]
+
+
+def _knn_ordered(pts: np.ndarray, k: int, nn: str):
+    """For every point its k nearest points of the cloud (itself included), ordered by (d^2, index), as lists of indices.
+    nn="brute": the whole row of d^2 per point, in blocks of _ROWS rows; nn="kdtree": candidates from scipy's cKDTree, d^2
+    recomputed by _sqdist, the same order, and a query widened until its farthest candidate is strictly beyond the k-th."""
+    n = len(pts)
+    if nn == "brute":
+        for a in range(0, n, _ROWS):
+            d2 = _sqdist(pts[a:a + _ROWS], pts)
+            for r in range(len(d2)):
+                yield np.lexsort((np.arange(n), d2[r]))[:k]
+        return
+    if nn != "kdtree":
+        raise ValueError("nn must be 'brute' or 'kdtree'")
+    from scipy.spatial import cKDTree
+    yield from _kd_rows(cKDTree(pts), pts, pts, k)
+
+
+def _kd_take(tree, pts: np.ndarray, p: np.ndarray, k: int) -> np.ndarray:
+    """The k nearest of p by (d^2, index) with d^2 by _sqdist: exact whatever the rounding of the tree's own distances."""
+    n = len(pts)
+    q = min(n, 2 * k + 8)
+    while True:
+        dist, idx = tree.query(p, k=q)
+        idx = np.atleast_1d(idx)
+        d2 = _sqdist(p[None, :], pts[idx])[0]
+        order = np.lexsort((idx, d2))[:k]
+        if q >= n:
+            return idx[order]
+        # every point outside the candidates is at least as far as the farthest candidate (up to the tree's rounding)
+        far = float(np.atleast_1d(dist)[-1]) ** 2
+        if far * (1.0 - 1e-9) > d2[order[-1]]:
+            return idx[order]
+        q = min(n, 2 * q)
+
+
+def _kd_rows(tree, pts: np.ndarray, queries: np.ndarray, k: int):
+    """_kd_take for every row of `queries` (finite), one vectorised query for all and _kd_take for the rows it does not settle."""
+    n = len(pts)
+    q = min(n, 2 * k + 8)
+    dist, idx = tree.query(queries, k=q)
+    dist = dist.reshape(len(queries), q); idx = idx.reshape(len(queries), q)
+    d = (queries[:, None, :] - pts[idx]) ** 2
+    d2 = d[..., 0] + d[..., 1] + d[..., 2]                    # (_sqdist, element for element)
+    order = np.lexsort((idx, d2), axis=-1)[:, :k]
+    take = np.take_along_axis(idx, order, 1)
+    kth = np.take_along_axis(d2, order[:, -1:], 1)[:, 0]
+    settled = np.full(len(queries), True) if q >= n else dist[:, -1] ** 2 * (1.0 - 1e-9) > kth
+    for i in range(len(queries)):
+        yield take[i] if settled[i] else _kd_take(tree, pts, queries[i], k)
+
+
+def estimate_normals(pts: np.ndarray, knn: int = KNN, nn: str = "brute") -> np.ndarray:
     """open3d EstimateNormals(KDTreeSearchParamKNN(30)): eigenvector of the smallest eigenvalue of
-    the covariance (E[xx^T] - E[x]E[x]^T) of the k nearest neighbours (self included)."""
+    the covariance (E[xx^T] - E[x]E[x]^T) of the k nearest neighbours (self included).  nn: "brute" or the
+    exact "kdtree" mode (same neighbour lists in the same order, so bit-identical)."""
     n = len(pts)
     out = np.zeros((n, 3))
-    d2 = ((pts[:, None, :] - pts[None, :, :]) ** 2)
-    d2 = d2[..., 0] + d2[..., 1] + d2[..., 2]
     k = min(knn, n)
-    for i in range(n):
-        nb = np.lexsort((np.arange(n), d2[i]))[:k]
+    for i, nb in enumerate(_knn_ordered(pts, k, nn)):
         if k < 3:
             out[i] = (0, 0, 1)
             continue
@@ -905,6 +963,11 @@ def estimate_normals(pts: np.ndarray, knn: int = KNN) -> np.ndarray:
         nrm = v[:, 0]
         out[i] = nrm if np.linalg.norm(nrm) > 0 else (0, 0, 1)
     return out
+
+
+def knn_lists(pts: np.ndarray, knn: int = KNN, nn: str = "brute") -> np.ndarray:
+    """The ordered neighbour lists estimate_normals uses, (n, min(knn, n)) (tests compare the modes)."""
+    return np.array(list(_knn_ordered(pts, min(knn, len(pts)), nn)), np.int64).reshape(len(pts), min(knn, len(pts)))
 
 
 def _rot_xyz(x):
@@ -919,13 +982,37 @@ def _rot_xyz(x):
     return T
 
 
-def _icp_eval(src, tgt, nrm, max_dist):
+def nearest(src: np.ndarray, tgt: np.ndarray, nn: str = "brute", tree=None):
+    """Nearest target of every source point by (d^2, index), d^2 by _sqdist: (index, d^2).  "brute": blocks of _ROWS rows of the
+    full distance matrix (argmin: the first minimum); "kdtree": the exact candidate rule of _kd_take."""
+    j = np.zeros(len(src), np.int64)
+    best = np.zeros(len(src))
+    if nn == "brute":
+        for a in range(0, len(src), _ROWS):
+            d2 = _sqdist(src[a:a + _ROWS], tgt)
+            jj = d2.argmin(1)                                 # first minimum = lowest index on ties
+            j[a:a + len(jj)] = jj
+            best[a:a + len(jj)] = d2[np.arange(len(jj)), jj]
+        return j, best
+    if nn != "kdtree":
+        raise ValueError("nn must be 'brute' or 'kdtree'")
+    if tree is None:
+        from scipy.spatial import cKDTree
+        tree = cKDTree(tgt)
+    fin = np.all(np.isfinite(src), 1)
+    j[~fin], best[~fin] = 0, np.nan                           # (brute force: a row of NaN d^2 -> argmin 0, d^2 NaN)
+    rows = np.nonzero(fin)[0]
+    if len(rows):
+        j[rows] = np.fromiter((r[0] for r in _kd_rows(tree, tgt, src[rows], 1)), np.int64, len(rows))
+        d = (src[rows] - tgt[j[rows]]) ** 2
+        best[rows] = d[:, 0] + d[:, 1] + d[:, 2]
+    return j, best
+
+
+def _icp_eval(src, tgt, nrm, max_dist, nn="brute", tree=None):
     """GetRegistrationResultAndCorrespondences + the JtJ/Jtr accumulation of
     TransformationEstimationPointToPlane::ComputeTransformation for the same correspondences."""
-    d2 = ((src[:, None, :] - tgt[None, :, :]) ** 2)
-    d2 = d2[..., 0] + d2[..., 1] + d2[..., 2]
-    j = d2.argmin(1)                                          # first minimum = lowest index on ties
-    best = d2[np.arange(len(src)), j]
+    j, best = nearest(src, tgt, nn, tree)
     ok = best < max_dist * max_dist
     n = int(ok.sum())
     if n == 0:
@@ -940,11 +1027,27 @@ def _icp_eval(src, tgt, nrm, max_dist):
     return fitness, rmse, n, JTJ, JTr
 
 
-def icp_point_to_plane(src, tgt, tgt_normals, init, max_dist=ICP_MAX_DIST, max_iter=ICP_MAX_ITER):
-    """open3d RegistrationICP(source, target, max_dist, init, PointToPlane, default criteria)."""
+def _eig_ratio(JTJ) -> float:
+    """Smallest / largest eigenvalue of JtJ (0 without correspondences): how well the 6 degrees of freedom are pinned."""
+    if JTJ is None:
+        return 0.0
+    w = np.linalg.eigvalsh(JTJ)
+    return float(w[0] / w[-1]) if w[-1] > 0 else 0.0
+
+
+def icp_point_to_plane(src, tgt, tgt_normals, init, max_dist=ICP_MAX_DIST, max_iter=ICP_MAX_ITER, nn="brute", history=None):
+    """open3d RegistrationICP(source, target, max_dist, init, PointToPlane, default criteria).
+    history: a list that receives one dict per evaluation (fitness, rmse, eig_ratio of its JtJ) — the evidence tests judge
+    well-posedness by."""
     T = np.array(init, np.float64)
+    tree = None
+    if nn == "kdtree":
+        from scipy.spatial import cKDTree
+        tree = cKDTree(tgt)
     pts = src @ T[:3, :3].T + T[:3, 3]
-    fit, rmse, n, JTJ, JTr = _icp_eval(pts, tgt, tgt_normals, max_dist)
+    fit, rmse, n, JTJ, JTr = _icp_eval(pts, tgt, tgt_normals, max_dist, nn, tree)
+    if history is not None:
+        history.append({"fitness": fit, "rmse": rmse, "eig_ratio": _eig_ratio(JTJ)})
     iters = 0
     for _ in range(max_iter):
         iters += 1
@@ -959,15 +1062,32 @@ def icp_point_to_plane(src, tgt, tgt_normals, init, max_dist=ICP_MAX_DIST, max_i
         T = upd @ T
         pts = pts @ upd[:3, :3].T + upd[:3, 3]
         bfit, brmse = fit, rmse
-        fit, rmse, n, JTJ, JTr = _icp_eval(pts, tgt, tgt_normals, max_dist)
+        fit, rmse, n, JTJ, JTr = _icp_eval(pts, tgt, tgt_normals, max_dist, nn, tree)
+        if history is not None:
+            history.append({"fitness": fit, "rmse": rmse, "eig_ratio": _eig_ratio(JTJ)})
         if abs(bfit - fit) < ICP_REL and abs(brmse - rmse) < ICP_REL:
             break
     return T, fit, rmse, iters
 
 
+def ill_posed(history, rel=ICP_REL) -> str:
+    """Why an ICP run is ill-posed on the oracle's own evidence ('' when well-posed): a convergence test within 1e-9 of
+    its threshold at some evaluation (another rounding may stop one evaluation earlier or later), or a final JtJ with an
+    eigenvalue ratio below 1e-8 (a direction the correspondences do not pin)."""
+    for e in range(1, len(history)):
+        for key in ("fitness", "rmse"):
+            d = abs(history[e - 1][key] - history[e][key])
+            if abs(d - rel) < 1e-9:
+                return "convergence test of %s at evaluation %d within 1e-9 of the threshold (%.3g)" % (key, e, d)
+    if history and history[-1]["eig_ratio"] < 1e-8:
+        return "final JtJ eigenvalue ratio %.3g" % history[-1]["eig_ratio"]
+    return ""
+
+
 def pose_refine(scene_depth, model_depth, sceneK, modelK, modelR, modelT, detect_x, detect_y,
-                scene_from_scene: bool = False):
-    """poseRefine::process (LL.cpp:27-155).  Returns dict(R (3,3) f64, t (3,) f64 mm, residual, ...)."""
+                scene_from_scene: bool = False, nn: str = "brute"):
+    """poseRefine::process (LL.cpp:27-155).  Returns dict(R (3,3) f64, t (3,) f64 mm, residual, ...; history: per evaluation).
+    nn: "brute" or the exact "kdtree" mode (bit-identical, for large clouds)."""
     init_base = np.zeros((4, 4), f32)
     init_base[:3, :3] = np.asarray(modelR, f32).reshape(3, 3)
     init_base[:3, 3] = np.asarray(modelT, f32).reshape(3)
@@ -981,9 +1101,10 @@ def pose_refine(scene_depth, model_depth, sceneK, modelK, modelR, modelT, detect
     init_guess[:3, 3] = tr
     src = voxel_down_sample(model_pts)
     tgt = voxel_down_sample(scene_pts if scene_from_scene else model_pts)   # LL.cpp:109 (sic: model)
-    nrm = estimate_normals(tgt)
-    T, fit, rmse, iters = icp_point_to_plane(src, tgt, nrm, init_guess)
+    nrm = estimate_normals(tgt, nn=nn)
+    history = []
+    T, fit, rmse, iters = icp_point_to_plane(src, tgt, nrm, init_guess, nn=nn, history=history)
     result = T @ init_base.astype(np.float64)
     return {"residual": float(f32(fit)), "R": result[:3, :3].copy(), "t": result[:3, 3] * 1000.0,
             "T_icp": T, "rmse": rmse, "iterations": iters, "n_source": len(src), "n_target": len(tgt),
-            "src": src, "tgt": tgt, "normals": nrm, "init_guess": init_guess}
+            "src": src, "tgt": tgt, "normals": nrm, "init_guess": init_guess, "history": history}

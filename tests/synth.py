@@ -115,10 +115,11 @@ def make_random_bank(seed: int, n: int, W: int = 640, H: int = 480, nfeat: Seque
 
 
 def make_planted_bank(seed: int, n: int, quant_pyr: Sequence[Tuple[np.ndarray, np.ndarray]], T: Sequence[int],
-                      nfeat: Sequence[int] = (150, 75), label_noise: float = 0.12):
+                      nfeat: Sequence[int] = (150, 75), label_noise: float = 0.12, windows=None):
     """n template pyramids cut out of the frame's quantised maps.  quant_pyr[l] = (colour u8 one-hot
     HxW, normal u8 one-hot HxW) at level l (from the GPU front end or from the oracle — they are
-    bit-identical).  A fraction `label_noise` of the labels is re-drawn uniformly."""
+    bit-identical).  A fraction `label_noise` of the labels is re-drawn uniformly.  windows: n boxes
+    (x0, y0, w, h) at level 0 to cut template i from (x0, y0 rounded down to even), instead of random ones."""
     rng = np.random.default_rng(seed)
     H0, W0 = quant_pyr[0][0].shape
     scale = W0 / 640.0
@@ -130,9 +131,13 @@ def make_planted_bank(seed: int, n: int, quant_pyr: Sequence[Tuple[np.ndarray, n
         guard += 1
         if guard > 50 * n + 1000:
             raise RuntimeError("could not plant templates: quantised maps too sparse")
-        w, h = int(rng.integers(40, 131) * scale), int(rng.integers(50, 146) * scale)
-        x0 = int(rng.integers(border, max(border + 1, W0 - w - border))) & ~1
-        y0 = int(rng.integers(border, max(border + 1, H0 - h - border))) & ~1
+        if windows is not None:
+            x0, y0, w, h = (int(v) for v in windows[len(all_wh) // (2 * len(nfeat))])
+            x0, y0 = x0 & ~1, y0 & ~1
+        else:
+            w, h = int(rng.integers(40, 131) * scale), int(rng.integers(50, 146) * scale)
+            x0 = int(rng.integers(border, max(border + 1, W0 - w - border))) & ~1
+            y0 = int(rng.integers(border, max(border + 1, H0 - h - border))) & ~1
         lv, ok = [], True
         for l, nf in enumerate(nfeat):
             xl, yl, wl, hl = x0 >> l, y0 >> l, max(2, w >> l), max(2, h >> l)

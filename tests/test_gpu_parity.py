@@ -8,7 +8,7 @@ import pytest
 
 import linemod_oracle as lo
 import synth
-from helpers import GOLDEN, load_bgr, load_gray, load_u16
+from helpers import DBG3_RESUME_IT, GOLDEN, K_CAM, load_bgr, load_gray, load_u16, oracle_matches, pipeline_oracle
 
 pytestmark = pytest.mark.gpu
 
@@ -22,15 +22,6 @@ def lm():
     lib = mod.load_library()
     assert lib.lm_device_count() >= 1, "GPU tests need a visible MI355X (no CPU fallback)"
     return mod
-
-
-def oracle_matches(od, rgb, dep, bank_arrays, T, thr, cls=0):
-    feat, offs, wh = bank_arrays
-    lms, sizes = od.linear_memories(rgb, dep)
-    P = (len(offs) - 1) // (2 * len(T))
-    raw, st = lo.match_bank_c(lo.PackedBank(P, len(T), feat, offs, wh), lms, sizes, T, thr)
-    raw["cls"] = cls
-    return raw, st
 
 
 def same_records(got, want):
@@ -1218,7 +1209,6 @@ def test_packed_bank_file_round_trip(lm, tmp_path):
 # ---------------------------------------------------------------------------------------------
 # poseRefine / ICP  (parity unpinned by the reference: GPU vs the oracle's Open3D restatement)
 # ---------------------------------------------------------------------------------------------
-K_CAM = np.array([572.4114, 0, 325.2611, 0, 573.57043, 242.04899, 0, 0, 1], np.float32).reshape(3, 3)
 
 
 def _perturbed_scene(md, K, rot_deg, t_mm, seed):
@@ -1506,7 +1496,7 @@ def test_icp_more_hypotheses_than_the_kernel_deals_out(lm, n):
     if n == 72:                                                   # (the builds with two and five points per thread are part of the first stage here)
         assert all(1 <= g["stage"] <= 2 for g in got)
     else:                                                         # the cut and the second launch: stage 1, resumed from IcpState
-        assert all(g["stage"] == 1 for g in got) and max(ctx.read_debug(h, 3)[-1] for h in range(n)) > 0
+        assert all(g["stage"] == 1 for g in got) and max(ctx.read_debug(h, 3)[DBG3_RESUME_IT] for h in range(n)) > 0
     for b in range(0, n, 8):
         want, _ = ctx.run(Ks[b:b + 8], Rs[b:b + 8], ts[b:b + 8], xy[b:b + 8], model_slots=slots[b:b + 8])
         for g, w in zip(got[b:b + 8], want):
@@ -1561,24 +1551,6 @@ def _pipeline_reference(mod, det, rgb, dep, wh, E, views, thr, top_k, iou, box=N
     xy = [(int(r["x"]), int(r["y"])) for r in sel]
     poses, _ = mod.pose_refine_batch(dep, K_CAM, mds, Ks, Rs, ts, xy, device=0, scene_from_scene=True)
     return sel, poses, len(m)
-
-
-def _pipeline_oracle(od, rgb, dep, bank, T, wh, E, views, thr, top_k, iou, box=None):
-    """The same driver loop on the CPU ORACLE only (nothing of the product): match_oracle.c -> canonical sort/unique ->
-    numpy nms (the driver's own function) -> oracle poseRefine per kept match."""
-    raw, _ = oracle_matches(od, rgb, dep, bank, T, thr)
-    m = lo.canonical_sort_unique(raw)
-    dets = np.zeros((len(m), 5))
-    for i, r in enumerate(m):
-        w, h = wh[int(r["tid"]) * E] if box is None else box[int(r["tid"])]
-        dets[i] = (r["x"], r["y"], r["x"] + w, r["y"] + h, r["sim"])
-    keep = lo.nms_boxes(dets, iou, stable=True)[:top_k] if len(m) else []      # planted templates tie in score
-    sel = [m[i] for i in keep]
-    poses = []
-    for r in sel:
-        md, K, R, t = views[int(r["tid"])]
-        poses.append(lo.pose_refine(dep, md, K_CAM, K, R, t, int(r["x"]), int(r["y"]), scene_from_scene=True))
-    return sel, poses
 
 
 @pytest.mark.parametrize("dup", [False, True])
@@ -1639,7 +1611,7 @@ def test_pipeline_equals_match_nms_pose_refine(lm, dup):
                 assert [(g["x"], g["y"], g["template_id"]) for g in got_n] == [(posed[i]["x"], posed[i]["y"], posed[i]["template_id"]) for i in keep]
             assert 1 <= len(got_n) <= len(posed)
         # ... and against the ORACLE's own chain (no product call on the expected side): detections exact, poses to 1e-4
-        osel, oposes = _pipeline_oracle(od, rgb, dep, (feat, offs, wh), T, wh, E, views, thr, top_k, 0.5, box)
+        osel, oposes = pipeline_oracle(od, rgb, dep, (feat, offs, wh), T, wh, E, views, thr, top_k, 0.5, box)
         assert len(got) == len(osel)
         for g, r, p in zip(got, osel, oposes):
             assert (g["x"], g["y"], g["template_id"], g["similarity"]) == (int(r["x"]), int(r["y"]), int(r["tid"]), float(r["sim"]))

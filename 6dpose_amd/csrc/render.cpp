@@ -50,7 +50,7 @@ extern "C" void lm_mesh_destroy(lm_mesh* m) {
     if (!m) return;
     (void)hipSetDevice(m->device);
     if (m->s) (void)hipStreamSynchronize(m->s);
-    void* p[] = {m->d_v, m->d_n, m->d_c, m->d_f, m->d_views, m->d_pv, m->d_zbuf, m->d_depth, m->d_rgb};
+    void* p[] = {m->d_v, m->d_n, m->d_c, m->d_f, m->d_views, m->d_pv, m->d_zbuf, m->d_depth, m->d_rgb, m->d_scene, m->d_pe_pairs, m->d_pe_partial};
     for (void* q : p) if (q) (void)hipFree(q);
     if (m->s) (void)hipStreamDestroy(m->s);
     delete m;

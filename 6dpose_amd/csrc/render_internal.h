@@ -29,6 +29,11 @@ struct lm_mesh {
     uint8_t* d_rgb = nullptr;
     size_t cap_views = 0, cap_pv = 0, cap_zbuf = 0, cap_depth = 0, cap_rgb = 0;
     int last_W = 0, last_H = 0, last_count = 0;
+    // pose-error scratch (pose_error.cpp): resident scene depth, pair parameters, per-block partials
+    float* d_scene = nullptr;
+    void* d_pe_pairs = nullptr;
+    void* d_pe_partial = nullptr;
+    size_t cap_scene = 0, cap_pe_pairs = 0, cap_pe_partial = 0;
 };
 
 // Renders `count` views into the mesh's device buffers (d_depth [count][H][W], d_rgb [count][H][W][3]) on m->s; no host copy.

@@ -37,7 +37,8 @@ from typing import List, Optional, Sequence
 
 import numpy as np
 
-__all__ = ["Detector", "Match", "poseRefine", "IcpContext", "Pipeline", "Mesh", "Template", "library_path", "load_library", "nms"]
+__all__ = ["Detector", "Match", "poseRefine", "IcpContext", "Pipeline", "Mesh", "Template", "library_path", "load_library", "nms",
+           "pose_errors", "gt_stats"]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB_NAME = "libamdlinemod.so"
@@ -234,6 +235,10 @@ def load_library():
     lib.lm_mesh_render.argtypes = [P, I, I, I, P, P, P, F, F, F, I, P, P]
     lib.lm_detector_add_templates_rendered.argtypes = [P, P, S, I, I, I, P, P, P, F, F, F, I, P, P]
     lib.lm_pipeline_set_views_rendered.argtypes = [P, P, S, I, I, P, P, P, F, F, P]
+    D = ctypes.c_double
+    lib.lm_mesh_pose_errors.argtypes = [P, I, P, P, I, P, P, P, I, I, P, I, D, D, I, D, D, P]
+    lib.lm_mesh_gt_stats.argtypes = [P, I, P, P, P, I, I, P, D, D, D, P, P, P, P]
+    lib.lm_mesh_diameter.argtypes = [P, ctypes.POINTER(D)]
     lib.lm_pipeline_create.argtypes = [P, I, I, ctypes.POINTER(P)]
     lib.lm_pipeline_destroy.argtypes = [P]
     lib.lm_pipeline_destroy.restype = None
@@ -1090,6 +1095,12 @@ class Mesh:
             return rgb
         return rgb, depth
 
+    def diameter(self) -> float:
+        """misc.calc_pts_diameter: the largest vertex-to-vertex distance (mm), on the device (k_pose_pts)."""
+        d = ctypes.c_double()
+        _check(self._lib.lm_mesh_diameter(self._h, ctypes.byref(d)))
+        return d.value
+
 
 def add_templates_rendered(detector: "Detector", mesh: Mesh, class_id: str, im_size, Ks, Rs, ts, clip_near=10.0, clip_far=10000.0,
                            ambient_weight=0.8, ssaa=4):
@@ -1102,3 +1113,78 @@ def add_templates_rendered(detector: "Detector", mesh: Mesh, class_id: str, im_s
                                                              _ptr(Rs), _ptr(ts), float(clip_near), float(clip_far), float(ambient_weight), int(ssaa),
                                                              _ptr(ids), _ptr(wh)))
     return ids, wh
+
+
+POSE_METRICS = ("vsd", "cou", "add", "adi", "re", "te")           # bit i of lm_mesh_pose_errors' mask = POSE_METRICS[i]
+
+
+def _pose_batch(R, t, what):
+    R = np.asarray(R, np.float64)
+    t = np.asarray(t, np.float64)
+    if R.shape == (3, 3):
+        R, t = R.reshape(1, 3, 3), t.reshape(1, 3)
+    if R.ndim != 3 or R.shape[1:] != (3, 3) or t.size != 3 * len(R):
+        raise ValueError("%s: R must be (3,3) or (n,3,3) and t (3,) or (n,3), got %s and %s" % (what, R.shape, t.shape))
+    return np.ascontiguousarray(R.reshape(-1, 9)), np.ascontiguousarray(t.reshape(-1, 3))
+
+
+def _scene_mm(scene_depth):
+    """Scene depth in mm as float32 (load_depth * depth_scale); uint16 is converted exactly."""
+    d = np.asarray(scene_depth)
+    if d.ndim != 2:
+        raise ValueError("scene_depth must be a (H, W) image")
+    if d.dtype not in (np.float32, np.uint16):
+        raise ValueError("scene_depth must be float32 (mm) or uint16 (mm), got %s" % d.dtype)
+    return np.ascontiguousarray(d, np.float32)
+
+
+def pose_errors(mesh: Mesh, R_est, t_est, R_gt, t_gt, K=None, scene_depth=None, metrics=POSE_METRICS, delta=15.0, tau=20.0, cost="step",
+                clip_near=100.0, clip_far=10000.0, im_size=None):
+    """pysixd.pose_error (vsd, cou, add, adi, re, te) for E estimates x G ground truths of one object in one frame, on the device
+    (lm_mesh_pose_errors).  Returns {metric: (E, G) float64}.  A single pose (3x3, 3) is a batch of one.  vsd needs scene_depth
+    (H, W); cou needs K and the image size, taken from scene_depth or im_size = (width, height) (pose_error.cou's im_size).
+    Defaults: the SIXD-17 settings of eval_calc_errors.py:40-42 and pysixd's clip planes for vsd / cou (pose_error.py:35-39)."""
+    Re, te = _pose_batch(R_est, t_est, "estimate")
+    Rg, tg = _pose_batch(R_gt, t_gt, "ground truth")
+    if isinstance(metrics, str):
+        metrics = (metrics,)
+    mask = 0
+    for name in metrics:
+        if name not in POSE_METRICS:
+            raise ValueError("unknown metric %r (one of %s)" % (name, ", ".join(POSE_METRICS)))
+        mask |= 1 << POSE_METRICS.index(name)
+    if cost not in ("step", "tlinear"):
+        raise ValueError("unknown vsd cost %r (step or tlinear)" % (cost,))
+    scene = None if scene_depth is None else _scene_mm(scene_depth)
+    if scene is not None:
+        W, H = scene.shape[1], scene.shape[0]
+        if im_size is not None and (int(im_size[0]), int(im_size[1])) != (W, H):
+            raise ValueError("im_size %s does not match scene_depth %s" % (tuple(im_size), scene.shape))
+    elif im_size is not None:
+        W, H = int(im_size[0]), int(im_size[1])
+    else:
+        W = H = 0
+    Kd = None if K is None else np.ascontiguousarray(np.asarray(K, np.float64).reshape(9))
+    order = [n for n in POSE_METRICS if mask >> POSE_METRICS.index(n) & 1]
+    out = np.zeros((len(order), len(Re), len(Rg)), np.float64)
+    _check(load_library().lm_mesh_pose_errors(mesh._h, len(Re), _ptr(Re), _ptr(te), len(Rg), _ptr(Rg), _ptr(tg), _ptr(Kd), W, H, _ptr(scene),
+                                              mask, float(delta), float(tau), 0 if cost == "step" else 1, float(clip_near), float(clip_far),
+                                              _ptr(out)))
+    return {n: out[i] for i, n in enumerate(order)}
+
+
+def gt_stats(mesh: Mesh, R_gt, t_gt, K, scene_depth, delta=15.0, clip_near=100.0, clip_far=2000.0):
+    """tools/calc_gt_stats.py:103-155 for each GT pose on the device (lm_mesh_gt_stats): a list of dicts with px_count_all,
+    px_count_visib, px_count_valid, visib_fract, bbox_obj and bbox_visib.  Clip planes: renderer.render's defaults."""
+    Rg, tg = _pose_batch(R_gt, t_gt, "ground truth")
+    scene = _scene_mm(scene_depth)
+    Kd = np.ascontiguousarray(np.asarray(K, np.float64).reshape(9))
+    n = len(Rg)
+    counts = np.zeros((n, 3), np.int64)
+    fract = np.zeros(n, np.float64)
+    bo = np.zeros((n, 4), np.int32)
+    bv = np.zeros((n, 4), np.int32)
+    _check(load_library().lm_mesh_gt_stats(mesh._h, n, _ptr(Rg), _ptr(tg), _ptr(Kd), scene.shape[1], scene.shape[0], _ptr(scene), float(delta),
+                                           float(clip_near), float(clip_far), _ptr(counts), _ptr(fract), _ptr(bo), _ptr(bv)))
+    return [{"px_count_all": int(counts[i, 0]), "px_count_visib": int(counts[i, 2]), "px_count_valid": int(counts[i, 1]),
+             "visib_fract": float(fract[i]), "bbox_obj": [int(e) for e in bo[i]], "bbox_visib": [int(e) for e in bv[i]]} for i in range(n)]

@@ -460,6 +460,34 @@ int lm_pipeline_set_views_rendered(lm_pipeline *p, lm_mesh *m, const char *class
                                    const float *Ks, const float *Rs, const float *ts, float clip_near, float clip_far,
                                    const int32_t *box_wh);
 
+/* ---- pose errors (pysixd/pose_error.py, tools/eval_calc_errors.py:142-178, tools/calc_gt_stats.py:103-155) ----------
+ * The batch E estimates x G ground truths of one object in one frame.  Poses: R [n][9] row-major f64, t [n][3] f64 (mm);
+ * K [9] f64.  Renders use R, t and K cast to float32 and the rasteriser of lm_mesh_render (float32 eye depth read from
+ * its z-buffer, not the truncated uint16 image); distance images, visibility and costs follow pysixd (DESIGN.md,
+ * "Pose errors").  scene_depth: float32 [height][width] in mm (load_depth * depth_scale). */
+#define LM_POSE_VSD 1   /* needs scene_depth, K, width, height; delta, tau, cost */
+#define LM_POSE_COU 2   /* needs K, width, height */
+#define LM_POSE_ADD 4
+#define LM_POSE_ADI 8
+#define LM_POSE_RE 16
+#define LM_POSE_TE 32
+#define LM_POSE_COST_STEP 0
+#define LM_POSE_COST_TLINEAR 1
+/* out: f64 [n_metrics][n_est][n_gt], the requested metrics in the order of their bits (VSD, COU, ADD, ADI, RE, TE).
+ * VSD without scene_depth -> LM_ERR_INVALID.  n_est == 0 or n_gt == 0 writes nothing.  pysixd renders with
+ * clip_near = 100, clip_far = 10000 for VSD and COU (pose_error.py:35-39). */
+int lm_mesh_pose_errors(lm_mesh *m, int n_est, const double *R_est, const double *t_est, int n_gt, const double *R_gt,
+                        const double *t_gt, const double *K, int width, int height, const float *scene_depth, int metrics,
+                        double delta, double tau, int cost, double clip_near, double clip_far, double *out);
+/* calc_gt_stats.py:103-155 for each GT pose: counts [n_gt][3] = px_count_all, px_count_valid, px_count_visib;
+ * visib_fract [n_gt]; bbox_obj, bbox_visib [n_gt][4] = x, y, w, h (misc.calc_2d_bbox; -1s when nothing is visible).
+ * pysixd renders with its defaults clip_near = 100, clip_far = 2000 here (renderer.py:306). */
+int lm_mesh_gt_stats(lm_mesh *m, int n_gt, const double *R_gt, const double *t_gt, const double *K, int width, int height,
+                     const float *scene_depth, double delta, double clip_near, double clip_far, int64_t *counts,
+                     double *visib_fract, int32_t *bbox_obj, int32_t *bbox_visib);
+/* misc.calc_pts_diameter: the largest vertex-to-vertex distance (mm). */
+int lm_mesh_diameter(lm_mesh *m, double *diameter);
+
 #ifdef __cplusplus
 }
 #endif

@@ -155,7 +155,7 @@ static __device__ __forceinline__ int nms_rounds(RecPtr rec, const int m, const 
             __syncthreads();
             continue;
         }
-        // (3) keep R, suppress what overlaps it (R itself has IoU 1)
+        // (3) keep R, retire it, suppress what overlaps it (R itself has IoU 1: at thresh >= 1 that alone does not retire it)
         const double x1 = (double)R.x, y1 = (double)R.y;
         const double x2 = x1 + (double)(rr.y & 0xFFFF), y2 = y1 + (double)((uint32_t)rr.y >> 16);
         const double ai = (x2 - x1 + 1) * (y2 - y1 + 1);
@@ -169,7 +169,7 @@ static __device__ __forceinline__ int nms_rounds(RecPtr rec, const int m, const 
             const double inter = w * h;
             const double aj = (bx2 - bx1 + 1) * (by2 - by1 + 1);
             const double ovr = __ddiv_rn(inter, ai + aj - inter);
-            if (!(ovr <= thresh)) rec[i].w = r.w | (int)0x80000000;
+            if (i == R.slot || !(ovr <= thresh)) rec[i].w = r.w | (int)0x80000000;
         }
         if (tid == 0) {
             TopkSel o;
@@ -251,16 +251,16 @@ k_topk_nms(int top_k, double thresh, int4* __restrict__ rec, const uint32_t* __r
     __shared__ int4 s_rec[kNmsLds];
     __shared__ Key128 s_keys[kNmsWG / 64];
     const int tid = threadIdx.x;
+    const int m = (int)(ctr[0] + 1u);                                              // distinct records packed (nsel_status[2]: the host reports it)
     if (ctr[1] == 0) {                                                             // a field does not fit the packed record
-        if (tid == 0) { nsel_status[0] = 0; nsel_status[1] = 1; }
+        if (tid == 0) { nsel_status[0] = 0; nsel_status[1] = 1; nsel_status[2] = m; }
         return;
     }
-    const int m = (int)(ctr[0] + 1u);
     if (m <= kNmsLds)
         for (int i = tid; i < m; i += kNmsWG) s_rec[i] = rec[i];
     __syncthreads();
     const int kept = m <= kNmsLds ? nms_rounds(s_rec, m, top_k, thresh, s_keys, sel) : nms_rounds(rec, m, top_k, thresh, s_keys, sel);
-    if (tid == 0) { nsel_status[0] = kept; nsel_status[1] = 0; }
+    if (tid == 0) { nsel_status[0] = kept; nsel_status[1] = 0; nsel_status[2] = m; }
 }
 
 void launch_topk_nms(const Candidate* matches_dev, const unsigned long long* counters, uint32_t cap, const int32_t* work_pyramids,

@@ -201,8 +201,8 @@ static int ensure_run_buffers(lm_pipeline* p, int top_k, int num_classes) {
         p->sel_cap = top_k;
     }
     if (!p->d_nsel) {
-        HIP_TRY(hipMalloc((void**)&p->d_nsel, 2 * sizeof(int32_t)));
-        HIP_TRY(hipHostMalloc((void**)&p->h_nsel, 2 * sizeof(int32_t), hipHostMallocDefault));
+        HIP_TRY(hipMalloc((void**)&p->d_nsel, 4 * sizeof(int32_t)));             // kept, refused, distinct records, (pad)
+        HIP_TRY(hipHostMalloc((void**)&p->h_nsel, 4 * sizeof(int32_t), hipHostMallocDefault));
     }
     if (num_classes > p->class_cap) {
         if (p->d_class_base) (void)hipFree(p->d_class_base);
@@ -268,7 +268,7 @@ extern "C" int lm_pipeline_run(lm_pipeline* p, float threshold, const char* cons
         // (k_icp_bind only binds views that were uploaded, and both upload paths work out the boxes: 0x100 = no k_icp_bbox)
         if ((rc = lm_icp_enqueue(c, B, (flags & 0xFF) | 0x100, c->h_st, s))) return rc;
         HIP_TRY(hipMemcpyAsync(p->h_sel, p->d_sel, (size_t)top_k * sizeof(TopkSel), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(p->h_nsel, p->d_nsel, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(p->h_nsel, p->d_nsel, 3 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
         HIP_TRY(hipGetLastError());
         rc = lm_collect_frame(d, -1, nullptr, nullptr);          // retires the frame; 1 = candidate buffer overflow, rerun
@@ -315,6 +315,7 @@ extern "C" int lm_pipeline_run(lm_pipeline* p, float threshold, const char* cons
         int its = 0;
         for (int i = 0; i < n; ++i) if (c->h_st[i].status == 0) its += c->h_st[i].iterations;
         tm->icp_iterations = its;
+        tm->nms_records = p->h_nsel[2];
     }
     return LM_OK;
 }

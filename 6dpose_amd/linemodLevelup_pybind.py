@@ -90,10 +90,10 @@ class PipelineTimings(ctypes.Structure):
     """lm_pipeline_timings (include/amd_linemod.h)."""
     _fields_ = [("match_ms", ctypes.c_float), ("nms_ms", ctypes.c_float), ("icp_ms", ctypes.c_float), ("total_ms", ctypes.c_float),
                 ("coarse_candidates", ctypes.c_int64), ("matches_pre_unique", ctypes.c_int64), ("icp_iterations", ctypes.c_int32),
-                ("reserved", ctypes.c_int32)]
+                ("nms_records", ctypes.c_int32)]
 
     def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 MATCH_DTYPE = np.dtype([("x", np.int32), ("y", np.int32), ("similarity", np.float32),

@@ -416,7 +416,8 @@ typedef struct lm_detection {
 typedef struct lm_pipeline_timings {
     float match_ms, nms_ms, icp_ms, total_ms;   /* HIP events on the detector's stream */
     int64_t coarse_candidates, matches_pre_unique;
-    int32_t icp_iterations, reserved;
+    int32_t icp_iterations;
+    int32_t nms_records;     /* distinct (x, y, template, class) records the on-device NMS ran over; > 8192: they stayed in HBM, else in LDS */
 } lm_pipeline_timings;
 int lm_pipeline_create(lm_detector *det, int width, int height, lm_pipeline **out);
 void lm_pipeline_destroy(lm_pipeline *p);

@@ -181,6 +181,25 @@ def synth_model_depth(seed: int, W: int = 640, H: int = 480, z0: float = 1000.0)
     return np.where(r2 < 1, depth, 0).astype(np.uint16)
 
 
+def bump(seed, a, b, z0=1000.0, amp=60.0, stripes=False, centre=(0.0, 0.0), W=640, H=480):
+    """A rendered-object stand-in (the shape of synth.synth_model_depth) with chosen half axes in pixels: an ellipsoidal cap
+    with ripples, centred in the image (the reference's anchor pixel lies on it unless `centre` moves it).  stripes: zero
+    depth in three of every six columns (holes narrower than the 4-pixel dilation of the mask: the scene window keeps the
+    whole surface, the model about half of it); the centre column stays."""
+    rng = np.random.default_rng(seed)
+    yy, xx = np.mgrid[0:H, 0:W].astype(np.float64)
+    cx, cy = W / 2 + centre[0] + rng.uniform(-3, 3), H / 2 + centre[1] + rng.uniform(-3, 3)
+    th = rng.uniform(0, np.pi)
+    u = (xx - cx) * np.cos(th) + (yy - cy) * np.sin(th)
+    v = -(xx - cx) * np.sin(th) + (yy - cy) * np.cos(th)
+    r2 = (u / a) ** 2 + (v / b) ** 2
+    depth = z0 - amp * np.sqrt(np.clip(1 - r2, 0, None)) + 8.0 * np.sin(u / 5.0) * np.cos(v / 7.0) * (r2 < 1)
+    inside = r2 < 1
+    if stripes:
+        inside &= ((xx.astype(np.int64) - W // 2) % 6) < 3
+    return np.where(inside, depth, 0).astype(np.uint16)
+
+
 def icosphere(level: int = 2, radius: float = 60.0, seed: int = 0):
     """A bumpy blob for the rasteriser tests / training benchmark: refined icosahedron (20 * 4**level triangles) with
     vertex normals and random vertex colours.  Returns (vertices f32 (n,3) mm, faces i32 (m,3), normals f32, colours u8)."""

@@ -21,6 +21,7 @@ import pytest
 
 import linemod_oracle as lo
 import synth
+from synth import bump
 from helpers import DBG3_BUILD, DBG3_RESUME_IT, DBG3_TEAM_NOTE, DBG3_TEAM_SIZE, K_CAM, h16, pipeline_oracle
 
 pytestmark = pytest.mark.gpu
@@ -43,25 +44,6 @@ BUILD_NAMES = {0: "sliced", 4: "<1,false>", 6: "<1,true> whole", 7: "<1,true> sl
 
 
 # ---- inputs --------------------------------------------------------------------------------------
-def bump(seed, a, b, z0=1000.0, amp=60.0, stripes=False, centre=(0.0, 0.0)):
-    """A rendered-object stand-in (the shape of synth.synth_model_depth) with chosen half axes in pixels: an ellipsoidal cap
-    with ripples, centred in the image (the reference's anchor pixel lies on it unless `centre` moves it).  stripes: zero
-    depth in three of every six columns (holes narrower than the 4-pixel dilation of the mask: the scene window keeps the
-    whole surface, the model about half of it); the centre column stays."""
-    rng = np.random.default_rng(seed)
-    yy, xx = np.mgrid[0:H, 0:W].astype(np.float64)
-    cx, cy = W / 2 + centre[0] + rng.uniform(-3, 3), H / 2 + centre[1] + rng.uniform(-3, 3)
-    th = rng.uniform(0, np.pi)
-    u = (xx - cx) * np.cos(th) + (yy - cy) * np.sin(th)
-    v = -(xx - cx) * np.sin(th) + (yy - cy) * np.cos(th)
-    r2 = (u / a) ** 2 + (v / b) ** 2
-    depth = z0 - amp * np.sqrt(np.clip(1 - r2, 0, None)) + 8.0 * np.sin(u / 5.0) * np.cos(v / 7.0) * (r2 < 1)
-    inside = r2 < 1
-    if stripes:
-        inside &= ((xx.astype(np.int64) - W // 2) % 6) < 3
-    return np.where(inside, depth, 0).astype(np.uint16)
-
-
 def surface(half_w, half_h, z0=2000.0):
     """A large curved, rippled depth patch (every pixel its own voxel at 2 m): a registration no sliding can satisfy."""
     yy, xx = np.mgrid[0:H, 0:W].astype(np.float64)

@@ -1,4 +1,5 @@
-// Internal interface between pose_refine.cpp (host) and icp.hip (kernels).  gfx950 only.
+// Internal interface between pose_refine.cpp / pipeline.cpp (host) and the ICP kernels: icp_clouds.hip (hypotheses, boxes,
+// back-projection), icp.hip (voxel down-sampling, search grid, kNN normals), icp_eval.hip and icp_team.hip (RegistrationICP).  gfx950 only.
 // The whole of poseRefine::process (LL.cpp:27-155) after the argument checks runs on the device:
 // bounding box + dilated mask + back-projection + centroid init (LL.cpp:43-104), the two
 // VoxelDownSample calls (LL.cpp:108-109), EstimateNormals (LL.cpp:127) and RegistrationICP
@@ -14,7 +15,7 @@ constexpr int kIcpGrid = 64;                      // NN search grid: at most 64 
 constexpr int kIcpCells = kIcpGrid * kIcpGrid + 1; // ... columns in x and y (+1 end marker)
 constexpr int kIcpCells16 = 4104;                 // kIcpCells rounded up to a multiple of 8 (16-byte copies of the u16 table)
 constexpr int kIcpStrips = 48;                    // row strips of the bounding box in k_icp_points
-constexpr int kIcpMaxSplit = 64;                  // workgroups (source slices) per hypothesis in k_icp_search
+constexpr int kIcpMaxSplit = 64;                  // workgroups (source slices) per hypothesis in k_icp_eval / members of a team in k_icp_team
 constexpr int kIcpSortGroups = 8;                 // workgroups that sort a cloud, each a contiguous range of the leading key coordinate (k_icp_voxel_wide / k_icp_grid_wide)
 constexpr int kIcpCovStride = 12;                 // 9 cumulants, neighbour count, squared nearest-neighbour separation, pad
 

@@ -1,5 +1,5 @@
 // Internal interface between the host orchestration (detector.cpp, pose_refine.cpp) and the HIP
-// kernels (frontend.hip, match.hip, icp.hip).  gfx950 only.  Not part of the public C ABI.
+// kernels (frontend.hip, match.hip, icp*.hip).  gfx950 only.  Not part of the public C ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -1,7 +1,7 @@
 // poseRefine::process (LL.cpp:27-155) behind the C ABI.  The host only validates arguments, stages
 // the depth images through pinned memory and composes the final [R|t] from the device result
 // (LL.cpp:146-154); everything between — bounding box, dilated mask, back-projection, centroid
-// init, both VoxelDownSample calls, EstimateNormals and the whole ICP loop — runs in icp.hip with
+// init, both VoxelDownSample calls, EstimateNormals and the whole ICP loop — runs in the icp*.hip units (icp_kernels.h) with
 // no host round trip.  An `lm_icp` context owns one HIP stream, the resident depth images and the
 // worst-case-sized arenas (W*H points per hypothesis and cloud: 288 GB of HBM make that free).
 #include <limits.h>

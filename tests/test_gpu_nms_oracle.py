@@ -1,4 +1,4 @@
-"""The middle of Pipeline.run — k_nms_pack, k_topk_nms (csrc/nms.hip) and k_icp_bind (csrc/icp.hip): which matches are kept, in
+"""The middle of Pipeline.run — k_nms_pack, k_topk_nms (csrc/nms.hip) and k_icp_bind (csrc/icp_clouds.hip): which matches are kept, in
 which order, with which box, and which rendered view each is bound to — against the ORACLE's own chain (helpers.nms_chain_oracle:
 match_oracle.c per class -> canonical sort / unique -> boxes -> numpy nms, stable; no product call on the expected side).
 

@@ -618,9 +618,9 @@ static int add_rendered_view_host(lm_detector* d, lm_mesh* m, int i, int width, 
     return add_template_resident(d, hmask.data(), width, height, class_id);
 }
 
-extern "C" int lm_detector_add_templates_rendered(lm_detector* d, lm_mesh* m, const char* class_id, int count, int width, int height,
-                                                  const float* Ks, const float* Rs, const float* ts, float clip_near, float clip_far,
-                                                  float ambient, int ssaa, int32_t* template_ids, int32_t* box_wh) {
+static int add_templates_rendered(lm_detector* d, lm_mesh* m, const char* class_id, int count, int width, int height, const float* Ks,
+                                  const float* Rs, const float* ts, float clip_near, float clip_far, float ambient, int ssaa,
+                                  int32_t* template_ids, int32_t* box_wh, const lm_shade_opts* shade) {
     if (!d || !m || !class_id || count < 0 || (count && (!Ks || !Rs || !ts || !template_ids)))
         return lm_set_error(LM_ERR_INVALID, "null argument");
     if (m->device != d->device) return lm_set_error(LM_ERR_INVALID, "mesh and detector live on different devices");
@@ -642,9 +642,10 @@ extern "C" int lm_detector_add_templates_rendered(lm_detector* d, lm_mesh* m, co
     int rc;
     for (int c0 = 0; c0 < count; c0 += chunk) {
         const int n = std::min(chunk, count - c0);
-        if ((rc = lm_mesh_render_device(m, n, width, height, Ks + 9 * (size_t)c0, Rs + 9 * (size_t)c0, ts + 3 * (size_t)c0, clip_near, clip_far,
-                                        ambient, ssaa, true, true)))
-            return rc;
+        rc = shade ? lm_mesh_render_device_shaded(m, n, width, height, Ks + 9 * (size_t)c0, Rs + 9 * (size_t)c0, ts + 3 * (size_t)c0, *shade, true, true)
+                   : lm_mesh_render_device(m, n, width, height, Ks + 9 * (size_t)c0, Rs + 9 * (size_t)c0, ts + 3 * (size_t)c0, clip_near, clip_far,
+                                           ambient, ssaa, true, true);
+        if (rc) return rc;
         HIP_TRY(hipStreamSynchronize(m->s));
         if ((rc = setup_geometry(d, width, height, false))) return rc;
         if (!on_device) {
@@ -711,6 +712,24 @@ extern "C" int lm_detector_add_templates_rendered(lm_detector* d, lm_mesh* m, co
         }
     }
     return LM_OK;
+}
+
+extern "C" int lm_detector_add_templates_rendered(lm_detector* d, lm_mesh* m, const char* class_id, int count, int width, int height,
+                                                  const float* Ks, const float* Rs, const float* ts, float clip_near, float clip_far,
+                                                  float ambient, int ssaa, int32_t* template_ids, int32_t* box_wh) {
+    return add_templates_rendered(d, m, class_id, count, width, height, Ks, Rs, ts, clip_near, clip_far, ambient, ssaa, template_ids, box_wh, nullptr);
+}
+
+// render_train with renderer.render's texture / shading / bg_color (linemod_and_levelup_test.py:193-227 passes texture=model_texture)
+extern "C" int lm_detector_add_templates_rendered_ex(lm_detector* d, lm_mesh* m, const char* class_id, int count, int width, int height,
+                                                     const float* Ks, const float* Rs, const float* ts, const lm_render_options* options,
+                                                     int32_t* template_ids, int32_t* box_wh) {
+    if (!d || !m || !class_id) return lm_set_error(LM_ERR_INVALID, "null argument");
+    lm_shade_opts o;
+    int rc = lm_parse_render_options(m, options, &o);
+    if (rc) return rc;
+    if (o.ssaa < 1 || o.ssaa > 8) return lm_set_error(LM_ERR_INVALID, "ssaa must be in 1..8");
+    return add_templates_rendered(d, m, class_id, count, width, height, Ks, Rs, ts, o.clip_near, o.clip_far, o.ambient, o.ssaa, template_ids, box_wh, &o);
 }
 
 extern "C" int lm_detector_read_class(lm_detector* d, const char* path, const char* class_id_override) {

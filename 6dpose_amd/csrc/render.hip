@@ -190,6 +190,165 @@ __global__ void k_resolve_rgb(MeshDev M, const ProjVtx* __restrict__ pv, const V
     for (int ch = 0; ch < 3; ++ch) o[ch] = (uint8_t)((2 * acc[ch] + n) / (2 * n));   // rounded mean (INTER_AREA)
 }
 
+// ---- shading options ------------------------------------------------------------------------------------
+// The rest of renderer.render's signature (texture, surf_color, bg_color, shading='flat'; renderer.py:306-420).  Coverage,
+// the depth test and the z-buffer are the kernels above; only the per-fragment resolve differs.  k_resolve_rgb stays the
+// resolve of the default call (phong, vertex colours, black background), so that call returns the bytes it always did.
+// As for the modes above the reference result depends on the GL implementation; tests/render_shade_ref.py restates these
+// rules in numpy and IS the definition:
+//   * flat: the reference's fragment shader takes the normal from the screen-space derivatives of the eye position,
+//     cross(dFdx(p), dFdy(p)) (renderer.py:62).  Inside a triangle p is linear in the screen coordinates of the plane
+//     the triangle spans, so that product is parallel to the face normal, and because dFdx / dFdy run along the
+//     screen axes whatever the winding, it points to the same side for every surface one can see: towards the viewer.
+//     So: n = cross(p1 - p0, p2 - p0) of the winning triangle's eye-space vertices p_i = R v_i + t (double, the
+//     operation order of k_project; cross as (a.y b.z - a.z b.y, a.z b.x - a.x b.z, a.x b.y - a.y b.x), vertices in
+//     the order the face lists them), turned towards the camera.  With the light at the eye (L = -e/|e|) turning n
+//     towards the camera makes the diffuse term |e.n| / (|e||n|): flat shading is two-sided.  e is the fragment's
+//     eye position from the pixel ray and the fragment depth, exactly as for phong, so the two modes differ in the
+//     normal only.  A face whose normal is zero gets diffuse 0.  light = min(1, ambient + diffuse).
+//   * texture: uv per vertex, interpolated perspective-correctly with the weights of the depth: l_i = w_i / area,
+//     s_i = l_i / z_i, S = (s0 + s1) + s2, u = ((s0 u0 + s1 u1) + s2 u2) / S, v likewise, all in double in this
+//     order (u_i, v_i are the float32 inputs widened).  Nearest texel, clamped to the edge: column =
+//     clamp(floor(u W_t), 0, W_t - 1), row = H_t - 1 - clamp(floor(v H_t), 0, H_t - 1).  The row is counted from the
+//     bottom because pysixd uploads np.flipud(texture) (renderer.py:319) and GL's v = 0 is the first uploaded row:
+//     v = 1 is the top row of the image the caller passed.  Nearest / clamp is OUR rule: glumpy's default filter
+//     could not be checked, this is not pinned to it.  colour = light * texel; vertex colours and surf_color are
+//     ignored (renderer.py:316-321).  Texels are stored r | g << 8 | b << 16: one dword load per lookup.
+//   * surf_color: one colour for every vertex in place of the vertex colours (renderer.py:324-333), quantised to
+//     8 bits by the caller (rint(255 x)) like a vertex colour; with ambient 1 the result is that byte.  One colour per
+//     launch or one per view (pose overlays draw every pose in its own colour, linemod_and_levelup_test.py:377).
+//   * bg_color: a supersample no fragment covers takes the (8-bit) background colour BEFORE the box average, as a
+//     GL clear followed by cv2.resize(INTER_AREA) gives; alpha is not used.
+// The mode is the same for a whole launch: flat / texture are template parameters, the surface colour a branch on a
+// kernel argument (scalar).  One thread per output pixel over its ssaa x ssaa supersamples, like k_resolve_rgb.
+static __device__ __forceinline__ void eye_vertex(const MeshDev& M, const ViewParams& V, int i, double p[3]) {
+    const double x = M.v[3 * (size_t)i], y = M.v[3 * (size_t)i + 1], z = M.v[3 * (size_t)i + 2];
+    p[0] = __dadd_rn(__dadd_rn(__dadd_rn(__dmul_rn(V.R[0], x), __dmul_rn(V.R[1], y)), __dmul_rn(V.R[2], z)), V.t[0]);
+    p[1] = __dadd_rn(__dadd_rn(__dadd_rn(__dmul_rn(V.R[3], x), __dmul_rn(V.R[4], y)), __dmul_rn(V.R[5], z)), V.t[1]);
+    p[2] = __dadd_rn(__dadd_rn(__dadd_rn(__dmul_rn(V.R[6], x), __dmul_rn(V.R[7], y)), __dmul_rn(V.R[8], z)), V.t[2]);
+}
+
+template <bool FLAT, bool TEX>
+__global__ void k_resolve_shaded(MeshDev M, const ProjVtx* __restrict__ pv, const ViewParams* __restrict__ views,
+                                 const unsigned long long* __restrict__ zbuf, int W, int H, int ssaa, ShadeParams sp, uint8_t* __restrict__ rgb) {
+    const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y, view = blockIdx.z;
+    if (x >= W) return;
+    const int Ws = W * ssaa, Hs = H * ssaa;
+    const ProjVtx* P = pv + (size_t)view * M.nv;
+    const ViewParams V = views[view];
+    const unsigned long long* Z = zbuf + (size_t)view * Ws * Hs;
+    const bool has_surf = sp.has_surf != 0 || sp.view_surf != nullptr;
+    const uint32_t surf = sp.view_surf ? sp.view_surf[view] : sp.surf;
+    const int bg[3] = {(int)(sp.bg & 255u), (int)((sp.bg >> 8) & 255u), (int)((sp.bg >> 16) & 255u)};
+    int acc[3] = {0, 0, 0};
+    for (int sy = 0; sy < ssaa; ++sy)
+        for (int sx = 0; sx < ssaa; ++sx) {
+            const int X = x * ssaa + sx, Y = y * ssaa + sy;
+            const unsigned long long k = Z[(size_t)Y * Ws + X];
+            if (k == ~0ull) { acc[0] += bg[0]; acc[1] += bg[1]; acc[2] += bg[2]; continue; }
+            const int f = (int)(unsigned int)k;
+            const int i0 = M.f[3 * (size_t)f], i1 = M.f[3 * (size_t)f + 1], i2 = M.f[3 * (size_t)f + 2];
+            const ProjVtx a = P[i0], b = P[i1], c = P[i2];
+            Tri t;
+            bool flipped;
+            if (!make_tri(a, b, c, t, flipped)) { acc[0] += bg[0]; acc[1] += bg[1]; acc[2] += bg[2]; continue; }   // not reached: a drawn triangle has area
+            long long w0, w1, w2;
+            (void)weights(t, (long long)X << 8, (long long)Y << 8, w0, w1, w2);
+            const int j1 = flipped ? i2 : i1, j2 = flipped ? i1 : i2;
+            const double z0 = a.z, z1 = flipped ? c.z : b.z, z2 = flipped ? b.z : c.z;
+            const double A = (double)t.area;
+            const double l0 = __ddiv_rn((double)w0, A), l1 = __ddiv_rn((double)w1, A), l2 = __ddiv_rn((double)w2, A);
+            const double s0 = __ddiv_rn(l0, z0), s1 = __ddiv_rn(l1, z1), s2 = __ddiv_rn(l2, z2);
+            const double S = __dadd_rn(__dadd_rn(s0, s1), s2);
+            const double z = __ddiv_rn(1.0, S);                         // = frag_depth
+            const float q0 = (float)((double)w0 / A / z0 * z), q1 = (float)((double)w1 / A / z1 * z), q2 = (float)((double)w2 / A / z2 * z);
+            float nx = 0.f, ny = 0.f, nz = -1.f;
+            if (FLAT) {
+                double p0[3], p1[3], p2[3];
+                eye_vertex(M, V, i0, p0); eye_vertex(M, V, i1, p1); eye_vertex(M, V, i2, p2);
+                const double ax = __dsub_rn(p1[0], p0[0]), ay = __dsub_rn(p1[1], p0[1]), az = __dsub_rn(p1[2], p0[2]);
+                const double bx = __dsub_rn(p2[0], p0[0]), by = __dsub_rn(p2[1], p0[1]), bz = __dsub_rn(p2[2], p0[2]);
+                nx = (float)__dsub_rn(__dmul_rn(ay, bz), __dmul_rn(az, by));
+                ny = (float)__dsub_rn(__dmul_rn(az, bx), __dmul_rn(ax, bz));
+                nz = (float)__dsub_rn(__dmul_rn(ax, by), __dmul_rn(ay, bx));
+            } else if (M.n) {
+                const float n0[3] = {M.n[3 * (size_t)i0], M.n[3 * (size_t)i0 + 1], M.n[3 * (size_t)i0 + 2]};
+                const float n1[3] = {M.n[3 * (size_t)j1], M.n[3 * (size_t)j1 + 1], M.n[3 * (size_t)j1 + 2]};
+                const float n2[3] = {M.n[3 * (size_t)j2], M.n[3 * (size_t)j2 + 1], M.n[3 * (size_t)j2 + 2]};
+                const float mx = q0 * n0[0] + q1 * n1[0] + q2 * n2[0], my = q0 * n0[1] + q1 * n1[1] + q2 * n2[1],
+                            mz = q0 * n0[2] + q1 * n1[2] + q2 * n2[2];
+                nx = (float)V.R[0] * mx + (float)V.R[1] * my + (float)V.R[2] * mz;
+                ny = (float)V.R[3] * mx + (float)V.R[4] * my + (float)V.R[5] * mz;
+                nz = (float)V.R[6] * mx + (float)V.R[7] * my + (float)V.R[8] * mz;
+            }
+            const float nl = sqrtf(nx * nx + ny * ny + nz * nz);
+            const float fz = (float)z;
+            const float ex = ((float)X - (float)(V.K[2] * ssaa)) / (float)(V.K[0] * ssaa) * fz;
+            const float ey = ((float)Y - (float)(V.K[5] * ssaa)) / (float)(V.K[4] * ssaa) * fz;
+            const float el = sqrtf(ex * ex + ey * ey + fz * fz);
+            float diff = 0.f;
+            if (nl > 0.f && el > 0.f) diff = -(ex * nx + ey * ny + fz * nz) / (el * nl);   // L = -p/|p| (light at the eye)
+            if (FLAT) diff = fabsf(diff);                               // the normal turned towards the camera
+            else if (diff < 0.f) diff = 0.f;
+            float lw = sp.ambient + diff;
+            if (lw > 1.f) lw = 1.f;
+            float col[3] = {0.5f, 0.5f, 0.5f};                          // renderer.py:331 default colour
+            if (TEX) {
+                const double u0 = sp.uv[2 * (size_t)i0], v0 = sp.uv[2 * (size_t)i0 + 1], u1 = sp.uv[2 * (size_t)j1], v1 = sp.uv[2 * (size_t)j1 + 1],
+                             u2 = sp.uv[2 * (size_t)j2], v2 = sp.uv[2 * (size_t)j2 + 1];
+                const double u = __ddiv_rn(__dadd_rn(__dadd_rn(__dmul_rn(s0, u0), __dmul_rn(s1, u1)), __dmul_rn(s2, u2)), S);
+                const double v = __ddiv_rn(__dadd_rn(__dadd_rn(__dmul_rn(s0, v0), __dmul_rn(s1, v1)), __dmul_rn(s2, v2)), S);
+                const double fu = floor(__dmul_rn(u, (double)sp.tex_w)), fv = floor(__dmul_rn(v, (double)sp.tex_h));
+                const int tc = fu >= (double)(sp.tex_w - 1) ? sp.tex_w - 1 : (fu > 0.0 ? (int)fu : 0);   // clamp to edge (NaN -> 0)
+                const int tr = fv >= (double)(sp.tex_h - 1) ? sp.tex_h - 1 : (fv > 0.0 ? (int)fv : 0);
+                const uint32_t texel = sp.tex[(size_t)(sp.tex_h - 1 - tr) * sp.tex_w + tc];
+                col[0] = (float)(texel & 255u) * (1.f / 255.f); col[1] = (float)((texel >> 8) & 255u) * (1.f / 255.f);
+                col[2] = (float)((texel >> 16) & 255u) * (1.f / 255.f);
+            } else if (has_surf) {
+                col[0] = (float)(surf & 255u) * (1.f / 255.f); col[1] = (float)((surf >> 8) & 255u) * (1.f / 255.f);
+                col[2] = (float)((surf >> 16) & 255u) * (1.f / 255.f);
+            } else if (M.c) {
+#pragma unroll
+                for (int ch = 0; ch < 3; ++ch)
+                    col[ch] = (q0 * M.c[3 * (size_t)i0 + ch] + q1 * M.c[3 * (size_t)j1 + ch] + q2 * M.c[3 * (size_t)j2 + ch]) * (1.f / 255.f);
+            }
+#pragma unroll
+            for (int ch = 0; ch < 3; ++ch) {
+                float v = lw * col[ch] * 255.f;
+                v = v < 0.f ? 0.f : (v > 255.f ? 255.f : v);
+                acc[ch] += (int)rintf(v);
+            }
+        }
+    const int n = ssaa * ssaa;
+    uint8_t* o = rgb + (((size_t)view * H + y) * W + x) * 3;
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) o[ch] = (uint8_t)((2 * acc[ch] + n) / (2 * n));   // rounded mean (INTER_AREA)
+}
+
+// ---- pose overlays --------------------------------------------------------------------------------------
+// linemod_and_levelup_test.py:377-383 and tools/vis_gt_poses.py:120-145: every pose rendered at the frame's size, then
+// pasted into the frame.  Layer p shows at a pixel where its rendered depth is > 0 and, with a scene depth image, where
+// scene == 0 or depth < scene (the driver's visible_mask, :379).  painter: the last such layer wins (the driver pastes
+// in order).  nearest: the layer with the smallest rendered depth wins, the lower index on a tie (vis_gt_poses'
+// resolve_visib).  One thread per pixel; the layer table is read with the same address by every lane.
+__global__ void k_overlay_compose(const OverlayLayer* __restrict__ layers, int count, const uint8_t* __restrict__ frame,
+                                  const uint16_t* __restrict__ scene, int npx, int nearest, uint8_t* __restrict__ out_rgb,
+                                  int8_t* __restrict__ out_index) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= npx) return;
+    const unsigned int sd = scene ? scene[i] : 0u;
+    int best = -1;
+    unsigned int best_d = 0xFFFFFFFFu;
+    for (int p = 0; p < count; ++p) {
+        const unsigned int d = layers[p].depth[i];
+        if (d == 0u || !(sd == 0u || d < sd)) continue;
+        if (!nearest || d < best_d) { best = p; best_d = d; }
+    }
+    const uint8_t* src = best >= 0 ? layers[best].rgb : frame;
+    out_rgb[3 * (size_t)i] = src[3 * (size_t)i]; out_rgb[3 * (size_t)i + 1] = src[3 * (size_t)i + 1]; out_rgb[3 * (size_t)i + 2] = src[3 * (size_t)i + 2];
+    out_index[i] = (int8_t)best;
+}
+
 void launch_project(const MeshDev& M, const ViewParams* views, int count, int scale, ProjVtx* out, hipStream_t s) {
     if (count <= 0 || M.nv <= 0) return;
     hipLaunchKernelGGL(k_project, dim3((M.nv + 255) / 256, count), dim3(256), 0, s, M, views, scale, out);
@@ -208,6 +367,22 @@ void launch_resolve_rgb(const MeshDev& M, const ProjVtx* pv, const ViewParams* v
                         int ssaa, float ambient, uint8_t* rgb, hipStream_t s) {
     if (count <= 0) return;
     hipLaunchKernelGGL(k_resolve_rgb, dim3((W + 255) / 256, H, count), dim3(256), 0, s, M, pv, views, zbuf, W, H, ssaa, ambient, rgb);
+}
+
+void launch_resolve_shaded(const MeshDev& M, const ProjVtx* pv, const ViewParams* views, const unsigned long long* zbuf, int count, int W, int H,
+                           int ssaa, const ShadeParams& sp, uint8_t* rgb, hipStream_t s) {
+    if (count <= 0) return;
+    const dim3 grid((W + 255) / 256, H, count), block(256);
+    const bool tex = sp.tex != nullptr && sp.uv != nullptr;
+    if (sp.flat && tex) hipLaunchKernelGGL((k_resolve_shaded<true, true>), grid, block, 0, s, M, pv, views, zbuf, W, H, ssaa, sp, rgb);
+    else if (sp.flat) hipLaunchKernelGGL((k_resolve_shaded<true, false>), grid, block, 0, s, M, pv, views, zbuf, W, H, ssaa, sp, rgb);
+    else if (tex) hipLaunchKernelGGL((k_resolve_shaded<false, true>), grid, block, 0, s, M, pv, views, zbuf, W, H, ssaa, sp, rgb);
+    else hipLaunchKernelGGL((k_resolve_shaded<false, false>), grid, block, 0, s, M, pv, views, zbuf, W, H, ssaa, sp, rgb);
+}
+void launch_overlay_compose(const OverlayLayer* layers, int count, const uint8_t* frame, const uint16_t* scene, int npx, int nearest,
+                            uint8_t* out_rgb, int8_t* out_index, hipStream_t s) {
+    if (npx <= 0) return;
+    hipLaunchKernelGGL(k_overlay_compose, dim3((npx + 255) / 256), dim3(256), 0, s, layers, count, frame, scene, npx, nearest, out_rgb, out_index);
 }
 
 }  // namespace lm

@@ -442,7 +442,7 @@ int lm_pipeline_run(lm_pipeline *p, float threshold, const char *const *class_id
 typedef struct lm_mesh lm_mesh;
 int lm_mesh_create(int device, const float *vertices /*[nv][3] mm*/, const float *normals /*[nv][3] or NULL*/,
                    const uint8_t *colors /*[nv][3] or NULL*/, int nv, const int32_t *faces /*[nf][3]*/, int nf, lm_mesh **out);
-int lm_mesh_load_ply(int device, const char *path, lm_mesh **out);   /* ascii / binary_little_endian, triangles */
+int lm_mesh_load_ply(int device, const char *path, lm_mesh **out);   /* ascii / binary_little_endian, triangles; texture_u/_v if present */
 void lm_mesh_destroy(lm_mesh *m);
 int lm_mesh_counts(const lm_mesh *m, int *nv, int *nf);
 /* render(model, (width, height), K, R, t, clip_near, clip_far, ambient_weight, shading='phong') for `count` views.
@@ -456,6 +456,58 @@ int lm_mesh_render(lm_mesh *m, int count, int width, int height, const float *Ks
 int lm_detector_add_templates_rendered(lm_detector *d, lm_mesh *m, const char *class_id, int count, int width, int height,
                                        const float *Ks, const float *Rs, const float *ts, float clip_near, float clip_far,
                                        float ambient, int ssaa, int32_t *template_ids /*[count]*/, int32_t *box_wh /*[count][2] or NULL*/);
+/* ---- the rest of renderer.render's signature (renderer.py:306: texture, surf_color, bg_color, shading) --------------
+ * lm_mesh_render and lm_detector_add_templates_rendered above keep their behaviour byte for byte; the entry points below
+ * take the options as a struct that starts with its own size (lm_render_options_init fills the defaults of
+ * lm_mesh_render: phong, ambient 0.8, ssaa 4, clip 10 / 10000, black background; pysixd's own defaults are flat and
+ * ambient 0.5).  The rules of every mode are stated in 6dpose_amd/csrc/render.hip ("shading options") and restated in
+ * numpy by tests/render_shade_ref.py; like the existing modes they are this library's specification, because the
+ * reference's result depends on the GL implementation. */
+#define LM_SHADING_PHONG 0  /* interpolated vertex normals, one-sided: max(0, L.N) */
+#define LM_SHADING_FLAT 1   /* face normal turned towards the camera (renderer.py:62), two-sided: |L.N| */
+typedef struct lm_render_options {
+    uint32_t size;          /* sizeof(lm_render_options); anything else -> LM_ERR_INVALID */
+    int32_t shading;        /* LM_SHADING_* */
+    int32_t use_texture;    /* colour = light * nearest texel at the interpolated uv (renderer.py:316-321); needs
+                               lm_mesh_set_texcoords and lm_mesh_set_texture; vertex colours and surf_color are ignored */
+    int32_t has_surf_color; /* surf_color replaces the vertex colours (renderer.py:324-333) */
+    float surf_color[3];    /* r, g, b in [0, 1], quantised to 8 bits (rint(255 x)) */
+    float bg_color[4];      /* r, g, b in [0, 1], quantised to 8 bits, given to uncovered supersamples before the box
+                               average; a accepted and ignored */
+    float ambient;          /* ambient_weight */
+    int32_t ssaa;           /* 1..8 */
+    float clip_near, clip_far;
+} lm_render_options;
+void lm_render_options_init(lm_render_options *o);
+/* texture_u / texture_v per vertex (inout.py:249-293; lm_mesh_load_ply reads them when the file has them); count must
+ * equal the number of vertices.  uv [count][2] float32; v = 1 is the top row of the texture image. */
+int lm_mesh_set_texcoords(lm_mesh *m, const float *uv, int count);
+/* The texture image, uint8 [height][width][3] as the caller sees it (row 0 = top; pysixd's np.flipud, renderer.py:319,
+ * is part of the lookup rule).  Kept in HBM as 4-byte texels. */
+int lm_mesh_set_texture(lm_mesh *m, const uint8_t *rgb, int width, int height);
+int lm_mesh_texture_info(const lm_mesh *m, int *has_texcoords, int *width, int *height);   /* 0 x 0: no image */
+/* lm_mesh_render with options.  LM_ERR_INVALID: unknown shading, a colour outside [0, 1], use_texture without texture
+ * coordinates or image. */
+int lm_mesh_render_ex(lm_mesh *m, int count, int width, int height, const float *Ks, const float *Rs, const float *ts,
+                      const lm_render_options *options, uint16_t *depth_out, uint8_t *rgb_out);
+/* lm_detector_add_templates_rendered with options: render_train for textured models (linemod_and_levelup_test.py:193-227
+ * passes texture=model_texture) and other backgrounds. */
+int lm_detector_add_templates_rendered_ex(lm_detector *d, lm_mesh *m, const char *class_id, int count, int width, int height,
+                                          const float *Ks, const float *Rs, const float *ts, const lm_render_options *options,
+                                          int32_t *template_ids /*[count]*/, int32_t *box_wh /*[count][2] or NULL*/);
+/* Pose overlays (linemod_and_levelup_test.py:377-383, tools/vis_gt_poses.py:120-145): pose i = meshes[i] at (Rs[i], ts[i])
+ * rendered at the frame's size with `options` (ssaa must be 1) and surface colour surf_colors[i] ([count][3] in [0, 1], or
+ * NULL for the mesh's own colours), then composed into a copy of rgb on the device: one batch of renders per distinct
+ * mesh and one compose kernel.  A pose shows at a pixel where its rendered depth is > 0 and, with scene_depth (uint16 mm,
+ * or NULL), where scene_depth == 0 or depth < scene_depth (the driver's visible_mask, :379).  PAINTER: the last such
+ * pose wins (the driver's paste order); NEAREST: the smallest rendered depth wins, the lower index on a tie
+ * (vis_gt_poses' resolve_visib).  rgb_out uint8 [height][width][3]; index_out int8 [height][width], -1 where no pose
+ * shows.  1 <= count <= 127. */
+#define LM_OVERLAY_PAINTER 0
+#define LM_OVERLAY_NEAREST 1
+int lm_mesh_overlay(lm_mesh *const *meshes, int count, int width, int height, const uint8_t *rgb, const float *Ks,
+                    const float *Rs, const float *ts, const float *surf_colors, const lm_render_options *options,
+                    const uint16_t *scene_depth, int mode, uint8_t *rgb_out, int8_t *index_out);
 /* Views of a pipeline rendered on the device: depth_ren of template first_template + i = the mesh at (Rs[i], ts[i]). */
 int lm_pipeline_set_views_rendered(lm_pipeline *p, lm_mesh *m, const char *class_id, int first_template, int count,
                                    const float *Ks, const float *Rs, const float *ts, float clip_near, float clip_far,

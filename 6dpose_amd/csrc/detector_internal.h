@@ -1,5 +1,7 @@
-// Private view of the detector shared by detector.cpp and pipeline.cpp (not part of the C ABI).
+// Private view of the detector shared by the detector's translation units (detector.cpp, detector_frame.cpp, detector_bank.cpp,
+// detector_stream.cpp, host_pool.cpp, match_lists.cpp), bank_file.cpp, comm.cpp, exchange.cpp and pipeline.cpp (not part of the C ABI).
 #pragma once
+#include <algorithm>
 #include <atomic>
 #include <chrono>
 #include <condition_variable>
@@ -281,9 +283,34 @@ struct lm_detector {
 
 
 // detector.cpp
+int ensure_pinned(lm_detector* d, size_t bytes);
+
+// detector_frame.cpp
+int setup_geometry(lm_detector* d, int W, int H, bool check_match_preconditions);
+int upload_frame(lm_detector* d, const uint8_t* rgb, const uint16_t* depth, int W, int H, const uint8_t* const* masks, bool check_match_preconditions);
+int run_frontend_training(lm_detector* d);
+
+// detector_bank.cpp
+int upload_bank(lm_detector* d);
+int build_work(lm_detector* d, const char* const* class_ids, int num_class_ids);
+
+// detector_stream.cpp
 int lm_submit_frame(lm_detector* d, float threshold, const char* const* class_ids, int num_class_ids);
 int lm_collect_frame(lm_detector* d, int sort_unique, lm_match** out, size_t* n_out);   // sort_unique < 0: discard the records
 int lm_launch_pending(lm_detector* d);                                                  // launches the frames waiting for their batch to fill
+
+// host_pool.cpp: the helper threads of the streamed path (HostPool above) and the staging copy they share with the caller
+bool pool_ready(lm_detector* d);
+bool pool_run_one(lm_detector* d);
+void pool_post(lm_detector* d, std::function<void()> job);
+void pool_stop(lm_detector* d);
+void staged_copy(lm_detector* d, uint8_t* dst, const uint8_t* a, size_t na, uint8_t* dst_b, const uint8_t* b, size_t nb);
+
+// match_lists.cpp
+struct ListClock { std::chrono::steady_clock::time_point converted, merged; };   // a result list: records converted, list sorted + uniqued
+size_t merge_matches_impl(lm_match* m, size_t n, bool distinct_input);
+lm_match* reference_order_list(const Candidate* recs, const Candidate* coarse, uint64_t ncand, size_t alive, const std::vector<int32_t>& wcls,
+                               const std::vector<int32_t>& wtid, size_t* n_out, ListClock* clock);
 
 // A writer on the frame stream (`stream`) — upload, frame selection with a geometry change, training — touches level buffers, arenas and the
 // resident frame that a batch in flight on the matching stream reads.  Stream order only runs the other way (order_after_default_stream: batch

@@ -1,4 +1,4 @@
-// Private view of lm_mesh shared by render.cpp, detector.cpp and pipeline.cpp (not part of the C ABI).
+// Private view of lm_mesh shared by render.cpp, detector_bank.cpp and pipeline.cpp (not part of the C ABI).
 #pragma once
 #include "../../include/amd_linemod.h"
 #include "render_kernels.h"

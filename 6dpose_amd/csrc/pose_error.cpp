@@ -3,7 +3,8 @@
 //
 // VSD and COU: the E + G views are rendered by lm_mesh_render_device (R, t, K cast to float32, as the renderer of
 // lm_mesh_render) and read as float32 eye depth from the z-buffer keys; then one k_vsd pass per (estimate, GT) pair.
-// ADD / ADI / diameter: k_pose_pts.  RE / TE: here, f64.
+// ADD / ADI / diameter: k_pose_pts.  RE / TE: here, f64.  MSSD / MSPD (lm_mesh_pose_errors_sym): the composed GT-side
+// transforms here in f64, then k_pose_sym and k_pose_sym_min.
 //
 // Deliberate differences from pysixd (also DESIGN.md, "Pose errors"):
 //   * the renders are this project's rasteriser, not OpenGL: its fill rule, no near-plane clipping (a triangle with a
@@ -30,7 +31,8 @@ namespace {
 
 constexpr size_t kZbufBudget = (size_t)512 << 20;   // bytes of z-buffer (8 B per pixel) per render call
 constexpr int kMaxViewsPerRender = 256;              // keeps the pair grid (views^2 / 4) below the launch limit
-constexpr int kMaxPtsPairs = 16384;                  // pairs per k_pose_pts launch
+constexpr int kMaxPtsPairs = 16384;                  // pairs per k_pose_pts / k_pose_sym launch
+constexpr size_t kSymPartialBudget = (size_t)256 << 20;   // bytes of k_pose_sym partials per launch (one pair may exceed it)
 
 int ensure(void** p, size_t& cap, size_t bytes) {
     if (bytes <= cap) return LM_OK;
@@ -135,6 +137,8 @@ extern "C" int lm_mesh_pose_errors(lm_mesh* m, int n_est, const double* R_est, c
     if (!m) return lm_set_error(LM_ERR_INVALID, "null mesh");
     if (n_est < 0 || n_gt < 0) return lm_set_error(LM_ERR_INVALID, "negative pose count");
     const int all = LM_POSE_VSD | LM_POSE_COU | LM_POSE_ADD | LM_POSE_ADI | LM_POSE_RE | LM_POSE_TE;
+    if (metrics & (LM_POSE_MSSD | LM_POSE_MSPD))
+        return lm_set_error(LM_ERR_INVALID, "LM_POSE_MSSD / LM_POSE_MSPD take a symmetry set: call lm_mesh_pose_errors_sym");
     if (metrics == 0 || (metrics & ~all)) return lm_set_error(LM_ERR_INVALID, "bad metrics mask 0x%x", metrics);
     const bool rendered = metrics & (LM_POSE_VSD | LM_POSE_COU);
     if (metrics & LM_POSE_VSD) {
@@ -255,6 +259,81 @@ extern "C" int lm_mesh_pose_errors(lm_mesh* m, int n_est, const double* R_est, c
                 }
             }
         }
+    }
+    return LM_OK;
+}
+
+extern "C" int lm_pose_sym_tile(void) { return kSymTile; }
+
+extern "C" int lm_mesh_pose_errors_sym(lm_mesh* m, int n_est, const double* R_est, const double* t_est, int n_gt, const double* R_gt,
+                                       const double* t_gt, int n_sym, const double* R_sym, const double* t_sym, const double* K, int metrics,
+                                       double* out) {
+    if (!m) return lm_set_error(LM_ERR_INVALID, "null mesh");
+    if (n_est < 0 || n_gt < 0) return lm_set_error(LM_ERR_INVALID, "negative pose count");
+    if (metrics == 0 || (metrics & ~(LM_POSE_MSSD | LM_POSE_MSPD)))
+        return lm_set_error(LM_ERR_INVALID, "bad metrics mask 0x%x (LM_POSE_MSSD | LM_POSE_MSPD)", metrics);
+    if (n_sym < 1) return lm_set_error(LM_ERR_INVALID, "n_sym = %d: the symmetry set holds at least the identity", n_sym);
+    const bool mssd = metrics & LM_POSE_MSSD, mspd = metrics & LM_POSE_MSPD;
+    if (mspd && !K) return lm_set_error(LM_ERR_INVALID, "mspd needs K (K is NULL)");
+    if (mspd && !finite_all(K, 9)) return lm_set_error(LM_ERR_INVALID, "K must be finite");
+    if (!R_sym || !t_sym) return lm_set_error(LM_ERR_INVALID, "null symmetry set");
+    if (!finite_all(R_sym, 9 * (size_t)n_sym) || !finite_all(t_sym, 3 * (size_t)n_sym)) return lm_set_error(LM_ERR_INVALID, "non-finite symmetry");
+    if (n_est == 0 || n_gt == 0) return LM_OK;
+    if (!R_est || !t_est || !R_gt || !t_gt || !out) return lm_set_error(LM_ERR_INVALID, "null argument");
+    if (!finite_all(R_est, 9 * (size_t)n_est) || !finite_all(t_est, 3 * (size_t)n_est) || !finite_all(R_gt, 9 * (size_t)n_gt) ||
+        !finite_all(t_gt, 3 * (size_t)n_gt))
+        return lm_set_error(LM_ERR_INVALID, "non-finite pose");
+    if ((size_t)n_gt * n_sym > ((size_t)1 << 24)) return lm_set_error(LM_ERR_INVALID, "n_gt * n_sym = %zu is too large", (size_t)n_gt * n_sym);
+    HIP_TRY(hipSetDevice(m->device));
+
+    // A[g][s] = R_g R_s, b[g][s] = R_g t_s + t_g, once per call
+    const size_t nxf = (size_t)n_gt * n_sym;
+    std::vector<SymXf> xf(nxf);
+    for (int g = 0; g < n_gt; ++g)
+        for (int s = 0; s < n_sym; ++s) {
+            SymXf& X = xf[(size_t)g * n_sym + s];
+            const double* Rg = R_gt + 9 * (size_t)g;
+            const double* ts = t_sym + 3 * (size_t)s;
+            matmul3(Rg, R_sym + 9 * (size_t)s, X.A);
+            for (int r = 0; r < 3; ++r) X.b[r] = ((Rg[3 * r] * ts[0] + Rg[3 * r + 1] * ts[1]) + Rg[3 * r + 2] * ts[2]) + t_gt[3 * (size_t)g + r];
+        }
+    SymCam cam;
+    for (int k = 0; k < 9; ++k) cam.K[k] = K ? K[k] : 0.0;
+
+    const size_t EG = (size_t)n_est * n_gt;
+    const int nm = (mssd ? 1 : 0) + (mspd ? 1 : 0), chunks = sym_chunks(m->nv);
+    const size_t per_pair = (size_t)chunks * nm * n_sym;                // partial doubles of one pair
+    const size_t batch = std::max<size_t>(1, std::min<size_t>(kMaxPtsPairs, (kSymPartialBudget / sizeof(double)) / per_pair));
+    const size_t xf_bytes = nxf * sizeof(SymXf);
+    std::vector<SymPair> pairs;
+    std::vector<double> res;
+    for (size_t p0 = 0; p0 < EG; p0 += batch) {
+        const size_t np = std::min(batch, EG - p0);
+        pairs.resize(np);
+        for (size_t p = 0; p < np; ++p) {
+            const size_t e = (p0 + p) / n_gt;
+            memcpy(pairs[p].Re, R_est + 9 * e, sizeof(pairs[p].Re));
+            memcpy(pairs[p].te, t_est + 3 * e, sizeof(pairs[p].te));
+            pairs[p].g = (int)((p0 + p) % n_gt);
+            pairs[p].pad = 0;
+        }
+        // one buffer holds the transforms and then the pairs; one holds the partials and then the results
+        int rc;
+        if ((rc = ensure(&m->d_pe_pairs, m->cap_pe_pairs, xf_bytes + np * sizeof(SymPair)))) return rc;
+        if ((rc = ensure(&m->d_pe_partial, m->cap_pe_partial, (np * per_pair + np * nm) * sizeof(double)))) return rc;
+        SymXf* d_xf = (SymXf*)m->d_pe_pairs;
+        SymPair* d_pairs = (SymPair*)((char*)m->d_pe_pairs + xf_bytes);
+        double* d_partial = (double*)m->d_pe_partial;
+        double* d_out = d_partial + np * per_pair;
+        HIP_TRY(hipMemcpyAsync(d_xf, xf.data(), xf_bytes, hipMemcpyHostToDevice, m->s));   // again after ensure() may have moved the buffer
+        HIP_TRY(hipMemcpyAsync(d_pairs, pairs.data(), np * sizeof(SymPair), hipMemcpyHostToDevice, m->s));
+        launch_pose_sym(m->d_v, m->nv, d_pairs, (int)np, d_xf, n_sym, cam, mssd, mspd, d_partial, d_out, m->s);
+        HIP_TRY(hipGetLastError());
+        res.resize(np * nm);
+        HIP_TRY(hipMemcpyAsync(res.data(), d_out, res.size() * sizeof(double), hipMemcpyDeviceToHost, m->s));
+        HIP_TRY(hipStreamSynchronize(m->s));
+        for (size_t p = 0; p < np; ++p)
+            for (int k = 0; k < nm; ++k) out[(size_t)k * EG + p0 + p] = res[p * nm + k];
     }
     return LM_OK;
 }

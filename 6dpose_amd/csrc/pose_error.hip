@@ -5,6 +5,8 @@
 //     keeps the index of the nearest (ADI) / farthest (diameter) vertex; that one distance is re-evaluated in f64 in
 //     the camera frame, so the result differs from an exact f64 search only where two candidates lie within f32
 //     resolution (~1e-5 mm) of each other.  ADD needs no search: f64 per vertex.
+//   * k_pose_sym, k_pose_sym_min — MSSD and MSPD: the largest surface / projection distance over the vertices, the smallest
+//     over an explicit set of symmetry transformations.  f64 throughout, no search; max and min only, no sums.
 //   * k_vsd — one pass per (estimate, GT) pair over the pixels: rendered depths from the rasteriser's z-buffer keys
 //     (float32 eye depth, high 32 bits), scene depth resident, distance images built on the fly in f64 with numpy's
 //     operation order, visibility with both distances cast to f32 (visibility.py:18), integer counts and the tlinear
@@ -115,6 +117,138 @@ void launch_pose_pts(const float* v, int nv, const PtsPair* pairs, int npairs, i
     if (mode == kPtsAddOnly) hipLaunchKernelGGL(k_pose_pts<kPtsAddOnly>, grid, dim3(kPtsThreads), 0, s, v, nv, pairs, partial);
     else if (mode == kPtsAdi) hipLaunchKernelGGL(k_pose_pts<kPtsAdi>, grid, dim3(kPtsThreads), 0, s, v, nv, pairs, partial);
     else hipLaunchKernelGGL(k_pose_pts<kPtsDiameter>, grid, dim3(kPtsThreads), 0, s, v, nv, pairs, partial);
+}
+
+// ---- symmetry-aware maxima (MSSD, MSPD) -------------------------------------------------------------------------
+// max and min are exact, so the kernels carry SQUARED distances and take one square root at the very end
+// (sqrt is monotonic and correctly rounded: sqrt(max d^2) == max sqrt(d^2) bit for bit).
+template <int CTRL>
+static __device__ __forceinline__ double dpp_f64(double x) {
+    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(x), CTRL, 0xf, 0xf, false);
+    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(x), CTRL, 0xf, 0xf, false);
+    return __hiloint2double(hi, lo);
+}
+// The maximum over the 64 lanes, wave-uniform.  Every lane of the wave must be active.
+static __device__ __forceinline__ double wave_max(double x) {
+    x = fmax(x, dpp_f64<0xB1>(x));                                      // quad_perm [1,0,3,2]
+    x = fmax(x, dpp_f64<0x4E>(x));                                      // quad_perm [2,3,0,1]
+    x = fmax(x, dpp_f64<0x141>(x));                                     // row_half_mirror
+    x = fmax(x, dpp_f64<0x140>(x));                                     // row_mirror: every lane holds its row's maximum
+    const int lo = __double2loint(x), hi = __double2hiint(x);
+    double r[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) r[k] = __hiloint2double(__builtin_amdgcn_readlane(hi, 16 * k), __builtin_amdgcn_readlane(lo, 16 * k));
+    return fmax(fmax(r[0], r[1]), fmax(r[2], r[3]));
+}
+// proj(p) = ((K p)[0] / (K p)[2], (K p)[1] / (K p)[2])
+static __device__ __forceinline__ void project(const SymCam& c, const double* p, double& u, double& v) {
+    double w[3];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) w[r] = (c.K[3 * r] * p[0] + c.K[3 * r + 1] * p[1]) + c.K[3 * r + 2] * p[2];
+    u = w[0] / w[2];
+    v = w[1] / w[2];
+}
+
+// One block per (pair, chunk of kSymThreads vertices).  A lane keeps its vertex, the estimate-side point and pixel in
+// registers and sweeps the GT's composed transforms, staged in LDS kSymTile at a time and read at one address per wave.
+// kSymFlight independent symmetries are evaluated before their maxima are reduced, so no lane waits on one f64 chain.
+template <bool SSD, bool SPD>
+__global__ __launch_bounds__(kSymThreads) void k_pose_sym(const float* __restrict__ v, int nv, const SymPair* __restrict__ pairs,
+                                                         const SymXf* __restrict__ xf, int n_sym, SymCam cam, double* __restrict__ partial) {
+    constexpr int NM = (SSD ? 1 : 0) + (SPD ? 1 : 0);
+    __shared__ double tile[kSymTile * 12];
+    __shared__ double red[NM][kSymWaves][kSymTile];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, chunk = blockIdx.x, pair = blockIdx.y;
+    const SymPair& P = pairs[pair];
+    const size_t i = (size_t)chunk * kSymThreads + tid;
+    const bool ok = i < (size_t)nv;
+    const double x = ok ? (double)v[3 * i] : 0.0, y = ok ? (double)v[3 * i + 1] : 0.0, z = ok ? (double)v[3 * i + 2] : 0.0;
+    double pe[3], ue = 0.0, ve = 0.0;
+    xform(P.Re, P.te, x, y, z, pe);
+    if (SPD) project(cam, pe, ue, ve);
+    const double* src = (const double*)(xf + (size_t)P.g * n_sym);
+    double* dst = partial + ((size_t)pair * gridDim.x + chunk) * NM * n_sym;
+    for (int s0 = 0; s0 < n_sym; s0 += kSymTile) {
+        const int n = min(kSymTile, n_sym - s0);
+        __syncthreads();                                                // the previous tile and its maxima have been read
+        for (int j = tid; j < 12 * n; j += kSymThreads) tile[j] = src[12 * (size_t)s0 + j];
+        __syncthreads();
+        for (int j0 = 0; j0 < n; j0 += kSymFlight) {
+            double d3[kSymFlight], d2[kSymFlight];
+#pragma unroll
+            for (int k = 0; k < kSymFlight; ++k) {
+                const double* T = tile + 12 * min(j0 + k, n - 1);       // the tail repeats the last transform
+                double q[3];
+                xform(T, T + 9, x, y, z, q);
+                if (SSD) {
+                    const double dx = pe[0] - q[0], dy = pe[1] - q[1], dz = pe[2] - q[2];
+                    d3[k] = ok ? (dx * dx + dy * dy) + dz * dz : 0.0;   // 0 is neutral: distances are >= 0
+                }
+                if (SPD) {
+                    double ug, vg;                                      // two divisions, as the definition: a pose against itself is 0
+                    project(cam, q, ug, vg);
+                    const double du = ue - ug, dv = ve - vg;
+                    d2[k] = ok ? du * du + dv * dv : 0.0;
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < kSymFlight; ++k) {
+                if (SSD) d3[k] = wave_max(d3[k]);
+                if (SPD) d2[k] = wave_max(d2[k]);
+            }
+            if (lane == 0) {
+#pragma unroll
+                for (int k = 0; k < kSymFlight; ++k)
+                    if (j0 + k < n) {
+                        if (SSD) red[0][wave][j0 + k] = d3[k];
+                        if (SPD) red[NM - 1][wave][j0 + k] = d2[k];
+                    }
+            }
+        }
+        __syncthreads();
+        if (tid < NM * n) {
+            const int mi = tid / n, j = tid % n;
+            double r = red[mi][0][j];
+#pragma unroll
+            for (int w = 1; w < kSymWaves; ++w) r = fmax(r, red[mi][w][j]);
+            dst[(size_t)mi * n_sym + s0 + j] = r;
+        }
+    }
+}
+
+// One block per (pair, metric): the maximum over the chunks for each symmetry (a wave per symmetry, a lane per chunk), the
+// minimum over the symmetries, one sqrt.
+__global__ __launch_bounds__(kSymThreads) void k_pose_sym_min(const double* __restrict__ partial, int chunks, int nm, int n_sym,
+                                                             double* __restrict__ out) {
+    __shared__ double red[kSymWaves];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, pair = blockIdx.x / nm, mi = blockIdx.x % nm;
+    const double* src = partial + ((size_t)pair * chunks * nm + mi) * n_sym;
+    double best = __builtin_huge_val();
+    for (int s = wave; s < n_sym; s += kSymWaves) {                     // wave-uniform: every lane reaches wave_max
+        double mx = 0.0;
+        for (int c = lane; c < chunks; c += 64) mx = fmax(mx, src[(size_t)c * nm * n_sym + s]);
+        best = fmin(best, wave_max(mx));
+    }
+    if (lane == 0) red[wave] = best;
+    __syncthreads();
+    if (tid == 0) {
+        double r = red[0];
+#pragma unroll
+        for (int w = 1; w < kSymWaves; ++w) r = fmin(r, red[w]);
+        out[blockIdx.x] = __dsqrt_rn(r);
+    }
+}
+
+void launch_pose_sym(const float* v, int nv, const SymPair* pairs, int npairs, const SymXf* xf, int n_sym, SymCam cam, bool mssd, bool mspd,
+                     double* partial, double* out, hipStream_t s) {
+    if (nv <= 0 || npairs <= 0 || n_sym <= 0 || !(mssd || mspd)) return;
+    const int chunks = sym_chunks(nv);
+    const dim3 grid(chunks, npairs), block(kSymThreads);
+    if (mssd && mspd) hipLaunchKernelGGL((k_pose_sym<true, true>), grid, block, 0, s, v, nv, pairs, xf, n_sym, cam, partial);
+    else if (mssd) hipLaunchKernelGGL((k_pose_sym<true, false>), grid, block, 0, s, v, nv, pairs, xf, n_sym, cam, partial);
+    else hipLaunchKernelGGL((k_pose_sym<false, true>), grid, block, 0, s, v, nv, pairs, xf, n_sym, cam, partial);
+    const int nm = (mssd ? 1 : 0) + (mspd ? 1 : 0);
+    hipLaunchKernelGGL(k_pose_sym_min, dim3(npairs * nm), block, 0, s, (const double*)partial, chunks, nm, n_sym, out);
 }
 
 // ---- pixel passes -----------------------------------------------------------------------------------------------

@@ -23,6 +23,28 @@ constexpr int kPtsThreads = 256, kPtsPer = 1, kPtsChunk = kPtsThreads * kPtsPer,
 
 void launch_pose_pts(const float* v, int nv, const PtsPair* pairs, int npairs, int mode, PtsPartial* partial, hipStream_t s);
 
+// Symmetry-aware maxima (MSSD, MSPD).  One composed GT-side transform per (GT, symmetry): A = R_g R_s, b = R_g t_s + t_g
+// (f64, host), stored [g][s]; a pair names its GT and carries the estimate's pose.
+struct SymXf {
+    double A[9], b[3];
+};
+struct SymPair {
+    double Re[9], te[3];
+    int g, pad;
+};
+struct SymCam {           // K, row-major f64
+    double K[9];
+};
+constexpr int kSymThreads = 256, kSymWaves = kSymThreads / 64;
+constexpr int kSymTile = 64;    // transforms staged in LDS at once (lm_pose_sym_tile)
+constexpr int kSymFlight = 4;   // symmetries evaluated per lane before the wave reduces them
+// metrics: LM_POSE_MSSD | LM_POSE_MSPD (nm = number of bits set, MSSD first).
+// partial: f64 [npairs][chunks][nm][n_sym], the largest SQUARED distance of the chunk's vertices, chunks = sym_chunks(nv).
+// out: f64 [npairs][nm] = sqrt(min over s of max over chunks).
+inline int sym_chunks(int nv) { return (nv + kSymThreads - 1) / kSymThreads; }
+void launch_pose_sym(const float* v, int nv, const SymPair* pairs, int npairs, const SymXf* xf, int n_sym, SymCam cam, bool mssd, bool mspd,
+                     double* partial, double* out, hipStream_t s);
+
 // Per (pair, block) counts of the pixel pass.  VSD: union / inter of the visibility masks and the step cost count;
 // COU: inter / union of the rendered masks.  tl: the block's tlinear cost sum (f64, fixed order).
 struct VsdPartial {

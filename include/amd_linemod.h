@@ -524,6 +524,8 @@ int lm_pipeline_set_views_rendered(lm_pipeline *p, lm_mesh *m, const char *class
 #define LM_POSE_ADI 8
 #define LM_POSE_RE 16
 #define LM_POSE_TE 32
+#define LM_POSE_MSSD 64   /* lm_mesh_pose_errors_sym only */
+#define LM_POSE_MSPD 128  /* lm_mesh_pose_errors_sym only; needs K */
 #define LM_POSE_COST_STEP 0
 #define LM_POSE_COST_TLINEAR 1
 /* out: f64 [n_metrics][n_est][n_gt], the requested metrics in the order of their bits (VSD, COU, ADD, ADI, RE, TE).
@@ -532,6 +534,20 @@ int lm_pipeline_set_views_rendered(lm_pipeline *p, lm_mesh *m, const char *class
 int lm_mesh_pose_errors(lm_mesh *m, int n_est, const double *R_est, const double *t_est, int n_gt, const double *R_gt,
                         const double *t_gt, const double *K, int width, int height, const float *scene_depth, int metrics,
                         double delta, double tau, int cost, double clip_near, double clip_far, double *out);
+/* Symmetry-aware errors of the BOP toolkit (maximum symmetry-aware surface / projection distance), for the mesh's
+ * vertices v (float32 on the device, widened to f64) and an explicit set of n_sym >= 1 symmetry transformations
+ * (R_sym [n_sym][9] row-major, t_sym [n_sym][3] mm; the identity is an entry like any other):
+ *   MSSD[e][g] = min_s max_v || (R_e v + t_e) - (R_g (R_s v + t_s) + t_g) ||                       (mm)
+ *   MSPD[e][g] = min_s max_v || proj(R_e v + t_e) - proj(R_g (R_s v + t_s) + t_g) ||               (pixels)
+ *   proj(p) = ((K p)[0] / (K p)[2], (K p)[1] / (K p)[2])
+ * f64 throughout; max and min only, so two calls are bit-identical.  metrics: LM_POSE_MSSD | LM_POSE_MSPD; out: f64
+ * [n_metrics][n_est][n_gt], MSSD then MSPD.  K may be NULL without MSPD.  A point with (K p)[2] <= 0 is the caller's
+ * problem, as in numpy: the division is carried out as it stands.  LM_ERR_INVALID: n_sym < 1, MSPD without K, other bits. */
+int lm_mesh_pose_errors_sym(lm_mesh *m, int n_est, const double *R_est, const double *t_est, int n_gt, const double *R_gt,
+                            const double *t_gt, int n_sym, const double *R_sym, const double *t_sym, const double *K,
+                            int metrics, double *out);
+/* Symmetry transformations lm_mesh_pose_errors_sym stages in LDS at once; larger sets are swept in tiles of this size. */
+int lm_pose_sym_tile(void);
 /* calc_gt_stats.py:103-155 for each GT pose: counts [n_gt][3] = px_count_all, px_count_valid, px_count_visib;
  * visib_fract [n_gt]; bbox_obj, bbox_visib [n_gt][4] = x, y, w, h (misc.calc_2d_bbox; -1s when nothing is visible).
  * pysixd renders with its defaults clip_near = 100, clip_far = 2000 here (renderer.py:306). */

@@ -1470,7 +1470,7 @@ void launch_icp_prepare(const IcpBuffers& B, int count, int W, int H, int flags,
     hipLaunchKernelGGL(k_icp_grid, dim3(count), dim3(kWG), 0, s, B, flags);
     hipLaunchKernelGGL(k_icp_knn, dim3(kn.knn_blocks > 0 ? kn.knn_blocks : (count <= 32 ? 64 : 32), count), dim3(kKnnWG), 0, s, B, knn);
     hipLaunchKernelGGL(k_icp_knn_far, dim3(kKnnFarBlocks, count), dim3(512), 0, s, B, knn);
-    hipLaunchKernelGGL(k_icp_normals, dim3(count <= 32 ? 64 : 16, count), dim3(256), 0, s, B);
+    if (!(flags & 2)) hipLaunchKernelGGL(k_icp_normals, dim3(count <= 32 ? 64 : 16, count), dim3(256), 0, s, B);   // (point-to-point reads no normals)
 }
 
 }  // namespace lm

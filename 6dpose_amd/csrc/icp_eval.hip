@@ -1,5 +1,6 @@
 // RegistrationICP + TransformationEstimationPointToPlane (reference LL.cpp:128-130), one launch per evaluation: the last stage of
-// the ICP ladder (pose_refine.cpp), which takes what k_icp_team (icp_team.hip) left, and the whole loop under LM_ICP_SLICED=1.
+// the ICP ladder (pose_refine.cpp), which takes what k_icp_team (icp_team.hip) left, and the whole loop under LM_ICP_SLICED=1, for
+// TransformationEstimationPointToPoint (k_icp_eval<true>; LL.cpp:132-134) and for criteria other than the defaults.
 //   k_icp_eval  once per ICP evaluation (<= 31 + 1): exact nearest neighbours through the grid (search radius = distance to the
 //               previous correspondence), 29 double sums by a halving wave reduction, then 6x6 LU, Rz*Ry*Rx update and the
 //               convergence test.
@@ -11,6 +12,7 @@
 #include <limits.h>
 
 #include "icp_device.h"
+#include "icp_kabsch.h"
 #include "icp_kernels.h"
 #include "knobs.h"
 
@@ -86,9 +88,14 @@ static __device__ __forceinline__ bool solve6(double (&M)[6][7], double (&x)[6])
 //       each, and all classes are walked in one sweep of the workgroup's lanes;
 // and the slice's 32 partial sums (21 JtJ upper + 6 Jtr + sum d^2 + count, padded) for the next prologue.
 // Returns true when the hypothesis is finished (converged, or evaluation max_iter done).
+// P2P: TransformationEstimationPointToPoint instead (the #else branch of LL.cpp:122-135).  Correspondences, fitness and inlier RMSE are
+// the same; the slice publishes n, sum d^2, sum p, sum q and sum q p^T (p = transformed source, q = target) in the same 32 slots (0-2,
+// 3-5, 6-14; 27 and 28 as before), and the prologue solves for [R | t] with kabsch_update (icp_kabsch.h) instead of the 6x6.  The
+// normals are not read.
+template <bool P2P>
 static __device__ __forceinline__ bool icp_eval_body(const IcpBuffers& B, IcpState& S, const int h, const int it, const int Gprev, const int max_shift, TgtRec* s_tgt,
                                                      unsigned short* s_cs, int* s_q, unsigned char* s_cls, const double max_dist,
-                                                     const int max_iter, const double rel_tol, double* fit_hist, double* rmse_hist) {
+                                                     const int max_iter, const double rel_fit, const double rel_rmse, double* fit_hist, double* rmse_hist) {
     __shared__ double s_part[kSearchWG / 64][32];
     __shared__ double s_sum[32];
     __shared__ double s_U[12];
@@ -160,7 +167,7 @@ static __device__ __forceinline__ bool icp_eval_body(const IcpBuffers& B, IcpSta
             const double fit = ncorr ? (double)ncorr / (double)ns : 0.0;
             const double rmse = ncorr ? sqrt(s_sum[27] / (double)ncorr) : 0.0;
             bool stop = false;
-            if (it > 1 && fabs(fit_hist[it & 1] - fit) < rel_tol && fabs(rmse_hist[it & 1] - rmse) < rel_tol) stop = true;
+            if (it > 1 && fabs(fit_hist[it & 1] - fit) < rel_fit && fabs(rmse_hist[it & 1] - rmse) < rel_rmse) stop = true;
             if (it - 1 == max_iter) stop = true;
             if (g == 0) { fit_hist[(it - 1) & 1] = fit; rmse_hist[(it - 1) & 1] = rmse; }
             if (g == 0) {
@@ -169,27 +176,33 @@ static __device__ __forceinline__ bool icp_eval_body(const IcpBuffers& B, IcpSta
             }
             s_stop = stop ? 1 : 0;
             if (!stop) {
-                double M[6][7], x[6];
-                {
-                    double up[21];
-#pragma unroll
-                    for (int q = 0; q < 21; ++q) up[q] = s_sum[q];
-                    int k = 0;
-#pragma unroll
-                    for (int a = 0; a < 6; ++a)
-#pragma unroll
-                        for (int c = a; c < 6; ++c) { M[a][c] = up[k]; M[c][a] = up[k]; ++k; }
-#pragma unroll
-                    for (int a = 0; a < 6; ++a) M[a][6] = -s_sum[21 + a];
-                }
                 double U[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
-                if (ncorr >= 6 && solve6(M, x)) {
-                    double sx, cx, sy, cy, sz, cz;
-                    sincos(x[0], &sx, &cx); sincos(x[1], &sy, &cy); sincos(x[2], &sz, &cz);
-                    // Rz(x2) * Ry(x1) * Rx(x0)
-                    U[0] = cz * cy; U[1] = cz * sy * sx - sz * cx; U[2] = cz * sy * cx + sz * sx; U[3] = x[3];
-                    U[4] = sz * cy; U[5] = sz * sy * sx + cz * cx; U[6] = sz * sy * cx - cz * sx; U[7] = x[4];
-                    U[8] = -sy;     U[9] = cy * sx;                U[10] = cy * cx;               U[11] = x[5];
+                if constexpr (P2P) {                        // (through LDS: a local array handed to the non-inlined solve would live in scratch)
+                    for (int a = 0; a < 12; ++a) s_U[a] = U[a];
+                    (void)kabsch_update(s_sum, ncorr, s_U);     // left as it is (the identity) when n < 3 or the result is not finite
+                    for (int a = 0; a < 12; ++a) U[a] = s_U[a];
+                } else {
+                    double M[6][7], x[6];
+                    {
+                        double up[21];
+#pragma unroll
+                        for (int q = 0; q < 21; ++q) up[q] = s_sum[q];
+                        int k = 0;
+#pragma unroll
+                        for (int a = 0; a < 6; ++a)
+#pragma unroll
+                            for (int c = a; c < 6; ++c) { M[a][c] = up[k]; M[c][a] = up[k]; ++k; }
+#pragma unroll
+                        for (int a = 0; a < 6; ++a) M[a][6] = -s_sum[21 + a];
+                    }
+                    if (ncorr >= 6 && solve6(M, x)) {
+                        double sx, cx, sy, cy, sz, cz;
+                        sincos(x[0], &sx, &cx); sincos(x[1], &sy, &cy); sincos(x[2], &sz, &cz);
+                        // Rz(x2) * Ry(x1) * Rx(x0)
+                        U[0] = cz * cy; U[1] = cz * sy * sx - sz * cx; U[2] = cz * sy * cx + sz * sx; U[3] = x[3];
+                        U[4] = sz * cy; U[5] = sz * sy * sx + cz * cx; U[6] = sz * sy * cx - cz * sx; U[7] = x[4];
+                        U[8] = -sy;     U[9] = cy * sx;                U[10] = cy * cx;               U[11] = x[5];
+                    }
                 }
                 for (int a = 0; a < 12; ++a) s_U[a] = U[a];
                 if (g == 0) {                               // transformation = update * transformation
@@ -465,18 +478,28 @@ static __device__ __forceinline__ bool icp_eval_body(const IcpBuffers& B, IcpSta
         double qx, qy, qz;
         tgt_xyz(bp, qx, qy, qz);
         const double bd = sqdist(px, py, pz, qx, qy, qz);
-        const double nx = N[3 * (size_t)bp], ny = N[3 * (size_t)bp + 1], nz = N[3 * (size_t)bp + 2];
-        const double r = (px - qx) * nx + (py - qy) * ny + (pz - qz) * nz;
-        const double J[6] = {py * nz - pz * ny, pz * nx - px * nz, px * ny - py * nx, nx, ny, nz};
-        int k = 0;
+        if constexpr (P2P) {
+            acc[0] += px; acc[1] += py; acc[2] += pz;
+            acc[3] += qx; acc[4] += qy; acc[5] += qz;
+            acc[6] += qx * px; acc[7] += qx * py; acc[8] += qx * pz;
+            acc[9] += qy * px; acc[10] += qy * py; acc[11] += qy * pz;
+            acc[12] += qz * px; acc[13] += qz * py; acc[14] += qz * pz;
+            acc[27] += bd;
+            acc[28] += 1.0;
+        } else {
+            const double nx = N[3 * (size_t)bp], ny = N[3 * (size_t)bp + 1], nz = N[3 * (size_t)bp + 2];
+            const double r = (px - qx) * nx + (py - qy) * ny + (pz - qz) * nz;
+            const double J[6] = {py * nz - pz * ny, pz * nx - px * nz, px * ny - py * nx, nx, ny, nz};
+            int k = 0;
 #pragma unroll
-        for (int a = 0; a < 6; ++a)
+            for (int a = 0; a < 6; ++a)
 #pragma unroll
-            for (int b = a; b < 6; ++b) acc[k++] += J[a] * J[b];
+                for (int b = a; b < 6; ++b) acc[k++] += J[a] * J[b];
 #pragma unroll
-        for (int a = 0; a < 6; ++a) acc[21 + a] += J[a] * r;
-        acc[27] += bd;
-        acc[28] += 1.0;
+            for (int a = 0; a < 6; ++a) acc[21 + a] += J[a] * r;
+            acc[27] += bd;
+            acc[28] += 1.0;
+        }
     }
     {
         const double v = wave_reduce32(acc, lane);
@@ -500,8 +523,9 @@ static __device__ __forceinline__ bool icp_eval_body(const IcpBuffers& B, IcpSta
     return false;
 }
 
+template <bool P2P>
 __global__ void __launch_bounds__(kSearchWG, 3)
-k_icp_eval(IcpBuffers B, int it, int prev_slices, int max_shift, double max_dist, int max_iter, double rel_tol) {
+k_icp_eval(IcpBuffers B, int it, int prev_slices, int max_shift, double max_dist, int max_iter, double rel_fit, double rel_rmse) {
     __shared__ TgtRec s_tgt[kSlabPts];
     __shared__ __attribute__((aligned(16))) unsigned short s_cs[kSlabCells + 8];
     __shared__ int s_q[kLoopQueue];
@@ -509,7 +533,7 @@ k_icp_eval(IcpBuffers B, int it, int prev_slices, int max_shift, double max_dist
     const int h = blockIdx.y;
     IcpState& S = B.st[h];
     if (S.status != 0 || S.stop != 0) return;
-    (void)icp_eval_body(B, S, h, it, prev_slices, max_shift, s_tgt, s_cs, s_q, s_cls, max_dist, max_iter, rel_tol, S.fit_hist, S.rmse_hist);
+    (void)icp_eval_body<P2P>(B, S, h, it, prev_slices, max_shift, s_tgt, s_cs, s_q, s_cls, max_dist, max_iter, rel_fit, rel_rmse, S.fit_hist, S.rmse_hist);
 }
 
 // the sliced launches of evaluations [it_from, max_iter + 1]: evaluation `it` is finished (convergence test, solve, update) by the prologue
@@ -524,7 +548,8 @@ static int icp_slices(int count, int it) {
     return it < kIcpFineFrom || kn.icp_splits > 0 ? splits : kIcpMaxSplit;
 }
 
-void launch_icp_evals(const IcpBuffers& B, int count, int it_from, int it_to, double max_dist, int max_iter, double rel_tol, hipStream_t s) {
+void launch_icp_evals(const IcpBuffers& B, int count, int it_from, int it_to, bool p2p, double max_dist, int max_iter, double rel_fit, double rel_rmse,
+                      hipStream_t s) {
     if (count <= 0) return;
     const Knobs& kn = knobs();
 #ifdef LM_DIAG
@@ -534,8 +559,9 @@ void launch_icp_evals(const IcpBuffers& B, int count, int it_from, int it_to, do
     for (int it = it_from; it <= it_to; ++it) {
         // lanes per searching point: at most 8 while every point searches (the first evaluations: more lanes only multiply the
         // set-up), 16 afterwards (few searches left: their latency is what counts) — measured, profiles/r02_icp_experiments.txt
-        hipLaunchKernelGGL(k_icp_eval, dim3(icp_slices(count, it), count), dim3(kSearchWG), 0, s, B, it, it > 0 ? icp_slices(count, it - 1) : 1,
-                           it < kIcpFineFrom ? kn.icp_maxshift : kn.icp_maxshift_late, max_dist, max_iter, rel_tol);
+        hipLaunchKernelGGL(p2p ? k_icp_eval<true> : k_icp_eval<false>, dim3(icp_slices(count, it), count), dim3(kSearchWG), 0, s, B, it,
+                           it > 0 ? icp_slices(count, it - 1) : 1, it < kIcpFineFrom ? kn.icp_maxshift : kn.icp_maxshift_late, max_dist, max_iter,
+                           rel_fit, rel_rmse);
     }
 }
 

@@ -34,15 +34,19 @@ struct lm_icp {
     int cus = 0;                   // compute units of the device: the grid of k_icp_team
     bool sliced_only = false;      // LM_ICP_SLICED=1: RegistrationICP as one launch per evaluation (k_icp_eval, rounds 1-5), no k_icp_team
     std::vector<int> stage;        // per hypothesis of the last run: the lm::IcpStage that finished it
+    lm_icp_options opt = {30, 0, 1e-6, 1e-6};   // ICPConvergenceCriteria (lm_icp_set_options)
+    bool run_p2p = false;          // the run in flight: LM_ICP_POINT_TO_POINT
+    int next_it = 0;               // the run in flight: first evaluation the sliced launches have not been enqueued for
 };
 
 
 // pose_refine.cpp
 // The ICP ladder of one run of B.count hypotheses on stream s, in two halves around the caller's synchronisation of s:
-//   enqueue: the preparation of the clouds and the first stage (k_icp_team, or the sliced launches under LM_ICP_SLICED=1), e1, then the
-//            read-back of the states into the pinned h_st;
-//   finish:  for what the first stage left unfinished the large team builds, then the sliced launches, each followed by e1, the read-back
-//            and a synchronisation; a hypothesis still unfinished after those is an error.  Fills c->stage.
+//   enqueue: the preparation of the clouds and the first stage (k_icp_team; the sliced launches under LM_ICP_SLICED=1, for
+//            LM_ICP_POINT_TO_POINT in flags and for criteria other than the defaults), e1, then the read-back of the states into the
+//            pinned h_st;
+//   finish:  for what the first stage left unfinished the large team builds, then the sliced launches (64 evaluations at a time), each
+//            followed by e1, the read-back and a synchronisation; a hypothesis still unfinished after those is an error.  Fills c->stage.
 int lm_icp_enqueue(lm_icp* c, const lm::IcpBuffers& B, int flags, lm::IcpState* h_st, hipStream_t s);
 int lm_icp_finish(lm_icp* c, const lm::IcpBuffers& B, lm::IcpState* h_st, hipStream_t s);
 int lm_icp_set_geometry(lm_icp* c, int W, int H);      // (re)allocates for a frame size; drops the slots when it changes

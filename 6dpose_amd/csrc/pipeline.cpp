@@ -78,6 +78,11 @@ extern "C" void lm_pipeline_destroy(lm_pipeline* p) {
     delete p;
 }
 
+extern "C" int lm_pipeline_set_icp_options(lm_pipeline* p, const lm_icp_options* options) {
+    if (!p) return lm_set_error(LM_ERR_INVALID, "null argument");
+    return lm_icp_set_options(p->icp, options);
+}
+
 extern "C" int lm_pipeline_set_views(lm_pipeline* p, const char* class_id, int first_template, int count, const uint16_t* const* depth_ren,
                                      const float* Ks, const float* Rs, const float* ts, const int32_t* box_wh) {
     if (!p || !class_id || first_template < 0 || count < 0 || (count && (!depth_ren || !Ks || !Rs || !ts)))

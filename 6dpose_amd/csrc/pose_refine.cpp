@@ -30,9 +30,10 @@ int lm_set_error(int code, const char* fmt, ...);   // detector.cpp
 namespace {
 constexpr double kVoxel = 0.0025;     // LL.cpp:106
 constexpr double kMaxDist = 0.01;     // LL.cpp:31
-constexpr int kMaxIter = 30;          // open3d ICPConvergenceCriteria default
+constexpr int kMaxIter = 30;          // open3d ICPConvergenceCriteria defaults (lm_icp_options_init)
 constexpr double kRelTol = 1e-6;
 constexpr int kKnn = 30;              // open3d KDTreeSearchParamKNN default
+constexpr int kEvalChunk = 64;        // evaluations the sliced launches are enqueued for at a time (the defaults need 32: one chunk)
 
 size_t pow2_at_least(size_t n) {
     size_t p = 1;
@@ -182,9 +183,27 @@ void lm_icp_compose_result(const IcpState& st, const float* model_R, const float
     o.n_target = st.n_tgt;
 }
 
+namespace {
+// k_icp_team is point-to-plane and is handed the default criteria only (it takes one tolerance for both tests, and its cut after
+// evaluation 3 and its resume path are exercised at max_iteration 30 alone): every other hypothesis goes straight to the sliced launches
+bool sliced_first(const lm_icp* c) {
+    return c->sliced_only || c->run_p2p || c->opt.max_iteration != kMaxIter || c->opt.relative_fitness != kRelTol || c->opt.relative_rmse != kRelTol;
+}
+
+// the next evaluations of the sliced launches, at most kEvalChunk of them, up to the prologue that finishes evaluation max_iteration
+void enqueue_evals(lm_icp* c, const IcpBuffers& B, hipStream_t s) {
+    const int last = c->opt.max_iteration + 1;
+    const int to = last - c->next_it < kEvalChunk ? last : c->next_it + kEvalChunk - 1;
+    launch_icp_evals(B, B.count, c->next_it, to, c->run_p2p, kMaxDist, c->opt.max_iteration, c->opt.relative_fitness, c->opt.relative_rmse, s);
+    c->next_it = to + 1;
+}
+}  // namespace
+
 int lm_icp_enqueue(lm_icp* c, const IcpBuffers& B, int flags, IcpState* h_st, hipStream_t s) {
+    c->run_p2p = (flags & LM_ICP_POINT_TO_POINT) != 0;
+    c->next_it = 0;
     launch_icp_prepare(B, B.count, c->W, c->H, flags, kVoxel, kKnn, s);
-    if (c->sliced_only) launch_icp_evals(B, B.count, 0, kMaxIter + 1, kMaxDist, kMaxIter, kRelTol, s);
+    if (sliced_first(c)) enqueue_evals(c, B, s);
     else launch_icp_team(B, B.count, kIcpStageTeam, c->cus, kMaxDist, kMaxIter, kRelTol, s);
     HIP_TRY(hipEventRecord(c->e1, s));
     HIP_TRY(hipMemcpyAsync(h_st, c->d_st, (size_t)B.count * sizeof(IcpState), hipMemcpyDeviceToHost, s));
@@ -193,7 +212,7 @@ int lm_icp_enqueue(lm_icp* c, const IcpBuffers& B, int flags, IcpState* h_st, hi
 
 int lm_icp_finish(lm_icp* c, const IcpBuffers& B, IcpState* h_st, hipStream_t s) {
     c->stage.assign((size_t)B.count, kIcpStageNone);
-    for (int stage = c->sliced_only ? kIcpStageSliced : kIcpStageTeam;; ++stage) {
+    for (int stage = sliced_first(c) ? kIcpStageSliced : kIcpStageTeam;;) {
         bool unfinished = false;                                     // (status 0, stop 0)
         for (int i = 0; i < B.count; ++i) {
             if (h_st[i].status != 0) continue;
@@ -203,9 +222,15 @@ int lm_icp_finish(lm_icp* c, const IcpBuffers& B, IcpState* h_st, hipStream_t s)
         if (!unfinished) return LM_OK;
         // clouds the first team builds do not hold (more than 704 source points per workgroup): the builds with more points per thread;
         // what those leave too, or a team that timed out: the sliced launches
-        if (stage == kIcpStageSliced) return lm_set_error(LM_ERR_HIP, "ICP: a hypothesis was left unfinished");
-        if (stage == kIcpStageTeam) launch_icp_team(B, B.count, kIcpStageLarge, c->cus, kMaxDist, kMaxIter, kRelTol, s);
-        else launch_icp_evals(B, B.count, 0, kMaxIter + 1, kMaxDist, kMaxIter, kRelTol, s);
+        // (more than kEvalChunk evaluations asked for: the next chunk)
+        if (stage == kIcpStageSliced && c->next_it > c->opt.max_iteration + 1) return lm_set_error(LM_ERR_HIP, "ICP: a hypothesis was left unfinished");
+        if (stage == kIcpStageTeam) {
+            launch_icp_team(B, B.count, kIcpStageLarge, c->cus, kMaxDist, kMaxIter, kRelTol, s);
+            stage = kIcpStageLarge;
+        } else {
+            stage = kIcpStageSliced;
+            enqueue_evals(c, B, s);
+        }
         HIP_TRY(hipEventRecord(c->e1, s));
         HIP_TRY(hipMemcpyAsync(h_st, c->d_st, (size_t)B.count * sizeof(IcpState), hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
@@ -233,6 +258,30 @@ extern "C" int lm_icp_create(int device, lm_icp** out) {
         return lm_set_error(LM_ERR_HIP, "could not create the ICP stream / events");
     }
     *out = c;
+    return LM_OK;
+}
+
+extern "C" void lm_icp_options_init(lm_icp_options* o) {
+    if (!o) return;
+    memset(o, 0, sizeof(*o));
+    o->max_iteration = kMaxIter;
+    o->relative_fitness = kRelTol;
+    o->relative_rmse = kRelTol;
+}
+
+extern "C" int lm_icp_set_options(lm_icp* c, const lm_icp_options* options) {
+    if (!c) return lm_set_error(LM_ERR_INVALID, "null argument");
+    lm_icp_options o;
+    lm_icp_options_init(&o);
+    if (options) o = *options;
+    if (o.max_iteration < 0) return lm_set_error(LM_ERR_INVALID, "max_iteration %d is negative", o.max_iteration);
+    if (o.max_iteration > INT_MAX - 2) return lm_set_error(LM_ERR_INVALID, "max_iteration %d is too large", o.max_iteration);
+    if (!(o.relative_fitness > 0.0) || !isfinite(o.relative_fitness))
+        return lm_set_error(LM_ERR_INVALID, "relative_fitness %g is not a positive finite number", o.relative_fitness);
+    if (!(o.relative_rmse > 0.0) || !isfinite(o.relative_rmse))
+        return lm_set_error(LM_ERR_INVALID, "relative_rmse %g is not a positive finite number", o.relative_rmse);
+    o.reserved = 0;
+    c->opt = o;
     return LM_OK;
 }
 

@@ -99,6 +99,7 @@ class PipelineTimings(ctypes.Structure):
 MATCH_DTYPE = np.dtype([("x", np.int32), ("y", np.int32), ("similarity", np.float32),
                         ("class_index", np.int32), ("template_id", np.int32)])
 LM_ICP_SCENE_FROM_SCENE = 1
+LM_ICP_POINT_TO_POINT = 2
 
 
 def library_path() -> str:
@@ -226,6 +227,10 @@ def load_library():
     lib.lm_icp_set_models.argtypes = [P, I, I, ctypes.POINTER(P)]
     lib.lm_icp_run.argtypes = [P, I, P, P, P, P, P, I, ctypes.POINTER(_CPoseResult), ctypes.POINTER(F)]
     lib.lm_icp_read_debug.argtypes = [P, I, I, P, ctypes.c_int64]
+    lib.lm_icp_options_init.argtypes = [ctypes.POINTER(IcpOptions)]
+    lib.lm_icp_options_init.restype = None
+    lib.lm_icp_set_options.argtypes = [P, ctypes.POINTER(IcpOptions)]
+    lib.lm_pipeline_set_icp_options.argtypes = [P, ctypes.POINTER(IcpOptions)]
     lib.lm_icp_read_debug.restype = ctypes.c_int64
     lib.lm_mesh_create.argtypes = [I, P, P, P, I, P, I, ctypes.POINTER(P)]
     lib.lm_mesh_load_ply.argtypes = [I, S, ctypes.POINTER(P)]
@@ -834,16 +839,49 @@ def NMSBoxes(bboxes, scores, score_threshold: float, nms_threshold: float, eta: 
     return keep[:n].tolist()
 
 
+class IcpOptions(ctypes.Structure):
+    """lm_icp_options (include/amd_linemod.h): open3d ICPConvergenceCriteria."""
+    _fields_ = [("max_iteration", ctypes.c_int32), ("reserved", ctypes.c_int32), ("relative_fitness", ctypes.c_double),
+                ("relative_rmse", ctypes.c_double)]
+
+
+ICP_ESTIMATIONS = ("point_to_plane", "point_to_point")
+
+
+def _icp_flags(scene_from_scene, estimation) -> int:
+    if estimation not in ICP_ESTIMATIONS:
+        raise RuntimeError("estimation must be 'point_to_plane' or 'point_to_point' (got %r)" % (estimation,))
+    return (LM_ICP_SCENE_FROM_SCENE if scene_from_scene else 0) | (LM_ICP_POINT_TO_POINT if estimation == "point_to_point" else 0)
+
+
+def _icp_options(max_iteration, relative_fitness, relative_rmse) -> Optional[IcpOptions]:
+    """The criteria as lm_icp_options, None when they are the defaults; the checks of lm_icp_set_options, made before anything is
+    created or launched."""
+    if int(max_iteration) != max_iteration or max_iteration < 0 or max_iteration > 2 ** 31 - 3:
+        raise RuntimeError("max_iteration must be an integer >= 0 (got %r)" % (max_iteration,))
+    for name, v in (("relative_fitness", relative_fitness), ("relative_rmse", relative_rmse)):
+        if not (float(v) > 0.0 and np.isfinite(float(v))):
+            raise RuntimeError("%s must be a positive finite number (got %r)" % (name, v))
+    o = IcpOptions(int(max_iteration), 0, float(relative_fitness), float(relative_rmse))
+    return None if (o.max_iteration, o.relative_fitness, o.relative_rmse) == (30, 1e-6, 1e-6) else o
+
+
 class poseRefine:
     """poseRefine (LL.h:8-19, LL.cpp:27-170).  `scene_from_scene=True` registers against the scene
-    cloud instead of reproducing LL.cpp:109 (which down-samples the model cloud twice)."""
+    cloud instead of reproducing LL.cpp:109 (which down-samples the model cloud twice).  estimation: "point_to_plane" (LL.cpp:128-130)
+    or "point_to_point" (the reference built without USE_OPEN3D_P2PL, LL.cpp:132-134); max_iteration, relative_fitness, relative_rmse:
+    open3d's ICPConvergenceCriteria (max_iteration=0: EvaluateRegistration of the initial guess).  With criteria other than the defaults
+    the object runs an IcpContext of its own instead of the shared per-device one."""
 
-    def __init__(self, device: Optional[int] = None, scene_from_scene: bool = False):
+    def __init__(self, device: Optional[int] = None, scene_from_scene: bool = False, estimation: str = "point_to_plane",
+                 max_iteration: int = 30, relative_fitness: float = 1e-6, relative_rmse: float = 1e-6):
         self.residual = -1.0                                   # poseRefine(): residual(-1)
         self._R = None
         self._t = None
         self.device = device
-        self.flags = LM_ICP_SCENE_FROM_SCENE if scene_from_scene else 0
+        self.flags = _icp_flags(scene_from_scene, estimation)
+        self._criteria = (max_iteration, relative_fitness, relative_rmse) if _icp_options(max_iteration, relative_fitness, relative_rmse) is not None else None
+        self._ctx = None
         self.info = {}
 
     def process(self, sceneDepth, modelDepth, sceneK, modelK, modelR, modelT, detectX: int, detectY: int) -> None:
@@ -861,8 +899,16 @@ class poseRefine:
         if dev is None:
             dev = int(os.environ.get("LOCAL_RANK", "0")) if lib.lm_device_count() > 1 else 0
         res = _CPoseResult()
-        _check(lib.lm_pose_refine(dev, _ptr(sd), _ptr(md), sd.shape[1], sd.shape[0], _ptr(sK), _ptr(mK), _ptr(R), _ptr(t),
-                                  int(detectX), int(detectY), self.flags, ctypes.byref(res)))
+        if self._criteria is not None:
+            if self._ctx is None:
+                self._ctx = IcpContext(dev, max_iteration=self._criteria[0], relative_fitness=self._criteria[1], relative_rmse=self._criteria[2])
+                self._ctx.flags = self.flags
+            self._ctx.set_scene(sd, sK)
+            self._ctx.set_models([md])
+            res = self._ctx._run_raw(mK, R, t, [(int(detectX), int(detectY))])[0][0]
+        else:
+            _check(lib.lm_pose_refine(dev, _ptr(sd), _ptr(md), sd.shape[1], sd.shape[0], _ptr(sK), _ptr(mK), _ptr(R), _ptr(t),
+                                      int(detectX), int(detectY), self.flags, ctypes.byref(res)))
         self.residual = float(res.residual)
         if self.residual == -1.0:                              # LL.cpp:52-55: outputs untouched
             return
@@ -882,9 +928,19 @@ class poseRefine:
 
 
 def pose_refine_batch(scene_depth, scene_K, model_depths, model_Ks, model_Rs, model_ts, detect_xy, device=0,
-                      scene_from_scene=False):
-    """lm_pose_refine_batch: top-K hypotheses of one frame in one ICP launch.  Returns (list of dict, device_ms)."""
+                      scene_from_scene=False, estimation="point_to_plane", max_iteration=30, relative_fitness=1e-6, relative_rmse=1e-6):
+    """lm_pose_refine_batch: top-K hypotheses of one frame in one ICP launch.  Returns (list of dict, device_ms).  estimation and the
+    criteria: see poseRefine; criteria other than the defaults run on an IcpContext of the call's own."""
     lib = load_library()
+    flags = _icp_flags(scene_from_scene, estimation)
+    if _icp_options(max_iteration, relative_fitness, relative_rmse) is not None:
+        ctx = IcpContext(device, scene_from_scene, estimation, max_iteration, relative_fitness, relative_rmse)
+        try:
+            ctx.set_scene(scene_depth, scene_K)
+            ctx.set_models(model_depths)
+            return ctx.run(model_Ks, model_Rs, model_ts, detect_xy)
+        finally:
+            ctx.close()
     sd = _as_depth(scene_depth, "scene_depth")
     n = len(model_depths)
     mds = [_as_depth(m, "model_depth") for m in model_depths]
@@ -897,8 +953,17 @@ def pose_refine_batch(scene_depth, scene_K, model_depths, model_Ks, model_Rs, mo
     res = (_CPoseResult * n)()
     ms = ctypes.c_float()
     _check(lib.lm_pose_refine_batch(device, _ptr(sd), sd.shape[1], sd.shape[0], _ptr(sK), n, ptrs, _ptr(Ks), _ptr(Rs), _ptr(ts),
-                                    _ptr(xy), LM_ICP_SCENE_FROM_SCENE if scene_from_scene else 0, res, ctypes.byref(ms)))
+                                    _ptr(xy), flags, res, ctypes.byref(ms)))
     return [_pose_dict(r) for r in res], float(ms.value)
+
+
+def evaluate_registration(scene_depth, scene_K, model_depths, model_Ks, model_Rs, model_ts, detect_xy, device=0, scene_from_scene=False):
+    """open3d EvaluateRegistration of every hypothesis' initial guess (LL.cpp:111-115): pose_refine_batch with max_iteration=0, nothing
+    is refined.  Returns (fitness, inlier_rmse), two float arrays with one entry per hypothesis; fitness -1 where the detection window
+    leaves the frame (LL.cpp:52-55)."""
+    res, _ = pose_refine_batch(scene_depth, scene_K, model_depths, model_Ks, model_Rs, model_ts, detect_xy, device=device,
+                               scene_from_scene=scene_from_scene, max_iteration=0)
+    return np.array([r["residual"] for r in res], np.float64), np.array([r["rmse"] for r in res], np.float64)
 
 
 def _pose_dict(r):
@@ -911,15 +976,20 @@ def _pose_dict(r):
 class IcpContext:
     """lm_icp (include/amd_linemod.h): batched poseRefine with the depth images resident in HBM.
     set_scene(depth, K) once per frame, set_models(list of depth_ren) into slots, then run(...) any
-    number of times; run returns (list of dict like pose_refine_batch, device_ms)."""
+    number of times; run returns (list of dict like pose_refine_batch, device_ms).  estimation and the criteria: see poseRefine."""
 
-    def __init__(self, device: int = 0, scene_from_scene: bool = False):
+    def __init__(self, device: int = 0, scene_from_scene: bool = False, estimation: str = "point_to_plane", max_iteration: int = 30,
+                 relative_fitness: float = 1e-6, relative_rmse: float = 1e-6):
+        flags = _icp_flags(scene_from_scene, estimation)
+        opt = _icp_options(max_iteration, relative_fitness, relative_rmse)
         lib = load_library()
         self._lib = lib
         self._h = ctypes.c_void_p()
         _check(lib.lm_icp_create(int(device), ctypes.byref(self._h)))
-        self.flags = LM_ICP_SCENE_FROM_SCENE if scene_from_scene else 0
+        self.flags = flags
         self.num_models = 0
+        if opt is not None:
+            _check(lib.lm_icp_set_options(self._h, ctypes.byref(opt)))
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
@@ -944,6 +1014,10 @@ class IcpContext:
         self.num_models = max(self.num_models, first_slot + len(mds))
 
     def run(self, model_Ks, model_Rs, model_ts, detect_xy, model_slots=None):
+        res, ms = self._run_raw(model_Ks, model_Rs, model_ts, detect_xy, model_slots)
+        return [_pose_dict(r) for r in res], ms
+
+    def _run_raw(self, model_Ks, model_Rs, model_ts, detect_xy, model_slots=None):
         n = len(detect_xy)
         Ks = np.ascontiguousarray(np.asarray(model_Ks, np.float32).reshape(n, 9))
         Rs = np.ascontiguousarray(np.asarray(model_Rs, np.float32).reshape(n, 9))
@@ -954,7 +1028,7 @@ class IcpContext:
         ms = ctypes.c_float()
         _check(self._lib.lm_icp_run(self._h, n, None if slots is None else _ptr(slots), _ptr(Ks), _ptr(Rs), _ptr(ts), _ptr(xy),
                                     self.flags, res, ctypes.byref(ms)))
-        return [_pose_dict(r) for r in res], float(ms.value)
+        return res, float(ms.value)
 
     def read_debug(self, hypothesis: int, kind: int):
         n = self._lib.lm_icp_read_debug(self._h, int(hypothesis), int(kind), None, 0)
@@ -971,14 +1045,19 @@ class Pipeline:
     nms, poseRefine on the first top_k kept matches — as one stream of device work on the detector's resident frame.
     set_views(class_id, depth_rens, Ks, Rs, ts) uploads what the driver renders per matched template; run(...) returns
     (list of dict(x, y, similarity, class_index, template_id, width, height, status, R, t, residual, iterations...),
-    timings dict)."""
+    timings dict).  estimation and the criteria of its poseRefine: see poseRefine."""
 
-    def __init__(self, detector: "Detector", width: int, height: int, scene_from_scene: bool = False):
+    def __init__(self, detector: "Detector", width: int, height: int, scene_from_scene: bool = False, estimation: str = "point_to_plane",
+                 max_iteration: int = 30, relative_fitness: float = 1e-6, relative_rmse: float = 1e-6):
+        flags = _icp_flags(scene_from_scene, estimation)
+        opt = _icp_options(max_iteration, relative_fitness, relative_rmse)
         self._lib = load_library()
         self._det = detector
         self._h = ctypes.c_void_p()
         _check(self._lib.lm_pipeline_create(detector._h, int(width), int(height), ctypes.byref(self._h)))
-        self.flags = LM_ICP_SCENE_FROM_SCENE if scene_from_scene else 0
+        self.flags = flags
+        if opt is not None:
+            _check(self._lib.lm_pipeline_set_icp_options(self._h, ctypes.byref(opt)))
         self.shape = (int(height), int(width))
 
     def close(self):

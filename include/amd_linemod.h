@@ -344,8 +344,14 @@ void lm_free(void *p);
  * t float32 3 (mm).  Outputs: R_out float64 3x3, t_out float64 3 (mm), residual (= ICP fitness,
  * or -1 when the detection window leaves the frame, LL.cpp:52-55).
  * flags: bit0 = LM_ICP_SCENE_FROM_SCENE: register against the SCENE cloud (evident intent) instead
- * of reproducing LL.cpp:109, which down-samples the model cloud twice. */
+ * of reproducing LL.cpp:109, which down-samples the model cloud twice.
+ * bit1 = LM_ICP_POINT_TO_POINT: TransformationEstimationPointToPoint (the reference built without USE_OPEN3D_P2PL,
+ * LL.cpp:132-134) instead of TransformationEstimationPointToPlane: the same correspondences, fitness and inlier RMSE, the
+ * update [R | t] of Eigen::umeyama without scaling (identity when there are fewer than 3 correspondences or it is not
+ * finite).  Such hypotheses run the sliced launches (stage 3).
+ * Public flag bits live in flags & 0xFF; 0x100 is internal. */
 #define LM_ICP_SCENE_FROM_SCENE 1
+#define LM_ICP_POINT_TO_POINT 2
 typedef struct lm_pose_result {
     double R[9];
     double t[3];
@@ -380,6 +386,19 @@ int lm_pose_refine_batch(int device, const uint16_t *scene_depth, int width, int
 typedef struct lm_icp lm_icp;
 int lm_icp_create(int device, lm_icp **out);
 void lm_icp_destroy(lm_icp *c);
+/* open3d ICPConvergenceCriteria of a context (lm_icp_options_init: the defaults, 30 / 1e-6 / 1e-6).  max_iteration >= 0;
+ * 0 is EvaluateRegistration (LL.cpp:111-115): no update, transformation_ = init_guess, fitness and inlier RMSE of that
+ * guess, iterations 0, the pose returned is init_guess * init_base.  relative_fitness, relative_rmse: > 0 and finite.
+ * Anything else: LM_ERR_INVALID, the context keeps what it had.  options == NULL restores the defaults.  Hypotheses of a
+ * context with other than the default criteria run the sliced launches (stage 3).  lm_pose_refine and
+ * lm_pose_refine_batch run a shared per-device context at the defaults. */
+typedef struct lm_icp_options {
+    int32_t max_iteration;
+    int32_t reserved;
+    double relative_fitness, relative_rmse;
+} lm_icp_options;
+void lm_icp_options_init(lm_icp_options *o);
+int lm_icp_set_options(lm_icp *c, const lm_icp_options *options);
 /* sceneDepth + sceneK of poseRefine::process (LL.cpp:27); defines the frame geometry (changing it drops the slots). */
 int lm_icp_set_scene(lm_icp *c, const uint16_t *scene_depth, int width, int height, const float *scene_K);
 /* modelDepth images (LL.cpp:27) into slots [first_slot, first_slot + count). */
@@ -421,6 +440,8 @@ typedef struct lm_pipeline_timings {
 } lm_pipeline_timings;
 int lm_pipeline_create(lm_detector *det, int width, int height, lm_pipeline **out);
 void lm_pipeline_destroy(lm_pipeline *p);
+/* lm_icp_set_options on the pipeline's own ICP context. */
+int lm_pipeline_set_icp_options(lm_pipeline *p, const lm_icp_options *options);
 /* Views of templates [first_template, first_template + count) of a class: depth rendering (uint16 [height][width],
  * mm), cam_K, cam_R_w2c (float32 3x3 row-major), cam_t_w2c (float32 3, mm); box_wh: NULL, or [count][2] int32
  * aTemplateInfo 'width','height' (the NMS box of the driver, :335-338); NULL / negative = the template's own size. */

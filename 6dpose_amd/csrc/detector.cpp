@@ -248,6 +248,40 @@ extern "C" int lm_detector_set_paths(lm_detector* d, int refine, int coarse) {
     return LM_OK;
 }
 
+extern "C" int lm_detector_set_response_table(lm_detector* d, const uint8_t r[5]) {
+    if (!d || !r) return lm_set_error(LM_ERR_INVALID, "null argument");
+    if (r[0] != 4) return lm_set_error(LM_ERR_INVALID, "response table: r[0] must be 4 (the score is raw * 100 / (4 * features)), got %d", (int)r[0]);
+    for (int k = 1; k < 5; ++k)
+        if (r[k] > r[k - 1]) return lm_set_error(LM_ERR_INVALID, "response table: must not increase with the distance, r[%d] = %d > r[%d] = %d", k, (int)r[k], k - 1, (int)r[k - 1]);
+    if (d->n_submitted != d->n_collected) return lm_set_error(LM_ERR_INVALID, "frames in flight: collect them before changing the response table");
+    int rc = lm_launch_pending(d);
+    if (rc) return rc;
+    for (int k = 0; k < 5; ++k) d->resp_table[k] = r[k];
+    d->resp = resp_pack(r);
+    d->resp_low_weight = resp_low_weight(r);
+    d->resp_two_planes = resp_two_planes(r);
+    // The byte planes the last front end left belong to the old table: lm_detector_read_stage kinds 2 / 3 build them again, from the quantised
+    // maps, under the new one.  (The bit planes, kinds 4 / 5, stay what the last match read until the next match rewrites them.)
+    d->fe_bytes_low = d->fe_bytes_top = false;
+    return LM_OK;
+}
+
+extern "C" int lm_detector_bit_arena_bytes(const lm_detector* d, uint64_t* strip_records, uint64_t* pair_stream) {
+    if (!d || !strip_records || !pair_stream) return lm_set_error(LM_ERR_INVALID, "null argument");
+    *strip_records = *pair_stream = 0;
+    for (int s = 0; s < lm_detector::kSlots; ++s) {                 // what is allocated, over all result slots (DevBuf holds bytes)
+        *strip_records += d->bits_arena[s].cap;
+        *pair_stream += d->cbits_arena[s].cap;
+    }
+    return LM_OK;
+}
+
+extern "C" int lm_detector_get_response_table(const lm_detector* d, uint8_t r[5]) {
+    if (!d || !r) return lm_set_error(LM_ERR_INVALID, "null argument");
+    for (int k = 0; k < 5; ++k) r[k] = d->resp_table[k];
+    return LM_OK;
+}
+
 extern "C" int lm_detector_set_direct_bits(lm_detector* d, int on) {
     if (!d) return lm_set_error(LM_ERR_INVALID, "null detector");
     if (d->n_submitted != d->n_collected) return lm_set_error(LM_ERR_INVALID, "frames in flight: collect them first");

@@ -274,7 +274,7 @@ extern "C" int64_t lm_detector_read_stage(lm_detector* d, int level, int kind, u
             const uint8_t* mask[2] = {sl.have_mask[0] ? b.mask[0].p : nullptr, sl.have_mask[1] ? b.mask[1].p : nullptr};
             uint8_t* lmp[2] = {d->lm_arena[d->last_arena].p + lv.lm_off[0], d->lm_arena[d->last_arena].p + lv.lm_off[1]};
             uint8_t* smp[2] = {strips ? d->sm_arena[d->last_arena].p + lv.sm_off[0] : nullptr, strips ? d->sm_arena[d->last_arena].p + lv.sm_off[1] : nullptr};
-            launch_build_lm(quant, mask, lmp, smp, q.W, q.H, lv.T, d->stream);
+            launch_build_lm(quant, mask, lmp, smp, q.W, q.H, lv.T, d->resp, d->stream);
             (void)hipStreamSynchronize(d->stream);
         }
         hipError_t e = hipMemcpy(dst, src, (size_t)std::min(size, capacity), hipMemcpyDeviceToHost);

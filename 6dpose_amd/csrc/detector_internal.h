@@ -175,6 +175,13 @@ struct lm_detector {
     // level below the top (default), 1 = byte strip planes with tiles (round 2-3's k_local), 2 = byte planes, every candidate on its own
     // (round 1).  coarse: 0 = pair stream when the refinement runs on bit planes (default), 1 = byte linear memories (k_coarse).
     int refine_mode = 0, coarse_mode = 0;
+    // The response table r[d], d = cyclic distance 0..4 (lm_detector_set_response_table; LL.cpp:1112-1124).  Per detector and per process: no file
+    // format carries it, training does not read it.  Every front end launch takes it along (FeStage::resp), so the next match of the resident frame
+    // rebuilds the response memories under the new table.  Tables with more than two distinct non-zero values run on the byte kernels.
+    uint8_t resp_table[5] = {4, 1, 0, 0, 0};
+    uint32_t resp = kRespDefault;                   // resp_pack(resp_table)
+    int resp_low_weight = 1;                        // the weight a of the bit-plane kernels' low plane
+    bool resp_two_planes = true;                    // at most two distinct non-zero values: the bit-plane kernels serve the table
     bool fe_direct = true;                          // lm_detector_set_direct_bits: the front end writes bit planes directly where nothing reads the bytes (0: bytes + k_pack_bits / k_pack_top)
     bool fe_keep_top = false;                       // lm_detector_set_direct_bits(d, 2)
     int fe_top_mode = 0;                            // lm_detector_set_direct_bits(d, 4 / 8): which writer of the pair stream (fe_job_top_bits)

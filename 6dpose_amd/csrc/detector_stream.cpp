@@ -92,6 +92,7 @@ static int run_frontend_batch(lm_detector* d, int first, int nb, hipStream_t s, 
         if ((rc = d->nrm_raw_x[b - 1].ensure((size_t)d->fW * d->fH))) return rc;
     }
     FeStage st{};
+    st.resp = d->resp;                                   // the detector's response table: every writer of response memories takes it from the launch
     auto flush = [&]() { if (st.njobs) { LM_CLOCK("launch_fe_stage"); launch_fe_stage(st, s); } st.njobs = 0; };
     auto room = [&](int jobs) { if (st.njobs + jobs > kFeMaxJobs) flush(); };
     auto build_lm_jobs = [&](int l) {                        // linear memories of level l of every frame (its quantised maps are complete)
@@ -163,9 +164,10 @@ static int run_frontend_batch(lm_detector* d, int first, int nb, hipStream_t s, 
 }
 
 // The bit-plane refinement (match.hip): any pyramid with a level below the top; entries of up to 16383 features (two
-// modalities of the reference's 8191, LL.cpp:1291).  LM_BITPLANES=0 / lm_detector_set_paths: the byte paths.
+// modalities of the reference's 8191, LL.cpp:1291).  LM_BITPLANES=0 / lm_detector_set_paths: the byte paths.  Two bits per cell carry a response
+// table of at most two distinct non-zero values; the others (4 3 2 1 0 ...) run on the byte kernels, and lm_detector_get_paths says so.
 static bool bits_active(const lm_detector* d, int num_work) {
-    return knobs().bitplanes && d->refine_mode == 0 && num_work > 0 && d->geom.levels >= 2 && d->bits_max_nf <= 16383;
+    return knobs().bitplanes && d->refine_mode == 0 && d->resp_two_planes && num_work > 0 && d->geom.levels >= 2 && d->bits_max_nf <= 16383;
 }
 // ... and the coarse pass on the pair stream of the top level (it plans no tiles, so only together with the bit-plane refinement)
 static bool cbits_active(const lm_detector* d, int num_work) {
@@ -436,7 +438,7 @@ static int record_front_end(lm_detector* d, const Batch& B) {
 static int enqueue_coarse(lm_detector* d, const Batch& B) {
     // the counters are zero on entry (reset by the slots' previous k_dedupe)
     { LM_CLOCK("launch_coarse");
-    if (B.cbits) launch_coarse_bits(B.fb, B.tb, d->geom, d->d_entries.p, d->d_feat_off.p, d->d_work.p, B.num_work, B.threshold, d->buf_cand_cap, d->cbits_byte0, d->cbits_max_nf, B.s);
+    if (B.cbits) launch_coarse_bits(B.fb, B.tb, d->geom, d->d_entries.p, d->d_feat_off.p, d->d_work.p, B.num_work, B.threshold, d->buf_cand_cap, d->cbits_byte0, d->cbits_max_nf, d->resp_low_weight, B.s);
     else launch_coarse(B.fb, d->geom, d->d_entries.p, d->d_feat_off.p, d->d_work.p, B.num_work, B.threshold, d->buf_cand_cap, B.tile_cap, B.s);
     }
     HIP_TRY(hipEventRecord(d->slot[B.first].ev[3], B.s));
@@ -450,7 +452,7 @@ static int enqueue_match(lm_detector* d, const Batch& B) {
     if (B.bits) {
         { LM_CLOCK("launch_local_bits");
         launch_local_bits(B.fb, B.bb, d->geom, d->d_entries.p, d->d_feat_word.p, d->d_work.p, d->buf_cand_cap, B.threshold, B.cap,
-                          (uint32_t)dedupe_table_slots(d->buf_cand_cap), bits_grid(d, B.nb), d->bits_max_nf, B.s); }
+                          (uint32_t)dedupe_table_slots(d->buf_cand_cap), bits_grid(d, B.nb), d->bits_max_nf, d->resp_low_weight, B.s); }
         if (B.bb.top_clear_units)     // the pair streams this launch zeroes again are clean for their slots' next frames
             for (int b = 0; b < B.nb; ++b)
                 if (B.bb.top_clear[b]) d->cbits_clean[B.slot(b)] = true;

@@ -469,8 +469,49 @@ static __device__ __forceinline__ uint32_t spread_or(const LmJob& J, const int x
     }
 }
 
+// ---- the response table (lm_kernels.h, resp_pack).  Every byte of a word is a spread byte (a lone one: the upper bytes zero). ----
+// every byte rotated left by d (1..7) inside itself
+static __device__ __forceinline__ uint32_t rot_bytes(uint32_t v, uint32_t d) {
+    const uint32_t keep = (0xFFu >> d) * 0x01010101u;                   // the bits that stay inside their byte
+    return ((v & keep) << d) | ((v >> (8u - d)) & ~(keep << d));
+}
+// bit `ori` of a byte: some orientation bit of the spread byte lies at cyclic distance <= k from ori
+static __device__ __forceinline__ uint32_t within(uint32_t v, uint32_t k) {
+    uint32_t m = v;
+    for (uint32_t d = 1; d <= k; ++d) m |= rot_bytes(v, d) | rot_bytes(v, 8u - d);
+    return m;
+}
+// the two bit planes of a table with at most two distinct non-zero values: hi = "the response is 4", lo = "it is the second value".
+// The default table (4 1 0 0 0) keeps the two rotations it always took.
+static __device__ __forceinline__ void resp_planes(uint32_t v, uint32_t resp, uint32_t& hi, uint32_t& lo) {
+    if (resp == kRespDefault) {                                         // wave-uniform
+        hi = v;
+        lo = (((v << 1) & 0xFEFEFEFEu) | ((v >> 7) & 0x01010101u) | ((v >> 1) & 0x7F7F7F7Fu) | ((v << 7) & 0x80808080u)) & ~v;
+    } else {
+        hi = within(v, (resp >> 20) & 7u);
+        lo = within(v, (resp >> 24) & 7u) & ~hi;
+    }
+}
+// the response bytes of label `ori` for the spread bytes of v, any table: r[d] = the sum of r[k] - r[k + 1] over k >= d (non-increasing, r[5] = 0)
+struct RespBytes {
+    uint32_t m[5], w[5];
+    __device__ __forceinline__ RespBytes(uint32_t v, uint32_t resp) {
+#pragma unroll
+        for (uint32_t k = 0; k < 5; ++k) {
+            m[k] = k == 0 ? v : m[k - 1] | rot_bytes(v, k) | rot_bytes(v, 8u - k);
+            w[k] = ((resp >> (4 * k)) & 15u) - (k < 4 ? (resp >> (4 * k + 4)) & 15u : 0u);
+        }
+    }
+    __device__ __forceinline__ uint32_t at(int ori) const {
+        uint32_t r = 0;
+#pragma unroll
+        for (int k = 0; k < 5; ++k) r += w[k] * ((m[k] >> ori) & 0x01010101u);
+        return r;
+    }
+};
+
 static __device__ __forceinline__ void build_lm_body(const int bx, const int by, const LmJob& J, int W, int H, int T, int Wd, int Hd, int NS, uint32_t m_wd,
-                                                     uint32_t m_t) {
+                                                     uint32_t m_t, uint32_t resp) {
     int idx = bx * 256 + threadIdx.x;                    // decimated raster index
     int phase = by;                                      // r_start*T + c_start
     int npos = Wd * Hd;
@@ -484,6 +525,16 @@ static __device__ __forceinline__ void build_lm_body(const int bx, const int by,
     uint8_t* o = J.lm + (size_t)phase * npos + idx;
     const size_t splane1 = (size_t)NS * Hd * 16;             // one (label, phase) plane in strip form
     uint8_t* so = J.strips ? J.strips + (size_t)phase * splane1 + ((size_t)(rx >> 4) * Hd + ry) * 16 + (rx & 15) : nullptr;
+    if (resp != kRespDefault) {                              // wave-uniform: another table than 4 1 0 0 0
+        const RespBytes rb(v, resp);
+#pragma unroll
+        for (int ori = 0; ori < 8; ++ori) {
+            const uint8_t r = (uint8_t)rb.at(ori);
+            o[plane * ori] = r;
+            if (so) so[splane1 * T * T * ori] = r;
+        }
+        return;
+    }
 #pragma unroll
     for (int ori = 0; ori < 8; ++ori) {
         uint8_t r = ((v >> ori) & 1u) ? 4 : (((adj >> ori) & 1u) ? 1 : 0);
@@ -497,7 +548,7 @@ static __device__ __forceinline__ void build_lm_body(const int bx, const int by,
 // one dword each to the flat plane and to the strip plane, 4 stores per lane instead of 16 byte stores (the launch is bound by the
 // number of store instructions: 44 MB per 4-frame batch took 48 us = 0.9 TB/s).
 static __device__ __forceinline__ void build_lm_body4(const int bx, const int by, const LmJob& J, int W, int H, int T, int Wd, int Hd, int NS, uint32_t m_wd,
-                                                      uint32_t m_t) {
+                                                      uint32_t m_t, uint32_t resp) {
     const int idx = bx * 256 + (int)threadIdx.x;         // decimated raster index
     const int phase = by;
     const int npos = Wd * Hd;
@@ -518,6 +569,17 @@ static __device__ __forceinline__ void build_lm_body4(const int bx, const int by
     const size_t splane1 = (size_t)NS * Hd * 16;
     uint8_t* o = J.lm + (size_t)phase * npos + idx0;
     uint8_t* so = J.strips ? J.strips + (size_t)phase * splane1 + ((size_t)(rx0 >> 4) * Hd + ry) * 16 + (rx0 & 15) : nullptr;
+    if (resp != kRespDefault) {                              // wave-uniform: another table than 4 1 0 0 0
+        const RespBytes rb(vq[0] | (vq[1] << 8) | (vq[2] << 16) | (vq[3] << 24), resp);
+#pragma unroll
+        for (int li = 0; li < 2; ++li) {
+            const int ori = 2 * k4 + li;
+            const uint32_t packed = rb.at(ori);
+            *reinterpret_cast<uint32_t*>(o + plane * ori) = packed;
+            if (so) *reinterpret_cast<uint32_t*>(so + splane1 * T * T * ori) = packed;
+        }
+        return;
+    }
 #pragma unroll
     for (int li = 0; li < 2; ++li) {
         const int ori = 2 * k4 + li;
@@ -532,16 +594,16 @@ static __device__ __forceinline__ void build_lm_body4(const int bx, const int by
     }
 }
 
-__global__ void __launch_bounds__(256) k_build_lm(LmJob j0, LmJob j1, int W, int H, int T, int Wd, int Hd, int NS, uint32_t m_wd, uint32_t m_t) {
-    if ((Wd & 3) == 0) build_lm_body4(blockIdx.x, blockIdx.y, blockIdx.z ? j1 : j0, W, H, T, Wd, Hd, NS, m_wd, m_t);
-    else build_lm_body(blockIdx.x, blockIdx.y, blockIdx.z ? j1 : j0, W, H, T, Wd, Hd, NS, m_wd, m_t);
+__global__ void __launch_bounds__(256) k_build_lm(LmJob j0, LmJob j1, int W, int H, int T, int Wd, int Hd, int NS, uint32_t m_wd, uint32_t m_t, uint32_t resp) {
+    if ((Wd & 3) == 0) build_lm_body4(blockIdx.x, blockIdx.y, blockIdx.z ? j1 : j0, W, H, T, Wd, Hd, NS, m_wd, m_t, resp);
+    else build_lm_body(blockIdx.x, blockIdx.y, blockIdx.z ? j1 : j0, W, H, T, Wd, Hd, NS, m_wd, m_t, resp);
 }
 
 void launch_build_lm(const uint8_t* const quant[2], const uint8_t* const mask[2], uint8_t* const lm[2], uint8_t* const strips[2],
-                     int W, int H, int T, hipStream_t s) {
+                     int W, int H, int T, uint32_t resp, hipStream_t s) {
     int Wd = W / T, Hd = H / T, NS = (Wd + 15) / 16;
     LmJob j0{quant[0], mask[0], lm[0], strips[0]}, j1{quant[1], mask[1], lm[1], strips[1]};
-    hipLaunchKernelGGL(k_build_lm, dim3((Wd * Hd + 255) / 256, T * T, 2), dim3(256), 0, s, j0, j1, W, H, T, Wd, Hd, NS, div_magic((uint32_t)Wd), div_magic((uint32_t)T));
+    hipLaunchKernelGGL(k_build_lm, dim3((Wd * Hd + 255) / 256, T * T, 2), dim3(256), 0, s, j0, j1, W, H, T, Wd, Hd, NS, div_magic((uint32_t)Wd), div_magic((uint32_t)T), resp);
 }
 
 // ---- the bit planes written directly -------------------------------------------------------------------------------
@@ -558,7 +620,7 @@ constexpr int kBitsCells = 1152;              // 16-bit cell words of a workgrou
 static __host__ __device__ inline int fe_bits_rows(int Wd) { const int wp = ((Wd + 15) / 16) * 16 + 16; const int r = kBitsCells / wp; return r < 8 ? r : 8; }
 
 static __device__ __forceinline__ void bits_rows_body(const int bx, const int by, const LmJob& J, int W, int H, int T, int Wd, int Hd, int NS, uint32_t m_wd,
-                                                      uint32_t m_t, uint16_t* __restrict__ s_cells /* kBitsCells */) {
+                                                      uint32_t m_t, uint16_t* __restrict__ s_cells /* kBitsCells */, uint32_t resp) {
     const int Wp = NS * 16 + 16, R = fe_bits_rows(Wd);
     const int phase = by, ry0 = bx * R;
     const int rows = Hd - ry0 < R ? Hd - ry0 : R;
@@ -574,8 +636,9 @@ static __device__ __forceinline__ void bits_rows_body(const int bx, const int by
         w[k] = 0;
         if (i < rows * Wp && rx < Wd) {
             const uint32_t v = spread_or(J, rx * T + cs, (ry0 + r) * T + rs, W, H, T);
-            const uint32_t adj = ((v << 1) | (v >> 7) | (v >> 1) | (v << 7)) & 0xFFu;
-            w[k] = (adj & ~v) | (v << 8);
+            uint32_t hi, lo;
+            resp_planes(v, resp, hi, lo);
+            w[k] = lo | (hi << 8);
         }
     }
 #pragma unroll
@@ -606,7 +669,7 @@ static __device__ __forceinline__ void bits_rows_body(const int bx, const int by
 // (phase, position) as in the byte stage; a wave's 64 consecutive positions of a label's plane are 64 consecutive bits of the stream at an
 // arbitrary bit offset (planes are not multiples of 32 positions): the ballots are shifted into place and OR-ed into the three dwords
 // they touch.  The stream was zeroed by a job of the batch's first launch (fe_job_zero).
-static __device__ __forceinline__ void top_bits_body(const int bx, const int by, const LmJob& J, int W, int H, int T, int Wd, int Hd, uint32_t m_wd, uint32_t m_t) {
+static __device__ __forceinline__ void top_bits_body(const int bx, const int by, const LmJob& J, int W, int H, int T, int Wd, int Hd, uint32_t m_wd, uint32_t m_t, uint32_t resp) {
     const int idx = bx * 256 + (int)threadIdx.x;
     const int phase = by, npos = Wd * Hd;
     const bool in = idx < npos;
@@ -616,7 +679,8 @@ static __device__ __forceinline__ void top_bits_body(const int bx, const int by,
         const int rs = (int)fast_div((uint32_t)phase, m_t, (uint32_t)T), cs = phase - rs * T;
         v = spread_or(J, rx * T + cs, ry * T + rs, W, H, T);
     }
-    const uint32_t one = (((v << 1) | (v >> 7) | (v >> 1) | (v << 7)) & 0xFFu) & ~v;
+    uint32_t one;
+    resp_planes(v, resp, v, one);                                         // from here on v = "the response is 4", one = "it is the second value"
     const int lane = (int)threadIdx.x & 63;
     const uint32_t idx0 = (uint32_t)(idx - lane);                         // the wave's first position (wave-uniform)
     uint32_t* stream = reinterpret_cast<uint32_t*>(J.lm);                 // pair p: stream[2 p] = is 1, stream[2 p + 1] = is 4
@@ -642,7 +706,7 @@ static __device__ __forceinline__ void top_bits_body(const int bx, const int by,
 // even number of... any grid whose T^2 W_d H_d is): one thread per bit of a label's T * T * positions planes taken as ONE run — phase and
 // position follow from the bit index —, a wave = 64 consecutive bits of that run in EVERY label's block, so its ballots are whole dwords:
 // lane `label` stores the two pairs {is 1, is 4} x 2 with one 16-byte store.  No atomics, nothing to zero beforehand.
-static __device__ __forceinline__ void top_bits_aligned_body(const int bx, const LmJob& J, int W, int H, int T, int Wd, int Hd, uint32_t m_wd, uint32_t m_t, uint32_t m_np) {
+static __device__ __forceinline__ void top_bits_aligned_body(const int bx, const LmJob& J, int W, int H, int T, int Wd, int Hd, uint32_t m_wd, uint32_t m_t, uint32_t m_np, uint32_t resp) {
     const int npos = Wd * Hd, run = T * T * npos;
     const int b = bx * 256 + (int)threadIdx.x;
     const bool in = b < run;
@@ -653,7 +717,8 @@ static __device__ __forceinline__ void top_bits_aligned_body(const int bx, const
         const int rs = (int)fast_div((uint32_t)phase, m_t, (uint32_t)T), cs = phase - rs * T;
         v = spread_or(J, rx * T + cs, ry * T + rs, W, H, T);
     }
-    const uint32_t one = (((v << 1) | (v >> 7) | (v >> 1) | (v << 7)) & 0xFFu) & ~v;
+    uint32_t one;
+    resp_planes(v, resp, v, one);                                         // v = "the response is 4", one = "it is the second value"
     const int lane = (int)threadIdx.x & 63;
     const uint32_t b0 = (uint32_t)(b - lane);                             // the wave's first bit of the run (a multiple of 64)
     uint4 mine = make_uint4(0u, 0u, 0u, 0u);
@@ -742,13 +807,9 @@ static __device__ __forceinline__ void tile_spread(const int ry, const LmJob& J,
     }
     __syncthreads();
 }
-// response 1 of a label = a neighbouring label's bit without its own (LL.cpp:1121), on four packed spread bytes
-static __device__ __forceinline__ uint32_t only_neighbours(uint32_t v) {
-    return (((v << 1) & 0xFEFEFEFEu) | ((v >> 7) & 0x01010101u) | ((v >> 1) & 0x7F7F7F7Fu) | ((v << 7) & 0x80808080u)) & ~v;
-}
 
 template <int kT>
-static __device__ __forceinline__ void top_bits_tile_body(const int ry, const LmJob& J, int W, int H, int Wd, int Hd, uint32_t* __restrict__ s_tile) {
+static __device__ __forceinline__ void top_bits_tile_body(const int ry, const LmJob& J, int W, int H, int Wd, int Hd, uint32_t* __restrict__ s_tile, uint32_t resp) {
     const int RW = W / 4 + kT / 4, tid = (int)threadIdx.x;
     uint32_t* const s_sp = s_tile + (2 * kT - 1) * RW;
     tile_spread<kT>(ry, J, W, H, RW, s_tile, s_sp);
@@ -761,9 +822,10 @@ static __device__ __forceinline__ void top_bits_tile_body(const int ry, const Lm
         unsigned long long v = 0;
 #pragma unroll
         for (int j = 0; j < 8; ++j) v |= (unsigned long long)sp[rs * (RW * 4) + (8 * g + j) * kT + cs] << (8 * j);
-        const unsigned long long adj = ((v << 1) & 0xFEFEFEFEFEFEFEFEull) | ((v >> 7) & 0x0101010101010101ull) |
-                                       ((v >> 1) & 0x7F7F7F7F7F7F7F7Full) | ((v << 7) & 0x8080808080808080ull);
-        const unsigned long long t4 = transpose8x8(v), t1 = transpose8x8(adj & ~v);
+        uint32_t h0, l0, h1, l1;
+        resp_planes((uint32_t)v, resp, h0, l0);
+        resp_planes((uint32_t)(v >> 32), resp, h1, l1);
+        const unsigned long long t4 = transpose8x8(((unsigned long long)h1 << 32) | h0), t1 = transpose8x8(((unsigned long long)l1 << 32) | l0);
         const uint32_t b = top_bit0 + (uint32_t)phase * (uint32_t)npos + (uint32_t)(ry * Wd + 8 * g);    // bit position (label 0) from the stream's start: a multiple of 8
 #pragma unroll
         for (int l = 0; l < 8; ++l) {
@@ -793,7 +855,7 @@ static __host__ __device__ inline int fe_rows_block_rows(int NS, int T) {       
     return 0;
 }
 template <int kT>
-static __device__ __forceinline__ void bits_rows_block_body(const int blk, const int part, const int csn, const LmJob& J, int W, int H, int Wd, int Hd, int NS, uint32_t* __restrict__ s_tile) {
+static __device__ __forceinline__ void bits_rows_block_body(const int blk, const int part, const int csn, const LmJob& J, int W, int H, int Wd, int Hd, int NS, uint32_t* __restrict__ s_tile, uint32_t resp) {
     const int rs = part / (kT / csn), cs0 = (part - rs * (kT / csn)) * csn;        // a workgroup takes csn of the kT column phases of its row phase
     const int RW = (NS + 1) * 4 * kT, R = fe_rows_block_rows(NS, kT);       // dwords per spread row: the pixels of 16 NS + 16 cells
     const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6, ry0 = blk * R;
@@ -855,8 +917,9 @@ static __device__ __forceinline__ void bits_rows_block_body(const int blk, const
             unsigned long long t[4];
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
-                const uint32_t v = (uint32_t)cell[(4 * k) * kT] | ((uint32_t)cell[(4 * k + 1) * kT] << 8) | ((uint32_t)cell[(4 * k + 2) * kT] << 16) | ((uint32_t)cell[(4 * k + 3) * kT] << 24);
-                const uint32_t o = only_neighbours(v);
+                uint32_t v = (uint32_t)cell[(4 * k) * kT] | ((uint32_t)cell[(4 * k + 1) * kT] << 8) | ((uint32_t)cell[(4 * k + 2) * kT] << 16) | ((uint32_t)cell[(4 * k + 3) * kT] << 24);
+                uint32_t o;
+                resp_planes(v, resp, v, o);                                // v = "is 4", o = "is the second value" (4 1 0 0 0: own bit / only a neighbour's)
                 // rows of the bit matrix: o0 v0 o1 v1 | o2 v2 o3 v3
                 const uint32_t lo = __builtin_amdgcn_perm(v, o, 0x05010400u), hi = __builtin_amdgcn_perm(v, o, 0x07030602u);
                 t[k] = transpose8x8(((unsigned long long)hi << 32) | lo);  // byte l = label l: bits 2c, 2c + 1 of cells 4 k .. 4 k + 3
@@ -912,8 +975,8 @@ k_fe_stage(FeStage st, int total) {
             case kFePyrDown: pyrdown_body(bx, by, (const uint8_t*)J.in, (uint8_t*)J.out0, J.W, J.H, J.a, J.b); break;
             case kFeNnDown: nn_down2_body(bx, by, (const uint8_t*)J.in, (uint8_t*)J.out0, J.W, J.a); break;
             case kFeBuildLm:
-                if ((J.Wd & 3) == 0) build_lm_body4(bx, by, J.lm[bz], J.W, J.H, J.a, J.Wd, J.Hd, (J.Wd + 15) >> 4, J.m_wd, J.m_t);
-                else build_lm_body(bx, by, J.lm[bz], J.W, J.H, J.a, J.Wd, J.Hd, (J.Wd + 15) >> 4, J.m_wd, J.m_t);
+                if ((J.Wd & 3) == 0) build_lm_body4(bx, by, J.lm[bz], J.W, J.H, J.a, J.Wd, J.Hd, (J.Wd + 15) >> 4, J.m_wd, J.m_t, st.resp);
+                else build_lm_body(bx, by, J.lm[bz], J.W, J.H, J.a, J.Wd, J.Hd, (J.Wd + 15) >> 4, J.m_wd, J.m_t, st.resp);
                 break;
             default: break;
         }
@@ -934,15 +997,15 @@ k_fe_bits(FeStage st, int total) {
         const int local = blk - J.first;
         const int bz = (int)fast_div((uint32_t)local, J.m_gxgy, (uint32_t)(J.gx * J.gy)), rem = local - bz * J.gx * J.gy;
         const int by = (int)fast_div((uint32_t)rem, J.m_gx, (uint32_t)J.gx), bx = rem - by * J.gx;
-        if (J.kind == kFeBitsRows) bits_rows_body(bx, by, J.lm[bz], J.W, J.H, J.a, J.Wd, J.Hd, (J.Wd + 15) >> 4, J.m_wd, J.m_t, reinterpret_cast<uint16_t*>(s_tile));
-        else if (J.kind == kFeTopBits) top_bits_body(bx, by, J.lm[bz], J.W, J.H, J.a, J.Wd, J.Hd, J.m_wd, J.m_t);
-        else if (J.kind == kFeTopBitsAligned) top_bits_aligned_body(bx, J.lm[bz], J.W, J.H, J.a, J.Wd, J.Hd, J.m_wd, J.m_t, J.m_np);
+        if (J.kind == kFeBitsRows) bits_rows_body(bx, by, J.lm[bz], J.W, J.H, J.a, J.Wd, J.Hd, (J.Wd + 15) >> 4, J.m_wd, J.m_t, reinterpret_cast<uint16_t*>(s_tile), st.resp);
+        else if (J.kind == kFeTopBits) top_bits_body(bx, by, J.lm[bz], J.W, J.H, J.a, J.Wd, J.Hd, J.m_wd, J.m_t, st.resp);
+        else if (J.kind == kFeTopBitsAligned) top_bits_aligned_body(bx, J.lm[bz], J.W, J.H, J.a, J.Wd, J.Hd, J.m_wd, J.m_t, J.m_np, st.resp);
         else if (J.kind == kFeBitsRowsTile) {
-            if (J.a == 8) bits_rows_block_body<8>(bx, by, J.b, J.lm[bz], J.W, J.H, J.Wd, J.Hd, (J.Wd + 15) >> 4, s_tile);
-            else if (J.a == 5) bits_rows_block_body<5>(bx, by, J.b, J.lm[bz], J.W, J.H, J.Wd, J.Hd, (J.Wd + 15) >> 4, s_tile);
-            else bits_rows_block_body<4>(bx, by, J.b, J.lm[bz], J.W, J.H, J.Wd, J.Hd, (J.Wd + 15) >> 4, s_tile);
+            if (J.a == 8) bits_rows_block_body<8>(bx, by, J.b, J.lm[bz], J.W, J.H, J.Wd, J.Hd, (J.Wd + 15) >> 4, s_tile, st.resp);
+            else if (J.a == 5) bits_rows_block_body<5>(bx, by, J.b, J.lm[bz], J.W, J.H, J.Wd, J.Hd, (J.Wd + 15) >> 4, s_tile, st.resp);
+            else bits_rows_block_body<4>(bx, by, J.b, J.lm[bz], J.W, J.H, J.Wd, J.Hd, (J.Wd + 15) >> 4, s_tile, st.resp);
         }
-        else if (J.kind == kFeTopBitsTile) { if (J.a == 8) top_bits_tile_body<8>(bx, J.lm[bz], J.W, J.H, J.Wd, J.Hd, s_tile); else top_bits_tile_body<4>(bx, J.lm[bz], J.W, J.H, J.Wd, J.Hd, s_tile); }
+        else if (J.kind == kFeTopBitsTile) { if (J.a == 8) top_bits_tile_body<8>(bx, J.lm[bz], J.W, J.H, J.Wd, J.Hd, s_tile, st.resp); else top_bits_tile_body<4>(bx, J.lm[bz], J.W, J.H, J.Wd, J.Hd, s_tile, st.resp); }
         if (blk + (int)gridDim.x < total) __syncthreads();      // the next block of rows reuses the cell words in LDS
     }
 }
@@ -1032,6 +1095,7 @@ void launch_fe_bits(FeStage& st, hipStream_t s) {
     if (knobs().fe_bits_split) {                          // LM_FE_BITS_SPLIT=1 (measurements): the strip-record jobs and the pair-stream jobs as two launches
         for (int kind : {kFeBitsRows, kFeTopBits}) {
             FeStage part{};
+            part.resp = st.resp;
             for (int i = 0; i < st.njobs; ++i) if ((st.job[i].kind == kFeBitsRows || st.job[i].kind == kFeBitsRowsTile) == (kind == kFeBitsRows)) part.job[part.njobs++] = st.job[i];
             const int total = fe_prepare(part);
             if (total > 0) hipLaunchKernelGGL(k_fe_bits, dim3(std::min(total, fe_cus() * 8)), dim3(256), 0, s, part, total);

@@ -6,6 +6,23 @@
 
 namespace lm {
 
+// ---- the response table (LL.cpp:1112-1124: five SIMILARITY_LUTs, :1121 the live one) ----
+// r[d] = the response to a feature whose label lies at cyclic distance d (0..4) from the nearest orientation bit of the spread byte; r[0] = 4,
+// non-increasing.  The kernels take it packed: nibble d = r[d]; bits 20..22 = kh, the largest d with r[d] = 4; bits 24..26 = kl, the largest d
+// whose response is the table's SECOND distinct non-zero value (kl = kh when there is none).  The two bit planes of the bit-plane kernels are
+// "distance <= kh" (weight 4) and "kh < distance <= kl" (weight a = r[kl]): exact for every table with at most two distinct non-zero values.
+constexpr uint32_t kRespDefault = 0x01000014u;   // 4 1 0 0 0: kh = 0, kl = 1
+inline uint32_t resp_pack(const uint8_t r[5]) {
+    uint32_t p = 0, kh = 0, kl;
+    for (int d = 0; d < 5; ++d) p |= (uint32_t)(r[d] & 15u) << (4 * d);
+    while (kh < 4 && r[kh + 1] == 4) ++kh;
+    kl = kh;
+    if (kh < 4 && r[kh + 1] != 0) { kl = kh + 1; while (kl < 4 && r[kl + 1] == r[kh + 1]) ++kl; }
+    return p | (kh << 20) | (kl << 24);
+}
+inline int resp_low_weight(const uint8_t r[5]) { const uint32_t p = resp_pack(r), kh = (p >> 20) & 7u, kl = (p >> 24) & 7u; return kl > kh ? r[kl] : 1; }   // a (1 when the low plane is empty)
+inline bool resp_two_planes(const uint8_t r[5]) { const uint32_t kl = (resp_pack(r) >> 24) & 7u; return kl == 4 || r[kl + 1] == 0; }          // nothing non-zero beyond the second value
+
 // ---- front end (frontend.hip): reference A1-A7, LL.cpp:350-505, 557-581, 729-880, 1026-1243 ----
 void upload_normal_lut(const uint8_t lut400[400]);
 // the colour chain (blur7 + sobel_quant + hysteresis) and the normal chain (normals + median5) as single tiled launches
@@ -17,7 +34,7 @@ void launch_nn_down2(const uint8_t* src, uint8_t* dst, int W, int H, hipStream_t
 // launch ([0] colour, [1] normals); mask[m] may be null; `strips[m]` (may be null) receives the strip-major copy used by
 // the refinement kernel.
 void launch_build_lm(const uint8_t* const quant[2], const uint8_t* const mask[2], uint8_t* const lm[2], uint8_t* const strips[2],
-                     int W, int H, int T, hipStream_t s);
+                     int W, int H, int T, uint32_t resp /* resp_pack */, hipStream_t s);
 
 // several independent jobs of the front end in one launch (frontend.hip, k_fe_stage)
 struct LmJob { const uint8_t* quant; const uint8_t* mask; uint8_t* lm; uint8_t* strips; };
@@ -37,7 +54,7 @@ struct FeJob {
     LmJob lm[2];                          // build_lm: [0] colour, [1] normals
 };
 constexpr int kFeMaxJobs = 24;            // 3-4 jobs per frame of a batch (stage 1), kMaxLevels per frame in the last stage: the struct is a kernel argument (< 4 KB)
-struct FeStage { int njobs; FeJob job[kFeMaxJobs]; };
+struct FeStage { int njobs; uint32_t resp = kRespDefault /* resp_pack: every writer of response memories of the launch */; FeJob job[kFeMaxJobs]; };
 static_assert(sizeof(FeStage) + 16 <= 4096, "FeStage is passed by value: kernel arguments are limited to 4 KB");
 void fe_job_colour(FeJob& j, const uint8_t* rgb, float* mag, uint8_t* onehot, int W, int H, float thr_sq);
 void fe_job_normals(FeJob& j, const uint16_t* depth, uint8_t* raw, uint8_t* med, int W, int H, int dist_thr, int diff_thr);
@@ -136,12 +153,12 @@ struct FrameBatch {
 struct BitsBatch { const uint8_t* strips[kMaxBatch]; uint8_t* bits[kMaxBatch];
                    uint8_t* top_clear[kMaxBatch]; uint32_t top_clear_units; };   // != 0: k_local_bits zeroes 16 x units bytes of every frame's pair stream (the front end ORs the next frame into it)
 constexpr int kBitsSmallMax = 511;            // features per template entry the 9-bit counters hold; larger entries (<= 16383) take the 14-bit instantiation
-void launch_pack_bits(const BitsBatch& B, int nb, const LevelGeom& lv, hipStream_t s);
+void launch_pack_bits(const BitsBatch& B, int nb, const LevelGeom& lv, hipStream_t s);      // bytes {0, a, 4} -> {is a, is 4}, any a in 1..3
 // Every level below the top: todo[ci] = 1 for the candidates it leaves to launch_local's per-candidate path (windows leaving their planes);
 // max_features = the largest nf of the bank's entries below the top level.
 void launch_local_bits(const FrameBatch& fb, const BitsBatch& B, const FrameGeom& g, const TemplEntry* entries, const uint32_t* feat_word,
                        const int32_t* work_pyramids, uint32_t cand_cap, float threshold, uint32_t cap, uint32_t dedupe_cap_slots, int grid_blocks,
-                       int max_features, hipStream_t s);
+                       int max_features, int low_weight /* a: the sum is a n_a + 4 n_4 */, hipStream_t s);
 // Coarse pass on bit planes: per frame of a batch the flat arena and the pair stream of bytes [byte0, byte0 + 32 npairs) of it (the top
 // level's blocks of both modalities with their zero tails): launch_pack_top packs it from the bytes, the front end writes it directly when
 // nothing reads the top level's bytes (frontend.hip, top_bits_body: the stream must be zero before).
@@ -149,7 +166,7 @@ struct TopBits { const uint8_t* lm[kMaxBatch]; uint8_t* bits[kMaxBatch]; };
 void launch_pack_top(const TopBits& B, int nb, uint32_t byte0, uint32_t npairs, hipStream_t s);
 // candidates only (no tiles); max_features = the largest nf of the bank's top-level entries
 void launch_coarse_bits(const FrameBatch& fb, const TopBits& B, const FrameGeom& g, const TemplEntry* entries, const int32_t* feat_off,
-                        const int32_t* work_pyramids, int num_work, float threshold, uint32_t cap, uint32_t byte0, int max_features, hipStream_t s);
+                        const int32_t* work_pyramids, int num_work, float threshold, uint32_t cap, uint32_t byte0, int max_features, int low_weight, hipStream_t s);
 bool tile_plan_possible(const FrameGeom& g);
 size_t coarse_plan_lds_bytes(int Wd, int Hd);
 // Per frame of the batch: counters[0] = number of candidates produced (may exceed cap: nothing is written past cap); with tiles

@@ -959,11 +959,37 @@ static __device__ __forceinline__ void add_eights1(uint32_t (&c)[kN], uint32_t e
     for (int k = 4; k < kN; ++k) { const uint32_t t = c[k] & k16; c[k] ^= k16; k16 = t; }
 }
 
+// The bit-sliced sum S = a n_a + 4 n_4 of two bit-sliced counts (kA = a: the weight of the low plane, lm_kernels.h resp_pack; 1 for the
+// default table 4 1 0 0 0, whose instantiation is the code it always was).  n_a + n_4 <= features, so kN + 3 bits hold any of them.
+template <int kA, int kN>
+static __device__ __forceinline__ void weighted_sum(uint32_t (&S)[kN + 3], const uint32_t (&na)[kN], const uint32_t (&n4)[kN]) {
+    constexpr int kS = kN + 3;
+    uint32_t carry = 0;
+    if (kA == 1) {
+        S[0] = na[0]; S[1] = na[1];
+#pragma unroll
+        for (int k = 2; k < kS; ++k) csa(S[k], carry, k < kN ? na[k] : 0u, k - 2 < kN ? n4[k - 2] : 0u, carry);
+    } else if (kA == 2) {
+        S[0] = 0u; S[1] = na[0];
+#pragma unroll
+        for (int k = 2; k < kS; ++k) csa(S[k], carry, k - 1 < kN ? na[k - 1] : 0u, k - 2 < kN ? n4[k - 2] : 0u, carry);
+    } else {                                                        // 3 n_a = n_a + 2 n_a first (kN + 2 bits), then + 4 n_4
+        uint32_t t[kN + 2];
+        t[0] = na[0];
+#pragma unroll
+        for (int k = 1; k < kN + 2; ++k) csa(t[k], carry, k < kN ? na[k] : 0u, k - 1 < kN ? na[k - 1] : 0u, carry);
+        carry = 0;
+        S[0] = t[0]; S[1] = t[1];
+#pragma unroll
+        for (int k = 2; k < kS; ++k) csa(S[k], carry, k < kN + 2 ? t[k] : 0u, k - 2 < kN ? n4[k - 2] : 0u, carry);
+    }
+}
+
 // 4 response bytes -> 8 bits, cell k at bits 2k (is 1 = bit 0 of the byte) and 2k + 1 (is 4 = bit 2 of the byte); the multiply gathers the
 // four 2-bit fields into the top byte (partial products land on distinct bits: no carries)
+// (any table of two planes: the bytes are 0, a or 4 with a = 1, 2 or 3 — "is a" = bit 0 or bit 1 of the byte)
 static __device__ __forceinline__ uint32_t pack4(uint32_t d) {
-    const uint32_t e = d & 0x05050505u;
-    const uint32_t t = (e | (e >> 1)) & 0x03030303u;
+    const uint32_t t = ((d | (d >> 1)) & 0x01010101u) | ((d >> 1) & 0x02020202u);
     return (t * 0x01041040u) >> 24;
 }
 static __device__ __forceinline__ uint32_t pack16(const uint4& v) { return pack4(v.x) | (pack4(v.y) << 8) | (pack4(v.z) << 16) | (pack4(v.w) << 24); }
@@ -998,7 +1024,7 @@ k_pack_bits(BitsBatch B, uint32_t sm_off0, uint32_t records, int NS, int Hd) {
 // All pyramid levels below the top are walked here (LL.cpp:1855: level by level, dropping a candidate as soon as it falls below the
 // threshold); a candidate whose windows leave their planes at some level (oversized template, features outside the frame) is marked in
 // `todo` and left, from the top, to k_local's per-candidate path.
-template <int kHi, int kWaves>
+template <int kHi, int kWaves, int kA>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kWaves, kWaves)))
 k_local_bits(FrameBatch fb, BitsBatch B, FrameGeom g, const TemplEntry* __restrict__ entries, const uint32_t* __restrict__ feat_word,
              const int32_t* __restrict__ work_pyramids, uint32_t cand_cap, float threshold, uint32_t cap, uint32_t dedupe_cap_slots) {
@@ -1139,7 +1165,7 @@ k_local_bits(FrameBatch fb, BitsBatch B, FrameGeom g, const TemplEntry* __restri
                 }
                 // Once per candidate and level: the two rows of the lane side by side — bit 2c = row 2j, bit 2c + 1 = row 2j + 1 of window
                 // column c —, S = n1 + 4 n4 bit-sliced, the lane's maximum by a descent from the top bit, its FIRST position in raster order.
-                uint32_t S[kS], carry = 0;
+                uint32_t S[kS];
                 {
                     uint32_t n1[kN], n4[kN];
 #pragma unroll
@@ -1147,12 +1173,7 @@ k_local_bits(FrameBatch fb, BitsBatch B, FrameGeom g, const TemplEntry* __restri
                         n1[k] = (cA[k] & 0x55555555u) | ((cB[k] << 1) & 0xAAAAAAAAu);
                         n4[k] = ((cA[k] >> 1) & 0x55555555u) | (cB[k] & 0xAAAAAAAAu);
                     }
-                    S[0] = n1[0]; S[1] = n1[1];
-#pragma unroll
-                    for (int k = 2; k < kS; ++k) {
-                        const uint32_t a = k < kN ? n1[k] : 0u, b = k - 2 < kN ? n4[k - 2] : 0u;
-                        csa(S[k], carry, a, b, carry);
-                    }
+                    weighted_sum<kA, kN>(S, n1, n4);
                 }
                 uint32_t mask = 0xFFFFFFFFu, val = 0;
 #pragma unroll
@@ -1213,11 +1234,14 @@ void launch_pack_bits(const BitsBatch& B, int nb, const LevelGeom& lv, hipStream
 }
 void launch_local_bits(const FrameBatch& fb, const BitsBatch& B, const FrameGeom& g, const TemplEntry* entries, const uint32_t* feat_word,
                        const int32_t* work_pyramids, uint32_t cand_cap, float threshold, uint32_t cap, uint32_t dedupe_cap_slots, int grid_blocks,
-                       int max_features, hipStream_t s) {
-    if (max_features > kBitsSmallMax)
-        hipLaunchKernelGGL((k_local_bits<10, 4>), dim3(grid_blocks), dim3(256), 0, s, fb, B, g, entries, feat_word, work_pyramids, cand_cap, threshold, cap, dedupe_cap_slots);
-    else
-        hipLaunchKernelGGL((k_local_bits<5, 4>), dim3(grid_blocks), dim3(256), 0, s, fb, B, g, entries, feat_word, work_pyramids, cand_cap, threshold, cap, dedupe_cap_slots);
+                       int max_features, int low_weight, hipStream_t s) {
+#define LM_LAUNCH_LOCAL_BITS(HI, A) \
+    hipLaunchKernelGGL((k_local_bits<HI, 4, A>), dim3(grid_blocks), dim3(256), 0, s, fb, B, g, entries, feat_word, work_pyramids, cand_cap, threshold, cap, dedupe_cap_slots)
+    const bool big = max_features > kBitsSmallMax;
+    if (low_weight == 2) { if (big) LM_LAUNCH_LOCAL_BITS(10, 2); else LM_LAUNCH_LOCAL_BITS(5, 2); }
+    else if (low_weight == 3) { if (big) LM_LAUNCH_LOCAL_BITS(10, 3); else LM_LAUNCH_LOCAL_BITS(5, 3); }
+    else { if (big) LM_LAUNCH_LOCAL_BITS(10, 1); else LM_LAUNCH_LOCAL_BITS(5, 1); }
+#undef LM_LAUNCH_LOCAL_BITS
 }
 
 // ---- Coarse pass on the pair stream (LL.cpp:1284-1354 similarity + :1835-1852 scan).  A wave per template, a lane = 32 consecutive
@@ -1236,12 +1260,12 @@ k_pack_top(TopBits B, uint32_t byte0, uint32_t npairs) {
     auto four = [](uint32_t d, int sh) -> uint32_t { return ((((d >> sh) & 0x01010101u) * 0x01020408u) >> 24) & 0xFu; };   // bit sh of 4 bytes -> 4 bits
     auto bits = [&](const uint4& v, int sh) -> uint32_t { return four(v.x, sh) | (four(v.y, sh) << 4) | (four(v.z, sh) << 8) | (four(v.w, sh) << 12); };
     uint2 r;
-    r.x = bits(a, 0) | (bits(b, 0) << 16);                           // response 1 = bit 0, response 4 = bit 2 of the byte
+    r.x = bits(a, 0) | bits(a, 1) | ((bits(b, 0) | bits(b, 1)) << 16);   // the low plane's response a = 1, 2 or 3: bit 0 or bit 1 of the byte; response 4 = bit 2
     r.y = bits(a, 2) | (bits(b, 2) << 16);
     *reinterpret_cast<uint2*>(B.bits[blockIdx.y] + (size_t)i * 8) = r;
 }
 
-template <int kHi, int kWaves>
+template <int kHi, int kWaves, int kA>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kWaves, kWaves)))
 k_coarse_bits(FrameBatch fb, TopBits B, LevelGeom lv, int level, int levels, const TemplEntry* __restrict__ entries, const int32_t* __restrict__ feat_off,
               const int32_t* __restrict__ work_pyramids, int num_work, float threshold, uint32_t cap, uint32_t byte0) {
@@ -1311,10 +1335,8 @@ k_coarse_bits(FrameBatch fb, TopBits B, LevelGeom lv, int level, int levels, con
                 }
             }
         }
-        uint32_t S[kS], carry = 0;
-        S[0] = c1[0]; S[1] = c1[1];
-#pragma unroll
-        for (int k = 2; k < kS; ++k) csa(S[k], carry, k < kN ? c1[k] : 0u, k - 2 < kN ? c4[k - 2] : 0u, carry);
+        uint32_t S[kS];
+        weighted_sum<kA, kN>(S, c1, c4);
         uint32_t gt = 0, eq = 0xFFFFFFFFu;                                  // S >= rmin, bit-sliced
 #pragma unroll
         for (int k = kS - 1; k >= 0; --k) {
@@ -1369,14 +1391,16 @@ void launch_pack_top(const TopBits& B, int nb, uint32_t byte0, uint32_t npairs, 
     hipLaunchKernelGGL(k_pack_top, dim3((npairs + 255) / 256, nb), dim3(256), 0, s, B, byte0, npairs);
 }
 void launch_coarse_bits(const FrameBatch& fb, const TopBits& B, const FrameGeom& g, const TemplEntry* entries, const int32_t* feat_off,
-                        const int32_t* work_pyramids, int num_work, float threshold, uint32_t cap, uint32_t byte0, int max_features, hipStream_t s) {
+                        const int32_t* work_pyramids, int num_work, float threshold, uint32_t cap, uint32_t byte0, int max_features, int low_weight, hipStream_t s) {
     if (num_work <= 0 || fb.nb <= 0) return;
     const int level = g.levels - 1;
-#define LM_LAUNCH_COARSE_BITS(HI, WAVES) \
-    hipLaunchKernelGGL((k_coarse_bits<HI, WAVES>), dim3((num_work + 3) / 4, fb.nb), dim3(256), 0, s, fb, B, g.lv[level], level, g.levels, entries, feat_off, \
+#define LM_LAUNCH_COARSE_BITS(HI, WAVES, A) \
+    hipLaunchKernelGGL((k_coarse_bits<HI, WAVES, A>), dim3((num_work + 3) / 4, fb.nb), dim3(256), 0, s, fb, B, g.lv[level], level, g.levels, entries, feat_off, \
                        work_pyramids, num_work, threshold, cap, byte0)
-    if (max_features > kBitsSmallMax) LM_LAUNCH_COARSE_BITS(10, 5);
-    else LM_LAUNCH_COARSE_BITS(5, 6);
+    const bool big = max_features > kBitsSmallMax;
+    if (low_weight == 2) { if (big) LM_LAUNCH_COARSE_BITS(10, 5, 2); else LM_LAUNCH_COARSE_BITS(5, 6, 2); }
+    else if (low_weight == 3) { if (big) LM_LAUNCH_COARSE_BITS(10, 5, 3); else LM_LAUNCH_COARSE_BITS(5, 6, 3); }
+    else { if (big) LM_LAUNCH_COARSE_BITS(10, 5, 1); else LM_LAUNCH_COARSE_BITS(5, 6, 1); }
 #undef LM_LAUNCH_COARSE_BITS
 }
 

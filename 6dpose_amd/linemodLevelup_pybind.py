@@ -608,6 +608,52 @@ class Detector:
         _check(f(self._h, ctypes.byref(r), ctypes.byref(c)))
         return ({v: k for k, v in self._REFINE.items()}[r.value], {v: k for k, v in self._COARSE.items()}[c.value])
 
+    # the reference's five SIMILARITY_LUTs (linemodLevelup.cpp:1112-1124) as r[d], d = cyclic distance 0..4 between a feature's label
+    # and the nearest orientation of the spread image
+    RESPONSE_TABLES = {
+        "linemod": (4, 3, 2, 1, 0),        # :1112, the original LINE-MOD / cv::linemod table
+        "drop1": (4, 2, 1, 0, 0),          # :1115
+        "drop1_keep3": (4, 3, 1, 0, 0),    # :1118
+        "levelup": (4, 1, 0, 0, 0),        # :1121, the reference's live one and the default here
+        "levelup2": (4, 2, 0, 0, 0),       # :1124
+    }
+
+    def setResponseTable(self, table) -> None:
+        """lm_detector_set_response_table: `table` is one of the names of RESPONSE_TABLES or five ints r[0..4] with r[0] == 4, non-increasing.
+        State of this detector in this process only: no file format stores it and training does not read it; ranks of a sharded run must
+        set the same table.  The next match (matchResident included) builds its response memories under it.  Refused with frames in
+        flight.  A threshold has to be chosen again per table."""
+        if isinstance(table, str):
+            if table not in self.RESPONSE_TABLES:
+                raise RuntimeError("unknown response table %r: one of %s or five ints" % (table, ", ".join(sorted(self.RESPONSE_TABLES))))
+            table = self.RESPONSE_TABLES[table]
+        r = list(table)
+        if len(r) != 5 or any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 0 or v > 4 for v in r):
+            raise RuntimeError("a response table is five values r[0..4], integers in 0..4, got %r" % (tuple(r),))
+        r = [int(v) for v in r]
+        f = self._lib.lm_detector_set_response_table
+        f.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint8)]
+        f.restype = ctypes.c_int
+        _check(f(self._h, (ctypes.c_uint8 * 5)(*r)))
+
+    def getResponseTable(self):
+        """lm_detector_get_response_table: the table in use, a tuple r[0..4]."""
+        f = self._lib.lm_detector_get_response_table
+        f.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint8)]
+        f.restype = ctypes.c_int
+        out = (ctypes.c_uint8 * 5)()
+        _check(f(self._h, out))
+        return tuple(int(v) for v in out)
+
+    def bitArenaBytes(self):
+        """lm_detector_bit_arena_bytes: device bytes allocated for (strip records, pair stream), over all result slots (tests)."""
+        f = self._lib.lm_detector_bit_arena_bytes
+        f.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
+        f.restype = ctypes.c_int
+        a, b = ctypes.c_uint64(), ctypes.c_uint64()
+        _check(f(self._h, ctypes.byref(a), ctypes.byref(b)))
+        return int(a.value), int(b.value)
+
     def getBatch(self) -> int:
         return int(self._lib.lm_detector_get_batch(self._h))
 

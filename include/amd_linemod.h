@@ -295,6 +295,22 @@ int lm_detector_refines_on_bit_planes(const lm_detector *d);
  * match): refine 0 / 1 / 2 and coarse 0 / 1 as above. */
 int lm_detector_set_paths(lm_detector *d, int refine, int coarse);
 int lm_detector_get_paths(const lm_detector *d, int *refine, int *coarse);
+/* The response table of computeResponseMaps: r[d] = the response to a feature whose label lies at cyclic distance d (0..4, eight orientations)
+ * from the nearest orientation set in the spread image.  The reference holds five such tables (LL.cpp:1112-1124) and compiles one; here it is
+ * detector state: 4 1 0 0 0 by default (LL.cpp:1121, the reference's live one), 4 3 2 1 0 is the original LINE-MOD / cv::linemod table (:1112).
+ * Accepted: r[0] == 4 (the score stays raw * 100 / (4 * features), LL.cpp:1842, 1918), values non-increasing — 70 tables; anything else is
+ * LM_ERR_INVALID.  Refused with frames in flight.  Every match runs the front end of its frame, so the next match — lm_detector_match_resident
+ * of the frame already resident included — builds its response memories under the new table.  The table is state of this detector in this
+ * process (lm_detector_read_stage: kinds 2 / 3 answer under the table in force — the byte planes are rebuilt from the last frame's quantised maps
+ * when the table changed since —, kinds 4 / 5 show what the last match read): lm_detector_write_classes / lm_detector_write / the packed bank do not store it, training (lm_detector_add_template) does not read
+ * it, and the ranks of a sharded run must each set the same one.  Tables with at most two distinct non-zero values (4 1 0 0 0, 4 2 0 0 0,
+ * 4 1 1 0 0, ...) run on the bit-plane kernels; the others (4 3 2 1 0, 4 2 1 0 0, 4 3 1 0 0, ...) run on the byte kernels, which
+ * lm_detector_get_paths reports.  Thresholds are not comparable between tables. */
+int lm_detector_set_response_table(lm_detector *d, const uint8_t r[5]);
+int lm_detector_get_response_table(const lm_detector *d, uint8_t r[5]);
+/* Device memory ALLOCATED for the bit planes, summed over the result slots: the strip records of the levels below the top and the pair
+ * stream of the top level (tests: no response table makes them grow). */
+int lm_detector_bit_arena_bytes(const lm_detector *d, uint64_t *strip_records, uint64_t *pair_stream);
 /* The response maps of spread / computeResponseMaps / linearize (LL.cpp:1026-1243) as bit planes straight from the quantised images
  * (default, on = 1: wherever the kernels in use read only bit planes, the byte linear memories are not written at all) or as the
  * reference's byte linear memories first, packed into bit planes by a second kernel (on = 0).  Bit 1 (on = 2, 3): the top level's bit

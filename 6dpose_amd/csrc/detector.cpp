@@ -121,6 +121,12 @@ extern "C" int lm_detector_create(int num_features, const int* T, int num_levels
             if (t < 1) { delete d; return lm_set_error(LM_ERR_INVALID, "T must be >= 1"); }
     }
     d->pyramid_levels = (int)d->T_at_level.size();
+    if ((d->num_features >> (d->pyramid_levels - 1)) < 1) {       // every level halves it: the last one would select 0 features
+        const int nf = d->num_features, L = d->pyramid_levels;
+        delete d;
+        return lm_set_error(LM_ERR_INVALID, "num_features %d leaves no feature at the last of %d pyramid levels (num_features /= 2 per level, "
+                            "LL.cpp:560; LL.cpp:632 then divides by zero)", nf, L);
+    }
     d->device = device;
     // Four streams: front end | coarse pass | refinement | duplicate removal + multi-GPU exchange.  Streams that share a hardware
     // queue run in submission order, so they must land on different queues.  The HIP runtime pools its hardware queues
@@ -263,6 +269,12 @@ extern "C" int lm_detector_set_response_table(lm_detector* d, const uint8_t r[5]
     // The byte planes the last front end left belong to the old table: lm_detector_read_stage kinds 2 / 3 build them again, from the quantised
     // maps, under the new one.  (The bit planes, kinds 4 / 5, stay what the last match read until the next match rewrites them.)
     d->fe_bytes_low = d->fe_bytes_top = false;
+    return LM_OK;
+}
+
+extern "C" int lm_detector_train_stats(const lm_detector* d, int64_t out[4]) {
+    if (!d || !out) return lm_set_error(LM_ERR_INVALID, "null argument");
+    for (int i = 0; i < 4; ++i) out[i] = d->train_stats[i];
     return LM_OK;
 }
 

@@ -24,7 +24,7 @@ static int validate_pyramid(const lm_detector* d, const TemplatePyramid& tp) {
 }
 
 // Detector::addTemplate on the frame resident in frame_rgb / frame_depth (LL.cpp:1943-1975).
-static int add_template_resident(lm_detector* d, const uint8_t* mask, int width, int height, const char* class_id) {
+static int resident_host_selection(lm_detector* d, const uint8_t* mask, int width, int height, const char* class_id) {
     // quantise() in addTemplate passes object_mask to every modality (LL.cpp:1957), but the masked
     // quantised image is not used by extractTemplate; only the unmasked maps + the mask are.
     int rc;
@@ -68,6 +68,14 @@ static int add_template_resident(lm_detector* d, const uint8_t* mask, int width,
     if ((rc = validate_pyramid(d, tp))) return rc;
     tps.push_back(std::move(tp));
     return (int)tps.size() - 1;
+}
+
+// ... counted for lm_detector_train_stats: a view of the host selection, and whether it failed
+static int add_template_resident(lm_detector* d, const uint8_t* mask, int width, int height, const char* class_id) {
+    ++d->train_stats[1];
+    const int id = resident_host_selection(d, mask, width, height, class_id);
+    if (id == -1) ++d->train_stats[2];
+    return id;
 }
 
 // The scratch of the device selection for `views` views of the current geometry, and the maps it reads (the detector's level buffers).
@@ -143,7 +151,8 @@ static int add_template_device(lm_detector* d, const uint8_t* mask, int width, i
     if (host_path) return add_template_resident(d, mask, width, height, class_id);
     std::vector<TemplatePyramid>& tps = d->class_templates[class_id];   // created even on failure, LL.cpp:1947
     d->bank_dirty = true;
-    if (!ok) return -1;
+    ++d->train_stats[0];
+    if (!ok) { ++d->train_stats[2]; return -1; }
     return push_selected_pyramid(d, tps, h_out.data(), out_words);
 }
 
@@ -192,7 +201,7 @@ static int add_rendered_view_host(lm_detector* d, lm_mesh* m, int i, int width, 
         box_wh_view[0] = x1 >= 0 ? x1 - x0 : 0;
         box_wh_view[1] = y1 >= 0 ? y1 - y0 : 0;
     }
-    if (x1 < 0) return -1;
+    if (x1 < 0) { ++d->train_stats[3]; return -1; }
     return add_template_resident(d, hmask.data(), width, height, class_id);
 }
 
@@ -278,9 +287,13 @@ static int add_templates_rendered(lm_detector* d, lm_mesh* m, const char* class_
                 if (host_path) {                                               // this view through the host selection, in view order
                     id = add_rendered_view_host(d, m, i, width, height, class_id, hdepth, hmask, nullptr);
                     if (id < -1) return id;
-                } else if (ok) {
-                    if ((id = push_selected_pyramid(d, tps, &h_out[(size_t)i * L * 2 * out_words], out_words)) < -1) return id;
+                } else {
+                    ++d->train_stats[0];
+                    if (!ok) ++d->train_stats[2];
+                    else if ((id = push_selected_pyramid(d, tps, &h_out[(size_t)i * L * 2 * out_words], out_words)) < -1) return id;
                 }
+            } else {
+                ++d->train_stats[3];
             }
             if (box_wh) {                                                      // xmax - xmin, ymax - ymin (:235-236)
                 box_wh[2 * ((size_t)c0 + i)] = any ? bb[2] + bb[0] : 0;
@@ -401,6 +414,9 @@ extern "C" int lm_detector_read_params(lm_detector* d, const char* path) {
     if (types.size() != 2 || types[0] != "ColorGradient" || types[1] != "DepthNormal")   // Modality::create (LL.cpp:320-328) knows these two
         return lm_set_error(LM_ERR_INVALID, "%s: modalities must be [ColorGradient, DepthNormal]", path);
     if (nf[0] <= 0 || nf[0] != nf[1]) return lm_set_error(LM_ERR_INVALID, "%s: the modalities must agree on num_features (one bank layout)", path);
+    if ((nf[0] >> (levels - 1)) < 1)
+        return lm_set_error(LM_ERR_INVALID, "%s: num_features %d leaves no feature at the last of %d pyramid levels (num_features /= 2 per level, "
+                            "LL.cpp:560; LL.cpp:632 then divides by zero)", path, nf[0], levels);
     for (int t : T) if (t < 1) return lm_set_error(LM_ERR_INVALID, "T must be >= 1");
     d->class_templates.clear();                                   // LL.cpp:2015
     d->bank_dirty = true; d->work_valid = false; d->frame_valid = false;
@@ -408,6 +424,7 @@ extern "C" int lm_detector_read_params(lm_detector* d, const char* path) {
     d->num_features = nf[0]; d->weak_threshold = weak; d->strong_threshold = strong;
     d->distance_threshold = dist; d->difference_threshold = diff; d->extract_threshold = ext;
     d->fW = d->fH = 0;                                            // geometry depends on T: rebuilt by the next frame
+    for (int64_t& c : d->train_stats) c = 0;
     return LM_OK;
 }
 

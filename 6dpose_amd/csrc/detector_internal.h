@@ -282,6 +282,7 @@ struct lm_detector {
         DevBuf<uint32_t> counts;
         DevBuf<int32_t> bbox, out;
     } train;
+    int64_t train_stats[4] = {};     // views since creation / read(): selected on the device, sent to the host selection, failed (-1), empty (lm_detector_train_stats)
 
     bool fe_fused = true;            // addTemplate's front end: independent jobs share a launch (k_fe_stage); LM_FE_FUSED=0: one launch per job
 

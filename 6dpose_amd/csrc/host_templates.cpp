@@ -107,6 +107,8 @@ struct ScoreDesc {
 
 static bool extract_color_full(const float* mag, const uint8_t* angle, const uint8_t* mask, int W, int H,
                                size_t num_features, float strong_threshold, int level, Template& out) {
+    out.features.clear();
+    if (num_features == 0) return false;   // LL.cpp:632 divides by it (num_features >> level == 0, LL.cpp:560): refused, never evaluated
     std::vector<uint8_t> local;
     if (mask) {
         std::vector<uint8_t> m(mask, mask + (size_t)W * H);
@@ -138,6 +140,8 @@ static bool extract_color_full(const float* mag, const uint8_t* angle, const uin
 
 static bool extract_normal_full(const uint8_t* normal, const uint8_t* mask, int W, int H, size_t num_features,
                                 int extract_threshold, int level, Template& out) {
+    out.features.clear();
+    if (num_features == 0) return false;   // LL.cpp:957 divides by sqrt(num_features): the same refusal as the colour modality
     const size_t N = (size_t)W * H;
     std::vector<uint8_t> local;
     if (mask) {

@@ -645,6 +645,16 @@ class Detector:
         _check(f(self._h, out))
         return tuple(int(v) for v in out)
 
+    def trainStats(self):
+        """lm_detector_train_stats: training views since creation or read() as (selected on the device, sent to the host selection,
+        failed with -1, empty).  The two selections give the same templates; this is how a test sees which one ran."""
+        f = self._lib.lm_detector_train_stats
+        f.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64)]
+        f.restype = ctypes.c_int
+        out = (ctypes.c_int64 * 4)()
+        _check(f(self._h, out))
+        return tuple(int(v) for v in out)
+
     def bitArenaBytes(self):
         """lm_detector_bit_arena_bytes: device bytes allocated for (strip records, pair stream), over all result slots (tests)."""
         f = self._lib.lm_detector_bit_arena_bytes

@@ -311,6 +311,12 @@ int lm_detector_get_response_table(const lm_detector *d, uint8_t r[5]);
 /* Device memory ALLOCATED for the bit planes, summed over the result slots: the strip records of the levels below the top and the pair
  * stream of the top level (tests: no response table makes them grow). */
 int lm_detector_bit_arena_bytes(const lm_detector *d, uint64_t *strip_records, uint64_t *pair_stream);
+/* Which selection served the training views (lm_detector_add_template, lm_detector_add_templates_rendered[_ex]) since the detector was
+ * created or lm_detector_read_params was called: out[0] views whose features the device selected (train.hip), out[1] views sent to the
+ * host selection (LM_TRAIN_HOST=1, no or a grey object mask, more than 1024 features, a candidate list beyond what the kernel sorts),
+ * out[2] views that failed with -1 (too few candidates; counted besides out[0] / out[1]), out[3] empty views (rendered views without
+ * a depth pixel; neither selection ran).  Tests: a fall-back to the host selection is otherwise invisible, it gives the same templates. */
+int lm_detector_train_stats(const lm_detector *d, int64_t out[4]);
 /* The response maps of spread / computeResponseMaps / linearize (LL.cpp:1026-1243) as bit planes straight from the quantised images
  * (default, on = 1: wherever the kernels in use read only bit planes, the byte linear memories are not written at all) or as the
  * reference's byte linear memories first, packed into bit planes by a second kernel (on = 0).  Bit 1 (on = 2, 3): the top level's bit

@@ -242,8 +242,10 @@ def _get_label(q: np.ndarray) -> np.ndarray:
     return np.log2(q.astype(np.float64)).astype(np.int32)
 
 
-def select_scattered(cands: np.ndarray, num_features: int, distance: float) -> Optional[np.ndarray]:
-    """selectScatteredFeatures (LL.cpp:279-318).  cands: (N,3) int x,y,label sorted by score."""
+def select_scattered(cands: np.ndarray, num_features: int, distance: float, stats: Optional[dict] = None) -> Optional[np.ndarray]:
+    """selectScatteredFeatures (LL.cpp:279-318).  cands: (N,3) int x,y,label sorted by score.
+    stats (optional) receives `passes`, the passes over the list that accepted a feature counted up to the last such one, and
+    `last_distance`, the distance of that pass; the result does not depend on it."""
     n = len(cands)
     feats: List[Tuple[int, int, int]] = []
     dist = f32(distance)
@@ -261,6 +263,8 @@ def select_scattered(cands: np.ndarray, num_features: int, distance: float) -> O
             keep = bool(np.all(dsq.astype(f32) >= dist_sq))
         if keep:
             feats.append((cx, cy, cl)); fx.append(cx); fy.append(cy)
+            if stats is not None:
+                stats["passes"], stats["last_distance"] = guard + 1, float(dist)
         i += 1
         if i == n:
             i = 0
@@ -282,8 +286,9 @@ def _erode3(mask: np.ndarray, iterations: int) -> np.ndarray:
 
 
 def extract_color_template(mag: np.ndarray, angle: np.ndarray, mask: Optional[np.ndarray],
-                           num_features: int, strong_threshold: float, level: int) -> Optional[Template]:
-    """ColorGradientPyramid::extractTemplate (LL.cpp:589-643)."""
+                           num_features: int, strong_threshold: float, level: int, stats: Optional[dict] = None) -> Optional[Template]:
+    """ColorGradientPyramid::extractTemplate (LL.cpp:589-643).  stats (optional) receives what goes into selectScatteredFeatures:
+    `n`, and when n >= num_features `cands` (sorted), `scores`, `distance`, `passes`, `last_distance`."""
     thr = f32(strong_threshold) * f32(strong_threshold)
     ok = (angle > 0) & (mag > thr)
     if mask is not None and mask.size:
@@ -291,21 +296,27 @@ def extract_color_template(mag: np.ndarray, angle: np.ndarray, mask: Optional[np
         local = np.clip(mask.astype(np.int32) - er.astype(np.int32), 0, 255)  # cv::subtract saturates
         ok &= local > 0
     ys, xs = np.nonzero(ok)                          # raster order, as the double loop
+    if stats is not None:
+        stats["n"] = len(ys)
     if len(ys) < num_features:
         return None
     score = mag[ys, xs]
     order = np.argsort(-score.astype(np.float64), kind="stable")   # std::stable_sort, descending
     cands = np.stack([xs[order], ys[order], _get_label(angle[ys, xs])[order]], 1).astype(np.int32)
     distance = float(len(cands) // num_features + 1)
-    feats = select_scattered(cands, num_features, distance)
+    if stats is not None:
+        stats.update(cands=cands, scores=score[order], distance=distance)
+    feats = select_scattered(cands, num_features, distance, stats)
     if feats is None:
         return None
     return Template(-1, -1, level, feats)
 
 
 def extract_normal_template(normal: np.ndarray, mask: Optional[np.ndarray], num_features: int,
-                            extract_threshold: int, level: int) -> Optional[Template]:
-    """DepthNormalPyramid::extractTemplate (LL.cpp:888-966)."""
+                            extract_threshold: int, level: int, stats: Optional[dict] = None) -> Optional[Template]:
+    """DepthNormalPyramid::extractTemplate (LL.cpp:888-966).  stats (optional) receives `n`, `labelled` (the pixels with a label inside
+    the twice eroded mask), `label_img`, `dist` (their distance transform values) and, when n >= num_features, `cands` (sorted),
+    `scores`, `label_counts`, `distance`, `passes`, `last_distance`."""
     from scipy.ndimage import distance_transform_cdt
     H, W = normal.shape
     no_mask = mask is None or mask.size == 0
@@ -336,6 +347,10 @@ def extract_normal_template(normal: np.ndarray, mask: Optional[np.ndarray], num_
     labs = lab_img[ys, xs]
     sc = dist[labs, ys, xs]
     keep = sc >= extract_threshold
+    if stats is not None:
+        dmap = np.zeros((H, W), f32)
+        dmap[ys, xs] = sc
+        stats.update(n=int(keep.sum()), labelled=ok, label_img=lab_img, dist=dmap)
     ys, xs, labs, sc = ys[keep], xs[keep], labs[keep], sc[keep]
     if len(ys) < num_features:
         return None
@@ -345,7 +360,9 @@ def extract_normal_template(normal: np.ndarray, mask: Optional[np.ndarray], num_
     cands = np.stack([xs[order], ys[order], labs[order]], 1).astype(np.int32)
     area = f32(normal.size) if no_mask else f32(np.count_nonzero(local))
     distance = f32(np.sqrt(area).astype(f32) / np.sqrt(f32(num_features)).astype(f32)) + f32(1.5)
-    feats = select_scattered(cands, num_features, float(distance))
+    if stats is not None:
+        stats.update(cands=cands, scores=sc[order], label_counts=counts, distance=float(distance))
+    feats = select_scattered(cands, num_features, float(distance), stats)
     if feats is None:      # reference ignores the return value (LL.cpp:958); keep what exists
         return None
     return Template(-1, -1, level, feats)
@@ -620,7 +637,9 @@ class OracleDetector:
         return out
 
     # ---- addTemplate (LL.cpp:1943-1975) --------------------------------------------------
-    def addTemplate(self, sources, class_id: str, object_mask: np.ndarray) -> int:
+    def addTemplate(self, sources, class_id: str, object_mask: np.ndarray, stats: Optional[list] = None) -> int:
+        """stats (optional list) receives per level {"color": ..., "normal": ..., "mask": ...}: what extract_*_template report about
+        their candidate lists, up to the level at which the view fails."""
         rgb, depth = sources
         pyr = self.quantize_pyramid(rgb, depth, object_mask)
         tps = self.class_templates.setdefault(class_id, [])
@@ -630,8 +649,11 @@ class OracleDetector:
             if l > 0:
                 nf //= 2                                     # num_features /= 2, LL.cpp:560, 860
                 ext //= 2                                    # extract_threshold /= 2, LL.cpp:861
-            t0 = extract_color_template(mag, ang, msk, nf, self.strong_threshold, l)
-            t1 = extract_normal_template(normal, msk, nf, ext, l)
+            sc, sn = {"nf": nf}, {"nf": nf, "extract_threshold": ext}
+            if stats is not None:
+                stats.append({"color": sc, "normal": sn, "mask": msk})
+            t0 = extract_color_template(mag, ang, msk, nf, self.strong_threshold, l, sc)
+            t1 = extract_normal_template(normal, msk, nf, ext, l, sn)
             if t0 is None or t1 is None:
                 return -1                                    # LL.cpp:1964-1966
             tp[2 * l], tp[2 * l + 1] = t0, t1

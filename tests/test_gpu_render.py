@@ -145,6 +145,16 @@ def test_rendered_training_equals_the_host_round_trip(lm, nfeat, T, views, dist,
             assert xs.max() == 639 or ys.min() == 0                                          # really cut by the frame
     assert ids.tolist() == want_ids
     assert (max(want_ids) >= 0) == (dist < 2000)
+    on_device, on_host, failed, empty = det_a.trainStats()                                 # which selection served the views
+    assert on_device + on_host == views and empty == 0 and failed == sum(t < 0 for t in want_ids)
+    if dist == 210.0:
+        assert on_host == views                                                            # "those views take the host path": all three
+    # The oracle's normal list of level 0 (extract_normal_template on the numpy rasteriser's depth) has 16711 entries for view 0 of the
+    # first configuration, above the 16384 the selection kernel sorts, and 15271 - 15905 for views 1 - 4; 10850 - 11663 in the third.
+    if (nfeat, views, dist) == (63, 5, 520.0):
+        assert (on_device, on_host) == (4, 1)
+    if (nfeat, views, dist) == (64, 6, 600.0):
+        assert on_host == 0
     for t in [t for t in want_ids if t >= 0]:
         for a, b in zip(det_a.getTemplates("obj", t), det_b.getTemplates("obj", t)):
             assert (a.width, a.height, a.pyramid_level) == (b.width, b.height, b.pyramid_level) and np.array_equal(a.features, b.features)

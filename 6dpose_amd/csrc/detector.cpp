@@ -1,7 +1,7 @@
 // libamdlinemod.so — host orchestration + C ABI (include/amd_linemod.h) of the MI355X LINE-MOD
 // detector.  Mirrors linemodLevelup::Detector (LL.cpp:1663-2146): bank bookkeeping and the greedy
 // template extraction on the host, every per-pixel / per-template stage in HIP kernels
-// (frontend.hip, match.hip).  No CPU fallback: creation fails without a HIP device.
+// (frontend.hip, match_bytes.hip, match_bits.hip).  No CPU fallback: creation fails without a HIP device.
 // This file: errors, thread binding, creation / destruction and the small setters and getters.  The frame and the training front
 // end are in detector_frame.cpp, the template bank in detector_bank.cpp, the streamed matching path in detector_stream.cpp (its
 // helper threads: host_pool.cpp), the host-side result lists and NMS in match_lists.cpp.
@@ -168,7 +168,6 @@ extern "C" int lm_detector_create(int num_features, const int* T, int num_levels
     }
     d->work_cls = std::make_shared<std::vector<int32_t>>();
     d->work_tid = std::make_shared<std::vector<int32_t>>();
-    if (const char* ff = getenv("LM_FE_FUSED")) d->fe_fused = ff[0] && ff[0] != '0';
     if (knobs().frame_batch > 0) d->batch_max = std::min(knobs().frame_batch, kMaxBatch);
     if (knobs().batch_queue > 0) d->keep_queued = knobs().batch_queue;
     if (knobs().launch_slack_us > 0) d->launch_slack_ms = knobs().launch_slack_us * 1e-3f;

@@ -130,7 +130,10 @@ int upload_frame(lm_detector* d, const uint8_t* rgb, const uint16_t* depth, int 
             const LevelBufs& a = d->lvl[l - 1];
             LevelBufs& b = d->lvl[l];
             if ((rc = b.mask[m].ensure((size_t)b.W * b.H))) return rc;
-            launch_nn_down2(a.mask[m].p, b.mask[m].p, a.W, a.H, d->stream);
+            FeStage st{};                                   // one launch per level: level l reads level l - 1
+            st.njobs = 1;
+            fe_job_nn_down2(st.job[0], a.mask[m].p, b.mask[m].p, a.W, a.H);
+            launch_fe_stage(st, d->stream);
         }
     }
     HIP_TRY(hipEventRecord(d->ev[7], d->stream));
@@ -147,34 +150,21 @@ int run_frontend_training(lm_detector* d) {
     // (events, also inside the hipGraph) cost more in cross-stream synchronisation (+26 us) than the
     // ~3 us kernels could overlap.  Instead the jobs of a level that do not depend on each other share a LAUNCH (k_fe_stage):
     // {colour chain, normals + median or their nearest-neighbour pyramid, pyrDown to the next level} — launch latency is the
-    // critical path of a training view.  LM_FE_FUSED=0: one launch per job.
+    // critical path of a training view.
     hipStream_t s = d->stream;
     const int L = d->pyramid_levels;
     const float thr_sq = d->weak_threshold * d->weak_threshold;
-    const bool fused = d->fe_fused;
     FeStage st{};
     for (int l = 0; l < L; ++l) {
         LevelBufs& b = d->lvl[l];
         const uint8_t* src = l == 0 ? d->cur_rgb : b.rgb.p;
-        if (fused) {
-            st.njobs = 0;
-            fe_job_colour(st.job[st.njobs++], src, b.mag.p, b.ang.p, b.W, b.H, thr_sq);                                   // LL.cpp:367-504
-            if (l == 0) fe_job_normals(st.job[st.njobs++], d->cur_depth, d->nrm_raw.p, b.nrm.p, b.W, b.H, d->distance_threshold,
-                                       d->difference_threshold);                                                          // LL.cpp:729-819
-            else fe_job_nn_down2(st.job[st.njobs++], d->lvl[l - 1].nrm.p, b.nrm.p, d->lvl[l - 1].W, d->lvl[l - 1].H);     // LL.cpp:857-880
-            if (l + 1 < L) fe_job_pyrdown(st.job[st.njobs++], src, d->lvl[l + 1].rgb.p, b.W, b.H);                        // LL.cpp:557-581
-            launch_fe_stage(st, s);
-            continue;
-        }
-        if (l > 0) {
-            const LevelBufs& a = d->lvl[l - 1];
-            launch_pyrdown_rgb(l == 1 ? d->cur_rgb : a.rgb.p, b.rgb.p, a.W, a.H, s);   // LL.cpp:557-581
-            launch_nn_down2(a.nrm.p, b.nrm.p, a.W, a.H, s);                                   // LL.cpp:857-880
-        } else {
-            launch_normals_fused(d->cur_depth, d->nrm_raw.p, b.nrm.p, b.W, b.H, d->distance_threshold,
-                                 d->difference_threshold, s);                                 // LL.cpp:729-819
-        }
-        launch_color_quant(src, b.mag.p, b.ang.p, b.W, b.H, thr_sq, s);                       // LL.cpp:367-504
+        st.njobs = 0;
+        fe_job_colour(st.job[st.njobs++], src, b.mag.p, b.ang.p, b.W, b.H, thr_sq);                                   // LL.cpp:367-504
+        if (l == 0) fe_job_normals(st.job[st.njobs++], d->cur_depth, d->nrm_raw.p, b.nrm.p, b.W, b.H, d->distance_threshold,
+                                   d->difference_threshold);                                                          // LL.cpp:729-819
+        else fe_job_nn_down2(st.job[st.njobs++], d->lvl[l - 1].nrm.p, b.nrm.p, d->lvl[l - 1].W, d->lvl[l - 1].H);     // LL.cpp:857-880
+        if (l + 1 < L) fe_job_pyrdown(st.job[st.njobs++], src, d->lvl[l + 1].rgb.p, b.W, b.H);                        // LL.cpp:557-581
+        launch_fe_stage(st, s);
     }
     HIP_TRY(hipGetLastError());
     return LM_OK;
@@ -267,14 +257,12 @@ extern "C" int64_t lm_detector_read_stage(lm_detector* d, int level, int kind, u
         if ((kind == 2 || kind == 3) && (level == d->pyramid_levels - 1 ? !d->fe_bytes_top : !d->fe_bytes_low)) {
             // the last front end wrote this level's bit planes only: build its byte planes now, from the quantised maps it left
             if (d->n_submitted != d->n_collected) return lm_set_error(LM_ERR_INVALID, "frames in flight: collect them first");
-            const LevelBufs& q = d->level_bufs(0, level);
-            const lm_detector::Slot& sl = d->slot[d->last_arena];
-            const bool strips = level < d->pyramid_levels - 1;
-            const uint8_t* quant[2] = {q.ang.p, q.nrm.p};
-            const uint8_t* mask[2] = {sl.have_mask[0] ? b.mask[0].p : nullptr, sl.have_mask[1] ? b.mask[1].p : nullptr};
-            uint8_t* lmp[2] = {d->lm_arena[d->last_arena].p + lv.lm_off[0], d->lm_arena[d->last_arena].p + lv.lm_off[1]};
-            uint8_t* smp[2] = {strips ? d->sm_arena[d->last_arena].p + lv.sm_off[0] : nullptr, strips ? d->sm_arena[d->last_arena].p + lv.sm_off[1] : nullptr};
-            launch_build_lm(quant, mask, lmp, smp, q.W, q.H, lv.T, d->resp, d->stream);
+            const LevelPtrs P = d->level_ptrs(0, level, d->last_arena);
+            FeStage st{};
+            st.resp = d->resp;
+            st.njobs = 1;
+            fe_job_build_lm(st.job[0], P.quant, P.mask, P.lm, P.strips, b.W, b.H, lv.T);
+            launch_fe_stage(st, d->stream);
             (void)hipStreamSynchronize(d->stream);
         }
         hipError_t e = hipMemcpy(dst, src, (size_t)std::min(size, capacity), hipMemcpyDeviceToHost);

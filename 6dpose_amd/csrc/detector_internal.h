@@ -56,6 +56,17 @@ struct LevelBufs {
     DevBuf<uint8_t> mask[2];  // per modality, optional
 };
 
+// What the linear-memory and bit-plane jobs of the front end take for one level of one frame (lm_detector::level_ptrs)
+struct LevelPtrs {
+    const uint8_t* quant[2];  // quantised maps: [0] colour, [1] normals
+    const uint8_t* mask[2];   // null where the slot's frame came without that mask
+    uint8_t* lm[2];           // flat linear memories
+    uint8_t* strips[2];       // their strip-major copy (null at the top level)
+    uint8_t* bits[2];         // strip records (null at the top level)
+    uint8_t* top_stream;      // pair stream of the slot; bit0[m] = modality m's block in it (meaningful at the top level)
+    uint32_t bit0[2];
+};
+
 struct lm_detector {
     // parameters (LL.cpp:1663-1692 + modality defaults :645-650, :968-974)
     int num_features = 63;
@@ -165,7 +176,7 @@ struct lm_detector {
         std::shared_ptr<std::vector<int32_t>> work_cls, work_tid;
         std::chrono::steady_clock::time_point t0, t1;
     } slot[kSlots];
-    // Bit planes (match.hip): both matching kernels read 1-bit response planes by default.
+    // Bit planes (match_bits.hip): both matching kernels read 1-bit response planes by default.
     DevBuf<uint8_t> cbits_arena[kSlots];            // pair stream of the top level's flat memories (k_coarse_bits)
     uint32_t cbits_byte0 = 0, cbits_npairs = 0;     // ... = arena bytes [byte0, byte0 + 32 npairs): the top level's two blocks with their zero tails
     DevBuf<uint8_t> bits_arena[kSlots];             // strip records of the levels below the top (the strip arena's layout at half the offsets; k_local_bits)
@@ -187,6 +198,23 @@ struct lm_detector {
     int fe_top_mode = 0;                            // lm_detector_set_direct_bits(d, 4 / 8): which writer of the pair stream (fe_job_top_bits)
     bool fe_bytes_low = true, fe_bytes_top = true;  // did the last front end write the byte planes of the levels below the top / of the top level (read_stage builds them on demand otherwise)
     hipEvent_t resident_reader = nullptr;           // front end (event of its batch) that reads the resident frame buffers: lm_detector_select_frame's copy waits for it
+    // frame b of a batch (its intermediates: level_bufs), level l, result slot `arena` (whose frame decides the masks)
+    LevelPtrs level_ptrs(int b, int l, int arena) {
+        const LevelBufs& q = level_bufs(b, l);
+        const LevelGeom& lv = geom.lv[l];
+        const bool low = l < pyramid_levels - 1;
+        LevelPtrs P{};
+        P.quant[0] = q.ang.p; P.quant[1] = q.nrm.p;
+        for (int m = 0; m < 2; ++m) {
+            P.mask[m] = slot[arena].have_mask[m] ? lvl[l].mask[m].p : nullptr;
+            P.lm[m] = lm_arena[arena].p + lv.lm_off[m];
+            P.strips[m] = low ? sm_arena[arena].p + lv.sm_off[m] : nullptr;
+            P.bits[m] = low ? bits_arena[arena].p + (lv.sm_off[m] >> 1) : nullptr;
+            P.bit0[m] = lv.lm_off[m] - cbits_byte0;
+        }
+        P.top_stream = cbits_arena[arena].p;
+        return P;
+    }
     bool cbits_clean[kSlots] = {};                  // the slot's pair stream is all zero (what the front end's OR-ing writer needs)
     uint64_t n_submitted = 0, n_collected = 0, n_launched = 0;
     // frames submitted but not launched yet: slots pend_first .. pend_first + pend_n - 1 (modulo kSlots), same threshold and work list
@@ -283,8 +311,6 @@ struct lm_detector {
         DevBuf<int32_t> bbox, out;
     } train;
     int64_t train_stats[4] = {};     // views since creation / read(): selected on the device, sent to the host selection, failed (-1), empty (lm_detector_train_stats)
-
-    bool fe_fused = true;            // addTemplate's front end: independent jobs share a launch (k_fe_stage); LM_FE_FUSED=0: one launch per job
 
     lm_timings timings{};
 };

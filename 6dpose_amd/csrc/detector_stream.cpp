@@ -98,17 +98,9 @@ static int run_frontend_batch(lm_detector* d, int first, int nb, hipStream_t s, 
     auto build_lm_jobs = [&](int l) {                        // linear memories of level l of every frame (its quantised maps are complete)
         if (l < L - 1 ? direct_low : direct_top) return;    // bit planes only: fe_bits_jobs below
         for (int b = 0; b < nb; ++b) {
-            const int arena = (first + b) % lm_detector::kSlots;
-            const lm_detector::Slot& sl = d->slot[arena];
-            LevelBufs& B = d->level_bufs(b, l);
-            const LevelGeom& lv = d->geom.lv[l];
-            const bool strips = l < L - 1;
-            const uint8_t* quant[2] = {B.ang.p, B.nrm.p};
-            const uint8_t* mask[2] = {sl.have_mask[0] ? d->lvl[l].mask[0].p : nullptr, sl.have_mask[1] ? d->lvl[l].mask[1].p : nullptr};
-            uint8_t* lmp[2] = {d->lm_arena[arena].p + lv.lm_off[0], d->lm_arena[arena].p + lv.lm_off[1]};
-            uint8_t* smp[2] = {strips ? d->sm_arena[arena].p + lv.sm_off[0] : nullptr, strips ? d->sm_arena[arena].p + lv.sm_off[1] : nullptr};
+            const LevelPtrs P = d->level_ptrs(b, l, (first + b) % lm_detector::kSlots);
             room(1);
-            fe_job_build_lm(st.job[st.njobs++], quant, mask, lmp, smp, B.W, B.H, lv.T);
+            fe_job_build_lm(st.job[st.njobs++], P.quant, P.mask, P.lm, P.strips, d->lvl[l].W, d->lvl[l].H, d->geom.lv[l].T);
         }
     };
     // Launch l quantises level l of every frame and — beside it, they only need level l - 1 — builds the linear memories of level
@@ -136,23 +128,14 @@ static int run_frontend_batch(lm_detector* d, int first, int nb, hipStream_t s, 
         st.njobs = 0;
         auto flush_bits = [&]() { if (st.njobs) { LM_CLOCK("launch_fe_bits"); launch_fe_bits(st, s); } st.njobs = 0; };
         for (int b = 0; b < nb; ++b) {
-            const int arena = (first + b) % lm_detector::kSlots;
-            const lm_detector::Slot& sl = d->slot[arena];
             for (int l = 0; l < L; ++l) {
                 const bool top = l == L - 1;
                 if (top ? !direct_top : !direct_low) continue;
-                LevelBufs& B = d->level_bufs(b, l);
-                const LevelGeom& lv = d->geom.lv[l];
-                const uint8_t* quant[2] = {B.ang.p, B.nrm.p};
-                const uint8_t* mask[2] = {sl.have_mask[0] ? d->lvl[l].mask[0].p : nullptr, sl.have_mask[1] ? d->lvl[l].mask[1].p : nullptr};
+                const LevelPtrs P = d->level_ptrs(b, l, (first + b) % lm_detector::kSlots);
+                const int W = d->lvl[l].W, H = d->lvl[l].H, T = d->geom.lv[l].T;
                 if (st.njobs + 1 > kFeMaxJobs) flush_bits();
-                if (top) {
-                    const uint32_t bit0[2] = {lv.lm_off[0] - d->cbits_byte0, lv.lm_off[1] - d->cbits_byte0};
-                    fe_job_top_bits(st.job[st.njobs++], quant, mask, d->cbits_arena[arena].p, bit0, B.W, B.H, lv.T, d->fe_top_mode);
-                } else {
-                    uint8_t* bits[2] = {d->bits_arena[arena].p + (lv.sm_off[0] >> 1), d->bits_arena[arena].p + (lv.sm_off[1] >> 1)};
-                    fe_job_bits_rows(st.job[st.njobs++], quant, mask, bits, B.W, B.H, lv.T, d->fe_top_mode == 0);
-                }
+                if (top) fe_job_top_bits(st.job[st.njobs++], P.quant, P.mask, P.top_stream, P.bit0, W, H, T, d->fe_top_mode);
+                else fe_job_bits_rows(st.job[st.njobs++], P.quant, P.mask, P.bits, W, H, T, d->fe_top_mode == 0);
             }
         }
         flush_bits();
@@ -163,7 +146,7 @@ static int run_frontend_batch(lm_detector* d, int first, int nb, hipStream_t s, 
     return LM_OK;
 }
 
-// The bit-plane refinement (match.hip): any pyramid with a level below the top; entries of up to 16383 features (two
+// The bit-plane refinement (match_bits.hip): any pyramid with a level below the top; entries of up to 16383 features (two
 // modalities of the reference's 8191, LL.cpp:1291).  LM_BITPLANES=0 / lm_detector_set_paths: the byte paths.  Two bits per cell carry a response
 // table of at most two distinct non-zero values; the others (4 3 2 1 0 ...) run on the byte kernels, and lm_detector_get_paths says so.
 static bool bits_active(const lm_detector* d, int num_work) {
@@ -235,7 +218,7 @@ static int slot_begin(lm_detector* d, float threshold, const char* const* class_
         HIP_TRY(hipMemset(d->d_counters.p, 0, (size_t)kCounterWords * K * sizeof(unsigned long long)));
         HIP_TRY(hipMemset(d->d_final.p, 0, 8 * (size_t)K * sizeof(unsigned long long)));
     }
-    // tile refinement (match.hip): two-level pyramids with a tileable geometry; the buffers exist per result slot
+    // tile refinement (match_bytes.hip): two-level pyramids with a tileable geometry; the buffers exist per result slot
     const bool tiled = (tiles_wanted(d) && num_work > 0 && tile_plan_possible(d->geom)) || bits_active(d, num_work);   // (the bit-plane path uses the todo bytes)
     const uint32_t tile_cap = d->buf_cand_cap / 2;      // a tile has at least two members
     if (tiled && (d->d_tiles.cap < (size_t)tile_cap * K || d->d_todo.cap < (size_t)d->buf_cand_cap * K)) {
@@ -336,6 +319,7 @@ struct Batch {
     FrameBatch fb, fb_rest;                   // fb_rest: for k_local's per-candidate path on what k_local_bits leaves (todo = 1)
     BitsBatch bb;
     TopBits tb;
+    BankDev bank;                             // the device bank and work list, as the matching launchers take them
     int slot(int b) const { return (first + b) % lm_detector::kSlots; }
 };
 
@@ -353,6 +337,7 @@ static int batch_begin(lm_detector* d, Batch& B) {
     B.cap = std::min<uint32_t>(lead.match_cap, d->buf_cand_cap);
     B.s = d->mstream;
     B.fb.nb = B.nb;
+    B.bank = BankDev{d->d_entries.p, d->d_feat_off.p, d->d_feat_word.p, d->d_run_mask.p, d->d_feat_xy.p, d->d_work.p};
     int rc;
     for (int b = 0; b < B.nb; ++b)
         if ((rc = frame_slot(d, B.slot(b), B.tiled, B.tile_cap, &B.fb.f[b]))) return rc;
@@ -438,8 +423,8 @@ static int record_front_end(lm_detector* d, const Batch& B) {
 static int enqueue_coarse(lm_detector* d, const Batch& B) {
     // the counters are zero on entry (reset by the slots' previous k_dedupe)
     { LM_CLOCK("launch_coarse");
-    if (B.cbits) launch_coarse_bits(B.fb, B.tb, d->geom, d->d_entries.p, d->d_feat_off.p, d->d_work.p, B.num_work, B.threshold, d->buf_cand_cap, d->cbits_byte0, d->cbits_max_nf, d->resp_low_weight, B.s);
-    else launch_coarse(B.fb, d->geom, d->d_entries.p, d->d_feat_off.p, d->d_work.p, B.num_work, B.threshold, d->buf_cand_cap, B.tile_cap, B.s);
+    if (B.cbits) launch_coarse_bits(B.fb, B.tb, d->geom, B.bank, B.num_work, B.threshold, d->buf_cand_cap, d->cbits_byte0, d->cbits_max_nf, d->resp_low_weight, B.s);
+    else launch_coarse(B.fb, d->geom, B.bank, B.num_work, B.threshold, d->buf_cand_cap, B.tile_cap, B.s);
     }
     HIP_TRY(hipEventRecord(d->slot[B.first].ev[3], B.s));
     return LM_OK;
@@ -449,20 +434,18 @@ static int enqueue_coarse(lm_detector* d, const Batch& B) {
 // read on the device (no host round trip), the records stored straight into the slots' pinned host memory; it also empties
 // the hash tables k_dedupe uses
 static int enqueue_match(lm_detector* d, const Batch& B) {
+    const uint32_t dedupe_slots = (uint32_t)dedupe_table_slots(d->buf_cand_cap);
     if (B.bits) {
         { LM_CLOCK("launch_local_bits");
-        launch_local_bits(B.fb, B.bb, d->geom, d->d_entries.p, d->d_feat_word.p, d->d_work.p, d->buf_cand_cap, B.threshold, B.cap,
-                          (uint32_t)dedupe_table_slots(d->buf_cand_cap), bits_grid(d, B.nb), d->bits_max_nf, d->resp_low_weight, B.s); }
+        launch_local_bits(B.fb, B.bb, d->geom, B.bank, d->buf_cand_cap, B.threshold, B.cap, dedupe_slots, bits_grid(d, B.nb), d->bits_max_nf, d->resp_low_weight, B.s); }
         if (B.bb.top_clear_units)     // the pair streams this launch zeroes again are clean for their slots' next frames
             for (int b = 0; b < B.nb; ++b)
                 if (B.bb.top_clear[b]) d->cbits_clean[B.slot(b)] = true;
         if (!d->bits_all_in)          // candidates whose windows leave their planes (marked in todo): k_local's per-candidate path
-            launch_local(B.fb_rest, d->geom, d->d_entries.p, d->d_feat_off.p, d->d_feat_word.p, d->d_run_mask.p, d->d_feat_xy.p, d->d_work.p, d->buf_cand_cap, B.threshold, B.cap,
-                         (uint32_t)dedupe_table_slots(d->buf_cand_cap), B.tile_cap, d->num_cus * 2, B.s);
+            launch_local(B.fb_rest, d->geom, B.bank, d->buf_cand_cap, B.threshold, B.cap, dedupe_slots, B.tile_cap, d->num_cus * 2, B.s);
     } else
     if (B.num_work > 0)
-        launch_local(B.fb, d->geom, d->d_entries.p, d->d_feat_off.p, d->d_feat_word.p, d->d_run_mask.p, d->d_feat_xy.p, d->d_work.p, d->buf_cand_cap, B.threshold, B.cap,
-                     (uint32_t)dedupe_table_slots(d->buf_cand_cap), B.tile_cap, local_grid(d, B.nb), B.s);
+        launch_local(B.fb, d->geom, B.bank, d->buf_cand_cap, B.threshold, B.cap, dedupe_slots, B.tile_cap, local_grid(d, B.nb), B.s);
     HIP_TRY(hipEventRecord(d->slot[B.first].ev[4], B.s));
     return LM_OK;
 }

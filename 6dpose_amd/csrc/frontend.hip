@@ -204,15 +204,6 @@ static __device__ __forceinline__ void color_quant_body(const int bx, const int 
     }
 }
 
-__global__ void __launch_bounds__(256)
-k_color_quant(const uint8_t* __restrict__ rgb, float* __restrict__ mag, uint8_t* __restrict__ onehot, int W, int H, float thr_sq) {
-    color_quant_body(blockIdx.x, blockIdx.y, rgb, mag, onehot, W, H, thr_sq);
-}
-
-void launch_color_quant(const uint8_t* rgb, float* mag, uint8_t* onehot, int W, int H, float thr_sq, hipStream_t s) {
-    hipLaunchKernelGGL(k_color_quant, dim3((W + kCTX - 1) / kCTX, (H + kCTY - 1) / kCTY), dim3(256), 0, s, rgb, mag, onehot, W, H, thr_sq);
-}
-
 // ---- cv::pyrDown 8UC3 (LL.cpp:566; Appendix A.6): 5x5 [1 4 6 4 1], REFLECT_101, (sum+128)>>8 ----
 static __device__ __forceinline__ int reflect101(int p, int n) {
     if (n == 1) return 0;
@@ -236,15 +227,6 @@ static __device__ __forceinline__ void pyrdown_body(const int bx, const int by, 
         s += w[j] * rs;
     }
     dst[(size_t)y * Wo * 3 + i] = (uint8_t)((s + 128) >> 8);
-}
-
-__global__ void __launch_bounds__(256) k_pyrdown_rgb(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, int W, int H, int Wo, int Ho) {
-    pyrdown_body(blockIdx.x, blockIdx.y, src, dst, W, H, Wo, Ho);
-}
-
-void launch_pyrdown_rgb(const uint8_t* src, uint8_t* dst, int W, int H, hipStream_t s) {
-    int Wo = W / 2, Ho = H / 2;
-    hipLaunchKernelGGL(k_pyrdown_rgb, dim3((Wo * 3 + 255) / 256, Ho), dim3(256), 0, s, src, dst, W, H, Wo, Ho);
 }
 
 // ---- quantizedNormals (LL.cpp:729-817; Appendix A.7) + cv::medianBlur(5) (LL.cpp:818), replicate border ----------
@@ -373,30 +355,11 @@ static __device__ __forceinline__ void normals_median_body(const int bx, const i
     }
 }
 
-__global__ void __launch_bounds__(256)
-k_normals_median(const uint16_t* __restrict__ depth, uint8_t* __restrict__ raw, uint8_t* __restrict__ med, int W, int H, int dist_thr,
-                 int diff_thr) {
-    normals_median_body(blockIdx.x, blockIdx.y, depth, raw, med, W, H, dist_thr, diff_thr);
-}
-
-void launch_normals_fused(const uint16_t* depth, uint8_t* raw, uint8_t* med, int W, int H, int dist_thr, int diff_thr, hipStream_t s) {
-    hipLaunchKernelGGL(k_normals_median, dim3((W + kCTX - 1) / kCTX, (H + kCTY - 1) / kCTY), dim3(256), 0, s, depth, raw, med, W, H, dist_thr,
-                       diff_thr);
-}
-
 // cv::resize(INTER_NEAREST) to (cols/2, rows/2) (LL.cpp:576, 867, 877) = pixel (2y, 2x)
 static __device__ __forceinline__ void nn_down2_body(const int bx, const int by, const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, int W, int Wo) {
     int x = bx * 256 + threadIdx.x, y = by;
     if (x >= Wo) return;
     dst[(size_t)y * Wo + x] = src[(size_t)(2 * y) * W + 2 * x];
-}
-__global__ void __launch_bounds__(256) k_nn_down2(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, int W, int Wo) {
-    nn_down2_body(blockIdx.x, blockIdx.y, src, dst, W, Wo);
-}
-
-void launch_nn_down2(const uint8_t* src, uint8_t* dst, int W, int H, hipStream_t s) {
-    int Wo = W / 2, Ho = H / 2;
-    hipLaunchKernelGGL(k_nn_down2, dim3((Wo + 255) / 256, Ho), dim3(256), 0, s, src, dst, W, Wo);
 }
 
 // ---- spread (LL.cpp:1094-1109) fused with computeResponseMaps (LL.cpp:1134-1203, active SIMILARITY_LUT
@@ -594,24 +557,12 @@ static __device__ __forceinline__ void build_lm_body4(const int bx, const int by
     }
 }
 
-__global__ void __launch_bounds__(256) k_build_lm(LmJob j0, LmJob j1, int W, int H, int T, int Wd, int Hd, int NS, uint32_t m_wd, uint32_t m_t, uint32_t resp) {
-    if ((Wd & 3) == 0) build_lm_body4(blockIdx.x, blockIdx.y, blockIdx.z ? j1 : j0, W, H, T, Wd, Hd, NS, m_wd, m_t, resp);
-    else build_lm_body(blockIdx.x, blockIdx.y, blockIdx.z ? j1 : j0, W, H, T, Wd, Hd, NS, m_wd, m_t, resp);
-}
-
-void launch_build_lm(const uint8_t* const quant[2], const uint8_t* const mask[2], uint8_t* const lm[2], uint8_t* const strips[2],
-                     int W, int H, int T, uint32_t resp, hipStream_t s) {
-    int Wd = W / T, Hd = H / T, NS = (Wd + 15) / 16;
-    LmJob j0{quant[0], mask[0], lm[0], strips[0]}, j1{quant[1], mask[1], lm[1], strips[1]};
-    hipLaunchKernelGGL(k_build_lm, dim3((Wd * Hd + 255) / 256, T * T, 2), dim3(256), 0, s, j0, j1, W, H, T, Wd, Hd, NS, div_magic((uint32_t)Wd), div_magic((uint32_t)T), resp);
-}
-
 // ---- the bit planes written directly -------------------------------------------------------------------------------
 // When nothing reads the byte planes of a level (bit-plane kernels for both passes, every window inside its plane) the linear-memory
 // stage does not write them at all: 8 response bytes per position and encoding (flat + strip-major: 9.8 MB per VGA frame at level 0)
 // become 2 bits per position and label (2.5 MB), and k_pack_bits / k_pack_top disappear from the batch.
 //
-// Strip records of a level below the top (match.hip: per plane row and 16-column strip 64 bits, cell c of [16 s, 16 s + 32) at bits 2c =
+// Strip records of a level below the top (match_bits.hip: per plane row and 16-column strip 64 bits, cell c of [16 s, 16 s + 32) at bits 2c =
 // "response is 1" and 2c + 1 = "response is 4").  A workgroup takes R rows of one (modality, phase): every thread ORs the T x T
 // pixels of a few cells (spread) and leaves {neighbour bits & ~own bits | own bits << 8} per cell in LDS — response 4 iff the label's own
 // bit is set, 1 iff only a neighbouring label's is (LL.cpp:1121) —; then one thread per (label, row, strip) gathers the label's two bits of
@@ -665,7 +616,7 @@ static __device__ __forceinline__ void bits_rows_body(const int bx, const int by
     }
 }
 
-// The pair stream of the top level (match.hip: {is-1 dword, is-4 dword} per 32 consecutive bytes of the flat arena).  One thread per
+// The pair stream of the top level (match_bits.hip: {is-1 dword, is-4 dword} per 32 consecutive bytes of the flat arena).  One thread per
 // (phase, position) as in the byte stage; a wave's 64 consecutive positions of a label's plane are 64 consecutive bits of the stream at an
 // arbitrary bit offset (planes are not multiples of 32 positions): the ballots are shifted into place and OR-ed into the three dwords
 // they touch.  The stream was zeroed by a job of the batch's first launch (fe_job_zero).
@@ -952,10 +903,10 @@ static __device__ __forceinline__ void bits_rows_block_body(const int blk, const
 }
 
 // ---- several independent front-end jobs in ONE launch ---------------------------------------------------------------------
-// The seven kernels of a frame are small (5-17 us) and dependent kernels on a queue start ~7 us apart, so the front end is
-// mostly launch latency.  The jobs that do not depend on each other share a launch: stage k = {colour chain of level k,
+// The seven jobs of a frame are small (5-17 us as kernels of their own, as they were in round 1) and dependent kernels on a queue
+// start ~7 us apart, so the front end is mostly launch latency.  The jobs that do not depend on each other share a launch: stage k = {colour chain of level k,
 // normals + median (k = 0) or nearest-neighbour normals of level k, pyrDown to level k + 1}; the last launch builds the linear
-// memories of every level.  A job is a range of the flat block index; the bodies are the kernels above, unchanged.
+// memories of every level.  A job is a range of the flat block index; the *_body functions above are the jobs, and k_fe_stage is their only kernel.
 // The workgroups are persistent: a tile takes a workgroup ~1.5 us, and the dispatcher hands an XCD a new workgroup only every
 // ~30 ns — with one workgroup per tile (10.8k for the first stage of four VGA frames) a CU held 1.3 workgroups on average and the
 // stage took as long as the dispatcher needed (42 us; profiles/r03_pmc.txt: 5 waves per CU).  A few workgroups per CU walk the

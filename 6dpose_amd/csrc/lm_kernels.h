@@ -1,5 +1,5 @@
 // Internal interface between the host orchestration (detector*.cpp, pose_refine.cpp) and the HIP
-// kernels (frontend.hip, match.hip, icp*.hip).  gfx950 only.  Not part of the public C ABI.
+// kernels (frontend.hip, match_bytes.hip, match_bits.hip, icp*.hip).  gfx950 only.  Not part of the public C ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -25,18 +25,12 @@ inline bool resp_two_planes(const uint8_t r[5]) { const uint32_t kl = (resp_pack
 
 // ---- front end (frontend.hip): reference A1-A7, LL.cpp:350-505, 557-581, 729-880, 1026-1243 ----
 void upload_normal_lut(const uint8_t lut400[400]);
-// the colour chain (blur7 + sobel_quant + hysteresis) and the normal chain (normals + median5) as single tiled launches
-void launch_color_quant(const uint8_t* rgb, float* mag, uint8_t* onehot, int W, int H, float thr_sq, hipStream_t s);
-void launch_normals_fused(const uint16_t* depth, uint8_t* raw, uint8_t* med, int W, int H, int dist_thr, int diff_thr, hipStream_t s);
-void launch_pyrdown_rgb(const uint8_t* src, uint8_t* dst, int W, int H, hipStream_t s);  // dst (W/2,H/2)
-void launch_nn_down2(const uint8_t* src, uint8_t* dst, int W, int H, hipStream_t s);     // dst (W/2,H/2)
-// spread (T x T OR) -> 8 response maps -> linearised layout LM[8][T*T][(W/T)*(H/T)] for both modalities of a level in one
-// launch ([0] colour, [1] normals); mask[m] may be null; `strips[m]` (may be null) receives the strip-major copy used by
-// the refinement kernel.
-void launch_build_lm(const uint8_t* const quant[2], const uint8_t* const mask[2], uint8_t* const lm[2], uint8_t* const strips[2],
-                     int W, int H, int T, uint32_t resp /* resp_pack */, hipStream_t s);
 
-// several independent jobs of the front end in one launch (frontend.hip, k_fe_stage)
+// Every job of the front end goes through one job table: several independent jobs in one launch (frontend.hip, k_fe_stage).
+// The jobs: the colour chain (blur7 + sobel_quant + hysteresis) and the normal chain (normals + median5) as tiled passes, the pyramid
+// steps (dst = (W/2, H/2)), and build_lm: spread (T x T OR) -> 8 response maps -> linearised layout LM[8][T*T][(W/T)*(H/T)] for both
+// modalities of a level ([0] colour, [1] normals); mask[m] may be null; `strips[m]` (may be null) receives the strip-major copy used
+// by the refinement kernel.
 struct LmJob { const uint8_t* quant; const uint8_t* mask; uint8_t* lm; uint8_t* strips; };
 // (the bit-plane jobs reuse the two output slots — 24 jobs of a batch of 8 frames must fit the 4 KB of kernel arguments —: `lm` = the strip
 // records of the level / the top level's pair stream, `strips` = for the pair stream the flat position of the modality's block in it, as an integer)
@@ -73,7 +67,7 @@ int fe_top_bits_kind(int W, int H, int T, const uint32_t bit0[2], int mode);   /
 void launch_fe_stage(FeStage& st, hipStream_t s);
 void launch_fe_bits(FeStage& st, hipStream_t s);      // a launch of bit-plane jobs only (fe_job_bits_rows, fe_job_top_bits)
 
-// ---- matching (match.hip): reference A8-A11, LL.cpp:1284-1428, 1788-1941 ----
+// ---- matching (match_bytes.hip, match_bits.hip): reference A8-A11, LL.cpp:1284-1428, 1788-1941 ----
 struct LevelGeom {        // one pyramid level of the current frame
     int W, H, T, Wd, Hd;  // image size, sampling step, decimated size
     uint32_t lm_off[2];   // byte offset of the colour / normal LM block inside the LM arena
@@ -93,13 +87,17 @@ struct TemplEntry {       // one (pyramid, level): both modalities, colour featu
     int32_t width, height;
     int16_t min_x, min_y, max_x, max_y;   // bounding box of the features (fast-path test of the refinement)
 };
+struct BankDev {          // the bank on the device, as the matching launchers take it (they unpack it: the kernels' parameters are the loose pointers)
+    const TemplEntry* entries; const int32_t* feat_off; const uint32_t* feat_word; const uint32_t* run_mask; const uint32_t* feat_xy;
+    const int32_t* work;  // the work list: template pyramids to search
+};
 struct Candidate {        // coarse hit, and (same layout) final match record
     int32_t x, y;
     float score;
     int32_t work;         // index into the work list (-> class position, template id)
 };
 
-// Tile refinement (match.hip): candidates of one template whose coarse cells are neighbours share most of their level-0
+// Tile refinement (match_bytes.hip): candidates of one template whose coarse cells are neighbours share most of their level-0
 // windows; k_coarse groups them into tiles, k_local accumulates a tile's window region once for all its members.
 constexpr int kTileStep = 4;      // most level-0 cells between the windows of neighbouring coarse cells: 2 * T_top / T_0 <= this
 constexpr int kTileMaskBits = 10; // member bits of TileRec::mask (kTileNx x kTileNy); above them the window steps, 3 bits each: columns 1..4, second row
@@ -147,7 +145,7 @@ struct FrameBatch {
     FrameSlot f[kMaxBatch];
 };
 
-// Bit planes (match.hip).  Levels below the top: per frame of a batch the strip arena the records are packed from
+// Bit planes (match_bits.hip).  Levels below the top: per frame of a batch the strip arena the records are packed from
 // (launch_pack_bits; the front end writes them itself when nothing reads the strip bytes) and its bit arena — the strip arena's layout at
 // half the offsets: per plane row and strip an 8-byte record of 32 cells x {is 1, is 4} instead of a 16-byte row.
 struct BitsBatch { const uint8_t* strips[kMaxBatch]; uint8_t* bits[kMaxBatch];
@@ -156,24 +154,21 @@ constexpr int kBitsSmallMax = 511;            // features per template entry the
 void launch_pack_bits(const BitsBatch& B, int nb, const LevelGeom& lv, hipStream_t s);      // bytes {0, a, 4} -> {is a, is 4}, any a in 1..3
 // Every level below the top: todo[ci] = 1 for the candidates it leaves to launch_local's per-candidate path (windows leaving their planes);
 // max_features = the largest nf of the bank's entries below the top level.
-void launch_local_bits(const FrameBatch& fb, const BitsBatch& B, const FrameGeom& g, const TemplEntry* entries, const uint32_t* feat_word,
-                       const int32_t* work_pyramids, uint32_t cand_cap, float threshold, uint32_t cap, uint32_t dedupe_cap_slots, int grid_blocks,
-                       int max_features, int low_weight /* a: the sum is a n_a + 4 n_4 */, hipStream_t s);
+void launch_local_bits(const FrameBatch& fb, const BitsBatch& B, const FrameGeom& g, const BankDev& bank, uint32_t cand_cap, float threshold,
+                       uint32_t cap, uint32_t dedupe_cap_slots, int grid_blocks, int max_features, int low_weight /* a: the sum is a n_a + 4 n_4 */, hipStream_t s);
 // Coarse pass on bit planes: per frame of a batch the flat arena and the pair stream of bytes [byte0, byte0 + 32 npairs) of it (the top
 // level's blocks of both modalities with their zero tails): launch_pack_top packs it from the bytes, the front end writes it directly when
 // nothing reads the top level's bytes (frontend.hip, top_bits_body: the stream must be zero before).
 struct TopBits { const uint8_t* lm[kMaxBatch]; uint8_t* bits[kMaxBatch]; };
 void launch_pack_top(const TopBits& B, int nb, uint32_t byte0, uint32_t npairs, hipStream_t s);
 // candidates only (no tiles); max_features = the largest nf of the bank's top-level entries
-void launch_coarse_bits(const FrameBatch& fb, const TopBits& B, const FrameGeom& g, const TemplEntry* entries, const int32_t* feat_off,
-                        const int32_t* work_pyramids, int num_work, float threshold, uint32_t cap, uint32_t byte0, int max_features, int low_weight, hipStream_t s);
+void launch_coarse_bits(const FrameBatch& fb, const TopBits& B, const FrameGeom& g, const BankDev& bank, int num_work, float threshold, uint32_t cap, uint32_t byte0, int max_features, int low_weight, hipStream_t s);
 bool tile_plan_possible(const FrameGeom& g);
 size_t coarse_plan_lds_bytes(int Wd, int Hd);
 // Per frame of the batch: counters[0] = number of candidates produced (may exceed cap: nothing is written past cap); with tiles
 // (and a geometry tile_plan_possible accepts) also counters[0] >> kCandBits = number of tiles, todo[slot] = 1 for the candidates
 // no tile serves.  Grid (workgroups of templates, frames).
-void launch_coarse(const FrameBatch& fb, const FrameGeom& g, const TemplEntry* entries, const int32_t* feat_off,
-                   const int32_t* work_pyramids, int num_work, float threshold, uint32_t cap, uint32_t tile_cap, hipStream_t s);
+void launch_coarse(const FrameBatch& fb, const FrameGeom& g, const BankDev& bank, int num_work, float threshold, uint32_t cap, uint32_t tile_cap, hipStream_t s);
 // Persistent grid: waves stride over the tiles of all frames of the batch, then over their candidates (counts read on the device).
 // matches_dev[ci] = refined candidate ci (work = -1: dropped).  Also empties the part of every frame's hash table k_dedupe will use.
 // Per feature of a level below the top ONE word, feat_word = base0 | cls: base0 = byte offset (a multiple of 16) inside the strip
@@ -185,9 +180,7 @@ void launch_coarse(const FrameBatch& fb, const FrameGeom& g, const TemplEntry* e
 // run_mask[f / 8] bit (f % 8): feature f starts a new class run (class change, or 62 features of one class: the packed-byte sums hold
 // 63 x 4).  Runs have even length and start at even indices (the per-candidate path loads same-class pairs).
 constexpr int kRunMax = 62;
-void launch_local(const FrameBatch& fb, const FrameGeom& g, const TemplEntry* entries, const int32_t* feat_off, const uint32_t* feat_word,
-                  const uint32_t* run_mask, const uint32_t* feat_xy, const int32_t* work_pyramids, uint32_t cand_cap, float threshold, uint32_t cap,
-                  uint32_t dedupe_cap_slots, uint32_t tile_cap, int grid_blocks, hipStream_t s);
+void launch_local(const FrameBatch& fb, const FrameGeom& g, const BankDev& bank, uint32_t cand_cap, float threshold, uint32_t cap, uint32_t dedupe_cap_slots, uint32_t tile_cap, int grid_blocks, hipStream_t s);
 // slots of k_dedupe's open-addressing table used for n records (power of two, >= 2n, <= cap_slots = dedupe_table_slots(cand_cap)):
 // k_local empties exactly these, k_dedupe hashes into exactly these
 __host__ __device__ inline uint32_t dedupe_slots_for(uint32_t n, uint32_t cap_slots) {

@@ -1,5 +1,7 @@
-// Similarity kernels of Detector::matchClass on gfx950 (reference LL.cpp:1284-1428 similarity /
-// similarityLocal, LL.cpp:1788-1941 matchClass).  Pure integer byte work: every response is a
+// Similarity kernels of Detector::matchClass on gfx950, on byte planes (reference LL.cpp:1284-1428 similarity /
+// similarityLocal, LL.cpp:1788-1941 matchClass): k_coarse with its tile planner, k_local, launch_coarse, launch_local,
+// tile_plan_possible, coarse_plan_lds_bytes.  The bit-plane kernels (k_local_bits, k_coarse_bits and their packers) are in
+// match_bits.hip, what both use in match_device.h.  Pure integer byte work: every response is a
 // u8 in {0,1,4}, summed per template position.  Nothing here is a dense contraction, so no MFMA;
 // the linear memories of one frame (1.2 MB coarse + 4.9 MB fine at VGA) live in L2 / Infinity
 // Cache; the byte kernels (k_coarse, k_local) are bound by the vector-L1 access rate (see "Gather discipline" below), the bit-plane refinement
@@ -18,7 +20,7 @@
 #include <algorithm>
 
 #include "knobs.h"
-#include "lm_kernels.h"
+#include "match_device.h"
 
 namespace lm {
 
@@ -26,11 +28,6 @@ static __device__ __forceinline__ uint32_t ld_u32(const uint8_t* p) {
     uint32_t v;
     __builtin_memcpy(&v, p, 4);   // unaligned global_load_dword (gfx950 unaligned access mode)
     return v;
-}
-
-// score = (raw * 100.f) / (4 * num_features)  — LL.cpp:1842, 1918; IEEE single, no contraction
-static __device__ __forceinline__ float score_of(int raw, int nfeat) {
-    return __fdiv_rn(__fmul_rn((float)raw, 100.f), (float)(4 * nfeat));
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -44,22 +41,6 @@ static __device__ __forceinline__ float score_of(int raw, int nfeat) {
 // argument, README.md:67-69) and realigns ONCE per class run (v_alignbyte + one neighbour exchange)
 // into the u16 position accumulators.
 // ---------------------------------------------------------------------------------------------
-
-// The gathers of the three fast paths go through buffer loads: `buffer_load_dwordx4 v, v_off, s[rsrc], s_off offen` takes the
-// arena as a resource in SGPRs, ONE 32-bit per-lane offset (constant for the whole item) and the feature's wave-uniform byte
-// offset in an SGPR.  As global loads the compiler kept a 64-bit VGPR address per load in flight — 16 VGPRs for a batch of 8 and
-// two VALU adds per load — which is what put k_local at 67 and k_coarse at 96 VGPRs (occupancy 7 / 5 waves per SIMD); the
-// kernels' speed follows their occupancy (profiles/r02_local_experiments.txt).
-using BufRsrc = __amdgpu_buffer_rsrc_t;
-static __device__ __forceinline__ BufRsrc make_rsrc(const void* base) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, -1 /* no range check: 2^32 - 1 bytes */, 0x00020000 /* gfx9: raw dwords */);
-}
-static __device__ __forceinline__ uint4 ld_buf16(BufRsrc r, uint32_t lane_off, uint32_t uniform_off) {
-    const auto v = __builtin_amdgcn_raw_buffer_load_b128(r, (int)lane_off, (int)uniform_off, 0);
-    uint4 u;
-    __builtin_memcpy(&u, &v, 16);
-    return u;
-}
 
 // widen 4 packed bytes of `v` into two packed u16x2 accumulators: e gets bytes 0,2 ; o gets bytes 1,3
 static __device__ __forceinline__ void add_bytes(uint32_t v, uint32_t& e, uint32_t& o) {
@@ -103,17 +84,6 @@ static __device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
 }
 static __device__ __forceinline__ unsigned long long bcast_u64(unsigned long long v, int src) {
     return ((unsigned long long)(uint32_t)__shfl((int)(v >> 32), src, 64) << 32) | (uint32_t)__shfl((int)(uint32_t)v, src, 64);
-}
-// exclusive prefix of `mine` over the lanes of the wave; total = the wave's sum
-static __device__ __forceinline__ int wave_excl_scan(int mine, int lane, int& total) {
-    int incl = mine;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        int t = __shfl_up(incl, o, 64);
-        if (lane >= o) incl += t;
-    }
-    total = __shfl(incl, 63, 64);
-    return incl - mine;
 }
 
 // A workgroup serves `group` templates at once, `wpt` waves each (blockDim = group * wpt * 64).  With tile planning ONE atomic
@@ -447,8 +417,7 @@ size_t coarse_plan_lds_bytes(int Wd, int Hd) {                 // per template o
     return (npos + nw + 4 * (size_t)kMaxTilesPerTemplate + kPlanHits) * sizeof(uint32_t);   // scores | hit bitmap | tile records | hit list
 }
 
-void launch_coarse(const FrameBatch& fb, const FrameGeom& g, const TemplEntry* entries, const int32_t* feat_off,
-                   const int32_t* work_pyramids, int num_work, float threshold, uint32_t cap, uint32_t tile_cap, hipStream_t s) {
+void launch_coarse(const FrameBatch& fb, const FrameGeom& g, const BankDev& bank, int num_work, float threshold, uint32_t cap, uint32_t tile_cap, hipStream_t s) {
     if (num_work <= 0 || fb.nb <= 0) return;
     const TileRec* tiles = fb.f[0].tiles;                      // tiles are planned for all frames of a batch or for none
     const uint8_t* todo = fb.f[0].todo;
@@ -483,8 +452,8 @@ void launch_coarse(const FrameBatch& fb, const FrameGeom& g, const TemplEntry* e
         group = std::max(1, std::min(std::min(4, std::max(1, max_group)), std::min(16 / waves, (int)((64 * 1024 - 256) / per))));
         lds = per * group + (4 * (size_t)group + 4) * sizeof(uint32_t);
     }
-    hipLaunchKernelGGL(k_coarse, dim3((num_work + group - 1) / group, fb.nb), dim3(group * waves * 64), lds, s, fb, lv, level, g.levels, entries,
-                       feat_off, work_pyramids, num_work, waves, cpw, threshold, cap, plan);
+    hipLaunchKernelGGL(k_coarse, dim3((num_work + group - 1) / group, fb.nb), dim3(group * waves * 64), lds, s, fb, lv, level, g.levels, bank.entries,
+                       bank.feat_off, bank.work, num_work, waves, cpw, threshold, cap, plan);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -911,508 +880,13 @@ k_local(FrameBatch fb, FrameGeom g, const TemplEntry* __restrict__ entries, cons
     }
 }
 
-// ---- Bit planes: the default encoding of the response memories for both matching kernels --------------------------
-// A response is 0, 1 or 4, so a position's sum is n1 + 4 n4 with n1 / n4 = the number of features whose response there is 1 / 4: two bits
-// per cell carry what the byte planes do, and the sums can be kept BIT-SLICED (one dword = 32 positions of one counter bit), features
-// entering through carry-save adders; integers are formed once per candidate / only for the hits.
-//
-// Levels below the top ("strip records", read by k_local_bits): the strip arena at half the offsets — per plane row and 16-column strip s an
-// 8-byte record holding cells [16 s, 16 s + 32) of that row with TWO BITS PER CELL, bit 2c = "the response of cell 16 s + c is 1", bit
-// 2c + 1 = "it is 4".  Strips are 32 cells wide at a stride of 16, so any 16-cell window of a row lies inside ONE record and comes out of it
-// with ONE funnel shift, v_alignbit(hi, lo, 2 (column & 15)): a dword of 16 positions x {is-1, is-4}.  (Round 3 kept the two planes in
-// separate dwords: 4 shifts + 2 ands + 2 or per lane and feature to cut the windows out, and every lane redid the address arithmetic of
-// every feature — 30 VALU instructions per lane and feature at 0.92 of the issue slots)
-// The top level ("pair stream", read by k_coarse_bits): the flat linear memories [label][phase][position] as one pair {is-1 dword, is-4
-// dword} per 32 consecutive arena bytes, so the reference's reads that run from one plane into the next stay what they are.
-// carry-save adder: two v_bitop3_b32 (gfx950's ternary logic op; truth tables with a = 0xF0, b = 0xCC, c = 0xAA: parity 0x96, majority 0xE8)
-static __device__ __forceinline__ void csa(uint32_t& sum, uint32_t& carry, uint32_t a, uint32_t b, uint32_t c) {
-    const uint32_t s = __builtin_amdgcn_bitop3_b32(a, b, c, 0x96);
-    carry = __builtin_amdgcn_bitop3_b32(a, b, c, 0xE8);
-    sum = s;
-}
-// eight 1-bit inputs into {ones, twos, fours}; returns the carry of weight 8 (7 carry-save adders = 14 v_bitop3)
-static __device__ __forceinline__ uint32_t add8(const uint32_t (&x)[8], uint32_t& ones, uint32_t& twos, uint32_t& fours) {
-    uint32_t ta, tb, fa, fb, e;
-    csa(ones, ta, ones, x[0], x[1]);
-    csa(ones, tb, ones, x[2], x[3]);
-    csa(twos, fa, twos, ta, tb);
-    csa(ones, ta, ones, x[4], x[5]);
-    csa(ones, tb, ones, x[6], x[7]);
-    csa(twos, fb, twos, ta, tb);
-    csa(fours, e, fours, fa, fb);
-    return e;
-}
-// Counter of kN bits per position: c[0..3] = ones, twos, fours, eights, c[4..] = 16s and up.  Two carries of weight 8 (16 features) enter
-// through one more adder and ONE ripple of the sixteens (Harley-Seal: 2.5 operations per input instead of 3.25 with a ripple per 8).
-template <int kN>
-static __device__ __forceinline__ void add_eights2(uint32_t (&c)[kN], uint32_t e1, uint32_t e2) {
-    uint32_t k16;
-    csa(c[3], k16, c[3], e1, e2);
-#pragma unroll
-    for (int k = 4; k < kN; ++k) { const uint32_t t = c[k] & k16; c[k] ^= k16; k16 = t; }
-}
-template <int kN>
-static __device__ __forceinline__ void add_eights1(uint32_t (&c)[kN], uint32_t e1) {
-    uint32_t k16 = c[3] & e1;
-    c[3] ^= e1;
-#pragma unroll
-    for (int k = 4; k < kN; ++k) { const uint32_t t = c[k] & k16; c[k] ^= k16; k16 = t; }
-}
-
-// The bit-sliced sum S = a n_a + 4 n_4 of two bit-sliced counts (kA = a: the weight of the low plane, lm_kernels.h resp_pack; 1 for the
-// default table 4 1 0 0 0, whose instantiation is the code it always was).  n_a + n_4 <= features, so kN + 3 bits hold any of them.
-template <int kA, int kN>
-static __device__ __forceinline__ void weighted_sum(uint32_t (&S)[kN + 3], const uint32_t (&na)[kN], const uint32_t (&n4)[kN]) {
-    constexpr int kS = kN + 3;
-    uint32_t carry = 0;
-    if (kA == 1) {
-        S[0] = na[0]; S[1] = na[1];
-#pragma unroll
-        for (int k = 2; k < kS; ++k) csa(S[k], carry, k < kN ? na[k] : 0u, k - 2 < kN ? n4[k - 2] : 0u, carry);
-    } else if (kA == 2) {
-        S[0] = 0u; S[1] = na[0];
-#pragma unroll
-        for (int k = 2; k < kS; ++k) csa(S[k], carry, k - 1 < kN ? na[k - 1] : 0u, k - 2 < kN ? n4[k - 2] : 0u, carry);
-    } else {                                                        // 3 n_a = n_a + 2 n_a first (kN + 2 bits), then + 4 n_4
-        uint32_t t[kN + 2];
-        t[0] = na[0];
-#pragma unroll
-        for (int k = 1; k < kN + 2; ++k) csa(t[k], carry, k < kN ? na[k] : 0u, k - 1 < kN ? na[k - 1] : 0u, carry);
-        carry = 0;
-        S[0] = t[0]; S[1] = t[1];
-#pragma unroll
-        for (int k = 2; k < kS; ++k) csa(S[k], carry, k < kN + 2 ? t[k] : 0u, k - 2 < kN ? n4[k - 2] : 0u, carry);
-    }
-}
-
-// 4 response bytes -> 8 bits, cell k at bits 2k (is 1 = bit 0 of the byte) and 2k + 1 (is 4 = bit 2 of the byte); the multiply gathers the
-// four 2-bit fields into the top byte (partial products land on distinct bits: no carries)
-// (any table of two planes: the bytes are 0, a or 4 with a = 1, 2 or 3 — "is a" = bit 0 or bit 1 of the byte)
-static __device__ __forceinline__ uint32_t pack4(uint32_t d) {
-    const uint32_t t = ((d | (d >> 1)) & 0x01010101u) | ((d >> 1) & 0x02020202u);
-    return (t * 0x01041040u) >> 24;
-}
-static __device__ __forceinline__ uint32_t pack16(const uint4& v) { return pack4(v.x) | (pack4(v.y) << 8) | (pack4(v.z) << 16) | (pack4(v.w) << 24); }
-
-// Strip records from the strip bytes (the front end writes the records itself when nothing reads the bytes: frontend.hip, bits_rows_body;
-// this kernel serves the banks and geometries that keep the byte planes — a fallback launch of k_local may follow — and the tests of both).
-__global__ void __launch_bounds__(256)
-k_pack_bits(BitsBatch B, uint32_t sm_off0, uint32_t records, int NS, int Hd) {
-    const uint32_t i = blockIdx.x * 256u + threadIdx.x;             // record = ((plane * NS + s) * Hd + row)
-    if (i >= records) return;
-    const uint32_t q = i / (uint32_t)Hd, s = q % (uint32_t)NS;
-    const uint8_t* src = B.strips[blockIdx.y] + sm_off0 + (size_t)i * 16;
-    const uint4 a = *reinterpret_cast<const uint4*>(src);
-    uint4 b = make_uint4(0, 0, 0, 0);
-    if (s + 1 < (uint32_t)NS) b = *reinterpret_cast<const uint4*>(src + (size_t)Hd * 16);      // the next strip of this row
-    uint2 r;
-    r.x = pack16(a);
-    r.y = pack16(b);
-    *reinterpret_cast<uint2*>(B.bits[blockIdx.y] + (sm_off0 >> 1) + (size_t)i * 8) = r;
-}
-
-// Refinement on strip records (LL.cpp:1855-1938, similarityLocal :1366-1428).  8 lanes per candidate — lane j owns window rows 2j and 2j + 1,
-// ONE 16-byte load = their two records —, 8 candidates per wave, one feature per candidate and load instruction: a wave load serves 8
-// (candidate, feature) pairs.  Per 16 features a lane fetches two feature words and forms, ONCE for its group, their record offsets (window
-// origin, strip carry) and shift amounts; the group's lanes pick them up with two ds_bpermute per feature and add only their own row term.
-// Per lane and feature: 1 add, 2 v_alignbit, 5 adder operations (two dwords x 2.5).  Counters of kN = 4 + kHi bits: kHi = 5 serves entries
-// of up to 511 features, kHi = 10 up to 16383 (the reference allows 8191 per modality, LL.cpp:1291, 1816).
-// What bounds it (round 5, profiles/r05_local_sharing/README.txt): the number of wave loads — one takes 20-23 CU cycles whatever the lanes or addresses —, and
-// what keeps its L2 traffic down is that the 8 candidates of a wave are CONSECUTIVE candidates of one template (x-neighbours: ~5 distinct lines per wave load
-// instead of 23).  Three schemes that share loads between neighbouring candidates by regrouping them (vertical runs, interleaved pairs, same-lane pairs) were
-// built, bit-exact, and ran no faster: fewer wave loads, more L2 requests.  Hence: candidates in slot order, a grid of the resident workgroups.
-// All pyramid levels below the top are walked here (LL.cpp:1855: level by level, dropping a candidate as soon as it falls below the
-// threshold); a candidate whose windows leave their planes at some level (oversized template, features outside the frame) is marked in
-// `todo` and left, from the top, to k_local's per-candidate path.
-template <int kHi, int kWaves, int kA>
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kWaves, kWaves)))
-k_local_bits(FrameBatch fb, BitsBatch B, FrameGeom g, const TemplEntry* __restrict__ entries, const uint32_t* __restrict__ feat_word,
-             const int32_t* __restrict__ work_pyramids, uint32_t cand_cap, float threshold, uint32_t cap, uint32_t dedupe_cap_slots) {
-    constexpr int kN = 4 + kHi;                                     // counter bits per plane
-    constexpr int kS = kN + 3;                                      // bits of n1 + 4 n4
-    __shared__ unsigned long long s_acc[kMaxBatch][2];
-    __shared__ uint32_t s_cnt[kMaxBatch];
-    const int lane = threadIdx.x & 63, grp = lane >> 3, j = lane & 7;
-    const int nb = fb.nb;
-    // Frame -> XCD affinity as in k_local (an XCD's L2 holds ONE frame's planes), for ANY batch size up to 8: frame f is served by the workgroups of
-    // the XCDs x with x % nb == f — 8 / nb of them each when nb divides 8, else some frames get one XCD more than others.  (Round 3 fell back to
-    // dealing the items of all frames to all workgroups unless nb divided 8: a 5-frame launch — the first and last launches of a short stream —
-    // then cost 35 us per frame against 26 in an 8-frame launch.)
-    int f_lo = 0, f_hi = nb;
-    uint32_t w_first = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), w_step = gridDim.x * (blockDim.x >> 6);
-    if (nb > 1 && nb <= 8 && (gridDim.x & 7) == 0) {
-        const int xcd = (int)(blockIdx.x & 7);
-        f_lo = xcd % nb; f_hi = f_lo + 1;
-        const uint32_t mine = (uint32_t)((7 - f_lo) / nb + 1);      // XCDs serving this frame: f_lo, f_lo + nb, ...
-        const uint32_t wpb = blockDim.x >> 6;
-        w_first = ((blockIdx.x >> 3) * mine + (uint32_t)(xcd / nb)) * wpb + (threadIdx.x >> 6);
-        w_step = (gridDim.x >> 3) * mine * wpb;
-    }
-    if ((int)threadIdx.x < nb) {
-        const unsigned long long nc = fb.f[threadIdx.x].counters[0] & kCandMask;
-        s_cnt[threadIdx.x] = nc < cand_cap ? (uint32_t)nc : cand_cap;
-        s_acc[threadIdx.x][0] = 0; s_acc[threadIdx.x][1] = 0;
-    }
-    __syncthreads();
-    for (int f = 0; f < nb; ++f) {                                  // k_dedupe's hash table, emptied here like k_local does
-        unsigned long long* table = fb.f[f].dedupe_table;
-        if (!table) continue;
-        const uint32_t tsize = dedupe_slots_for(s_cnt[f], dedupe_cap_slots);
-        for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < tsize; i += gridDim.x * blockDim.x) table[i] = ~0ull;
-    }
-    // The pair stream k_coarse_bits has just read is zeroed for the slot's next frame: the front end ORs it together (frontend.hip, top_bits_body)
-    if (B.top_clear_units)
-        for (int f = 0; f < nb; ++f)
-            for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < B.top_clear_units; i += gridDim.x * blockDim.x)
-                reinterpret_cast<uint4*>(B.top_clear[f])[i] = make_uint4(0u, 0u, 0u, 0u);
-    const int src0 = (lane & ~7) << 2;                              // ds_bpermute address of the group's first lane
-    const uint32_t rowoff = 16u * (uint32_t)j;                      // records of rows 2j, 2j + 1 behind the window's first row
-    for (int fr = f_lo; fr < f_hi; ++fr) {
-        const FrameSlot& F = fb.f[fr];
-        const BufRsrc bits = make_rsrc(B.bits[fr]);
-        const uint32_t nc = s_cnt[fr], ngroups = (nc + 7u) >> 3;
-        for (uint32_t gi = w_first; gi < ngroups; gi += w_step) {
-            const uint32_t ci = gi * 8u + (uint32_t)grp;
-            const bool valid = ci < nc;
-            Candidate cd{0, 0, 0.f, 0};
-            if (valid) cd = F.cands[ci];
-            const int work = cd.work;
-            const int pyr = work_pyramids[work];
-            int mx = cd.x, my = cd.y;
-            float sim = cd.score;
-            bool alive = valid, leave = false;                      // leave: k_local's per-candidate path takes this candidate (from the top)
-            uint32_t evals = 0, bytes = 0;
-            for (int l = g.levels - 2; l >= 0; --l) {
-                const LevelGeom& lv = g.lv[l];
-                const int T = lv.T, W = lv.W, H = lv.H, Wd = lv.Wd, Hd = lv.Hd;
-                const int border = 8 * T, offset = T / 2 + (T % 2 - 1);
-                const uint32_t HS8 = (uint32_t)Hd * 8u;
-                const uint32_t zero_off = (lv.sm_off[1] + 8u * (uint32_t)(T * T) * ((uint32_t)lv.NS * (uint32_t)Hd * 16u)) >> 1;   // the level's all-zero plane
-                const TemplEntry e = entries[(size_t)pyr * g.levels + l];
-                // LL.cpp:1871-1880 (the clamp) and 1380-1381 (window origin), exactly as k_local
-                const int max_x = W - e.width - border, max_y = H - e.height - border;
-                int x = mx * 2 + 1, y = my * 2 + 1;
-                x = x > border ? x : border;  y = y > border ? y : border;
-                x = x < max_x ? x : max_x;    y = y < max_y ? y : max_y;
-                const int gx = x / T - 8, gy = y / T - 8;
-                const int off_x = gx * T, off_y = gy * T;
-                const bool all_in = e.min_x >= 0 && e.min_y >= 0 && gx >= 0 && gy >= 0 &&
-                                    ((e.max_x + off_x) / T + 16 <= Wd) && ((e.max_y + off_y) / T + 16 <= Hd);
-                const bool want = alive && !leave;
-                if (want && !all_in) leave = true;
-                const bool run = want && all_in;
-                const int nf = e.nf, nfp = run ? (int)e.nf_padded : 0;
-                int nmax = nfp;
-#pragma unroll
-                for (int o = 32; o > 0; o >>= 1) { const int t = __shfl_xor(nmax, o, 64); nmax = t > nmax ? t : nmax; }
-                nmax = __builtin_amdgcn_readfirstlane(nmax);
-                const uint32_t Kbase = (uint32_t)(((gx >> 4) * Hd + gy) * 8);
-                const uint32_t gxl = (uint32_t)(gx & 15);
-                const uint32_t* fw = feat_word + e.feat_start;
-                uint32_t cA[kN], cB[kN];                            // bit-sliced counters of rows 2j / 2j + 1: even bits count the 1s, odd bits the 4s
-#pragma unroll
-                for (int k = 0; k < kN; ++k) { cA[k] = 0; cB[k] = 0; }
-                // lane j fetches the words of features f0 + 2j, f0 + 2j + 1 (entries start at multiples of 8 words, f0 is a multiple of 16)
-                auto fetch = [&](int f0) -> uint2 {
-                    uint2 w = make_uint2(0u, 0u);
-                    if (f0 + 2 * j < nfp) w = *reinterpret_cast<const uint2*>(fw + f0 + 2 * j);
-                    return w;
-                };
-                // a feature word (base0 | column class, lm_kernels.h) -> offset of its first record in the bit arena, 2 x the window's cell inside it
-                auto prep = [&](uint32_t w, bool on, uint32_t& off, uint32_t& s2) {
-                    s2 = ((w & 15u) + gxl) << 1;
-                    const uint32_t o = ((w & ~15u) >> 1) + Kbase + ((s2 >> 5) ? HS8 : 0u);
-                    off = on ? o : zero_off;                        // beyond this candidate's features (or no candidate): the zero plane
-                };
-                uint32_t offx = 0, offy = 0, sx = 0, sy = 0;
-                auto batch = [&](int half, uint32_t& eA, uint32_t& eB) {           // features 8 half .. 8 half + 7 of the current 16
-                    uint4 v[8];
-                    uint32_t sh[8];
-#pragma unroll
-                    for (int u = 0; u < 8; ++u) {
-                        const int src = src0 + 4 * (4 * half + (u >> 1));          // the lane that fetched feature 8 half + u
-                        const uint32_t o = (uint32_t)__builtin_amdgcn_ds_bpermute(src, (int)((u & 1) ? offy : offx));
-                        sh[u] = (uint32_t)__builtin_amdgcn_ds_bpermute(src, (int)((u & 1) ? sy : sx));
-                        v[u] = ld_buf16(bits, o + rowoff, 0u);      // rows 2j, 2j + 1: 32 cells x 2 bits each
-                    }
-                    uint32_t xa[8], xb[8];
-#pragma unroll
-                    for (int u = 0; u < 8; ++u) {
-                        xa[u] = __builtin_amdgcn_alignbit(v[u].y, v[u].x, sh[u]);      // 16 window cells of row 2j: bits 2c (is 1), 2c + 1 (is 4)
-                        xb[u] = __builtin_amdgcn_alignbit(v[u].w, v[u].z, sh[u]);      // ... of row 2j + 1
-                    }
-                    eA = add8(xa, cA[0], cA[1], cA[2]);
-                    eB = add8(xb, cB[0], cB[1], cB[2]);
-                };
-                uint2 wn = fetch(0);
-                for (int f0 = 0; f0 < nmax; f0 += 16) {
-                    const uint2 w = wn;
-                    const bool on = f0 + 2 * j < nfp;
-                    wn = fetch(f0 + 16);                            // the next 16 words while these are worked on
-                    prep(w.x, on, offx, sx);
-                    prep(w.y, on, offy, sy);
-                    uint32_t e1A, e1B;
-                    batch(0, e1A, e1B);
-                    if (f0 + 8 < nmax) {                            // wave-uniform
-                        uint32_t e2A, e2B;
-                        batch(1, e2A, e2B);
-                        add_eights2<kN>(cA, e1A, e2A);
-                        add_eights2<kN>(cB, e1B, e2B);
-                    } else {
-                        add_eights1<kN>(cA, e1A);
-                        add_eights1<kN>(cB, e1B);
-                    }
-                }
-                // Once per candidate and level: the two rows of the lane side by side — bit 2c = row 2j, bit 2c + 1 = row 2j + 1 of window
-                // column c —, S = n1 + 4 n4 bit-sliced, the lane's maximum by a descent from the top bit, its FIRST position in raster order.
-                uint32_t S[kS];
-                {
-                    uint32_t n1[kN], n4[kN];
-#pragma unroll
-                    for (int k = 0; k < kN; ++k) {
-                        n1[k] = (cA[k] & 0x55555555u) | ((cB[k] << 1) & 0xAAAAAAAAu);
-                        n4[k] = ((cA[k] >> 1) & 0x55555555u) | (cB[k] & 0xAAAAAAAAu);
-                    }
-                    weighted_sum<kA, kN>(S, n1, n4);
-                }
-                uint32_t mask = 0xFFFFFFFFu, val = 0;
-#pragma unroll
-                for (int k = kS - 1; k >= 0; --k) {
-                    const uint32_t t = mask & S[k];
-                    if (t) { mask = t; val |= 1u << k; }
-                }
-                const uint32_t upper = mask & 0x55555555u;           // positions of row 2j attaining the maximum come first in raster order
-                const uint32_t pick = upper ? upper : mask;
-                const uint32_t bitp = (uint32_t)__ffs((int)pick) - 1u;
-                const uint32_t pos = ((2u * (uint32_t)j + (bitp & 1u)) << 4) + (bitp >> 1);   // row * 16 + column
-                uint32_t key = (val << 8) | (255u - pos);
-#pragma unroll
-                for (int o = 1; o < 8; o <<= 1) { const uint32_t t = (uint32_t)__shfl_xor((int)key, o, 64); key = t > key ? t : key; }
-                const int raw = (int)(key >> 8);
-                int br = -1, bc = -1;                               // LL.cpp:1910-1911
-                float best = 0.f;
-                if (raw > 0) {
-                    const int idx = 255 - (int)(key & 0xFF);
-                    br = idx >> 4; bc = idx & 15;
-                    best = score_of(raw, nf);
-                }
-                if (run) {
-                    ++evals;
-                    bytes += 256u * (uint32_t)nf;                   // algorithmic response bytes of this 16x16 evaluation
-                    sim = best;
-                    mx = (x / T - 8 + bc) * T + offset;             // LL.cpp:1930-1931
-                    my = (y / T - 8 + br) * T + offset;
-                    if (sim < threshold) alive = false;             // LL.cpp:1935
-                }
-            }
-            if (valid && j == 0) {
-                F.todo[ci] = leave ? 1 : 0;
-                if (!leave) {
-                    if (ci < cap) {
-                        Candidate m;
-                        m.x = mx; m.y = my; m.score = sim;
-                        m.work = alive ? work : -1;
-                        F.matches_dev[ci] = m;
-                    }
-                    atomicAdd(&s_acc[fr][0], (unsigned long long)evals);
-                    atomicAdd(&s_acc[fr][1], (unsigned long long)bytes);
-                }
-            }
-        }
-    }
-    __syncthreads();
-    if ((int)threadIdx.x < nb && s_acc[threadIdx.x][0] != 0) {
-        unsigned long long* st = fb.f[threadIdx.x].counters + 8 + 2 * (blockIdx.x & (kStatShards - 1));
-        atomicAdd(st, s_acc[threadIdx.x][0]);
-        atomicAdd(st + 1, s_acc[threadIdx.x][1]);
-    }
-}
-
-void launch_pack_bits(const BitsBatch& B, int nb, const LevelGeom& lv, hipStream_t s) {
-    const uint32_t records = (uint32_t)(2 * 8 * lv.T * lv.T) * (uint32_t)lv.NS * (uint32_t)lv.Hd;
-    hipLaunchKernelGGL(k_pack_bits, dim3((records + 255) / 256, nb), dim3(256), 0, s, B, lv.sm_off[0], records, lv.NS, lv.Hd);
-}
-void launch_local_bits(const FrameBatch& fb, const BitsBatch& B, const FrameGeom& g, const TemplEntry* entries, const uint32_t* feat_word,
-                       const int32_t* work_pyramids, uint32_t cand_cap, float threshold, uint32_t cap, uint32_t dedupe_cap_slots, int grid_blocks,
-                       int max_features, int low_weight, hipStream_t s) {
-#define LM_LAUNCH_LOCAL_BITS(HI, A) \
-    hipLaunchKernelGGL((k_local_bits<HI, 4, A>), dim3(grid_blocks), dim3(256), 0, s, fb, B, g, entries, feat_word, work_pyramids, cand_cap, threshold, cap, dedupe_cap_slots)
-    const bool big = max_features > kBitsSmallMax;
-    if (low_weight == 2) { if (big) LM_LAUNCH_LOCAL_BITS(10, 2); else LM_LAUNCH_LOCAL_BITS(5, 2); }
-    else if (low_weight == 3) { if (big) LM_LAUNCH_LOCAL_BITS(10, 3); else LM_LAUNCH_LOCAL_BITS(5, 3); }
-    else { if (big) LM_LAUNCH_LOCAL_BITS(10, 1); else LM_LAUNCH_LOCAL_BITS(5, 1); }
-#undef LM_LAUNCH_LOCAL_BITS
-}
-
-// ---- Coarse pass on the pair stream (LL.cpp:1284-1354 similarity + :1835-1852 scan).  A wave per template, a lane = 32 consecutive
-// positions of the template's map: a feature's load = two consecutive pairs per lane (16 bytes) at pair index (offset >> 5) + lane,
-// funnel-shifted by offset & 31 — the offset is wave-uniform, so both are scalar —, i.e. ONE wave load per feature and 2048 positions
-// (the byte kernel: one per 1008 positions and 16 bytes per position and lane).  Sums bit-sliced as in k_local_bits; the threshold test is
-// a bit-sliced comparison with the smallest raw sum that passes, so integers are formed only for the hits.  The workgroup's 4 templates
-// reserve their candidate slots with ONE atomic on the frame's counter (same-address atomics serialise in the L2: 2000 per frame cost
-// the byte kernel 16 us).  No tiles: the bit-plane refinement needs none.
-__global__ void __launch_bounds__(256)
-k_pack_top(TopBits B, uint32_t byte0, uint32_t npairs) {
-    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-    if (i >= npairs) return;
-    const uint8_t* src = B.lm[blockIdx.y] + byte0 + (size_t)i * 32;
-    const uint4 a = *reinterpret_cast<const uint4*>(src), b = *reinterpret_cast<const uint4*>(src + 16);
-    auto four = [](uint32_t d, int sh) -> uint32_t { return ((((d >> sh) & 0x01010101u) * 0x01020408u) >> 24) & 0xFu; };   // bit sh of 4 bytes -> 4 bits
-    auto bits = [&](const uint4& v, int sh) -> uint32_t { return four(v.x, sh) | (four(v.y, sh) << 4) | (four(v.z, sh) << 8) | (four(v.w, sh) << 12); };
-    uint2 r;
-    r.x = bits(a, 0) | bits(a, 1) | ((bits(b, 0) | bits(b, 1)) << 16);   // the low plane's response a = 1, 2 or 3: bit 0 or bit 1 of the byte; response 4 = bit 2
-    r.y = bits(a, 2) | (bits(b, 2) << 16);
-    *reinterpret_cast<uint2*>(B.bits[blockIdx.y] + (size_t)i * 8) = r;
-}
-
-template <int kHi, int kWaves, int kA>
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kWaves, kWaves)))
-k_coarse_bits(FrameBatch fb, TopBits B, LevelGeom lv, int level, int levels, const TemplEntry* __restrict__ entries, const int32_t* __restrict__ feat_off,
-              const int32_t* __restrict__ work_pyramids, int num_work, float threshold, uint32_t cap, uint32_t byte0) {
-    constexpr int kN = 4 + kHi, kS = kN + 3;
-    __shared__ uint32_t s_tot[4];
-    __shared__ unsigned long long s_base;
-    const FrameSlot& F = fb.f[blockIdx.y];
-    Candidate* __restrict__ cands = F.cands;
-    unsigned long long* __restrict__ counters = F.counters;
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int work_raw = (int)blockIdx.x * 4 + wave;                       // a wave per template
-    const bool live = work_raw < num_work;
-    const int work = live ? work_raw : num_work - 1;                       // idle waves of the last workgroup shadow a real template and emit nothing
-    const int pyr = work_pyramids[work];
-    const TemplEntry e = entries[(size_t)pyr * levels + level];
-    const int nf = e.nf, nfp = e.nf_padded;
-    const int32_t* fo = feat_off + e.feat_start;
-    const int Wd = lv.Wd, Hd = lv.Hd, T = lv.T, npos = Wd * Hd;
-    const int wf = (e.width - 1) / T + 1, hf = (e.height - 1) / T + 1;      // LL.cpp:1299-1309
-    const int tp = (Hd - hf) * Wd + (Wd - wf) + 1;
-    const int offset = T / 2 + (T % 2 - 1);                                 // LL.cpp:1846
-    const int limit = tp < npos ? tp : npos;                                // positions that carry sums
-    // the smallest raw sum whose score passes (score_of is monotone in raw): LL.cpp:1844 `> threshold`
-    int rmin = (int)(threshold * (float)(4 * nf) / 100.f);
-    if (!(rmin >= 0)) rmin = 0;
-    if (rmin > 4 * nf + 1) rmin = 4 * nf + 1;
-    while (rmin > 0 && score_of(rmin, nf) > threshold) --rmin;
-    while (rmin <= 4 * nf && !(score_of(rmin, nf) > threshold)) ++rmin;
-    const bool zero_passes = score_of(0, nf) > threshold;
-    const BufRsrc bits = make_rsrc(B.bits[blockIdx.y]);
-    for (int P0 = 0; P0 < npos; P0 += 2048) {                               // (the same number of passes for every wave of the workgroup)
-        const int pos0 = P0 + 32 * lane;                                    // first position of this lane
-        uint32_t c1[kN], c4[kN];
-#pragma unroll
-        for (int k = 0; k < kN; ++k) { c1[k] = 0; c4[k] = 0; }
-        if (live && P0 < limit && nfp > 0 && pos0 < limit) {                // (lanes beyond the map sit the loads out)
-            auto batch = [&](int f, uint32_t& e1, uint32_t& e4) {
-                uint4 v[8];
-                uint32_t sh[8];
-#pragma unroll
-                for (int u = 0; u < 8; ++u) {
-                    const uint32_t ob = (uint32_t)fo[f + u] - byte0 + (uint32_t)P0;      // wave-uniform -> SMEM / SALU
-                    sh[u] = ob & 31u;
-                    v[u] = ld_buf16(bits, (uint32_t)lane * 8u, (ob >> 5) * 8u);          // pairs q + lane and q + lane + 1
-                }
-                uint32_t x1[8], x4[8];
-#pragma unroll
-                for (int u = 0; u < 8; ++u) {
-                    x1[u] = __builtin_amdgcn_alignbit(v[u].z, v[u].x, sh[u]);            // bits [s, s + 32) of {is-1 of pair q + lane + 1 : pair q + lane}
-                    x4[u] = __builtin_amdgcn_alignbit(v[u].w, v[u].y, sh[u]);
-                }
-                e1 = add8(x1, c1[0], c1[1], c1[2]);
-                e4 = add8(x4, c4[0], c4[1], c4[2]);
-            };
-            for (int f = 0; f < nfp; f += 16) {
-                uint32_t a1, a4;
-                batch(f, a1, a4);
-                if (f + 8 < nfp) {
-                    uint32_t b1, b4;
-                    batch(f + 8, b1, b4);
-                    add_eights2<kN>(c1, a1, b1);
-                    add_eights2<kN>(c4, a4, b4);
-                } else {
-                    add_eights1<kN>(c1, a1);
-                    add_eights1<kN>(c4, a4);
-                }
-            }
-        }
-        uint32_t S[kS];
-        weighted_sum<kA, kN>(S, c1, c4);
-        uint32_t gt = 0, eq = 0xFFFFFFFFu;                                  // S >= rmin, bit-sliced
-#pragma unroll
-        for (int k = kS - 1; k >= 0; --k) {
-            if ((rmin >> k) & 1) eq &= S[k];                                // wave-uniform
-            else { gt |= eq & S[k]; eq &= ~S[k]; }
-        }
-        uint32_t hit_mask = rmin < (1 << kS) ? (gt | eq) : 0u;
-        // positions at or beyond the template's position count hold zero sums (LL.cpp:1299-1309): they are hits only if zero passes
-        const int sums = limit - pos0;                                      // positions of this lane that carry sums
-        const uint32_t summed = sums >= 32 ? 0xFFFFFFFFu : (sums > 0 ? (1u << sums) - 1u : 0u);
-        const int inmap = npos - pos0;
-        const uint32_t mapped = inmap >= 32 ? 0xFFFFFFFFu : (inmap > 0 ? (1u << inmap) - 1u : 0u);
-        hit_mask = (hit_mask & summed) | (zero_passes ? (mapped & ~summed) : 0u);
-        if (!live) hit_mask = 0;
-        int total;
-        const int before = wave_excl_scan(__popc(hit_mask), lane, total);
-        // one atomic per workgroup and pass
-        if (lane == 0) s_tot[wave] = (uint32_t)total;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            const unsigned long long all = (unsigned long long)s_tot[0] + s_tot[1] + s_tot[2] + s_tot[3];
-            s_base = all ? atomicAdd(&counters[0], all) : 0ull;
-        }
-        __syncthreads();
-        unsigned long long slot = s_base + (unsigned long long)before;
-        for (int w = 0; w < wave; ++w) slot += s_tot[w];
-        __syncthreads();                                                    // s_tot / s_base are rewritten by the next pass
-        if (total > 0) {                                                    // wave-uniform
-            uint32_t m = hit_mask;
-            while (m) {
-                const int b = __ffs((int)m) - 1;
-                m &= m - 1;
-                if (slot < cap) {
-                    int raw = 0;
-                    if ((summed >> b) & 1u) {
-#pragma unroll
-                        for (int k = 0; k < kS; ++k) raw |= (int)((S[k] >> b) & 1u) << k;
-                    }
-                    const int jpos = pos0 + b;
-                    const int cy = jpos / Wd, cx = jpos - cy * Wd;
-                    Candidate c;
-                    c.x = cx * T + offset; c.y = cy * T + offset; c.score = score_of(raw, nf); c.work = work;
-                    cands[slot] = c;
-                }
-                ++slot;
-            }
-        }
-    }
-}
-
-void launch_pack_top(const TopBits& B, int nb, uint32_t byte0, uint32_t npairs, hipStream_t s) {
-    hipLaunchKernelGGL(k_pack_top, dim3((npairs + 255) / 256, nb), dim3(256), 0, s, B, byte0, npairs);
-}
-void launch_coarse_bits(const FrameBatch& fb, const TopBits& B, const FrameGeom& g, const TemplEntry* entries, const int32_t* feat_off,
-                        const int32_t* work_pyramids, int num_work, float threshold, uint32_t cap, uint32_t byte0, int max_features, int low_weight, hipStream_t s) {
-    if (num_work <= 0 || fb.nb <= 0) return;
-    const int level = g.levels - 1;
-#define LM_LAUNCH_COARSE_BITS(HI, WAVES, A) \
-    hipLaunchKernelGGL((k_coarse_bits<HI, WAVES, A>), dim3((num_work + 3) / 4, fb.nb), dim3(256), 0, s, fb, B, g.lv[level], level, g.levels, entries, feat_off, \
-                       work_pyramids, num_work, threshold, cap, byte0)
-    const bool big = max_features > kBitsSmallMax;
-    if (low_weight == 2) { if (big) LM_LAUNCH_COARSE_BITS(10, 5, 2); else LM_LAUNCH_COARSE_BITS(5, 6, 2); }
-    else if (low_weight == 3) { if (big) LM_LAUNCH_COARSE_BITS(10, 5, 3); else LM_LAUNCH_COARSE_BITS(5, 6, 3); }
-    else { if (big) LM_LAUNCH_COARSE_BITS(10, 5, 1); else LM_LAUNCH_COARSE_BITS(5, 6, 1); }
-#undef LM_LAUNCH_COARSE_BITS
-}
-
-void launch_local(const FrameBatch& fb, const FrameGeom& g, const TemplEntry* entries, const int32_t* feat_off, const uint32_t* feat_word,
-                  const uint32_t* run_mask, const uint32_t* feat_xy, const int32_t* work_pyramids, uint32_t cand_cap, float threshold, uint32_t cap,
-                  uint32_t dedupe_cap_slots, uint32_t tile_cap, int grid_blocks, hipStream_t s) {
+void launch_local(const FrameBatch& fb, const FrameGeom& g, const BankDev& bank, uint32_t cand_cap, float threshold, uint32_t cap, uint32_t dedupe_cap_slots, uint32_t tile_cap, int grid_blocks, hipStream_t s) {
     if (grid_blocks <= 0 || fb.nb <= 0) return;
     int dbg = 0;
 #ifdef LM_DIAG
     dbg = knobs().local_dbg;                                    // timing experiments (wrong results): 1 = tiles only, 2 = singles only
 #endif
-    hipLaunchKernelGGL(k_local, dim3(grid_blocks), dim3(256), 0, s, fb, g, entries, feat_off, feat_word, run_mask, feat_xy, work_pyramids, cand_cap,
+    hipLaunchKernelGGL(k_local, dim3(grid_blocks), dim3(256), 0, s, fb, g, bank.entries, bank.feat_off, bank.feat_word, bank.run_mask, bank.feat_xy, bank.work, cand_cap,
                        threshold, cap, dedupe_cap_slots, tile_cap, dbg);
 }
 

@@ -1,4 +1,4 @@
-"""Model (CPU, numpy) of the bit-plane refinement of DESIGN.md section 3.6 as built in round 4 (match.hip: k_pack_bits, k_local_bits): two bits
+"""Model (CPU, numpy) of the bit-plane refinement of DESIGN.md section 3.6 as built in round 4 (match_bits.hip: k_pack_bits, k_local_bits): two bits
 per response cell instead of a byte, 32-cell strip records at a stride of 16, a 16 x 16 window = 8 lanes x (2 rows x 16 positions x {is 1,
 is 4}), one funnel shift per row and feature, sums kept bit-sliced (Harley-Seal, 16 features per trip).
 Checks, on the bench workload (frame 1 of bench.noisy_frames, planted bank, every `STEP`-th template): the lane-level emulation gives
@@ -25,7 +25,7 @@ H0, W0 = pyr[0][0].shape
 Hd, Wd = H0 // T0, W0 // T0
 R = [[lo.response_np(lo.spread_np(pyr[l][m], T[l])) for m in range(2)] for l in range(2)]        # [level][mod][label][H][W], values 0 / 1 / 4
 
-# ---- the strip records of level 0 (match.hip, k_pack_bits): rec[mod][label][phase][strip][row] = 64 bits, cell c of [16 s, 16 s + 32) at
+# ---- the strip records of level 0 (match_bits.hip, k_pack_bits): rec[mod][label][phase][strip][row] = 64 bits, cell c of [16 s, 16 s + 32) at
 # bits 2c (response is 1) and 2c + 1 (response is 4) ----
 NS = (Wd + 15) // 16
 def pack4(d):
@@ -64,7 +64,7 @@ print("bit-plane memories of level 0: %.2f MB (byte planes: %.2f MB), built in %
 def csa(a, b, c):
     return a ^ b ^ c, (a & b) | (a & c) | (b & c)
 def add8(x, c):
-    """eight dwords into c[0..2] (ones, twos, fours); returns the carry of weight 8 (match.hip add8)."""
+    """eight dwords into c[0..2] (ones, twos, fours); returns the carry of weight 8 (match_bits.hip add8)."""
     c[0], ta = csa(c[0], x[0], x[1]); c[0], tb = csa(c[0], x[2], x[3]); c[1], fa = csa(c[1], ta, tb)
     c[0], ta = csa(c[0], x[4], x[5]); c[0], tb = csa(c[0], x[6], x[7]); c[1], fb = csa(c[1], ta, tb)
     c[2], e = csa(c[2], fa, fb)

@@ -114,8 +114,34 @@ def test_frontend_masks(lm):
         assert np.array_equal(det.readStage(l, 3), lo.build_linear_memories(np.where(b > 0, qn, 0).astype(np.uint8), T[l])[:n])
 
 
+def test_frontend_masks_three_levels(lm):
+    """The mask pyramid of setFrame over two nearest-neighbour steps, one launch of the job table per level: 24 x 32 at T = 2, 2, 2 is the
+    smallest frame three levels accept whose width is a multiple of 4 and not of 16 (levels 24 x 32, 12 x 16, 6 x 8: every level a multiple
+    of 16 pixels and of T).  The assertion of test_frontend_masks, at every level."""
+    W, H, T = 24, 32, [2, 2, 2]
+    rgb, dep = synth.make_frame(9, W, H, 6)
+    rng = np.random.default_rng(1)
+    m0 = (rng.uniform(0, 1, dep.shape) < 0.7).astype(np.uint8) * 255
+    m1 = (rng.uniform(0, 1, dep.shape) < 0.5).astype(np.uint8)      # (the normals live in the frame's middle: a mask that cuts there, at every level)
+    od = lo.OracleDetector(64, T)
+    pyr = od.quantize_pyramid(rgb, dep)
+    det = lm.Detector(64, T, device=0)
+    det.addClassPacked("e", np.zeros((0, 3), np.int32), np.zeros(1, np.int32), np.zeros((0, 2), np.int32))
+    det.setFrame([rgb, dep], [m0, m1])
+    det.matchResident(75.0, [])
+    a, b = m0, m1
+    for l, (qc, qn, *_r) in enumerate(pyr):
+        if l > 0:
+            a, b = lo.nn_down2(a), lo.nn_down2(b)
+        n = 8 * qc.size
+        want = [lo.build_linear_memories(np.where(a > 0, qc, 0).astype(np.uint8), T[l])[:n], lo.build_linear_memories(np.where(b > 0, qn, 0).astype(np.uint8), T[l])[:n]]
+        for m in range(2):
+            assert want[m].any() and not np.array_equal(want[m], lo.build_linear_memories((qc, qn)[m], T[l])[:n]), ("the mask must matter", l, m)
+            assert np.array_equal(det.readStage(l, 2 + m), want[m]), (l, m)
+
+
 def _strip_records(lm_flat, T, Wd, Hd):
-    """numpy statement of the strip records (match.hip): [label][phase][strip][row] uint64, cell c of [16 s, 16 s + 32) of the row at bits
+    """numpy statement of the strip records (match_bits.hip):[label][phase][strip][row] uint64, cell c of [16 s, 16 s + 32) of the row at bits
     2c (response is 1) and 2c + 1 (response is 4), from a flat linear memory [8][T*T][Hd*Wd]."""
     NS = (Wd + 15) // 16
     planes = lm_flat[:8 * T * T * Wd * Hd].reshape(8, T * T, Hd, Wd)

@@ -2,6 +2,7 @@
 kernel path, the streamed path, switching on one detector and the pipeline — against the unchanged CPU oracle fed with linear memories that
 response_table_ref.py builds in numpy for the table.  test_response_table_ref.py pins that spec to the oracle and shows that the inputs used
 here tell the tables apart."""
+import functools
 import os
 
 import numpy as np
@@ -269,22 +270,37 @@ def test_switching_tables_on_one_detector(lm):
     det.setResponseTable("linemod")                            # ... and accepted once it is collected
 
 
-@pytest.mark.parametrize("paths", [("bits", "bits"), ("tiles", "bytes")], ids=["bits", "bytes"])
-def test_read_stage_between_a_set_and_the_next_match(lm, paths):
+@functools.lru_cache(maxsize=None)
+def _narrow_scene():
+    """104 x 96 at T = 4, 4: 26 and 13 cells per row, whole dwords at neither level (G2 has 48 and 15).  Templates of at most 16 x 17 pixels:
+    every window stays inside its planes, so the default paths leave bit planes only at both levels."""
+    W, H, T = 104, 96, [4, 4]
+    rgb, dep = synth.make_frame(34, W, H, 14)
+    pyr = lo.OracleDetector(150, T).quantize_pyramid(rgb, dep)
+    bank = synth.make_random_bank(44, 8, W, H, (16, 8))
+    assert bank[2].max() <= 32 and bank[0][:, :2].min() >= 0 and W - 32 - 16 * T[0] >= 0 and H - 32 - 16 * T[0] >= 0
+    return {"W": W, "H": H, "T": T, "rgb": rgb, "dep": dep, "pyr": pyr, "banks": {"planted": bank}}
+
+
+@pytest.mark.parametrize("geom,paths,direct", [("G2", ("bits", "bits"), 2), ("G2", ("tiles", "bytes"), 2), ("narrow", ("bits", "bits"), None)],
+                         ids=["bits", "bytes", "narrow-bits-default"])
+def test_read_stage_between_a_set_and_the_next_match(lm, geom, paths, direct):
     """readStage(level, 2 / 3) answers under the table in force, whether the last front end left byte planes (now stale: rebuilt) or bit
-    planes only (built on demand); the bit planes (kinds 4 / 5) stay what the last match read."""
-    geom = "G2"
-    sc = rt.scene(geom)
+    planes only (built on demand: a linear-memory job of the front end's job table, which takes the table from the launch); the bit planes
+    (kinds 4 / 5) stay what the last match read.  G2 rebuilds rows of whole dwords (level 0) and of bytes (level 1); "narrow": rows of bytes
+    at both levels, under the detector's default paths."""
+    sc = rt.scene(geom) if geom != "narrow" else _narrow_scene()
     W, H, T = sc["W"], sc["H"], sc["T"]
     det = lm.Detector(150, T, device=0)
-    det.setPaths(paths[0], paths[1], 2)
+    if direct is not None:
+        det.setPaths(paths[0], paths[1], direct)
     det.addClassPacked("planted", *sc["banks"]["planted"])
     det.matchArray([sc["rgb"], sc["dep"]], 70.0, ["planted"])
     assert det.getPaths() == paths
     bits = [det.readStage(0, 4).tobytes(), det.readStage(1, 5).tobytes()] if paths[0] == "bits" else None
     for name in ("linemod", "levelup2", "levelup"):
         det.setResponseTable(name)
-        lms, _ = rt.memories(geom, rt.NAMED[name])
+        lms, _ = rt.memories(geom, rt.NAMED[name]) if geom != "narrow" else rt.linear_memories(sc["pyr"], T, rt.NAMED[name])
         for l in range(2):
             for m in range(2):
                 assert np.array_equal(det.readStage(l, 2 + m), lms[l][m][:8 * (W >> l) * (H >> l)]), (name, l, m)

@@ -4,8 +4,10 @@
 // holds the same information — class id, per template width / height / pyramid level, per feature x, y, label — as
 // flat arrays that are mmap'ed and walked once:
 //
-//   BankHeader                      magic, version, pyramid_levels, class count, directory offset, file size
-//   per class:  TemplRec[P*E]       width, height, first feature (index into the class's feature array); E = levels*2,
+//   BankHeader                      magic, version, pyramid_levels, class count, modality set, directory offset, file size
+//                                   (modality set: 0 = [ColorGradient, DepthNormal] — the word was reserved and zero before the set existed, so
+//                                   every older file reads as a two-modality bank —, 1 = [ColorGradient], 2 = [DepthNormal])
+//   per class:  TemplRec[P*E]       width, height, first feature (index into the class's feature array); E = levels * modalities,
 //                                   reference TemplatePyramid order (LL.h:336-337), +1 end record
 //               uint32 feat[n]      x:int16 | y:int13 << 16 | label << 29
 //   directory:  ClassRec[classes]   name offset/length, pyramid count, offsets of the two arrays
@@ -31,7 +33,7 @@ constexpr uint32_t kVersion = 1;
 
 struct BankHeader {
     char magic[8];
-    uint32_t version, pyramid_levels, num_classes, reserved;
+    uint32_t version, pyramid_levels, num_classes, modality_set;   // modality_set: 0 both, 1 colour only, 2 normals only
     uint64_t dir_offset, file_bytes;
 };
 struct ClassRec {
@@ -44,6 +46,9 @@ struct TemplRec {
     uint64_t feat_begin;
 };
 static_assert(sizeof(BankHeader) == 40 && sizeof(ClassRec) == 40 && sizeof(TemplRec) == 16, "bank file layout");
+
+inline uint32_t set_code(const lm_detector* d) { return d->nmod == 2 ? 0u : (uint32_t)d->mod_kind[0] + 1u; }
+inline const char* set_name(uint32_t code) { return code == 0 ? "[ColorGradient, DepthNormal]" : (code == 1 ? "[ColorGradient]" : "[DepthNormal]"); }
 
 inline bool pack_feature(const Feature& f, uint32_t& out) {
     if (f.x < -32768 || f.x > 32767 || f.y < -4096 || f.y > 4095 || f.label < 0 || f.label > 7) return false;
@@ -92,11 +97,12 @@ extern "C" int lm_detector_write_bank(const lm_detector* d, const char* path, co
     BankHeader h{};
     memcpy(h.magic, kMagic, 8);
     h.version = kVersion; h.pyramid_levels = (uint32_t)d->pyramid_levels; h.num_classes = (uint32_t)sel.size();
+    h.modality_set = set_code(d);
     w.put(&h, sizeof(h));
     std::vector<ClassRec> dir(sel.size());
     std::vector<TemplRec> recs;
     std::vector<uint32_t> feats;
-    const size_t E = (size_t)d->pyramid_levels * 2;
+    const size_t E = (size_t)d->pyramid_levels * d->nmod;
     for (size_t c = 0; c < sel.size(); ++c) {
         const std::vector<TemplatePyramid>& tps = sel[c]->second;
         recs.clear(); feats.clear();
@@ -157,6 +163,7 @@ int map_bank(const char* path, Mapping& m, BankHeader& h, const ClassRec*& dir) 
     m.p = (const uint8_t*)p; m.n = (size_t)st.st_size;
     memcpy(&h, m.p, sizeof(h));
     if (memcmp(h.magic, kMagic, 8) != 0 || h.version != kVersion) return lm_set_error(LM_ERR_IO, "not a bank file (magic / version): %s", path);
+    if (h.modality_set > 2) return lm_set_error(LM_ERR_IO, "bank file names an unknown modality set (%u): %s", h.modality_set, path);
     if (h.file_bytes != m.n) return lm_set_error(LM_ERR_IO, "bank file truncated: header says %llu bytes, file has %zu", (unsigned long long)h.file_bytes, m.n);
     if (!m.span(h.dir_offset, (uint64_t)h.num_classes * sizeof(ClassRec))) return lm_set_error(LM_ERR_IO, "bank directory outside the file");
     dir = (const ClassRec*)(m.p + h.dir_offset);
@@ -181,6 +188,16 @@ extern "C" int lm_bank_file_info(const char* path, int32_t* pyramid_levels, int3
     return LM_OK;
 }
 
+extern "C" int lm_bank_file_modalities(const char* path, const char* names[2]) {
+    if (!path) return lm_set_error(LM_ERR_INVALID, "null argument");
+    Mapping m; BankHeader h; const ClassRec* dir = nullptr;
+    int rc = map_bank(path, m, h, dir);
+    if (rc) return rc;
+    const int n = h.modality_set == 0 ? 2 : 1;
+    for (int i = 0; names && i < n; ++i) names[i] = kModalityName[h.modality_set == 0 ? i : (int)h.modality_set - 1];
+    return n;
+}
+
 extern "C" int lm_bank_file_class_id(const char* path, int index, char* out, int capacity) {
     if (!path || !out || capacity <= 0) return lm_set_error(LM_ERR_INVALID, "bad argument");
     Mapping m; BankHeader h; const ClassRec* dir = nullptr;
@@ -203,7 +220,9 @@ extern "C" int lm_detector_read_bank(lm_detector* d, const char* path, const cha
     if (rc) return rc;
     if ((int)h.pyramid_levels != d->pyramid_levels)
         return lm_set_error(LM_ERR_INVALID, "bank has %u pyramid levels, detector %d [LL.cpp:2052]", h.pyramid_levels, d->pyramid_levels);
-    const size_t E = (size_t)d->pyramid_levels * 2;
+    if (h.modality_set != set_code(d))
+        return lm_set_error(LM_ERR_INVALID, "bank holds modalities %s, detector %s [LL.cpp:2047-2051]", set_name(h.modality_set), set_name(set_code(d)));
+    const size_t E = (size_t)d->pyramid_levels * d->nmod;
     std::vector<uint32_t> pick;
     auto name_of = [&](uint32_t c) { return std::string((const char*)m.p + dir[c].name_offset, dir[c].name_len); };
     if (num_class_ids == 0) {
@@ -242,7 +261,7 @@ extern "C" int lm_detector_read_bank(lm_detector* d, const char* path, const cha
                 if (b < a || b > cr.num_features) return lm_set_error(LM_ERR_IO, "feature index of class '%s' not monotone", cid.c_str());
                 if (b - a > 8191) return lm_set_error(LM_ERR_INVALID, "templ.features.size() <= 8191 [LL.cpp:1291]");
                 Template& t = tp[e];
-                t.width = r.width; t.height = r.height; t.pyramid_level = (int)(e / 2);
+                t.width = r.width; t.height = r.height; t.pyramid_level = (int)(e / (size_t)d->nmod);
                 t.features.resize((size_t)(b - a));
                 for (uint64_t i = a; i < b; ++i) t.features[(size_t)(i - a)] = unpack_feature(feats[i]);
             }

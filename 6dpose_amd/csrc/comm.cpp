@@ -110,6 +110,7 @@ extern "C" int lm_comm_world(const lm_comm* c) { return c ? c->world : 0; }
 
 extern "C" int lm_exchange_allgather(lm_detector* d, lm_comm* c, const void* send, void* recv, size_t bytes_per_rank) {
     if (!d || !c || !send || !recv) return lm_set_error(LM_ERR_INVALID, "null argument");
+    if (int rc = lm_need_both(d, "the multi-GPU exchange")) return rc;
     if (c->device != d->device) return lm_set_error(LM_ERR_INVALID, "the communicator lives on device %d, the detector on %d", c->device, d->device);
     hipStream_t s = (hipStream_t)lm_detector_exchange_stream(d);
     if (!s) return LM_ERR_HIP;

@@ -102,9 +102,37 @@ static void make_normal_lut(uint8_t lut[400]) {
         }
 }
 
+const char* const kModalityName[2] = {"ColorGradient", "DepthNormal"};
+int lm_need_both(const lm_detector* d, const char* what) {
+    return d->nmod == 2 ? LM_OK : lm_set_error(LM_ERR_INVALID, "%s needs both modalities (this detector has %s only)", what, kModalityName[d->mod_kind[0]]);
+}
+
 extern "C" int lm_detector_create(int num_features, const int* T, int num_levels, int device, lm_detector** out) {
+    return lm_detector_create_modalities(num_features, T, num_levels, device, nullptr, 0, out);
+}
+
+extern "C" int lm_detector_get_modalities(const lm_detector* d, const char* names[2]) {
+    if (!d) return 0;
+    for (int i = 0; names && i < d->nmod; ++i) names[i] = kModalityName[d->mod_kind[i]];
+    return d->nmod;
+}
+
+extern "C" int lm_detector_create_modalities(int num_features, const int* T, int num_levels, int device, const char* const* modalities,
+                                             int num_modalities, lm_detector** out) {
     if (!out) return lm_set_error(LM_ERR_INVALID, "out is null");
     *out = nullptr;
+    // the sets the kernels serve: the reference's pair in its order (LL.cpp:1684-1692), or one of the two alone
+    int nmod = 2, kind0 = 0;
+    if (modalities) {
+        nmod = num_modalities;
+        bool ok = nmod == 1 || nmod == 2;
+        for (int i = 0; ok && i < nmod; ++i) ok = modalities[i] && (!strcmp(modalities[i], kModalityName[0]) || !strcmp(modalities[i], kModalityName[1]));
+        if (ok && nmod == 2) ok = !strcmp(modalities[0], kModalityName[0]) && !strcmp(modalities[1], kModalityName[1]);
+        if (!ok)
+            return lm_set_error(LM_ERR_INVALID, "modalities must be [ColorGradient, DepthNormal], [ColorGradient] or [DepthNormal] "
+                                "(Modality::create, LL.cpp:320-328, knows these two; no duplicates)");
+        kind0 = !strcmp(modalities[0], kModalityName[1]) ? 1 : 0;
+    }
     int ndev = 0;
     hipError_t e = hipGetDeviceCount(&ndev);
     if (e != hipSuccess || ndev <= 0)
@@ -114,6 +142,8 @@ extern "C" int lm_detector_create(int num_features, const int* T, int num_levels
     if (T && (num_levels < 1 || num_levels > kMaxLevels))
         return lm_set_error(LM_ERR_INVALID, "num_levels must be in 1..%d", kMaxLevels);
     lm_detector* d = new lm_detector();
+    d->nmod = nmod;
+    if (nmod == 1) { d->mod_kind[0] = kind0; d->mod_kind[1] = -1; d->use[kind0] = true; d->use[1 - kind0] = false; }
     if (num_features > 0) d->num_features = num_features;
     if (T) {
         d->T_at_level.assign(T, T + num_levels);

@@ -9,9 +9,9 @@
 
 // ---- bank -----------------------------------------------------------------------------------------
 static int validate_pyramid(const lm_detector* d, const TemplatePyramid& tp) {
-    if ((int)tp.size() != d->pyramid_levels * 2)
+    if ((int)tp.size() != d->pyramid_levels * d->nmod)
         return lm_set_error(LM_ERR_INVALID, "template pyramid has %d entries, detector expects %d", (int)tp.size(),
-                            d->pyramid_levels * 2);
+                            d->pyramid_levels * d->nmod);
     for (const Template& t : tp) {
         if (t.features.size() > 8191) return lm_set_error(LM_ERR_INVALID, "templ.features.size() <= 8191 [LL.cpp:1291]");
         for (const Feature& f : t.features) {
@@ -33,7 +33,8 @@ static int resident_host_selection(lm_detector* d, const uint8_t* mask, int widt
     const int L = d->pyramid_levels;
     std::vector<TemplatePyramid>& tps = d->class_templates[class_id];   // created even on failure, LL.cpp:1947
     d->bank_dirty = true;
-    TemplatePyramid tp((size_t)2 * L);
+    const int nm = d->nmod;
+    TemplatePyramid tp((size_t)nm * L);                                 // levels x modalities of the set (matchClass's layout, LL.cpp:1806-1812)
     std::vector<uint8_t> hmask, nmask;
     if (mask) hmask.assign(mask, mask + (size_t)width * height);
     size_t nf = (size_t)d->num_features;
@@ -55,16 +56,20 @@ static int resident_host_selection(lm_detector* d, const uint8_t* mask, int widt
             }
         }
         mag.resize(n); ang.resize(n); nrm.resize(n);
-        HIP_TRY(hipMemcpyAsync(mag.data(), b.mag.p, n * sizeof(float), hipMemcpyDeviceToHost, d->stream));
-        HIP_TRY(hipMemcpyAsync(ang.data(), b.ang.p, n, hipMemcpyDeviceToHost, d->stream));
-        HIP_TRY(hipMemcpyAsync(nrm.data(), b.nrm.p, n, hipMemcpyDeviceToHost, d->stream));
+        if (d->use[0]) HIP_TRY(hipMemcpyAsync(mag.data(), b.mag.p, n * sizeof(float), hipMemcpyDeviceToHost, d->stream));
+        if (d->use[0]) HIP_TRY(hipMemcpyAsync(ang.data(), b.ang.p, n, hipMemcpyDeviceToHost, d->stream));
+        if (d->use[1]) HIP_TRY(hipMemcpyAsync(nrm.data(), b.nrm.p, n, hipMemcpyDeviceToHost, d->stream));
         HIP_TRY(hipStreamSynchronize(d->stream));
         const uint8_t* mp = mask ? hmask.data() : nullptr;
         // reference order is modality-major (LL.cpp:1954-1968); the outcome (-1 on any failure) is the same
-        if (!extract_color_template(mag.data(), ang.data(), mp, b.W, b.H, nf, d->strong_threshold, l, tp[2 * l])) return -1;
-        if (!extract_normal_template(nrm.data(), mp, b.W, b.H, nf, ext, l, tp[2 * l + 1])) return -1;
+        // (only the modalities of the set decide: a colour-only detector accepts a view with flat depth)
+        for (int i = 0; i < nm; ++i) {
+            Template& t = tp[(size_t)nm * l + i];
+            if (d->mod_kind[i] == 0 ? !extract_color_template(mag.data(), ang.data(), mp, b.W, b.H, nf, d->strong_threshold, l, t)
+                                    : !extract_normal_template(nrm.data(), mp, b.W, b.H, nf, ext, l, t)) return -1;
+        }
     }
-    crop_templates(tp);
+    crop_templates(tp);                                                 // the bounding box of the set's templates only (LL.cpp:234-277)
     if ((rc = validate_pyramid(d, tp))) return rc;
     tps.push_back(std::move(tp));
     return (int)tps.size() - 1;
@@ -103,11 +108,12 @@ static int train_buffers(lm_detector* d, int views, TrainGeom& g) {
 // the bank's limits, push_back.  Returns the template id.
 static int push_selected_pyramid(lm_detector* d, std::vector<TemplatePyramid>& tps, const int32_t* out_view, size_t out_words) {
     const int L = d->pyramid_levels;
-    TemplatePyramid tp((size_t)2 * L);
-    for (int e = 0; e < 2 * L; ++e) {
-        const int32_t* o = out_view + (size_t)e * out_words;
+    const int nm = d->nmod;
+    TemplatePyramid tp((size_t)nm * L);
+    for (int e = 0; e < nm * L; ++e) {                                  // the device layout stays [levels][2 kinds]; a set of one reads its kind's records
+        const int32_t* o = out_view + (size_t)((e / nm) * 2 + d->mod_kind[e % nm]) * out_words;
         Template& t = tp[e];
-        t.pyramid_level = e / 2;
+        t.pyramid_level = e / nm;
         t.features.resize((size_t)o[1]);
         for (int k = 0; k < o[1]; ++k) t.features[k] = Feature{o[4 + 3 * k], o[4 + 3 * k + 1], o[4 + 3 * k + 2]};
     }
@@ -134,9 +140,10 @@ static int add_template_device(lm_detector* d, const uint8_t* mask, int width, i
     HIP_TRY(hipMemcpyAsync(T.user_mask.p, mask, npx, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemsetAsync(T.counts.p, 0, (size_t)L * 16 * sizeof(uint32_t), s));
     HIP_TRY(hipMemsetAsync(T.bbox.p, 0x80, 4 * sizeof(int32_t), s));
+    const int mods = (d->use[0] ? 1 : 0) | (d->use[1] ? 2 : 0);
     launch_train_prep(d->frame_depth.p, T.user_mask.p, g, d->strong_threshold * d->strong_threshold, d->extract_threshold, T.keys.p, kTrainCap, T.counts.p,
-                      T.bbox.p, s);
-    if (launch_train_select(T.keys.p, T.counts.p, g, kTrainCap, d->num_features, nf_cap, 1, T.out.p, s))
+                      T.bbox.p, s, mods);
+    if (launch_train_select(T.keys.p, T.counts.p, g, kTrainCap, d->num_features, nf_cap, 1, T.out.p, s, mods))
         return lm_set_error(LM_ERR_HIP, "cannot reserve LDS for the selection kernel");
     HIP_TRY(hipGetLastError());
     std::vector<int32_t> h_out((size_t)L * 2 * out_words);
@@ -144,6 +151,7 @@ static int add_template_device(lm_detector* d, const uint8_t* mask, int width, i
     HIP_TRY(hipStreamSynchronize(s));
     bool ok = true, host_path = false;
     for (int e = 0; e < 2 * L; ++e) {
+        if (!d->use[e & 1]) continue;                                   // nothing was selected for a kind outside the set
         const int32_t st = h_out[(size_t)e * out_words];
         host_path |= st == 2;
         ok &= st == 1;
@@ -159,7 +167,7 @@ static int add_template_device(lm_detector* d, const uint8_t* mask, int width, i
 extern "C" int lm_detector_add_template(lm_detector* d, const uint8_t* rgb, const uint16_t* depth, const uint8_t* mask,
                                         int width, int height, const char* class_id) {
     if (!d || !class_id) return lm_set_error(LM_ERR_INVALID, "null argument");
-    int rc = upload_frame(d, rgb, depth, width, height, nullptr, false);
+    int rc = upload_frame(d, rgb, depth, width, height, nullptr, false);   // (checks the sources against the modality set)
     if (rc) return rc;
     // with an object mask (what every training loop of the reference passes) the selection runs on the device; LM_TRAIN_HOST=1 and
     // detectors beyond kTrainMaxFeatures features keep it on the host, as does a call without mask (no erosion, candidates anywhere)
@@ -186,8 +194,8 @@ static int add_rendered_view_host(lm_detector* d, lm_mesh* m, int i, int width, 
     d->frame_valid = false;
     d->have_mask[0] = d->have_mask[1] = false;
     d->cur_rgb = d->frame_rgb.p; d->cur_depth = d->frame_depth.p;
-    HIP_TRY(hipMemcpyAsync(d->frame_rgb.p, m->d_rgb + (size_t)i * npx * 3, npx * 3, hipMemcpyDeviceToDevice, d->stream));
-    HIP_TRY(hipMemcpyAsync(d->frame_depth.p, m->d_depth + (size_t)i * npx, npx * 2, hipMemcpyDeviceToDevice, d->stream));
+    if (d->use[0]) HIP_TRY(hipMemcpyAsync(d->frame_rgb.p, m->d_rgb + (size_t)i * npx * 3, npx * 3, hipMemcpyDeviceToDevice, d->stream));
+    if (d->use[1]) HIP_TRY(hipMemcpyAsync(d->frame_depth.p, m->d_depth + (size_t)i * npx, npx * 2, hipMemcpyDeviceToDevice, d->stream));
     HIP_TRY(hipMemcpyAsync(hdepth.data(), m->d_depth + (size_t)i * npx, npx * 2, hipMemcpyDeviceToHost, d->stream));
     HIP_TRY(hipStreamSynchronize(d->stream));
     int x0 = width, y0 = height, x1 = -1, y1 = -1;
@@ -229,9 +237,11 @@ static int add_templates_rendered(lm_detector* d, lm_mesh* m, const char* class_
     int rc;
     for (int c0 = 0; c0 < count; c0 += chunk) {
         const int n = std::min(chunk, count - c0);
-        rc = shade ? lm_mesh_render_device_shaded(m, n, width, height, Ks + 9 * (size_t)c0, Rs + 9 * (size_t)c0, ts + 3 * (size_t)c0, *shade, true, true)
+        // the depth image is always resolved: it is the object mask (:238) also where no normals are taken from it; the shaded colour only for a
+        // detector that has the colour modality
+        rc = shade ? lm_mesh_render_device_shaded(m, n, width, height, Ks + 9 * (size_t)c0, Rs + 9 * (size_t)c0, ts + 3 * (size_t)c0, *shade, true, d->use[0])
                    : lm_mesh_render_device(m, n, width, height, Ks + 9 * (size_t)c0, Rs + 9 * (size_t)c0, ts + 3 * (size_t)c0, clip_near, clip_far,
-                                           ambient, ssaa, true, true);
+                                           ambient, ssaa, true, d->use[0]);
         if (rc) return rc;
         HIP_TRY(hipStreamSynchronize(m->s));
         if ((rc = setup_geometry(d, width, height, false))) return rc;
@@ -254,15 +264,17 @@ static int add_templates_rendered(lm_detector* d, lm_mesh* m, const char* class_
         d->frame_valid = false;
         d->have_mask[0] = d->have_mask[1] = false;
         const float strong_sq = d->strong_threshold * d->strong_threshold;
+        const int mods = (d->use[0] ? 1 : 0) | (d->use[1] ? 2 : 0);
         for (int i = 0; i < n; ++i) {
             d->cur_rgb = d->frame_rgb.p; d->cur_depth = d->frame_depth.p;
-            HIP_TRY(hipMemcpyAsync(d->frame_rgb.p, m->d_rgb + (size_t)i * npx * 3, npx * 3, hipMemcpyDeviceToDevice, s));
-            HIP_TRY(hipMemcpyAsync(d->frame_depth.p, m->d_depth + (size_t)i * npx, npx * 2, hipMemcpyDeviceToDevice, s));
+            const uint16_t* view_depth = m->d_depth + (size_t)i * npx;    // a colour-only detector has no depth frame: the mask comes from the rasteriser's buffer
+            if (d->use[0]) HIP_TRY(hipMemcpyAsync(d->frame_rgb.p, m->d_rgb + (size_t)i * npx * 3, npx * 3, hipMemcpyDeviceToDevice, s));
+            if (d->use[1]) HIP_TRY(hipMemcpyAsync(d->frame_depth.p, view_depth, npx * 2, hipMemcpyDeviceToDevice, s));
             if ((rc = run_frontend_training(d))) return rc;
-            launch_train_prep(d->frame_depth.p, nullptr, g, strong_sq, d->extract_threshold, T.keys.p + keys_view * i, kTrainCap, T.counts.p + counts_view * i,
-                              T.bbox.p + 4 * (size_t)i, s);
+            launch_train_prep(d->use[1] ? d->frame_depth.p : view_depth, nullptr, g, strong_sq, d->extract_threshold, T.keys.p + keys_view * i, kTrainCap,
+                              T.counts.p + counts_view * i, T.bbox.p + 4 * (size_t)i, s, mods);
         }
-        if (launch_train_select(T.keys.p, T.counts.p, g, kTrainCap, d->num_features, nf_cap, n, T.out.p, s))
+        if (launch_train_select(T.keys.p, T.counts.p, g, kTrainCap, d->num_features, nf_cap, n, T.out.p, s, mods))
             return lm_set_error(LM_ERR_HIP, "cannot reserve LDS for the selection kernel");
         HIP_TRY(hipGetLastError());
         h_out.resize((size_t)n * L * 2 * out_words);
@@ -280,6 +292,7 @@ static int add_templates_rendered(lm_detector* d, lm_mesh* m, const char* class_
             if (any) {
                 bool ok = true;
                 for (int e = 0; e < 2 * L; ++e) {
+                    if (!d->use[e & 1]) continue;
                     const int32_t st = h_out[((size_t)i * L * 2 + e) * out_words];
                     host_path |= st == 2;
                     ok &= st == 1;
@@ -333,8 +346,9 @@ extern "C" int lm_detector_read_class(lm_detector* d, const char* path, const ch
         bool assertion = err.find("LL.cpp") != std::string::npos;
         return lm_set_error(assertion ? LM_ERR_INVALID : LM_ERR_IO, "%s", err.c_str());
     }
-    if (mods.size() != 2 || mods[0] != "ColorGradient" || mods[1] != "DepthNormal")
-        return lm_set_error(LM_ERR_INVALID, "modalities mismatch [LL.cpp:2047-2051]");
+    bool same = (int)mods.size() == d->nmod;                        // the file's list against the detector's, element by element
+    for (int i = 0; same && i < d->nmod; ++i) same = mods[i] == kModalityName[d->mod_kind[i]];
+    if (!same) return lm_set_error(LM_ERR_INVALID, "modalities mismatch [LL.cpp:2047-2051]");
     if (levels != d->pyramid_levels)
         return lm_set_error(LM_ERR_INVALID, "(int)fn[\"pyramid_levels\"] == pyramid_levels violated (%d vs %d) [LL.cpp:2052]",
                             levels, d->pyramid_levels);
@@ -352,7 +366,8 @@ extern "C" int lm_detector_write_class(lm_detector* d, const char* class_id, con
     auto it = d->class_templates.find(class_id);
     if (it == d->class_templates.end()) return lm_set_error(LM_ERR_NOT_FOUND, "unknown class '%s' [LL.cpp:2096]", class_id);
     std::string err;
-    if (!write_class_yaml(path, it->first, it->second, d->pyramid_levels, err)) return lm_set_error(LM_ERR_IO, "%s", err.c_str());
+    const std::string mods = d->nmod == 2 ? "ColorGradient, DepthNormal" : kModalityName[d->mod_kind[0]];
+    if (!write_class_yaml(path, it->first, it->second, d->pyramid_levels, err, mods.c_str())) return lm_set_error(LM_ERR_IO, "%s", err.c_str());
     return LM_OK;
 }
 
@@ -372,8 +387,10 @@ extern "C" int lm_detector_write_params(const lm_detector* d, const char* path) 
     fprintf(f, "%%YAML:1.0\n---\npyramid_levels: %d\nT: [", d->pyramid_levels);
     for (size_t i = 0; i < d->T_at_level.size(); ++i) fprintf(f, "%s %d", i ? "," : "", d->T_at_level[i]);
     fprintf(f, " ]\nmodalities:\n");
+    if (d->use[0])
     fprintf(f, "   -\n      type: ColorGradient\n      weak_threshold: %s\n      num_features: %d\n      strong_threshold: %s\n",
             real(d->weak_threshold).c_str(), d->num_features, real(d->strong_threshold).c_str());
+    if (d->use[1])
     fprintf(f, "   -\n      type: DepthNormal\n      distance_threshold: %d\n      difference_threshold: %d\n      num_features: %d\n"
                "      extract_threshold: %d\n",
             d->distance_threshold, d->difference_threshold, d->num_features, d->extract_threshold);
@@ -411,8 +428,15 @@ extern "C" int lm_detector_read_params(lm_detector* d, const char* path) {
     }
     fclose(f);
     if (levels < 1 || levels > kMaxLevels || (int)T.size() != levels) return lm_set_error(LM_ERR_IO, "%s: pyramid_levels / T missing or inconsistent", path);
-    if (types.size() != 2 || types[0] != "ColorGradient" || types[1] != "DepthNormal")   // Modality::create (LL.cpp:320-328) knows these two
-        return lm_set_error(LM_ERR_INVALID, "%s: modalities must be [ColorGradient, DepthNormal]", path);
+    // Modality::create (LL.cpp:320-328) knows these two.  The reference's read() REPLACES the modality list; here the set is fixed at creation
+    // (buffers, job tables and the bank layout follow from it), so a file with another list is refused.
+    bool same = (int)types.size() == d->nmod;
+    for (int i = 0; same && i < d->nmod; ++i) same = types[i] == kModalityName[d->mod_kind[i]];
+    if (!same) {
+        if (d->nmod == 2) return lm_set_error(LM_ERR_INVALID, "%s: modalities must be [ColorGradient, DepthNormal]", path);
+        return lm_set_error(LM_ERR_INVALID, "%s: modalities must be [%s], the detector's set", path, kModalityName[d->mod_kind[0]]);
+    }
+    if (d->nmod == 1) nf[0] = nf[1] = nf[d->mod_kind[0]];
     if (nf[0] <= 0 || nf[0] != nf[1]) return lm_set_error(LM_ERR_INVALID, "%s: the modalities must agree on num_features (one bank layout)", path);
     if ((nf[0] >> (levels - 1)) < 1)
         return lm_set_error(LM_ERR_INVALID, "%s: num_features %d leaves no feature at the last of %d pyramid levels (num_features /= 2 per level, "
@@ -433,7 +457,7 @@ extern "C" int lm_detector_add_class_packed(lm_detector* d, const char* class_id
     if (!d || !class_id || num_pyramids < 0 || (num_pyramids && (!features || !tmpl_offsets || !tmpl_wh)))
         return lm_set_error(LM_ERR_INVALID, "bad argument");
     if (d->class_templates.count(class_id)) return lm_set_error(LM_ERR_INVALID, "class '%s' already present", class_id);
-    const int E = d->pyramid_levels * 2;
+    const int E = d->pyramid_levels * d->nmod;
     std::vector<TemplatePyramid> tps((size_t)num_pyramids);
     for (int p = 0; p < num_pyramids; ++p) {
         TemplatePyramid& tp = tps[p];
@@ -441,7 +465,7 @@ extern "C" int lm_detector_add_class_packed(lm_detector* d, const char* class_id
         for (int e = 0; e < E; ++e) {
             size_t k = (size_t)p * E + e;
             Template& t = tp[e];
-            t.width = tmpl_wh[2 * k]; t.height = tmpl_wh[2 * k + 1]; t.pyramid_level = e / 2;
+            t.width = tmpl_wh[2 * k]; t.height = tmpl_wh[2 * k + 1]; t.pyramid_level = e / d->nmod;
             int a = tmpl_offsets[k], b = tmpl_offsets[k + 1];
             if (a < 0 || b < a) return lm_set_error(LM_ERR_INVALID, "tmpl_offsets not monotone");
             t.features.resize((size_t)(b - a));
@@ -497,6 +521,7 @@ extern "C" int lm_detector_get_template(const lm_detector* d, const char* class_
 
 extern "C" int lm_detector_set_shard(lm_detector* d, int rank, int world) {
     if (!d || world < 1 || rank < 0 || rank >= world) return lm_set_error(LM_ERR_INVALID, "bad shard (%d of %d)", rank, world);
+    if (int rc = lm_need_both(d, "lm_detector_set_shard")) return rc;
     d->shard_rank = rank; d->shard_world = world;
     return LM_OK;
 }
@@ -531,20 +556,22 @@ int upload_bank(lm_detector* d) {
                 const uint32_t szero = (uint32_t)((long)lv.sm_off[1] + (long)8 * lv.T * lv.T * splane);   // the all-zero strip plane
                 TemplEntry e{};
                 e.feat_start = (uint32_t)off.size();
-                const size_t n0 = tp[2 * l].features.size(), n1 = tp[2 * l + 1].features.size();
-                e.nf = (uint16_t)(n0 + n1);
-                e.width = tp[2 * l].width;      // matchClass uses tp[start] (first modality) for the clamp,
-                e.height = tp[2 * l].height;    // similarity() each template's own size: checked equal below
-                if (tp[2 * l + 1].width != e.width || tp[2 * l + 1].height != e.height)
+                const int nm = d->nmod;           // templates of the level: tp[nm * l + i], i-th modality of the set (kind mod_kind[i])
+                size_t nfeat = 0;
+                for (int i = 0; i < nm; ++i) nfeat += tp[(size_t)nm * l + i].features.size();
+                e.nf = (uint16_t)nfeat;           // the score's denominator: the features of the set's modalities (LL.cpp:1826-1831)
+                e.width = tp[(size_t)nm * l].width;      // matchClass uses tp[start] (first modality) for the clamp,
+                e.height = tp[(size_t)nm * l].height;    // similarity() each template's own size: checked equal below
+                if (nm == 2 && (tp[2 * l + 1].width != e.width || tp[2 * l + 1].height != e.height))
                     return lm_set_error(LM_ERR_INVALID, "modalities of one pyramid level disagree on width/height");
                 int mnx = 32767, mny = 32767, mxx = -32768, mxy = -32768;
                 struct Rec { int32_t off; uint32_t xy; uint32_t base0; int cls; };
                 std::vector<Rec> recs;
                 const bool top = (l == L - 1);
                 const long zero16 = (zero_off + 15) & ~15L;      // 16-aligned start of the zero tail
-                for (int m = 0; m < 2; ++m)
-                    for (const Feature& f : tp[2 * l + m].features) {
-                        const int T = lv.T;
+                for (int i = 0; i < nm; ++i)
+                    for (const Feature& f : tp[(size_t)nm * l + i].features) {
+                        const int T = lv.T, m = d->mod_kind[i];          // the feature reads its KIND's arena block
                         const int gx = f.x - floordiv(f.x, T) * T, gy = f.y - floordiv(f.y, T) * T;   // floor modulo
                         long o = (long)lv.lm_off[m] + ((long)f.label * T * T + (gy * T + gx)) * npos + (long)floordiv(f.y, T) * lv.Wd +
                                  floordiv(f.x, T);

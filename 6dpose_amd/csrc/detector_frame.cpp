@@ -55,9 +55,10 @@ int setup_geometry(lm_detector* d, int W, int H, bool check_match_preconditions)
     }
     const size_t n0 = (size_t)W * H;
     int rc;
-    if ((rc = d->frame_rgb.ensure(n0 * 3))) return rc;
-    if ((rc = d->frame_depth.ensure(n0))) return rc;
-    if ((rc = d->nrm_raw.ensure(n0))) return rc;
+    // (a modality outside the detector's set has no frame buffer and no intermediates; its arena blocks exist, stay zero and are never written)
+    if (d->use[0] && (rc = d->frame_rgb.ensure(n0 * 3))) return rc;
+    if (d->use[1] && (rc = d->frame_depth.ensure(n0))) return rc;
+    if (d->use[1] && (rc = d->nrm_raw.ensure(n0))) return rc;
 
     for (int a = 0; a < lm_detector::kSlots; ++a) {
         const bool realloc_arena = arena > d->lm_arena[a].cap;
@@ -87,10 +88,10 @@ int setup_geometry(lm_detector* d, int W, int H, bool check_match_preconditions)
         LevelBufs& b = d->lvl[l];
         b.W = g.lv[l].W; b.H = g.lv[l].H;
         size_t n = (size_t)b.W * b.H;
-        if (l > 0 && (rc = b.rgb.ensure(n * 3))) return rc;
-        if ((rc = b.mag.ensure(n))) return rc;
-        if ((rc = b.ang.ensure(n))) return rc;
-        if ((rc = b.nrm.ensure(n))) return rc;
+        if (d->use[0] && l > 0 && (rc = b.rgb.ensure(n * 3))) return rc;
+        if (d->use[0] && (rc = b.mag.ensure(n))) return rc;
+        if (d->use[0] && (rc = b.ang.ensure(n))) return rc;
+        if (d->use[1] && (rc = b.nrm.ensure(n))) return rc;
     }
     d->geom = g;
     d->fW = W; d->fH = H;
@@ -98,7 +99,8 @@ int setup_geometry(lm_detector* d, int W, int H, bool check_match_preconditions)
 }
 
 int upload_frame(lm_detector* d, const uint8_t* rgb, const uint16_t* depth, int W, int H, const uint8_t* const* masks, bool check_match_preconditions) {
-    if (!rgb || !depth) return lm_set_error(LM_ERR_INVALID, "rgb/depth is null");
+    if ((d->use[0] && !rgb) || (d->use[1] && !depth)) return lm_set_error(LM_ERR_INVALID, "rgb/depth is null");
+    if ((!d->use[0] && rgb) || (!d->use[1] && depth)) return lm_set_error(LM_ERR_INVALID, "a source was given for a modality outside the detector's set");
     if (W < 16 || H < 16 || W > 16384 || H > 16384) return lm_set_error(LM_ERR_INVALID, "unsupported frame size %dx%d", W, H);
     HIP_TRY(hipSetDevice(d->device));
     d->frame_valid = false;
@@ -109,20 +111,23 @@ int upload_frame(lm_detector* d, const uint8_t* rgb, const uint16_t* depth, int 
     if (rc) return rc;
     d->cur_rgb = d->frame_rgb.p; d->cur_depth = d->frame_depth.p;
     const size_t n = (size_t)W * H;
-    const bool m0 = masks && masks[0], m1 = masks && masks[1];
-    size_t bytes = n * 3 + n * 2 + (m0 ? n : 0) + (m1 ? n : 0);
+    const bool m0 = masks && masks[0], m1 = masks && d->nmod == 2 && masks[1];
+    const size_t nc = d->use[0] ? n * 3 : 0, nd = d->use[1] ? n * 2 : 0;     // only the sources of the set are staged and uploaded
+    size_t bytes = nc + nd + (m0 ? n : 0) + (m1 ? n : 0);
     if ((rc = ensure_pinned(d, bytes))) return rc;
     uint8_t* st = (uint8_t*)d->pinned;
-    memcpy(st, rgb, n * 3);
-    memcpy(st + n * 3, depth, n * 2);
+    if (nc) memcpy(st, rgb, nc);
+    if (nd) memcpy(st + nc, depth, nd);
     HIP_TRY(hipEventRecord(d->ev[6], d->stream));
-    HIP_TRY(hipMemcpyAsync(d->frame_rgb.p, st, n * 3, hipMemcpyHostToDevice, d->stream));
-    HIP_TRY(hipMemcpyAsync(d->frame_depth.p, st + n * 3, n * 2, hipMemcpyHostToDevice, d->stream));
-    size_t off = n * 5;
-    for (int m = 0; m < 2; ++m) {
-        d->have_mask[m] = masks && masks[m];
+    if (nc) HIP_TRY(hipMemcpyAsync(d->frame_rgb.p, st, nc, hipMemcpyHostToDevice, d->stream));
+    if (nd) HIP_TRY(hipMemcpyAsync(d->frame_depth.p, st + nc, nd, hipMemcpyHostToDevice, d->stream));
+    size_t off = nc + nd;
+    d->have_mask[0] = d->have_mask[1] = false;
+    for (int i = 0; i < d->nmod; ++i) {                      // masks[i] belongs to the set's i-th modality; the buffers are indexed by kind
+        const int m = d->mod_kind[i];
+        d->have_mask[m] = masks && masks[i];
         if (!d->have_mask[m]) continue;
-        memcpy(st + off, masks[m], n);
+        memcpy(st + off, masks[i], n);
         if ((rc = d->lvl[0].mask[m].ensure(n))) return rc;
         HIP_TRY(hipMemcpyAsync(d->lvl[0].mask[m].p, st + off, n, hipMemcpyHostToDevice, d->stream));
         off += n;
@@ -158,12 +163,14 @@ int run_frontend_training(lm_detector* d) {
     for (int l = 0; l < L; ++l) {
         LevelBufs& b = d->lvl[l];
         const uint8_t* src = l == 0 ? d->cur_rgb : b.rgb.p;
-        st.njobs = 0;
-        fe_job_colour(st.job[st.njobs++], src, b.mag.p, b.ang.p, b.W, b.H, thr_sq);                                   // LL.cpp:367-504
-        if (l == 0) fe_job_normals(st.job[st.njobs++], d->cur_depth, d->nrm_raw.p, b.nrm.p, b.W, b.H, d->distance_threshold,
-                                   d->difference_threshold);                                                          // LL.cpp:729-819
-        else fe_job_nn_down2(st.job[st.njobs++], d->lvl[l - 1].nrm.p, b.nrm.p, d->lvl[l - 1].W, d->lvl[l - 1].H);     // LL.cpp:857-880
-        if (l + 1 < L) fe_job_pyrdown(st.job[st.njobs++], src, d->lvl[l + 1].rgb.p, b.W, b.H);                        // LL.cpp:557-581
+        st.njobs = 0;                                                                                                 // (the chains of the set's modalities only)
+        if (d->use[0]) fe_job_colour(st.job[st.njobs++], src, b.mag.p, b.ang.p, b.W, b.H, thr_sq);                    // LL.cpp:367-504
+        if (d->use[1]) {
+            if (l == 0) fe_job_normals(st.job[st.njobs++], d->cur_depth, d->nrm_raw.p, b.nrm.p, b.W, b.H, d->distance_threshold,
+                                       d->difference_threshold);                                                      // LL.cpp:729-819
+            else fe_job_nn_down2(st.job[st.njobs++], d->lvl[l - 1].nrm.p, b.nrm.p, d->lvl[l - 1].W, d->lvl[l - 1].H); // LL.cpp:857-880
+        }
+        if (d->use[0] && l + 1 < L) fe_job_pyrdown(st.job[st.njobs++], src, d->lvl[l + 1].rgb.p, b.W, b.H);           // LL.cpp:557-581
         launch_fe_stage(st, s);
     }
     HIP_TRY(hipGetLastError());
@@ -177,7 +184,8 @@ extern "C" int lm_detector_set_frame(lm_detector* d, const uint8_t* rgb, const u
 }
 
 extern "C" int lm_detector_store_frame(lm_detector* d, int slot, const uint8_t* rgb, const uint16_t* depth, int width, int height) {
-    if (!d || !rgb || !depth || slot < 0 || slot > 4095) return lm_set_error(LM_ERR_INVALID, "bad argument");
+    if (!d || slot < 0 || slot > 4095) return lm_set_error(LM_ERR_INVALID, "bad argument");
+    if ((d->use[0] != (rgb != nullptr)) || (d->use[1] != (depth != nullptr))) return lm_set_error(LM_ERR_INVALID, "bad argument: the sources must be those of the detector's modality set");
     if (width < 16 || height < 16 || width > 16384 || height > 16384) return lm_set_error(LM_ERR_INVALID, "unsupported frame size %dx%d", width, height);
     HIP_TRY(hipSetDevice(d->device));
     if ((size_t)slot >= d->slot_rgb.size()) {
@@ -186,18 +194,19 @@ extern "C" int lm_detector_store_frame(lm_detector* d, int slot, const uint8_t* 
     }
     const size_t n = (size_t)width * height;
     int rc;
-    if (d->slot_rgb[slot].cap < n * 3 || d->slot_depth[slot].cap < n)       // about to be reallocated: a frame in flight may still be
+    const size_t nc = rgb ? n * 3 : 0, nd = depth ? n : 0;                   // elements of the set's sources
+    if (d->slot_rgb[slot].cap < nc || d->slot_depth[slot].cap < nd)         // about to be reallocated: a frame in flight may still be
         HIP_TRY(hipStreamSynchronize(d->stream));                          // copying out of the old buffer
-    if ((rc = d->slot_rgb[slot].ensure(n * 3))) return rc;
-    if ((rc = d->slot_depth[slot].ensure(n))) return rc;
+    if (nc && (rc = d->slot_rgb[slot].ensure(nc))) return rc;
+    if (nd && (rc = d->slot_depth[slot].ensure(nd))) return rc;
     // staged through the detector's pinned buffer like every other upload (a pageable hipMemcpy stages internally, chunk by chunk)
-    if ((rc = ensure_pinned(d, n * 5))) return rc;
+    if ((rc = ensure_pinned(d, nc + nd * 2))) return rc;
     HIP_TRY(hipStreamSynchronize(d->stream));                              // the staging buffer is shared with upload_frame
     uint8_t* st = (uint8_t*)d->pinned;
-    memcpy(st, rgb, n * 3);
-    memcpy(st + n * 3, depth, n * 2);
-    HIP_TRY(hipMemcpyAsync(d->slot_rgb[slot].p, st, n * 3, hipMemcpyHostToDevice, d->stream));
-    HIP_TRY(hipMemcpyAsync(d->slot_depth[slot].p, st + n * 3, n * 2, hipMemcpyHostToDevice, d->stream));
+    if (nc) memcpy(st, rgb, nc);
+    if (nd) memcpy(st + nc, depth, nd * 2);
+    if (nc) HIP_TRY(hipMemcpyAsync(d->slot_rgb[slot].p, st, nc, hipMemcpyHostToDevice, d->stream));
+    if (nd) HIP_TRY(hipMemcpyAsync(d->slot_depth[slot].p, st + nc, nd * 2, hipMemcpyHostToDevice, d->stream));
     HIP_TRY(hipStreamSynchronize(d->stream));
     d->slot_w[slot] = width; d->slot_h[slot] = height;
     return LM_OK;
@@ -223,8 +232,8 @@ extern "C" int lm_detector_select_frame(lm_detector* d, int slot) {
         HIP_TRY(hipStreamWaitEvent(d->stream, d->resident_reader, 0));
         d->resident_reader = nullptr;
     }
-    HIP_TRY(hipMemcpyAsync(d->frame_rgb.p, d->slot_rgb[slot].p, n * 3, hipMemcpyDeviceToDevice, d->stream));
-    HIP_TRY(hipMemcpyAsync(d->frame_depth.p, d->slot_depth[slot].p, n * 2, hipMemcpyDeviceToDevice, d->stream));
+    if (d->use[0]) HIP_TRY(hipMemcpyAsync(d->frame_rgb.p, d->slot_rgb[slot].p, n * 3, hipMemcpyDeviceToDevice, d->stream));
+    if (d->use[1]) HIP_TRY(hipMemcpyAsync(d->frame_depth.p, d->slot_depth[slot].p, n * 2, hipMemcpyDeviceToDevice, d->stream));
     d->have_mask[0] = d->have_mask[1] = false;
     d->last_h2d_ms = 0.f;
     d->frame_valid = true;
@@ -234,6 +243,8 @@ extern "C" int lm_detector_select_frame(lm_detector* d, int slot) {
 extern "C" int64_t lm_detector_read_stage(lm_detector* d, int level, int kind, uint8_t* dst, int64_t capacity) {
     if (!d || level < 0 || level >= d->pyramid_levels || kind < 0 || kind > 5) return lm_set_error(LM_ERR_INVALID, "bad argument");
     if (d->fW <= 0) return lm_set_error(LM_ERR_INVALID, "no frame processed yet");
+    if (kind < 4 && !d->use[kind & 1])            // kinds 0, 2: colour; 1, 3: normals
+        return lm_set_error(LM_ERR_INVALID, "stage %d belongs to %s, which is not in the detector's modality set", kind, kModalityName[kind & 1]);
     const LevelBufs& b = d->lvl[level];
     const LevelGeom& lv = d->geom.lv[level];
     const uint8_t* src = nullptr;
@@ -245,7 +256,8 @@ extern "C" int64_t lm_detector_read_stage(lm_detector* d, int level, int kind, u
         case 3: src = d->lm_arena[d->last_arena].p + lv.lm_off[1]; size = (int64_t)8 * lv.T * lv.T * lv.Wd * lv.Hd; break;
         case 4:       // strip records of a level below the top, colour block then normal block (what k_local_bits reads)
             if (level == d->pyramid_levels - 1) return lm_set_error(LM_ERR_INVALID, "the top level has no strip records");
-            src = d->bits_arena[d->last_arena].p + (lv.sm_off[0] >> 1); size = (int64_t)2 * 8 * lv.T * lv.T * lv.NS * lv.Hd * 8; break;
+            // (a set of one: its own block only)
+            src = d->bits_arena[d->last_arena].p + (lv.sm_off[d->mod_kind[0]] >> 1); size = (int64_t)d->nmod * 8 * lv.T * lv.T * lv.NS * lv.Hd * 8; break;
         default:      // pair stream of the top level (what k_coarse_bits reads)
             if (level != d->pyramid_levels - 1) return lm_set_error(LM_ERR_INVALID, "only the top level has a pair stream");
             src = d->cbits_arena[d->last_arena].p; size = (int64_t)d->cbits_npairs * 8; break;
@@ -261,7 +273,7 @@ extern "C" int64_t lm_detector_read_stage(lm_detector* d, int level, int kind, u
             FeStage st{};
             st.resp = d->resp;
             st.njobs = 1;
-            fe_job_build_lm(st.job[0], P.quant, P.mask, P.lm, P.strips, b.W, b.H, lv.T);
+            fe_job_build_lm(st.job[0], P.quant, P.mask, P.lm, P.strips, b.W, b.H, lv.T, d->mod_kind[0], d->nmod);
             launch_fe_stage(st, d->stream);
             (void)hipStreamSynchronize(d->stream);
         }

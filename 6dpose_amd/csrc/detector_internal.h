@@ -75,6 +75,12 @@ struct lm_detector {
     float weak_threshold = 10.0f, strong_threshold = 55.0f;
     int distance_threshold = 2000, difference_threshold = 50, extract_threshold = 2;
     TemplatesMap class_templates;
+    // The modality set, fixed at creation (lm_detector_create_modalities): kind 0 = ColorGradient, 1 = DepthNormal.  mod_kind[i] is the kind of the
+    // set's i-th modality (the order of sources, masks and of the templates of a pyramid level); use[k] says whether kind k is in the set.  Device
+    // buffers, arena blocks and LevelPtrs stay indexed by KIND: a set of one leaves the other kind's blocks allocated, zero and never written.
+    int nmod = 2;
+    int mod_kind[2] = {0, 1};
+    bool use[2] = {true, true};
 
     // device
     int device = 0;
@@ -318,6 +324,8 @@ struct lm_detector {
 
 // detector.cpp
 int ensure_pinned(lm_detector* d, size_t bytes);
+int lm_need_both(const lm_detector* d, const char* what);   // LM_OK for the default set, else LM_ERR_INVALID "<what> needs both modalities"
+extern const char* const kModalityName[2];                  // "ColorGradient", "DepthNormal"
 
 // detector_frame.cpp
 int setup_geometry(lm_detector* d, int W, int H, bool check_match_preconditions);

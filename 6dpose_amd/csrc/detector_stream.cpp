@@ -84,13 +84,14 @@ static int run_frontend_batch(lm_detector* d, int first, int nb, hipStream_t s, 
             LevelBufs& B = d->level_bufs(b, l);
             B.W = d->lvl[l].W; B.H = d->lvl[l].H;
             const size_t n = (size_t)B.W * B.H;
-            if (l > 0 && (rc = B.rgb.ensure(n * 3))) return rc;
-            if ((rc = B.mag.ensure(n))) return rc;
-            if ((rc = B.ang.ensure(n))) return rc;
-            if ((rc = B.nrm.ensure(n))) return rc;
+            if (d->use[0] && l > 0 && (rc = B.rgb.ensure(n * 3))) return rc;
+            if (d->use[0] && (rc = B.mag.ensure(n))) return rc;
+            if (d->use[0] && (rc = B.ang.ensure(n))) return rc;
+            if (d->use[1] && (rc = B.nrm.ensure(n))) return rc;
         }
-        if ((rc = d->nrm_raw_x[b - 1].ensure((size_t)d->fW * d->fH))) return rc;
+        if (d->use[1] && (rc = d->nrm_raw_x[b - 1].ensure((size_t)d->fW * d->fH))) return rc;
     }
+    const int m0 = d->mod_kind[0], nm = d->nmod;         // the modality set: the quantising chains and the writers' slices of the set only
     FeStage st{};
     st.resp = d->resp;                                   // the detector's response table: every writer of response memories takes it from the launch
     auto flush = [&]() { if (st.njobs) { LM_CLOCK("launch_fe_stage"); launch_fe_stage(st, s); } st.njobs = 0; };
@@ -100,7 +101,7 @@ static int run_frontend_batch(lm_detector* d, int first, int nb, hipStream_t s, 
         for (int b = 0; b < nb; ++b) {
             const LevelPtrs P = d->level_ptrs(b, l, (first + b) % lm_detector::kSlots);
             room(1);
-            fe_job_build_lm(st.job[st.njobs++], P.quant, P.mask, P.lm, P.strips, d->lvl[l].W, d->lvl[l].H, d->geom.lv[l].T);
+            fe_job_build_lm(st.job[st.njobs++], P.quant, P.mask, P.lm, P.strips, d->lvl[l].W, d->lvl[l].H, d->geom.lv[l].T, m0, nm);
         }
     };
     // Launch l quantises level l of every frame and — beside it, they only need level l - 1 — builds the linear memories of level
@@ -113,11 +114,13 @@ static int run_frontend_batch(lm_detector* d, int first, int nb, hipStream_t s, 
             LevelBufs& B = d->level_bufs(b, l);
             const uint8_t* src = l == 0 ? sl.in_rgb : B.rgb.p;
             room(3);
-            fe_job_colour(st.job[st.njobs++], src, nullptr /* magnitudes: addTemplate only */, B.ang.p, B.W, B.H, thr_sq);      // LL.cpp:367-504
-            if (l == 0) fe_job_normals(st.job[st.njobs++], sl.in_depth, b == 0 ? d->nrm_raw.p : d->nrm_raw_x[b - 1].p, B.nrm.p, B.W, B.H,
-                                       d->distance_threshold, d->difference_threshold);                                          // LL.cpp:729-819
-            else fe_job_nn_down2(st.job[st.njobs++], d->level_bufs(b, l - 1).nrm.p, B.nrm.p, d->level_bufs(b, l - 1).W, d->level_bufs(b, l - 1).H);   // LL.cpp:857-880
-            if (l + 1 < L) fe_job_pyrdown(st.job[st.njobs++], src, d->level_bufs(b, l + 1).rgb.p, B.W, B.H);                     // LL.cpp:557-581
+            if (d->use[0]) fe_job_colour(st.job[st.njobs++], src, nullptr /* magnitudes: addTemplate only */, B.ang.p, B.W, B.H, thr_sq);      // LL.cpp:367-504
+            if (d->use[1]) {
+                if (l == 0) fe_job_normals(st.job[st.njobs++], sl.in_depth, b == 0 ? d->nrm_raw.p : d->nrm_raw_x[b - 1].p, B.nrm.p, B.W, B.H,
+                                           d->distance_threshold, d->difference_threshold);                                      // LL.cpp:729-819
+                else fe_job_nn_down2(st.job[st.njobs++], d->level_bufs(b, l - 1).nrm.p, B.nrm.p, d->level_bufs(b, l - 1).W, d->level_bufs(b, l - 1).H);   // LL.cpp:857-880
+            }
+            if (d->use[0] && l + 1 < L) fe_job_pyrdown(st.job[st.njobs++], src, d->level_bufs(b, l + 1).rgb.p, B.W, B.H);                     // LL.cpp:557-581
         }
         if (l > 0) build_lm_jobs(l - 1);
         flush();
@@ -134,8 +137,8 @@ static int run_frontend_batch(lm_detector* d, int first, int nb, hipStream_t s, 
                 const LevelPtrs P = d->level_ptrs(b, l, (first + b) % lm_detector::kSlots);
                 const int W = d->lvl[l].W, H = d->lvl[l].H, T = d->geom.lv[l].T;
                 if (st.njobs + 1 > kFeMaxJobs) flush_bits();
-                if (top) fe_job_top_bits(st.job[st.njobs++], P.quant, P.mask, P.top_stream, P.bit0, W, H, T, d->fe_top_mode);
-                else fe_job_bits_rows(st.job[st.njobs++], P.quant, P.mask, P.bits, W, H, T, d->fe_top_mode == 0);
+                if (top) fe_job_top_bits(st.job[st.njobs++], P.quant, P.mask, P.top_stream, P.bit0, W, H, T, d->fe_top_mode, m0, nm);
+                else fe_job_bits_rows(st.job[st.njobs++], P.quant, P.mask, P.bits, W, H, T, d->fe_top_mode == 0, m0, nm);
             }
         }
         flush_bits();
@@ -366,7 +369,7 @@ static int choose_bit_writers(lm_detector* d, Batch& B) {
     for (int l = 0; l + 1 < d->geom.levels; ++l) B.direct_low = B.direct_low && fe_bits_rows_possible(d->geom.lv[l].W, d->geom.lv[l].T);
     const LevelGeom& topl = d->geom.lv[d->geom.levels - 1];
     const uint32_t top_bit0[2] = {topl.lm_off[0] - d->cbits_byte0, topl.lm_off[1] - d->cbits_byte0};
-    B.top_ored = B.direct_top && fe_top_bits_kind(topl.W, topl.H, topl.T, top_bit0, d->fe_top_mode) == kFeTopBits;   // (else whole bytes / dwords are stored: nothing to clear)
+    B.top_ored = B.direct_top && fe_top_bits_kind(topl.W, topl.H, topl.T, top_bit0, d->fe_top_mode, d->mod_kind[0], d->nmod) == kFeTopBits;   // (else whole bytes / dwords are stored: nothing to clear)
     if (B.top_ored)                                      // the pair stream is OR-ed together: it has to be zero (k_local_bits leaves it so; k_pack_top and first use do not)
         for (int b = 0; b < B.nb; ++b) {
             const int si = B.slot(b);
@@ -415,7 +418,7 @@ static int record_front_end(lm_detector* d, const Batch& B) {
         const lm_detector::Slot& sl = d->slot[B.slot(b)];
         if (sl.ring < 0 && d->ingest.stream)
             for (int r = 0; r < lm_detector::kSlots; ++r)
-                if (d->ingest.d_rgb[r].p && sl.in_rgb == d->ingest.d_rgb[r].p) d->ingest.reader[r] = lead.fe_done;
+                if (d->ingest.d_rgb[r].p && (sl.in_rgb ? sl.in_rgb == d->ingest.d_rgb[r].p : (const void*)sl.in_depth == (const void*)d->ingest.d_rgb[r].p)) d->ingest.reader[r] = lead.fe_done;   // (a depth-only entry starts with the depth image)
     }
     return LM_OK;
 }
@@ -785,8 +788,8 @@ static int ingest_entry(lm_detector* d, int r, size_t n) {
         HIP_TRY(hipStreamCreateWithFlags(&g.stream, hipStreamNonBlocking));
         for (int i = 0; i < lm_detector::kSlots; ++i) { HIP_TRY(hipEventCreate(&g.t0[i])); HIP_TRY(hipEventCreate(&g.t1[i])); }
     }
-    g.depth_off = (n * 3 + 15) & ~(size_t)15;                       // the depth image behind the colour image, 16-byte aligned (host entry and device entry alike)
-    const size_t bytes = g.depth_off + n * 2;
+    g.depth_off = d->use[0] ? (n * 3 + 15) & ~(size_t)15 : 0;       // the depth image behind the colour image, 16-byte aligned (host entry and device entry alike);
+    const size_t bytes = g.depth_off + (d->use[1] ? n * 2 : 0);     // a detector with one modality keeps (and uploads) only that modality's image
     if (g.pinned_bytes[r] < bytes) {
         if (g.pinned[r]) (void)hipHostFree(g.pinned[r]);
         g.pinned[r] = nullptr; g.pinned_bytes[r] = 0;
@@ -795,7 +798,7 @@ static int ingest_entry(lm_detector* d, int r, size_t n) {
     }
     int rc;
     if ((rc = g.d_rgb[r].ensure(bytes))) return rc;
-    g.d_depth[r] = reinterpret_cast<uint16_t*>(g.d_rgb[r].p + g.depth_off);
+    g.d_depth[r] = d->use[1] ? reinterpret_cast<uint16_t*>(g.d_rgb[r].p + g.depth_off) : nullptr;
     return LM_OK;
 }
 
@@ -827,36 +830,40 @@ extern "C" int lm_detector_ingest_buffer(lm_detector* d, int width, int height, 
     *rgb = nullptr; *depth = nullptr;
     int r, rc = ingest_begin(d, width, height, &r);
     if (rc) return rc;
-    *rgb = (uint8_t*)d->ingest.pinned[r];
-    *depth = (uint16_t*)((uint8_t*)d->ingest.pinned[r] + d->ingest.depth_off);
+    if (d->use[0]) *rgb = (uint8_t*)d->ingest.pinned[r];             // (null stays for a modality outside the set)
+    if (d->use[1]) *depth = (uint16_t*)((uint8_t*)d->ingest.pinned[r] + d->ingest.depth_off);
     return LM_OK;
 }
 
 extern "C" int lm_detector_submit_frame(lm_detector* d, const uint8_t* rgb, const uint16_t* depth, int width, int height, float threshold,
                                         const char* const* class_ids, int num_class_ids) {
-    if (!d || !rgb || !depth) return lm_set_error(LM_ERR_INVALID, "null argument");
+    if (!d) return lm_set_error(LM_ERR_INVALID, "null argument");
+    if ((d->use[0] && !rgb) || (d->use[1] && !depth)) return lm_set_error(LM_ERR_INVALID, "null argument");
+    if ((!d->use[0] && rgb) || (!d->use[1] && depth)) return lm_set_error(LM_ERR_INVALID, "a source was given for a modality outside the detector's set");
     int r, rc = ingest_begin(d, width, height, &r);
     if (rc) return rc;
     const size_t n = (size_t)width * height;
     lm_detector::Ingest& g = d->ingest;
     uint8_t* st = (uint8_t*)g.pinned[r];
     const auto tp0 = std::chrono::steady_clock::now();
-    staged_copy(d, st, rgb, n * 3, st + g.depth_off, (const uint8_t*)depth, n * 2);  // zero-copy when the caller filled lm_detector_ingest_buffer's pointers
+    const size_t nc = d->use[0] ? n * 3 : 0, nd = d->use[1] ? n * 2 : 0;
+    staged_copy(d, st, rgb, nc, st + g.depth_off, (const uint8_t*)depth, nd);  // zero-copy when the caller filled lm_detector_ingest_buffer's pointers
     const auto tp1 = std::chrono::steady_clock::now();
     if (g.reader[r]) {                                            // a resident re-match of the entry's previous frame may still read it (another slot's front end)
         HIP_TRY(hipStreamWaitEvent(g.stream, g.reader[r], 0));
         g.reader[r] = nullptr;
     }
     HIP_TRY(hipEventRecord(g.t0[r], g.stream));
-    HIP_TRY(hipMemcpyAsync(g.d_rgb[r].p, st, g.depth_off + n * 2, hipMemcpyHostToDevice, g.stream));   // colour + depth: one copy (two cost the copy engine a second set-up: 0.061 -> ~0.05 ms, and the host a call)
+    HIP_TRY(hipMemcpyAsync(g.d_rgb[r].p, st, g.depth_off + nd, hipMemcpyHostToDevice, g.stream));   // colour + depth: one copy (two cost the copy engine a second set-up: 0.061 -> ~0.05 ms, and the host a call)
     HIP_TRY(hipEventRecord(g.t1[r], g.stream));                   // the batch's front end waits for it (lm_launch_pending)
-    d->cur_rgb = g.d_rgb[r].p; d->cur_depth = g.d_depth[r];
+    const uint8_t* const in_rgb = d->use[0] ? g.d_rgb[r].p : nullptr;
+    d->cur_rgb = in_rgb; d->cur_depth = g.d_depth[r];
     d->have_mask[0] = d->have_mask[1] = false;
     d->last_h2d_ms = 0.f;
     d->frame_valid = true;
     const uint64_t before = d->n_submitted;
     const auto tp2 = std::chrono::steady_clock::now();
-    rc = slot_begin(d, threshold, class_ids, num_class_ids, g.d_rgb[r].p, g.d_depth[r], d->have_mask, r);
+    rc = slot_begin(d, threshold, class_ids, num_class_ids, in_rgb, g.d_depth[r], d->have_mask, r);
     if (rc) return rc;
     if (d->n_submitted == before + 1) g.used[r] = true;
     const auto tp3 = std::chrono::steady_clock::now();

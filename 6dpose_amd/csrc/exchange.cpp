@@ -50,6 +50,7 @@ extern "C" uint64_t lm_detector_frames_collected(const lm_detector* d) { return 
 // launch of each kernel serves the group.
 extern "C" int lm_detector_exchange_pack_group(lm_detector* d, uint64_t first, int n, void* send_blocks, int capacity) {
     if (!d || !send_blocks || n < 1 || n > kMaxBatch) return lm_set_error(LM_ERR_INVALID, "bad argument");
+    if (int rc = lm_need_both(d, "the multi-GPU exchange")) return rc;
     if (!valid_capacity(capacity)) return lm_set_error(LM_ERR_INVALID, "capacity must be a power of two in [256, %u]", kXchgMaxCapacity);
     if (first < d->n_collected || first + (uint64_t)n > d->n_launched)
         return lm_set_error(LM_ERR_INVALID, "frames %llu..%llu are not all in flight on the device (collected %llu, launched %llu, submitted %llu)", (unsigned long long)first,
@@ -87,6 +88,7 @@ extern "C" int lm_detector_exchange_pack_group(lm_detector* d, uint64_t first, i
 // (0 = n * block bytes: every rank sent its n blocks back to back).
 extern "C" int lm_detector_exchange_merge_group_strided(lm_detector* d, uint64_t first, int n, const void* recv_blocks, int world, int capacity, size_t rank_stride_bytes) {
     if (!d || !recv_blocks || world < 1 || n < 1 || n > kMaxBatch || (rank_stride_bytes & 3)) return lm_set_error(LM_ERR_INVALID, "bad argument");
+    if (int rc = lm_need_both(d, "the multi-GPU exchange")) return rc;
     if (first < d->n_collected || first + (uint64_t)n > d->n_launched) return lm_set_error(LM_ERR_INVALID, "frames %llu.. are not in flight on the device", (unsigned long long)first);
     const size_t blk = lm_exchange_block_bytes(capacity);
     if (!blk) return lm_set_error(LM_ERR_INVALID, "bad capacity");
@@ -144,6 +146,7 @@ extern "C" int lm_detector_exchange_merge_frame(lm_detector* d, uint64_t frame_n
 // The frame just submitted (launching whatever waits for its batch): the one-frame-at-a-time form of the two calls above.
 extern "C" int lm_detector_exchange_pack(lm_detector* d, void* send_block, int capacity) {
     if (!d) return lm_set_error(LM_ERR_INVALID, "null argument");
+    if (int rc = lm_need_both(d, "the multi-GPU exchange")) return rc;
     if (d->n_submitted == d->n_collected) return lm_set_error(LM_ERR_INVALID, "no frame in flight: call lm_detector_submit first");
     int rc = lm_launch_pending(d);                                                   // the exchange follows the frame's kernels in stream order
     if (rc) return rc;
@@ -152,6 +155,7 @@ extern "C" int lm_detector_exchange_pack(lm_detector* d, void* send_block, int c
 
 extern "C" int lm_detector_exchange_merge(lm_detector* d, const void* recv_blocks, int world, int capacity) {
     if (!d) return lm_set_error(LM_ERR_INVALID, "bad argument");
+    if (int rc = lm_need_both(d, "the multi-GPU exchange")) return rc;
     if (d->n_submitted == d->n_collected) return lm_set_error(LM_ERR_INVALID, "no frame in flight");
     return lm_detector_exchange_merge_frame(d, d->n_submitted - 1, recv_blocks, world, capacity);
 }

@@ -977,38 +977,43 @@ void fe_job_nn_down2(FeJob& j, const uint8_t* src, uint8_t* dst, int W, int H) {
     j = FeJob{}; j.kind = kFeNnDown; j.a = W / 2; j.gx = (j.a + 255) / 256; j.gy = H / 2; j.gz = 1;
     j.in = src; j.out0 = dst; j.W = W; j.H = H;
 }
+// The writers of response memories run over the modalities [m0, m0 + nm) of the arrays they are given (indexed by kind: [0] colour, [1] normals):
+// the job's blocks are gz = nm slices, slice z serves j.lm[z] = modality m0 + z.  A detector with one modality therefore launches half the blocks
+// and its kernels never see the other modality's pointers.
 void fe_job_build_lm(FeJob& j, const uint8_t* const quant[2], const uint8_t* const mask[2], uint8_t* const lm[2], uint8_t* const strips[2],
-                     int W, int H, int T) {
-    j = FeJob{}; j.kind = kFeBuildLm; j.a = T; j.gx = ((W / T) * (H / T) + 255) / 256; j.gy = T * T; j.gz = 2; j.W = W; j.H = H;
+                     int W, int H, int T, int m0, int nm) {
+    j = FeJob{}; j.kind = kFeBuildLm; j.a = T; j.gx = ((W / T) * (H / T) + 255) / 256; j.gy = T * T; j.gz = nm; j.W = W; j.H = H;
     j.Wd = W / T; j.Hd = H / T; j.m_wd = div_magic((uint32_t)j.Wd); j.m_t = div_magic((uint32_t)T);
-    j.lm[0] = LmJob{quant[0], mask[0], lm[0], strips[0]}; j.lm[1] = LmJob{quant[1], mask[1], lm[1], strips[1]};
+    for (int z = 0; z < nm; ++z) j.lm[z] = LmJob{quant[m0 + z], mask[m0 + z], lm[m0 + z], strips[m0 + z]};
 }
 // strip records of a level below the top, written directly (bits[m]: the level's record block of modality m inside the bit arena)
 bool fe_bits_rows_possible(int W, int T) { return fe_bits_rows(W / T) >= 1; }
-void fe_job_bits_rows(FeJob& j, const uint8_t* const quant[2], const uint8_t* const mask[2], uint8_t* const bits[2], int W, int H, int T, bool tiles) {
+void fe_job_bits_rows(FeJob& j, const uint8_t* const quant[2], const uint8_t* const mask[2], uint8_t* const bits[2], int W, int H, int T, bool tiles, int m0, int nm) {
     j = FeJob{}; j.kind = kFeBitsRows; j.a = T; j.W = W; j.H = H;
     j.Wd = W / T; j.Hd = H / T; j.m_wd = div_magic((uint32_t)j.Wd); j.m_t = div_magic((uint32_t)T);
     const int R = fe_bits_rows(j.Wd);
-    j.gx = (j.Hd + R - 1) / R; j.gy = T * T; j.gz = 2;
+    j.gx = (j.Hd + R - 1) / R; j.gy = T * T; j.gz = nm;
     if (tiles && fe_rows_tile_fits(W, T)) {                // a workgroup per block of rows of cells and pixel-row phase
         const int Rb = fe_rows_block_rows((j.Wd + 15) / 16, T);
         const int k = knobs().fe_rows_cs;
         j.b = k >= 1 && k <= T && T % k == 0 ? k : (T % 2 == 0 ? 2 : 1);   // column phases per workgroup, a divisor of T (LM_FE_ROWS_CS; VGA level 0 at T = 4, per 8-frame batch: all four 23.7 us, two 21.1, one 25.9)
         j.kind = kFeBitsRowsTile; j.gx = (j.Hd + Rb - 1) / Rb; j.gy = T * (T / j.b);
     }
-    j.lm[0] = LmJob{quant[0], mask[0], bits[0], nullptr}; j.lm[1] = LmJob{quant[1], mask[1], bits[1], nullptr};
+    for (int z = 0; z < nm; ++z) j.lm[z] = LmJob{quant[m0 + z], mask[m0 + z], bits[m0 + z], nullptr};
 }
 // pair stream of the top level, written directly; bit0[m] = flat arena offset of modality m's block less the stream's first byte
-int fe_top_bits_kind(int W, int H, int T, const uint32_t bit0[2], int mode) {
-    if (mode != 1 && mode != 2 && fe_top_tile_fits(W, T) && bit0[0] % 8 == 0 && bit0[1] % 8 == 0) return kFeTopBitsTile;
+int fe_top_bits_kind(int W, int H, int T, const uint32_t bit0[2], int mode, int m0, int nm) {
+    bool bytes = true;                                      // every block written starts on a byte of the stream
+    for (int z = 0; z < nm; ++z) bytes = bytes && bit0[m0 + z] % 8 == 0;
+    if (mode != 1 && mode != 2 && fe_top_tile_fits(W, T) && bytes) return kFeTopBitsTile;
     if (mode != 1 && ((long)T * T * (W / T) * (H / T)) % 64 == 0) return kFeTopBitsAligned;
     return kFeTopBits;
 }
-void fe_job_top_bits(FeJob& j, const uint8_t* const quant[2], const uint8_t* const mask[2], uint8_t* stream, const uint32_t bit0[2], int W, int H, int T, int mode) {
-    j = FeJob{}; j.kind = kFeTopBits; j.a = T; j.gx = ((W / T) * (H / T) + 255) / 256; j.gy = T * T; j.gz = 2; j.W = W; j.H = H;
+void fe_job_top_bits(FeJob& j, const uint8_t* const quant[2], const uint8_t* const mask[2], uint8_t* stream, const uint32_t bit0[2], int W, int H, int T, int mode, int m0, int nm) {
+    j = FeJob{}; j.kind = kFeTopBits; j.a = T; j.gx = ((W / T) * (H / T) + 255) / 256; j.gy = T * T; j.gz = nm; j.W = W; j.H = H;
     j.Wd = W / T; j.Hd = H / T; j.m_wd = div_magic((uint32_t)j.Wd); j.m_t = div_magic((uint32_t)T);
-    j.lm[0] = LmJob{quant[0], mask[0], stream, reinterpret_cast<uint8_t*>((uintptr_t)bit0[0])}; j.lm[1] = LmJob{quant[1], mask[1], stream, reinterpret_cast<uint8_t*>((uintptr_t)bit0[1])};
-    const int kind = fe_top_bits_kind(W, H, T, bit0, mode);
+    for (int z = 0; z < nm; ++z) j.lm[z] = LmJob{quant[m0 + z], mask[m0 + z], stream, reinterpret_cast<uint8_t*>((uintptr_t)bit0[m0 + z])};
+    const int kind = fe_top_bits_kind(W, H, T, bit0, mode, m0, nm);
     if (kind == kFeTopBitsTile) {                           // a workgroup per row of cells: whole bytes, no atomics, nothing to clear
         j.kind = kFeTopBitsTile; j.gx = j.Hd; j.gy = 1;
     } else if (kind == kFeTopBitsAligned) {                 // whole dwords per wave: no atomics, nothing to clear

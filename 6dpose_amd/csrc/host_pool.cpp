@@ -112,8 +112,8 @@ static void copy_staging(uint8_t* dst, const uint8_t* src, size_t n) { memcpy(ds
 void staged_copy(lm_detector* d, uint8_t* dst, const uint8_t* a, size_t na, uint8_t* dst_b, const uint8_t* b, size_t nb) {
     const bool same_a = a == dst, same_b = b == dst_b;              // zero-copy: the caller filled lm_detector_ingest_buffer's pointers
     if (same_a || same_b || na + nb < (1u << 19) || !pool_ready(d)) {   // small frames: one thread
-        if (!same_a) memcpy(dst, a, na);
-        if (!same_b) memcpy(dst_b, b, nb);
+        if (!same_a && na) memcpy(dst, a, na);                      // (na / nb = 0, a / b null: a detector without that modality)
+        if (!same_b && nb) memcpy(dst_b, b, nb);
         return;
     }
     const int parts = d->pool.threads + 1;

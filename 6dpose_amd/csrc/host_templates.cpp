@@ -258,10 +258,10 @@ void crop_templates(TemplatePyramid& tp) {
 // ---- YAML -------------------------------------------------------------------------------------
 
 bool write_class_yaml(const std::string& path, const std::string& class_id, const std::vector<TemplatePyramid>& tps,
-                      int pyramid_levels, std::string& err) {
+                      int pyramid_levels, std::string& err, const char* modalities) {
     FILE* f = fopen(path.c_str(), "w");
     if (!f) { err = "cannot open for writing: " + path; return false; }
-    fprintf(f, "%%YAML:1.0\n---\nclass_id: \"%s\"\nmodalities: [ ColorGradient, DepthNormal ]\n", class_id.c_str());
+    fprintf(f, "%%YAML:1.0\n---\nclass_id: \"%s\"\nmodalities: [ %s ]\n", class_id.c_str(), modalities);
     fprintf(f, "pyramid_levels: %d\ntemplate_pyramids:\n", pyramid_levels);
     for (size_t i = 0; i < tps.size(); ++i) {
         fprintf(f, "   -\n      template_id: %d\n      templates:\n", (int)i);

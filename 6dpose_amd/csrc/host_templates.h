@@ -17,7 +17,7 @@ struct Template {                                           // LL.h:36-45
     int width = -1, height = -1, pyramid_level = 0;
     std::vector<Feature> features;
 };
-using TemplatePyramid = std::vector<Template>;              // LL.h:361: [l0 colour, l0 normal, l1 colour, ...]
+using TemplatePyramid = std::vector<Template>;              // LL.h:361: [l0 colour, l0 normal, l1 colour, ...]; one template per level when the detector has one modality
 using TemplatesMap = std::map<std::string, std::vector<TemplatePyramid>>;   // LL.h:362
 
 // ColorGradientPyramid::extractTemplate (LL.cpp:589-643).  mask may be null (no mask).
@@ -31,7 +31,7 @@ void crop_templates(TemplatePyramid& tp);
 
 // writeClass / readClass (LL.cpp:2043-2122).  Return false and fill err on failure.
 bool write_class_yaml(const std::string& path, const std::string& class_id, const std::vector<TemplatePyramid>& tps,
-                      int pyramid_levels, std::string& err);
+                      int pyramid_levels, std::string& err, const char* modalities = "ColorGradient, DepthNormal");
 bool read_class_yaml(const std::string& path, std::string& class_id, std::vector<std::string>& modalities,
                      int& pyramid_levels, std::vector<TemplatePyramid>& tps, std::string& err);
 

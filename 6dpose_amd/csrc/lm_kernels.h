@@ -54,16 +54,18 @@ void fe_job_colour(FeJob& j, const uint8_t* rgb, float* mag, uint8_t* onehot, in
 void fe_job_normals(FeJob& j, const uint16_t* depth, uint8_t* raw, uint8_t* med, int W, int H, int dist_thr, int diff_thr);
 void fe_job_pyrdown(FeJob& j, const uint8_t* src, uint8_t* dst, int W, int H);
 void fe_job_nn_down2(FeJob& j, const uint8_t* src, uint8_t* dst, int W, int H);
+// The writers below take their arrays indexed by modality kind ([0] colour, [1] normals) and serve the kinds [m0, m0 + nm): (0, 2) for the
+// default set, (0, 1) or (1, 1) for a detector with one modality (gz = nm slices of blocks; the absent kind's pointers are never read).
 void fe_job_build_lm(FeJob& j, const uint8_t* const quant[2], const uint8_t* const mask[2], uint8_t* const lm[2], uint8_t* const strips[2],
-                     int W, int H, int T);
+                     int W, int H, int T, int m0 = 0, int nm = 2);
 // the bit planes straight from the quantised maps, when nothing reads the byte planes (frontend.hip)
 bool fe_bits_rows_possible(int W, int T);     // the level's rows fit the stage's LDS
-void fe_job_bits_rows(FeJob& j, const uint8_t* const quant[2], const uint8_t* const mask[2], uint8_t* const bits[2], int W, int H, int T, bool tiles);   // tiles: from pixel tiles where the geometry allows (T = 4, 5 or 8, the row fits the LDS pool)
+void fe_job_bits_rows(FeJob& j, const uint8_t* const quant[2], const uint8_t* const mask[2], uint8_t* const bits[2], int W, int H, int T, bool tiles, int m0 = 0, int nm = 2);   // tiles: from pixel tiles where the geometry allows (T = 4, 5 or 8, the row fits the LDS pool)
 // (the writer of whole dwords when the label planes start on 64-position boundaries — fe_top_bits_kind —, else, or when forced, the one that ORs
 // shifted ballots into a stream that must be zero beforehand)
 // mode: 0 = the cheapest writer the geometry allows (pixel tiles -> whole dwords per wave -> OR-ed ballots), 1 = the OR-ing writer, 2 = no tiles (tests)
-void fe_job_top_bits(FeJob& j, const uint8_t* const quant[2], const uint8_t* const mask[2], uint8_t* stream, const uint32_t bit0[2], int W, int H, int T, int mode);
-int fe_top_bits_kind(int W, int H, int T, const uint32_t bit0[2], int mode);   // kFeTopBitsTile / kFeTopBitsAligned / kFeTopBits (the only one that needs a zeroed stream)
+void fe_job_top_bits(FeJob& j, const uint8_t* const quant[2], const uint8_t* const mask[2], uint8_t* stream, const uint32_t bit0[2], int W, int H, int T, int mode, int m0 = 0, int nm = 2);
+int fe_top_bits_kind(int W, int H, int T, const uint32_t bit0[2], int mode, int m0 = 0, int nm = 2);   // kFeTopBitsTile / kFeTopBitsAligned / kFeTopBits (the only one that needs a zeroed stream)
 void launch_fe_stage(FeStage& st, hipStream_t s);
 void launch_fe_bits(FeStage& st, hipStream_t s);      // a launch of bit-plane jobs only (fe_job_bits_rows, fe_job_top_bits)
 
@@ -231,10 +233,10 @@ struct TrainGeom {                            // the maps of the view being prep
 // keys_view: [levels][2][cap] sort keys / (distance, position, label) records; counts_view: [levels][16]; bbox_view: [4] = {max(-x), max(-y), max(x), max(y)}
 // user_mask (W0 x H0, nonzero = object) replaces depth > 0 when given
 void launch_train_prep(const uint16_t* depth, const uint8_t* user_mask, const TrainGeom& g, float strong_sq, int extract_threshold, unsigned long long* keys_view,
-                       uint32_t cap, uint32_t* counts_view, int32_t* bbox_view, hipStream_t s);
+                       uint32_t cap, uint32_t* counts_view, int32_t* bbox_view, hipStream_t s, int mods = 3);   // mods: bit 0 colour, bit 1 normals — the detector's modality set
 // out: [views][levels][2][4 + 3 * nf_cap]: status (1 ok, 0 too few candidates, 2 leave it to the host path), count, -, -, then x, y, label
 int launch_train_select(const unsigned long long* keys, const uint32_t* counts, const TrainGeom& g, uint32_t cap, int num_features, int nf_cap,
-                        int views, int32_t* out, hipStream_t s);
+                        int views, int32_t* out, hipStream_t s, int mods = 3);
 
 // ---- multi-GPU exchange of match records (exchange.hip) ----
 // Block a rank contributes to the all-gather: 4 header words {count, flags, capacity, 0} + capacity 128-bit keys (a sorted run).

@@ -48,6 +48,7 @@ struct lm_pipeline {
 extern "C" int lm_pipeline_create(lm_detector* det, int width, int height, lm_pipeline** out) {
     if (!det || !out || width <= 0 || height <= 0) return lm_set_error(LM_ERR_INVALID, "null argument");
     *out = nullptr;
+    if (int rc = lm_need_both(det, "lm_pipeline_create")) return rc;   // the ICP stage reads the scene depth of the detector's frame
     HIP_TRY(hipSetDevice(det->device));
     lm_pipeline* p = new lm_pipeline();
     p->det = det; p->W = width; p->H = height;

@@ -54,6 +54,9 @@ k_train_mask(const uint16_t* __restrict__ depth, const uint8_t* __restrict__ use
 }
 
 // counts: [0] colour candidates, [1] normal candidates, [2] pixels inside erode^2(mask), [3..10] candidates per label
+// kMods: bit 0 = the detector has the colour modality, bit 1 = the normals.  3 is the kernel as it always was; with one bit the other modality's
+// maps are not read (they do not exist: g.ang / g.mag or g.nrm are null) and only the erosion that modality needs is computed.
+template <int kMods>
 __global__ void __launch_bounds__(256)
 k_train_prep(TrainGeom g, float strong_sq, unsigned long long* __restrict__ keys_view, uint32_t cap, uint32_t* __restrict__ counts_view) {
     const int l = blockIdx.y;                                 // one launch for all levels: grid.x covers level 0, higher levels leave early
@@ -69,27 +72,30 @@ k_train_prep(TrainGeom g, float strong_sq, unsigned long long* __restrict__ keys
         uint8_t lab = 0;
         if (mask[i]) {
             uint8_t e3 = 255, e5 = 255;                       // cv::erode(3x3, BORDER_REPLICATE) once / twice (LL.cpp:595, 894)
-            for (int dy = -2; dy <= 2; ++dy) {
+            constexpr int kR = (kMods & 2) ? 2 : 1;           // colour alone looks one pixel out
+            for (int dy = -kR; dy <= kR; ++dy) {
                 const int yy = clampi(y + dy, 0, H - 1);
-                for (int dx = -2; dx <= 2; ++dx) {
+                for (int dx = -kR; dx <= kR; ++dx) {
                     const uint8_t v = mask[(size_t)yy * W + clampi(x + dx, 0, W - 1)];
                     e5 = min(e5, v);
                     if (dy >= -1 && dy <= 1 && dx >= -1 && dx <= 1) e3 = min(e3, v);
                 }
             }
+            if (kMods & 1) {
             const uint8_t q = g.ang[l][i];
             const float m = g.mag[l][i];
             if (!e3 && q > 0 && m > strong_sq) {              // mask - erode(mask): the object's one-pixel rim (LL.cpp:596-624)
                 cand = true;
                 key = ((unsigned long long)(~__float_as_uint(m)) << 32) | ((uint32_t)i << 3) | (uint32_t)(__ffs((int)q) - 1);
             }
-            if (e5) {
+            }
+            if ((kMods & 2) && e5) {
                 inside = true;
                 const uint8_t n = g.nrm[l][i];
                 if (n != 0 && n != 255) lab = (uint8_t)__ffs((int)n);   // label + 1 (one-hot by construction of the quantiser)
             }
         }
-        g.lab[l][i] = lab;
+        if (kMods & 2) g.lab[l][i] = lab;
     }
     const unsigned long long mc = __ballot(cand), mi = __ballot(inside);
     const int lane = threadIdx.x & 63;
@@ -170,14 +176,14 @@ k_train_dt(TrainGeom g, int extract_threshold0, unsigned long long* __restrict__
     }
 }
 
-// grid (levels * 2, views).  keys: [views][levels][2][cap]; counts: [views][levels][16]; out: [views][levels][2][4 + 3 * nf_cap]
+// grid (levels * 2, views), or (levels, views) for a detector with the one modality `only_mod` (-1: both).  keys: [views][levels][2][cap]; counts: [views][levels][16]; out: [views][levels][2][4 + 3 * nf_cap]
 // (status: 1 ok, 0 too few candidates, 2 the list did not fit `cap`; number of features; then x, y, label triples).
 __global__ void __launch_bounds__(256)
 k_train_select(const unsigned long long* __restrict__ keys_all, const uint32_t* __restrict__ counts_all, TrainGeom g, uint32_t cap,
-               int num_features, int nf_cap, int32_t* __restrict__ out_all) {
+               int num_features, int nf_cap, int32_t* __restrict__ out_all, int only_mod) {
     extern __shared__ unsigned long long s_keys[];            // [P2]
     __shared__ short s_fx[kTrainMaxFeatures], s_fy[kTrainMaxFeatures];
-    const int l = blockIdx.x >> 1, mod = blockIdx.x & 1, view = blockIdx.y;
+    const int l = only_mod < 0 ? blockIdx.x >> 1 : blockIdx.x, mod = only_mod < 0 ? blockIdx.x & 1 : only_mod, view = blockIdx.y;   // (the layouts keep both slots)
     const int W = g.W[l];
     const unsigned long long* keys = keys_all + (((size_t)view * g.levels + l) * 2 + mod) * cap;
     const uint32_t* counts = counts_all + ((size_t)view * g.levels + l) * 16;
@@ -260,24 +266,27 @@ k_train_select(const unsigned long long* __restrict__ keys_all, const uint32_t* 
 }
 
 void launch_train_prep(const uint16_t* depth, const uint8_t* user_mask, const TrainGeom& g, float strong_sq, int extract_threshold, unsigned long long* keys_view,
-                       uint32_t cap, uint32_t* counts_view, int32_t* bbox_view, hipStream_t s) {
+                       uint32_t cap, uint32_t* counts_view, int32_t* bbox_view, hipStream_t s, int mods) {
     const int n0 = g.W[0] * g.H[0];
     hipLaunchKernelGGL(k_train_mask, dim3((n0 + 255) / 256), dim3(256), 0, s, depth, user_mask, g, bbox_view);
     const dim3 grid((n0 + 255) / 256, g.levels);              // level l uses the first W_l * H_l / 256 blocks of its row
-    hipLaunchKernelGGL(k_train_prep, grid, dim3(256), 0, s, g, strong_sq, keys_view, cap, counts_view);
+    if (mods == 1) { hipLaunchKernelGGL(k_train_prep<1>, grid, dim3(256), 0, s, g, strong_sq, keys_view, cap, counts_view); return; }   // colour only: no labels, runs or distances
+    if (mods == 2) hipLaunchKernelGGL(k_train_prep<2>, grid, dim3(256), 0, s, g, strong_sq, keys_view, cap, counts_view);
+    else hipLaunchKernelGGL(k_train_prep<3>, grid, dim3(256), 0, s, g, strong_sq, keys_view, cap, counts_view);
     hipLaunchKernelGGL(k_train_runs, grid, dim3(256), 0, s, g);
     hipLaunchKernelGGL(k_train_dt, grid, dim3(256), 0, s, g, extract_threshold < 0 ? 0 : extract_threshold, keys_view, cap, counts_view);
 }
 
 int launch_train_select(const unsigned long long* keys, const uint32_t* counts, const TrainGeom& g, uint32_t cap, int num_features, int nf_cap,
-                        int views, int32_t* out, hipStream_t s) {
+                        int views, int32_t* out, hipStream_t s, int mods) {
     static size_t configured = 0;
     const size_t lds = (size_t)cap * sizeof(unsigned long long);
     if (lds > configured) {
         if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_train_select), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return -1;
         configured = lds;
     }
-    hipLaunchKernelGGL(k_train_select, dim3(g.levels * 2, views), dim3(256), lds, s, keys, counts, g, cap, num_features, nf_cap, out);
+    const int only_mod = mods == 3 ? -1 : mods - 1;
+    hipLaunchKernelGGL(k_train_select, dim3(g.levels * (only_mod < 0 ? 2 : 1), views), dim3(256), lds, s, keys, counts, g, cap, num_features, nf_cap, out, only_mod);
     return 0;
 }
 

@@ -142,6 +142,9 @@ def load_library():
     lib.lm_version.restype = S
     lib.lm_device_count.restype = I
     lib.lm_detector_create.argtypes = [I, ctypes.POINTER(I), I, I, ctypes.POINTER(P)]
+    lib.lm_detector_create_modalities.argtypes = [I, ctypes.POINTER(I), I, I, ctypes.POINTER(ctypes.c_char_p), I, ctypes.POINTER(P)]
+    lib.lm_detector_get_modalities.argtypes = [P, ctypes.POINTER(ctypes.c_char_p)]
+    lib.lm_bank_file_modalities.argtypes = [ctypes.c_char_p, ctypes.POINTER(ctypes.c_char_p)]
     lib.lm_detector_destroy.argtypes = [P]
     lib.lm_detector_destroy.restype = None
     lib.lm_detector_add_template.argtypes = [P, P, P, P, I, I, S]
@@ -273,10 +276,10 @@ def _ptr(a: Optional[np.ndarray]):
     return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
 
 
-def _as_rgb(a) -> np.ndarray:
+def _as_rgb(a, what="sources[0]") -> np.ndarray:
     a = np.asarray(a)
     if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3:
-        raise RuntimeError("sources[0] must be a uint8 HxWx3 image (got %s %s)" % (a.dtype, a.shape))
+        raise RuntimeError("%s must be a uint8 HxWx3 image (got %s %s)" % (what, a.dtype, a.shape))
     return np.ascontiguousarray(a)
 
 
@@ -361,7 +364,11 @@ class Comm:
 class Detector:
     """linemodLevelup::Detector (LL.h:264-375) running on one MI355X."""
 
-    def __init__(self, *args, device: Optional[int] = None):
+    def __init__(self, *args, device: Optional[int] = None, modalities: Optional[Sequence[str]] = None):
+        """Detector(), Detector(T), Detector(num_features, T) (pybind11.cpp:26-28).  modalities= selects the modality set, the
+        counterpart of Detector(const std::vector<Ptr<Modality>>&, T) (LL.cpp:1694-1700): ("ColorGradient", "DepthNormal") — the
+        default —, ("ColorGradient",) or ("DepthNormal",), with the parameters of the reference's constructors (LL.cpp:1684-1692).
+        `sources` and `masks` then carry one array per modality of the set, in its order."""
         lib = load_library()
         num_features, T = 0, None
         if len(args) == 1:
@@ -374,7 +381,17 @@ class Detector:
             device = int(os.environ.get("LOCAL_RANK", "0")) if lib.lm_device_count() > 1 else 0
         self._h = ctypes.c_void_p()
         Tarr = (ctypes.c_int * len(T))(*T) if T is not None else None
-        _check(lib.lm_detector_create(num_features, Tarr, len(T) if T is not None else 0, device, ctypes.byref(self._h)))
+        if modalities is None:
+            _check(lib.lm_detector_create(num_features, Tarr, len(T) if T is not None else 0, device, ctypes.byref(self._h)))
+        else:
+            if isinstance(modalities, (str, bytes)):
+                raise RuntimeError("modalities must be a sequence of names, e.g. ('ColorGradient',)")
+            names = [str(m).encode() for m in modalities]
+            marr = (ctypes.c_char_p * max(1, len(names)))(*names)
+            _check(lib.lm_detector_create_modalities(num_features, Tarr, len(T) if T is not None else 0, device, marr, len(names),
+                                                     ctypes.byref(self._h)))
+        out = (ctypes.c_char_p * 2)()
+        self._mods = tuple(out[i].decode() for i in range(lib.lm_detector_get_modalities(self._h, out)))
         self._lib = lib
         self.device = device
         self._shard = (0, 1)
@@ -384,15 +401,32 @@ class Detector:
         if h is not None and h.value and getattr(self, "_lib", None) is not None:
             self._lib.lm_detector_destroy(h)
 
+    def getModalities(self) -> tuple:
+        """The detector's modality set, names as in the class YAML (lm_detector_get_modalities)."""
+        return self._mods
+
+    def _sources(self, sources, check_len: bool = False):
+        """(rgb or None, depth or None, (H, W)): one array per modality of the set, in its order."""
+        if check_len and len(sources) != len(self._mods):
+            raise RuntimeError("sources.size() == modalities.size() [LL.cpp:1707]")
+        if len(self._mods) == 2:
+            rgb, depth = _as_rgb(sources[0]), _as_depth(sources[1])
+            if rgb.shape[:2] != depth.shape:
+                raise RuntimeError("rgb and depth sizes differ")
+            return rgb, depth, depth.shape
+        if len(sources) != 1:
+            raise RuntimeError("sources.size() == modalities.size() [LL.cpp:1707]")
+        if self._mods[0] == "ColorGradient":
+            rgb = _as_rgb(sources[0])
+            return rgb, None, rgb.shape[:2]
+        depth = _as_depth(sources[0], "sources[0]")
+        return None, depth, depth.shape
+
     # ---- training -------------------------------------------------------------------------------
     def addTemplate(self, sources: Sequence[np.ndarray], class_id: str, object_mask: np.ndarray) -> int:
-        if len(sources) != 2:
-            raise RuntimeError("sources.size() == modalities.size() [LL.cpp:1707]")
-        rgb, depth = _as_rgb(sources[0]), _as_depth(sources[1])
-        if rgb.shape[:2] != depth.shape:
-            raise RuntimeError("rgb and depth sizes differ")
-        mask = _as_mask(object_mask, depth.shape)
-        rc = self._lib.lm_detector_add_template(self._h, _ptr(rgb), _ptr(depth), _ptr(mask), depth.shape[1], depth.shape[0],
+        rgb, depth, shape = self._sources(sources, True)
+        mask = _as_mask(object_mask, shape)
+        rc = self._lib.lm_detector_add_template(self._h, _ptr(rgb), _ptr(depth), _ptr(mask), shape[1], shape[0],
                                                 class_id.encode())
         if rc < -1:
             _check(rc)
@@ -420,7 +454,7 @@ class Detector:
         features = np.ascontiguousarray(features, np.int32).reshape(-1, 3)
         tmpl_offsets = np.ascontiguousarray(tmpl_offsets, np.int32)
         tmpl_wh = np.ascontiguousarray(tmpl_wh, np.int32).reshape(-1, 2)
-        E = 2 * self.pyramidLevels()
+        E = len(self._mods) * self.pyramidLevels()
         if (len(tmpl_offsets) - 1) % E or len(tmpl_wh) != len(tmpl_offsets) - 1:
             raise RuntimeError("packed bank arrays have inconsistent sizes")
         _check(self._lib.lm_detector_add_class_packed(self._h, class_id.encode(), (len(tmpl_offsets) - 1) // E,
@@ -463,7 +497,7 @@ class Detector:
 
     def getTemplates(self, class_id: str, template_id: int) -> List[Template]:
         out = []
-        for idx in range(2 * self.pyramidLevels()):
+        for idx in range(len(self._mods) * self.pyramidLevels()):
             w, h, lvl, n = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
             _check(self._lib.lm_detector_get_template(self._h, class_id.encode(), template_id, idx, ctypes.byref(w), ctypes.byref(h),
                                                       ctypes.byref(lvl), ctypes.byref(n), None, 0))
@@ -500,25 +534,21 @@ class Detector:
     def _mask_args(self, masks, shape):
         if masks is None or len(masks) == 0:
             return None, []
-        if len(masks) != 2:
+        if len(masks) != len(self._mods):
             raise RuntimeError("masks.size() == modalities.size() [LL.cpp:1714]")
         keep = [_as_mask(m, shape) for m in masks]
-        arr = (ctypes.c_void_p * 2)(*[None if m is None else m.ctypes.data for m in keep])
+        arr = (ctypes.c_void_p * 2)(*[None if m is None else m.ctypes.data for m in keep])       # (one entry used by a set of one)
         return arr, keep
 
     def setFrame(self, sources, masks=()) -> None:
-        rgb, depth = _as_rgb(sources[0]), _as_depth(sources[1])
-        if rgb.shape[:2] != depth.shape:
-            raise RuntimeError("rgb and depth sizes differ")
-        marr, keep = self._mask_args(masks, depth.shape)
-        _check(self._lib.lm_detector_set_frame(self._h, _ptr(rgb), _ptr(depth), depth.shape[1], depth.shape[0], marr))
+        rgb, depth, shape = self._sources(sources)
+        marr, keep = self._mask_args(masks, shape)
+        _check(self._lib.lm_detector_set_frame(self._h, _ptr(rgb), _ptr(depth), shape[1], shape[0], marr))
 
     def storeFrame(self, slot: int, sources) -> None:
         """Parks a frame in HBM slot `slot` (lm_detector_store_frame)."""
-        rgb, depth = _as_rgb(sources[0]), _as_depth(sources[1])
-        if rgb.shape[:2] != depth.shape:
-            raise RuntimeError("rgb and depth sizes differ")
-        _check(self._lib.lm_detector_store_frame(self._h, slot, _ptr(rgb), _ptr(depth), depth.shape[1], depth.shape[0]))
+        rgb, depth, shape = self._sources(sources)
+        _check(self._lib.lm_detector_store_frame(self._h, slot, _ptr(rgb), _ptr(depth), shape[1], shape[0]))
 
     def selectFrame(self, slot: int) -> None:
         """Makes a parked frame current with a device-to-device copy (lm_detector_select_frame)."""
@@ -543,11 +573,9 @@ class Detector:
         a time (or at flush() / the collect() that needs them); collect() returns the results in submission
         order.  Up to lm_detector_max_in_flight() frames in flight.  `sources` are borrowed only during the call; arrays
         obtained from ingestBuffers() skip the staging copy."""
-        rgb, depth = _as_rgb(sources[0]), _as_depth(sources[1])
-        if rgb.shape[:2] != depth.shape:
-            raise RuntimeError("rgb and depth sizes differ")
+        rgb, depth, shape = self._sources(sources)
         carr, n, _names = self._class_args(class_ids)
-        _check(self._lib.lm_detector_submit_frame(self._h, _ptr(rgb), _ptr(depth), depth.shape[1], depth.shape[0], float(threshold), carr, n))
+        _check(self._lib.lm_detector_submit_frame(self._h, _ptr(rgb), _ptr(depth), shape[1], shape[0], float(threshold), carr, n))
 
     def flush(self) -> None:
         """Launches the streamed frames that are still waiting for their batch to fill (lm_detector_flush); collect() does it by itself."""
@@ -670,13 +698,16 @@ class Detector:
     def ingestBuffers(self, width: int, height: int):
         """(rgb uint8 HxWx3, depth uint16 HxW) views of the pinned staging memory the NEXT submitFrame() will upload from
         (lm_detector_ingest_buffer): fill them in place and pass them to submitFrame — no staging copy.  Valid until that
-        frame has been collected."""
+        frame has been collected.  A detector with one modality returns a 1-tuple: the buffer of that modality."""
         pr, pd = ctypes.c_void_p(), ctypes.c_void_p()
         _check(self._lib.lm_detector_ingest_buffer(self._h, int(width), int(height), ctypes.byref(pr), ctypes.byref(pd)))
         n = int(width) * int(height)
-        rgb = np.ctypeslib.as_array(ctypes.cast(pr, ctypes.POINTER(ctypes.c_uint8)), shape=(n * 3,)).reshape(height, width, 3)
-        depth = np.ctypeslib.as_array(ctypes.cast(pd, ctypes.POINTER(ctypes.c_uint16)), shape=(n,)).reshape(height, width)
-        return rgb, depth
+        rgb = depth = None
+        if pr.value:
+            rgb = np.ctypeslib.as_array(ctypes.cast(pr, ctypes.POINTER(ctypes.c_uint8)), shape=(n * 3,)).reshape(height, width, 3)
+        if pd.value:
+            depth = np.ctypeslib.as_array(ctypes.cast(pd, ctypes.POINTER(ctypes.c_uint16)), shape=(n,)).reshape(height, width)
+        return tuple(b for b in (rgb, depth) if b is not None)
 
     def matchStream(self, frames, threshold: float, class_ids: Sequence[str] = (), depth: int = 3):
         """The dataset / camera loop of the reference (linemod_and_levelup_test.py:314-327: one Detector.match per frame) as a
@@ -799,15 +830,11 @@ class Detector:
 
     def matchArray(self, sources, threshold: float, class_ids: Sequence[str] = (), masks=()) -> np.ndarray:
         """match() returning a structured array (class_index refers to class_ids / sorted classIds())."""
-        if len(sources) != 2:
-            raise RuntimeError("sources.size() == modalities.size() [LL.cpp:1707]")
-        rgb, depth = _as_rgb(sources[0]), _as_depth(sources[1])
-        if rgb.shape[:2] != depth.shape:
-            raise RuntimeError("rgb and depth sizes differ")
+        rgb, depth, shape = self._sources(sources, True)
         carr, n, _names = self._class_args(class_ids)
-        marr, keep = self._mask_args(masks, depth.shape)
+        marr, keep = self._mask_args(masks, shape)
         out, cnt = ctypes.POINTER(_CMatch)(), ctypes.c_size_t()
-        _check(self._lib.lm_detector_match(self._h, _ptr(rgb), _ptr(depth), depth.shape[1], depth.shape[0], float(threshold),
+        _check(self._lib.lm_detector_match(self._h, _ptr(rgb), _ptr(depth), shape[1], shape[0], float(threshold),
                                            carr, n, marr, ctypes.byref(out), ctypes.byref(cnt)))
         return self._take(out, cnt.value)
 
@@ -851,6 +878,13 @@ def bank_file_info(path) -> dict:
         _check(lib.lm_bank_file_class_id(os.fspath(path).encode(), i, buf, len(buf)))
         ids.append(buf.value.decode())
     return {"pyramid_levels": lv.value, "class_ids": ids, "num_pyramids": npyr.value, "num_features": nf.value}
+
+
+def bank_file_modalities(path) -> tuple:
+    """The modality set a packed bank file was written for (no detector, no GPU; lm_bank_file_modalities).  Files from before the set existed
+    report ("ColorGradient", "DepthNormal")."""
+    out = (ctypes.c_char_p * 2)()
+    return tuple(out[i].decode() for i in range(_check(load_library().lm_bank_file_modalities(os.fspath(path).encode(), out))))
 
 
 def merge_matches(records: np.ndarray) -> np.ndarray:

@@ -86,6 +86,25 @@ int lm_bind_thread_near_device(int device, char *cpulist_out, size_t cap);
  * Detector(), Detector(T), Detector(num_features, T): pybind11.cpp:26-28, LL.cpp:1663-1692.
  * num_features <= 0 selects the default 63; T==NULL selects {5,8}.  `device` is the HIP ordinal. */
 int lm_detector_create(int num_features, const int *T, int num_levels, int device, lm_detector **out);
+/* The modality set: Detector(const std::vector<Ptr<Modality>>&, const std::vector<int>& T), LL.cpp:1694-1700.  `modalities` names the
+ * set as the class YAML does: {"ColorGradient", "DepthNormal"} (what lm_detector_create builds; modalities == NULL selects it too),
+ * {"ColorGradient"} or {"DepthNormal"}; any other list (unknown name, duplicate, the pair reversed) is LM_ERR_INVALID.  The parameters
+ * are those of the reference's own constructors (LL.cpp:1684-1692): ColorGradient(10, num_features, 55), DepthNormal(2000, 50,
+ * num_features, 2).  The set is fixed for the detector's life.  With ONE modality:
+ *   - every call that takes the two sources (lm_detector_match, _set_frame, _store_frame, _submit_frame, _add_template) takes NULL for
+ *     the absent one (a non-NULL pointer there is LM_ERR_INVALID, as NULL for a present source always was); nothing of the absent
+ *     image is uploaded, quantised or written.  lm_detector_ingest_buffer returns NULL for it.
+ *   - `masks`, where a call takes them, has one entry: masks[0] belongs to the set's modality.
+ *   - a template pyramid has `levels` templates (not levels * 2): lm_detector_get_template's index, lm_detector_add_class_packed's arrays,
+ *     class files (`modalities: [ ColorGradient ]`) and the packed bank follow; the score is raw * 100 / (4 * features of that modality),
+ *     cropTemplates takes its box over that modality's features, and lm_detector_add_template returns -1 by that modality alone.
+ *   - lm_detector_read_class / _read_bank / _read_params refuse a file written for another set (LL.cpp:2047-2051), in both directions.
+ *   - lm_detector_read_stage refuses the absent modality's kinds; kind 4 returns the one block.
+ *   - lm_pipeline_create, lm_detector_set_shard and the exchange calls return LM_ERR_INVALID ("... needs both modalities").
+ * lm_detector_get_modalities returns the number of modalities (0 for a NULL detector) and, when `names` is given, static strings. */
+int lm_detector_create_modalities(int num_features, const int *T, int num_levels, int device, const char *const *modalities,
+                                  int num_modalities, lm_detector **out);
+int lm_detector_get_modalities(const lm_detector *d, const char *names[2]);
 void lm_detector_destroy(lm_detector *d);
 
 /* Detector::addTemplate (pybind11.cpp:29, LL.cpp:1943-1975).  Returns the new template_id (>=0),
@@ -126,6 +145,10 @@ int lm_detector_write_bank(const lm_detector *d, const char *path, const char *c
 int lm_detector_read_bank(lm_detector *d, const char *path, const char *const *class_ids, int num_class_ids);
 int lm_bank_file_info(const char *path, int32_t *pyramid_levels, int32_t *num_classes, int64_t *num_pyramids, int64_t *num_features);
 int lm_bank_file_class_id(const char *path, int index, char *out, int capacity);
+/* The modality set a bank file was written for: returns the count (1 or 2; < 0 = LM_ERR_*) and the names as static strings.  The set
+ * lives in a header word that was reserved (zero) before: every older file reads as [ColorGradient, DepthNormal].  lm_detector_read_bank
+ * refuses a file whose set differs from the detector's. */
+int lm_bank_file_modalities(const char *path, const char *names[2]);
 
 /* Detector::numClasses / classIds / numTemplates (LL.h:343, LL.cpp:1984-2011). */
 int lm_detector_num_classes(const lm_detector *d);

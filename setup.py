@@ -32,7 +32,7 @@ setup(
     version="0.2.0",
     description="MI355X-native linemodLevelup Detector / poseRefine (drop-in for linemodLevelup_pybind)",
     package_dir={"": "6dpose_amd"},
-    py_modules=["linemodLevelup_pybind", "sharded", "views"],
+    py_modules=["linemodLevelup_pybind", "lm_abi", "lm_detector", "lm_icp", "lm_render", "lm_pose_error", "sharded", "views"],
     cmdclass={"build_py": BuildWithHip},
     python_requires=">=3.8",
     install_requires=["numpy"],

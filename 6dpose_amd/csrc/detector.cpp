@@ -233,7 +233,7 @@ extern "C" void lm_detector_destroy(lm_detector* d) {
     }
     if (d->ingest.stream) (void)hipStreamDestroy(d->ingest.stream);
     for (int a = 0; a < lm_detector::kSlots; ++a) { d->lm_arena[a].release(); d->sm_arena[a].release(); }
-    for (int a = 0; a < lm_detector::kSlots; ++a) { d->bits_arena[a].release(); d->cbits_arena[a].release(); }
+    for (int a = 0; a < lm_detector::kSlots; ++a) { d->bits_arena[a].release(); d->cbits_arena[a].release(); d->wbits_arena[a].release(); d->wcbits_arena[a].release(); }
     for (auto& b : d->slot_rgb) b.release();
     for (auto& b : d->slot_depth) b.release();
     for (auto& l : d->lvl) { l.rgb.release(); l.mag.release(); l.ang.release(); l.nrm.release(); l.mask[0].release(); l.mask[1].release(); }
@@ -275,7 +275,10 @@ extern "C" int lm_detector_set_reference_order(lm_detector* d, int on) {
 
 extern "C" int lm_detector_set_paths(lm_detector* d, int refine, int coarse) {
     if (!d) return lm_set_error(LM_ERR_INVALID, "null detector");
-    if (refine < 0 || refine > 2 || coarse < 0 || coarse > 1) return lm_set_error(LM_ERR_INVALID, "refine must be 0 (bit planes), 1 (tiles) or 2 (per candidate), coarse 0 (bit planes) or 1 (bytes)");
+    if (refine < 0 || refine > 3 || coarse < 0 || coarse > 2)
+        return lm_set_error(LM_ERR_INVALID, "refine must be 0 (bit planes), 1 (tiles), 2 (per candidate) or 3 (wide bit planes), coarse 0 (bit planes), 1 (bytes) or 2 (wide bit planes)");
+    if (coarse == 2 && refine != 3) return lm_set_error(LM_ERR_INVALID, "coarse 2 (wide bit planes) plans no tiles: it needs refine 3 (wide bit planes)");
+    if (refine == 3 && d->shard_world > 1) return lm_set_error(LM_ERR_INVALID, "the wide paths are not available on a sharded detector (%d ranks)", d->shard_world);
     if (d->n_submitted != d->n_collected) return lm_set_error(LM_ERR_INVALID, "frames in flight: collect them first");
     int rc = lm_launch_pending(d);
     if (rc) return rc;
@@ -313,6 +316,16 @@ extern "C" int lm_detector_bit_arena_bytes(const lm_detector* d, uint64_t* strip
     for (int s = 0; s < lm_detector::kSlots; ++s) {                 // what is allocated, over all result slots (DevBuf holds bytes)
         *strip_records += d->bits_arena[s].cap;
         *pair_stream += d->cbits_arena[s].cap;
+    }
+    return LM_OK;
+}
+
+extern "C" int lm_detector_wide_arena_bytes(const lm_detector* d, uint64_t* strip_records, uint64_t* pair_stream) {
+    if (!d || !strip_records || !pair_stream) return lm_set_error(LM_ERR_INVALID, "null argument");
+    *strip_records = *pair_stream = 0;
+    for (int s = 0; s < lm_detector::kSlots; ++s) {                 // the second set: nothing until a wide table has run on a wide path
+        *strip_records += d->wbits_arena[s].cap;
+        *pair_stream += d->wcbits_arena[s].cap;
     }
     return LM_OK;
 }

@@ -522,6 +522,7 @@ extern "C" int lm_detector_get_template(const lm_detector* d, const char* class_
 extern "C" int lm_detector_set_shard(lm_detector* d, int rank, int world) {
     if (!d || world < 1 || rank < 0 || rank >= world) return lm_set_error(LM_ERR_INVALID, "bad shard (%d of %d)", rank, world);
     if (int rc = lm_need_both(d, "lm_detector_set_shard")) return rc;
+    if (world > 1 && d->refine_mode == 3) return lm_set_error(LM_ERR_INVALID, "the wide paths are not available on a sharded detector: lm_detector_set_paths first");
     d->shard_rank = rank; d->shard_world = world;
     return LM_OK;
 }

@@ -83,6 +83,14 @@ int setup_geometry(lm_detector* d, int W, int H, bool check_match_preconditions)
             if ((rc = d->bits_arena[a].ensure(bbytes))) return rc;
             if (realloc_bits || d->fW != W || d->fH != H) HIP_TRY(hipMemsetAsync(d->bits_arena[a].p, 0, d->bits_arena[a].cap, d->stream));
         }
+        // the second set of the wide paths follows the first where a wide match has allocated it (detector_stream.cpp, ensure_wide_arenas)
+        for (DevBuf<uint8_t>* w : {&d->wbits_arena[a], &d->wcbits_arena[a]}) {
+            if (!w->cap) continue;
+            const size_t bytes = w == &d->wbits_arena[a] ? d->bits_arena[a].cap : d->cbits_arena[a].cap;
+            const bool realloc_wide = bytes > w->cap;
+            if ((rc = w->ensure(bytes))) return rc;
+            if (realloc_wide || d->fW != W || d->fH != H) HIP_TRY(hipMemsetAsync(w->p, 0, w->cap, d->stream));
+        }
     }
     for (int l = 0; l < L; ++l) {
         LevelBufs& b = d->lvl[l];
@@ -241,7 +249,7 @@ extern "C" int lm_detector_select_frame(lm_detector* d, int slot) {
 }
 
 extern "C" int64_t lm_detector_read_stage(lm_detector* d, int level, int kind, uint8_t* dst, int64_t capacity) {
-    if (!d || level < 0 || level >= d->pyramid_levels || kind < 0 || kind > 5) return lm_set_error(LM_ERR_INVALID, "bad argument");
+    if (!d || level < 0 || level >= d->pyramid_levels || kind < 0 || kind > 7) return lm_set_error(LM_ERR_INVALID, "bad argument");
     if (d->fW <= 0) return lm_set_error(LM_ERR_INVALID, "no frame processed yet");
     if (kind < 4 && !d->use[kind & 1])            // kinds 0, 2: colour; 1, 3: normals
         return lm_set_error(LM_ERR_INVALID, "stage %d belongs to %s, which is not in the detector's modality set", kind, kModalityName[kind & 1]);
@@ -258,9 +266,17 @@ extern "C" int64_t lm_detector_read_stage(lm_detector* d, int level, int kind, u
             if (level == d->pyramid_levels - 1) return lm_set_error(LM_ERR_INVALID, "the top level has no strip records");
             // (a set of one: its own block only)
             src = d->bits_arena[d->last_arena].p + (lv.sm_off[d->mod_kind[0]] >> 1); size = (int64_t)d->nmod * 8 * lv.T * lv.T * lv.NS * lv.Hd * 8; break;
-        default:      // pair stream of the top level (what k_coarse_bits reads)
+        case 5:       // pair stream of the top level (what k_coarse_bits reads)
             if (level != d->pyramid_levels - 1) return lm_set_error(LM_ERR_INVALID, "only the top level has a pair stream");
             src = d->cbits_arena[d->last_arena].p; size = (int64_t)d->cbits_npairs * 8; break;
+        case 6:       // the second set of strip records (k_local_wide reads kinds 4 and 6): the layout and size of kind 4
+            if (level == d->pyramid_levels - 1) return lm_set_error(LM_ERR_INVALID, "the top level has no strip records");
+            if (!d->wbits_arena[d->last_arena].cap) return lm_set_error(LM_ERR_INVALID, "no second set of strip records: the last match did not refine on the wide path");
+            src = d->wbits_arena[d->last_arena].p + (lv.sm_off[d->mod_kind[0]] >> 1); size = (int64_t)d->nmod * 8 * lv.T * lv.T * lv.NS * lv.Hd * 8; break;
+        default:      // the second pair stream (k_coarse_wide reads kinds 5 and 7): the layout and size of kind 5
+            if (level != d->pyramid_levels - 1) return lm_set_error(LM_ERR_INVALID, "only the top level has a pair stream");
+            if (!d->wcbits_arena[d->last_arena].cap) return lm_set_error(LM_ERR_INVALID, "no second pair stream: the last match did not run its coarse pass on the wide path");
+            src = d->wcbits_arena[d->last_arena].p; size = (int64_t)d->cbits_npairs * 8; break;
     }
     if (dst && capacity > 0) {
         if (hipSetDevice(d->device) != hipSuccess) return lm_set_error(LM_ERR_HIP, "hipSetDevice failed");

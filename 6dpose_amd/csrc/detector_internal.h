@@ -191,7 +191,11 @@ struct lm_detector {
     // Which kernels match() uses (lm_detector_set_paths; tests and measurements of the byte paths).  refine: 0 = bit planes when the pyramid has a
     // level below the top (default), 1 = byte strip planes with tiles (round 2-3's k_local), 2 = byte planes, every candidate on its own
     // (round 1).  coarse: 0 = pair stream when the refinement runs on bit planes (default), 1 = byte linear memories (k_coarse).
+    // refine 3 / coarse 2 = "wide": what 0 is for a table of two planes, and two sets of bit planes (match_wide.hip) for the tables that need them.
     int refine_mode = 0, coarse_mode = 0;
+    // Second set of bit planes of the wide paths, per result slot: allocated (and zeroed) when a batch first runs a wide table on a wide path,
+    // at the sizes of bits_arena / cbits_arena; a geometry change resizes and clears the ones that exist (setup_geometry).
+    DevBuf<uint8_t> wbits_arena[kSlots], wcbits_arena[kSlots];
     // The response table r[d], d = cyclic distance 0..4 (lm_detector_set_response_table; LL.cpp:1112-1124).  Per detector and per process: no file
     // format carries it, training does not read it.  Every front end launch takes it along (FeStage::resp), so the next match of the resident frame
     // rebuilds the response memories under the new table.  Tables with more than two distinct non-zero values run on the byte kernels.

@@ -152,12 +152,22 @@ static int run_frontend_batch(lm_detector* d, int first, int nb, hipStream_t s, 
 // The bit-plane refinement (match_bits.hip): any pyramid with a level below the top; entries of up to 16383 features (two
 // modalities of the reference's 8191, LL.cpp:1291).  LM_BITPLANES=0 / lm_detector_set_paths: the byte paths.  Two bits per cell carry a response
 // table of at most two distinct non-zero values; the others (4 3 2 1 0 ...) run on the byte kernels, and lm_detector_get_paths says so.
+// Under refine 3 / coarse 2 ("wide") a table of two planes runs exactly this; the others run the wide kernels below.
 static bool bits_active(const lm_detector* d, int num_work) {
-    return knobs().bitplanes && d->refine_mode == 0 && d->resp_two_planes && num_work > 0 && d->geom.levels >= 2 && d->bits_max_nf <= 16383;
+    return knobs().bitplanes && (d->refine_mode == 0 || d->refine_mode == 3) && d->resp_two_planes && num_work > 0 && d->geom.levels >= 2 && d->bits_max_nf <= 16383;
 }
 // ... and the coarse pass on the pair stream of the top level (it plans no tiles, so only together with the bit-plane refinement)
 static bool cbits_active(const lm_detector* d, int num_work) {
-    return bits_active(d, num_work) && knobs().coarse_bits && d->coarse_mode == 0 && d->cbits_max_nf <= 16383;
+    return bits_active(d, num_work) && knobs().coarse_bits && (d->coarse_mode == 0 || d->coarse_mode == 2) && d->cbits_max_nf <= 16383;
+}
+// The wide refinement (match_wide.hip): only when the table does not fit two planes and the path was asked for; the
+// conditions that send a bank or geometry off the bit planes are those of bits_active.
+static bool wide_active(const lm_detector* d, int num_work) {
+    return knobs().bitplanes && d->refine_mode == 3 && !d->resp_two_planes && num_work > 0 && d->geom.levels >= 2 && d->bits_max_nf <= kWideMaxFeatures;
+}
+// ... and the wide coarse pass (no tiles either: only together with the wide refinement)
+static bool cwide_active(const lm_detector* d, int num_work) {
+    return wide_active(d, num_work) && knobs().coarse_bits && d->coarse_mode == 2 && d->cbits_max_nf <= kWideMaxFeatures;
 }
 // Device pointers of result slot `si` (everything a frame in flight owns).
 static int frame_slot(lm_detector* d, int si, bool tiled, uint32_t tile_cap, FrameSlot* out) {
@@ -222,7 +232,7 @@ static int slot_begin(lm_detector* d, float threshold, const char* const* class_
         HIP_TRY(hipMemset(d->d_final.p, 0, 8 * (size_t)K * sizeof(unsigned long long)));
     }
     // tile refinement (match_bytes.hip): two-level pyramids with a tileable geometry; the buffers exist per result slot
-    const bool tiled = (tiles_wanted(d) && num_work > 0 && tile_plan_possible(d->geom)) || bits_active(d, num_work);   // (the bit-plane path uses the todo bytes)
+    const bool tiled = (tiles_wanted(d) && num_work > 0 && tile_plan_possible(d->geom)) || bits_active(d, num_work) || wide_active(d, num_work);   // (the bit-plane paths use the todo bytes)
     const uint32_t tile_cap = d->buf_cand_cap / 2;      // a tile has at least two members
     if (tiled && (d->d_tiles.cap < (size_t)tile_cap * K || d->d_todo.cap < (size_t)d->buf_cand_cap * K)) {
         if ((rc = lm_launch_pending(d))) return rc;
@@ -316,12 +326,14 @@ struct Batch {
     int nb, first, num_work;
     float threshold;
     bool bits, cbits, tiled;                  // refinement on bit planes / coarse pass on the pair stream / tile refinement
+    bool wide, cwide;                         // ... on two sets of bit planes (match_wide.hip): bits / cbits are set as well
     bool direct_low, direct_top, top_ored;    // the front end writes the bit planes below the top / of the top level itself; ... by OR-ing into a zeroed pair stream
     uint32_t tile_cap, cap;
     hipStream_t s;                            // every kernel of a batch on the matching stream (one queue; the end of a stage is the start of the next)
     FrameBatch fb, fb_rest;                   // fb_rest: for k_local's per-candidate path on what k_local_bits leaves (todo = 1)
     BitsBatch bb;
     TopBits tb;
+    WidePlanes wb, wt;                        // the second set of strip records / of the pair stream
     BankDev bank;                             // the device bank and work list, as the matching launchers take them
     int slot(int b) const { return (first + b) % lm_detector::kSlots; }
 };
@@ -333,8 +345,10 @@ static int batch_begin(lm_detector* d, Batch& B) {
     const lm_detector::Slot& lead = d->slot[B.first];
     B.num_work = lead.num_work;
     B.threshold = lead.threshold;
-    B.bits = bits_active(d, B.num_work);
-    B.cbits = cbits_active(d, B.num_work);
+    B.wide = wide_active(d, B.num_work);
+    B.cwide = cwide_active(d, B.num_work);
+    B.bits = B.wide || bits_active(d, B.num_work);
+    B.cbits = B.cwide || cbits_active(d, B.num_work);
     B.tiled = !B.bits && tiles_wanted(d) && B.num_work > 0 && tile_plan_possible(d->geom);
     B.tile_cap = d->buf_cand_cap / 2;
     B.cap = std::min<uint32_t>(lead.match_cap, d->buf_cand_cap);
@@ -364,8 +378,8 @@ static int order_batch(lm_detector* d, const Batch& B) {
 // The front end writes the bit planes directly where nothing reads the byte planes: below the top when no candidate can leave its planes
 // (then k_local never runs behind k_local_bits), at the top level when the coarse pass runs on the pair stream.
 static int choose_bit_writers(lm_detector* d, Batch& B) {
-    B.direct_low = knobs().fe_bits && d->fe_direct && B.bits && d->bits_all_in;
-    B.direct_top = knobs().fe_bits && d->fe_direct && B.cbits;
+    B.direct_low = knobs().fe_bits && d->fe_direct && B.bits && !B.wide && d->bits_all_in;   // (a wide table: byte planes, packed — the front end's writers know two planes)
+    B.direct_top = knobs().fe_bits && d->fe_direct && B.cbits && !B.cwide;
     for (int l = 0; l + 1 < d->geom.levels; ++l) B.direct_low = B.direct_low && fe_bits_rows_possible(d->geom.lv[l].W, d->geom.lv[l].T);
     const LevelGeom& topl = d->geom.lv[d->geom.levels - 1];
     const uint32_t top_bit0[2] = {topl.lm_off[0] - d->cbits_byte0, topl.lm_off[1] - d->cbits_byte0};
@@ -379,6 +393,22 @@ static int choose_bit_writers(lm_detector* d, Batch& B) {
     return LM_OK;
 }
 
+// The second arenas of the batch's slots, at the sizes of the first: allocated and zeroed (the zero planes and tails of set 1 are read like
+// those of set 0) when a slot first serves a wide batch.  The slot is free — its previous frame was collected —, so nothing reads what is replaced.
+static int ensure_wide_arenas(lm_detector* d, const Batch& B) {
+    for (int b = 0; b < B.nb; ++b) {
+        const int si = B.slot(b);
+        DevBuf<uint8_t>* w[2] = {B.wide ? &d->wbits_arena[si] : nullptr, B.cwide ? &d->wcbits_arena[si] : nullptr};
+        const size_t bytes[2] = {d->bits_arena[si].cap, d->cbits_arena[si].cap};
+        for (int k = 0; k < 2; ++k) {
+            if (!w[k] || w[k]->cap >= bytes[k]) continue;
+            if (int rc = w[k]->ensure(bytes[k])) return rc;
+            HIP_TRY(hipMemsetAsync(w[k]->p, 0, w[k]->cap, B.s));
+        }
+    }
+    return LM_OK;
+}
+
 // The tables of the bit-plane kernels (BitsBatch, TopBits), and the bit planes themselves where the front end left byte planes.
 static void pack_bit_planes(lm_detector* d, Batch& B) {
     B.fb_rest = B.fb;
@@ -389,6 +419,10 @@ static void pack_bit_planes(lm_detector* d, Batch& B) {
             B.fb.f[b].todo = B.fb_rest.f[b].todo = d->d_todo.p + (size_t)d->buf_cand_cap * si;
             B.fb_rest.f[b].tiles = d->d_tiles.p + (size_t)B.tile_cap * si;   // non-null: "only the candidates marked todo"; no tile was planned
         }
+        if (B.wide) {
+            for (int b = 0; b < B.nb; ++b) B.wb.set1[b] = d->wbits_arena[B.slot(b)].p;
+            for (int l = 0; l + 1 < d->geom.levels; ++l) launch_pack_wide(B.bb, B.wb, B.nb, d->geom.lv[l], B.s);
+        } else
         if (!B.direct_low)
             for (int l = 0; l + 1 < d->geom.levels; ++l) launch_pack_bits(B.bb, B.nb, d->geom.lv[l], B.s);
     }
@@ -400,6 +434,10 @@ static void pack_bit_planes(lm_detector* d, Batch& B) {
             else d->cbits_clean[si] = false;
         }
         if (B.top_ored && !d->fe_keep_top) B.bb.top_clear_units = (d->cbits_npairs * 8u + 15u) / 16u;
+        if (B.cwide) {
+            for (int b = 0; b < B.nb; ++b) B.wt.set1[b] = d->wcbits_arena[B.slot(b)].p;
+            launch_pack_top_wide(B.tb, B.wt, B.nb, d->cbits_byte0, d->cbits_npairs, B.s);
+        } else
         if (!B.direct_top) launch_pack_top(B.tb, B.nb, d->cbits_byte0, d->cbits_npairs, B.s);
     }
 }
@@ -426,7 +464,8 @@ static int record_front_end(lm_detector* d, const Batch& B) {
 static int enqueue_coarse(lm_detector* d, const Batch& B) {
     // the counters are zero on entry (reset by the slots' previous k_dedupe)
     { LM_CLOCK("launch_coarse");
-    if (B.cbits) launch_coarse_bits(B.fb, B.tb, d->geom, B.bank, B.num_work, B.threshold, d->buf_cand_cap, d->cbits_byte0, d->cbits_max_nf, d->resp_low_weight, B.s);
+    if (B.cwide) launch_coarse_wide(B.fb, B.tb, B.wt, d->geom, B.bank, B.num_work, B.threshold, d->buf_cand_cap, d->cbits_byte0, d->cbits_max_nf, B.s);
+    else if (B.cbits) launch_coarse_bits(B.fb, B.tb, d->geom, B.bank, B.num_work, B.threshold, d->buf_cand_cap, d->cbits_byte0, d->cbits_max_nf, d->resp_low_weight, B.s);
     else launch_coarse(B.fb, d->geom, B.bank, B.num_work, B.threshold, d->buf_cand_cap, B.tile_cap, B.s);
     }
     HIP_TRY(hipEventRecord(d->slot[B.first].ev[3], B.s));
@@ -440,7 +479,8 @@ static int enqueue_match(lm_detector* d, const Batch& B) {
     const uint32_t dedupe_slots = (uint32_t)dedupe_table_slots(d->buf_cand_cap);
     if (B.bits) {
         { LM_CLOCK("launch_local_bits");
-        launch_local_bits(B.fb, B.bb, d->geom, B.bank, d->buf_cand_cap, B.threshold, B.cap, dedupe_slots, bits_grid(d, B.nb), d->bits_max_nf, d->resp_low_weight, B.s); }
+        if (B.wide) launch_local_wide(B.fb, B.bb, B.wb, d->geom, B.bank, d->buf_cand_cap, B.threshold, B.cap, dedupe_slots, bits_grid(d, B.nb), d->bits_max_nf, B.s);
+        else launch_local_bits(B.fb, B.bb, d->geom, B.bank, d->buf_cand_cap, B.threshold, B.cap, dedupe_slots, bits_grid(d, B.nb), d->bits_max_nf, d->resp_low_weight, B.s); }
         if (B.bb.top_clear_units)     // the pair streams this launch zeroes again are clean for their slots' next frames
             for (int b = 0; b < B.nb; ++b)
                 if (B.bb.top_clear[b]) d->cbits_clean[B.slot(b)] = true;
@@ -495,6 +535,7 @@ int lm_launch_pending(lm_detector* d) {
         LM_CLOCK("step waits+ev0");
         HIP_TRY(hipSetDevice(d->device));
         if ((rc = batch_begin(d, B)) || (rc = order_batch(d, B)) || (rc = choose_bit_writers(d, B))) return rc;
+        if ((B.wide || B.cwide) && (rc = ensure_wide_arenas(d, B))) return rc;
     }
     { LM_CLOCK("step front end"); if ((rc = run_frontend_batch(d, B.first, B.nb, B.s, B.direct_low, B.direct_top))) return rc; }
     { LM_CLOCK("step bits tables+ev1"); pack_bit_planes(d, B); if ((rc = record_front_end(d, B))) return rc; }
@@ -896,13 +937,14 @@ extern "C" int lm_detector_submit_frame(lm_detector* d, const uint8_t* rgb, cons
 // 1 when the refinement of the current bank and frame geometry runs on bit planes (k_local_bits), 0 when on the byte strip planes
 // (k_local: single-level pyramids have no refinement; LM_BITPLANES=0; lm_detector_set_paths).  Valid after a match.
 extern "C" int lm_detector_refines_on_bit_planes(const lm_detector* d) {
-    return d && !d->bank_dirty && bits_active(d, 1) ? 1 : 0;
+    return d && !d->bank_dirty && (bits_active(d, 1) || wide_active(d, 1)) ? 1 : 0;   // (k_local_bits or k_local_wide)
 }
 
 extern "C" int lm_detector_get_paths(const lm_detector* d, int* refine, int* coarse) {
     if (!d || !refine || !coarse) return lm_set_error(LM_ERR_INVALID, "null argument");
     if (d->bank_dirty) return lm_set_error(LM_ERR_INVALID, "no match yet: the paths follow from the bank and the frame geometry");
     const bool bits = bits_active(d, 1);
+    if (wide_active(d, 1)) { *refine = 3; *coarse = cwide_active(d, 1) ? 2 : 1; return LM_OK; }
     *refine = bits ? 0 : (d->geom.levels >= 2 && tiles_wanted(d) && tile_plan_possible(d->geom) ? 1 : 2);
     *coarse = cbits_active(d, 1) ? 0 : 1;
     return LM_OK;

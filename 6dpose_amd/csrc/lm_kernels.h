@@ -1,5 +1,5 @@
 // Internal interface between the host orchestration (detector*.cpp, pose_refine.cpp) and the HIP
-// kernels (frontend.hip, match_bytes.hip, match_bits.hip, icp*.hip).  gfx950 only.  Not part of the public C ABI.
+// kernels (frontend.hip, match_bytes.hip, match_bits.hip, match_wide.hip, icp*.hip).  gfx950 only.  Not part of the public C ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -165,6 +165,20 @@ struct TopBits { const uint8_t* lm[kMaxBatch]; uint8_t* bits[kMaxBatch]; };
 void launch_pack_top(const TopBits& B, int nb, uint32_t byte0, uint32_t npairs, hipStream_t s);
 // candidates only (no tiles); max_features = the largest nf of the bank's top-level entries
 void launch_coarse_bits(const FrameBatch& fb, const TopBits& B, const FrameGeom& g, const BankDev& bank, int num_work, float threshold, uint32_t cap, uint32_t byte0, int max_features, int low_weight, hipStream_t s);
+// Wide bit planes (match_wide.hip): tables with three or four distinct non-zero values.  A response v = 0..4 is three
+// binary digits.  Set 0 lives in the arenas above with their layout: bit 2c of a strip record = v & 1 of cell c, bit 2c + 1 = (v == 4); the
+// pair stream's low dword = v & 1, its high dword = (v == 4).  Set 1 — a second arena of the same layout and size per frame — holds (v >> 1) & 1
+// where set 0 holds v & 1 and zero where set 0 holds (v == 4).  The sum is c0 + 2 c1 + 4 c2: three bit-sliced counters.  (The second arenas
+// travel in a struct of their own: the argument blocks of k_local_bits, k_coarse_bits and k_pack_* stay what they are.)
+struct WidePlanes { uint8_t* set1[kMaxBatch]; };
+constexpr int kWideMaxFeatures = 16383;       // features per template entry the wide kernels' counters hold (9 bits up to kBitsSmallMax, 14 beyond)
+void launch_pack_wide(const BitsBatch& B, const WidePlanes& P, int nb, const LevelGeom& lv, hipStream_t s);           // bytes 0..4 -> both sets of strip records
+void launch_pack_top_wide(const TopBits& B, const WidePlanes& P, int nb, uint32_t byte0, uint32_t npairs, hipStream_t s);   // ... of the pair stream
+// as launch_local_bits / launch_coarse_bits (todo, candidates only, max_features), for any response table
+void launch_local_wide(const FrameBatch& fb, const BitsBatch& B, const WidePlanes& P, const FrameGeom& g, const BankDev& bank, uint32_t cand_cap, float threshold,
+                       uint32_t cap, uint32_t dedupe_cap_slots, int grid_blocks, int max_features, hipStream_t s);
+void launch_coarse_wide(const FrameBatch& fb, const TopBits& B, const WidePlanes& P, const FrameGeom& g, const BankDev& bank, int num_work, float threshold, uint32_t cap,
+                        uint32_t byte0, int max_features, hipStream_t s);
 bool tile_plan_possible(const FrameGeom& g);
 size_t coarse_plan_lds_bytes(int Wd, int Hd);
 // Per frame of the batch: counters[0] = number of candidates produced (may exceed cap: nothing is written past cap); with tiles

@@ -1,111 +1,74 @@
-// Similarity kernels of Detector::matchClass on gfx950, on bit planes (the default): the bit-sliced
-// carry-save adders and weighted_sum, k_pack_bits / k_local_bits (strip records of the levels below the top, reference
-// similarityLocal LL.cpp:1366-1428, 1855-1938), k_pack_top / k_coarse_bits (pair stream of the top level, LL.cpp:1284-1354,
-// 1835-1852), their launchers and the LM_LAUNCH_* macros that pick the instantiation.  The byte kernels are in match_bytes.hip,
-// what both use in match_device.h; data layout and bank: match_bytes.hip.
+// Similarity kernels of Detector::matchClass on gfx950 for response tables of three or four distinct non-zero values (4 3 2 1 0, 4 2 1 0 0,
+// 4 3 1 0 0, ...), selected with lm_detector_set_paths(3, 2): the schemes of match_bits.hip on TWO sets of bit planes.
+// A response v = 0..4 is three binary digits: set 0 keeps the two-plane layout with bit 2c = v & 1 and bit 2c + 1 = (v == 4), set 1 — a second
+// arena of the same layout and size — holds (v >> 1) & 1 at bit 2c and nothing at bit 2c + 1, so the same v_alignbit windows cut both.  The sum of
+// a position is c0 + 2 c1 + 4 c2 with c_i = the number of features whose digit i is set there: three bit-sliced counters instead of two.
+// k_pack_wide / k_local_wide: strip records of the levels below the top; k_pack_top_wide / k_coarse_wide: pair stream of the top level.  The
+// front end writes the byte planes for such tables and these kernels pack them (the front end's own bit-plane writers know two planes).
 #include "match_device.h"
 
 namespace lm {
 
-// ---- Bit planes: the default encoding of the response memories for both matching kernels --------------------------
-// A response is 0, 1 or 4, so a position's sum is n1 + 4 n4 with n1 / n4 = the number of features whose response there is 1 / 4: two bits
-// per cell carry what the byte planes do, and the sums can be kept BIT-SLICED (one dword = 32 positions of one counter bit), features
-// entering through carry-save adders; integers are formed once per candidate / only for the hits.
-//
-// Levels below the top ("strip records", read by k_local_bits): the strip arena at half the offsets — per plane row and 16-column strip s an
-// 8-byte record holding cells [16 s, 16 s + 32) of that row with TWO BITS PER CELL, bit 2c = "the response of cell 16 s + c is 1", bit
-// 2c + 1 = "it is 4".  Strips are 32 cells wide at a stride of 16, so any 16-cell window of a row lies inside ONE record and comes out of it
-// with ONE funnel shift, v_alignbit(hi, lo, 2 (column & 15)): a dword of 16 positions x {is-1, is-4}.  (Round 3 kept the two planes in
-// separate dwords: 4 shifts + 2 ands + 2 or per lane and feature to cut the windows out, and every lane redid the address arithmetic of
-// every feature — 30 VALU instructions per lane and feature at 0.92 of the issue slots)
-// The top level ("pair stream", read by k_coarse_bits): the flat linear memories [label][phase][position] as one pair {is-1 dword, is-4
-// dword} per 32 consecutive arena bytes, so the reference's reads that run from one plane into the next stay what they are.
-// (the carry-save adders and the Harley-Seal counters: match_device.h — match_wide.hip counts three planes with them)
-// The bit-sliced sum S = a n_a + 4 n_4 of two bit-sliced counts (kA = a: the weight of the low plane, lm_kernels.h resp_pack; 1 for the
-// default table 4 1 0 0 0, whose instantiation is the code it always was).  n_a + n_4 <= features, so kN + 3 bits hold any of them.
-template <int kA, int kN>
-static __device__ __forceinline__ void weighted_sum(uint32_t (&S)[kN + 3], const uint32_t (&na)[kN], const uint32_t (&n4)[kN]) {
+// S = n1 + 2 n2 + 4 n4, bit-sliced: each count <= features < 2^kN, so n1 + 2 n2 fits kN + 2 bits and S <= 4 features fits kN + 3
+template <int kN>
+static __device__ __forceinline__ void weighted_sum_wide(uint32_t (&S)[kN + 3], const uint32_t (&n1)[kN], const uint32_t (&n2)[kN], const uint32_t (&n4)[kN]) {
     constexpr int kS = kN + 3;
+    uint32_t t[kN + 2];
     uint32_t carry = 0;
-    if (kA == 1) {
-        S[0] = na[0]; S[1] = na[1];
+    t[0] = n1[0];
 #pragma unroll
-        for (int k = 2; k < kS; ++k) csa(S[k], carry, k < kN ? na[k] : 0u, k - 2 < kN ? n4[k - 2] : 0u, carry);
-    } else if (kA == 2) {
-        S[0] = 0u; S[1] = na[0];
+    for (int k = 1; k < kN + 2; ++k) csa(t[k], carry, k < kN ? n1[k] : 0u, k - 1 < kN ? n2[k - 1] : 0u, carry);
+    carry = 0;
+    S[0] = t[0]; S[1] = t[1];
 #pragma unroll
-        for (int k = 2; k < kS; ++k) csa(S[k], carry, k - 1 < kN ? na[k - 1] : 0u, k - 2 < kN ? n4[k - 2] : 0u, carry);
-    } else {                                                        // 3 n_a = n_a + 2 n_a first (kN + 2 bits), then + 4 n_4
-        uint32_t t[kN + 2];
-        t[0] = na[0];
-#pragma unroll
-        for (int k = 1; k < kN + 2; ++k) csa(t[k], carry, k < kN ? na[k] : 0u, k - 1 < kN ? na[k - 1] : 0u, carry);
-        carry = 0;
-        S[0] = t[0]; S[1] = t[1];
-#pragma unroll
-        for (int k = 2; k < kS; ++k) csa(S[k], carry, k < kN + 2 ? t[k] : 0u, k - 2 < kN ? n4[k - 2] : 0u, carry);
-    }
+    for (int k = 2; k < kS; ++k) csa(S[k], carry, k < kN + 2 ? t[k] : 0u, k - 2 < kN ? n4[k - 2] : 0u, carry);
 }
 
-// 4 response bytes -> 8 bits, cell k at bits 2k (is 1 = bit 0 of the byte) and 2k + 1 (is 4 = bit 2 of the byte); the multiply gathers the
-// four 2-bit fields into the top byte (partial products land on distinct bits: no carries)
-// (any table of two planes: the bytes are 0, a or 4 with a = 1, 2 or 3 — "is a" = bit 0 or bit 1 of the byte)
-static __device__ __forceinline__ uint32_t pack4(uint32_t d) {
-    const uint32_t t = ((d | (d >> 1)) & 0x01010101u) | ((d >> 1) & 0x02020202u);
-    return (t * 0x01041040u) >> 24;
-}
-static __device__ __forceinline__ uint32_t pack16(const uint4& v) { return pack4(v.x) | (pack4(v.y) << 8) | (pack4(v.z) << 16) | (pack4(v.w) << 24); }
+// 4 response bytes -> 8 bits, cell k at bits 2k and 2k + 1 (the multiply of match_bits.hip's pack4: partial products land on distinct bits).
+// Set 0: bit 0 of the byte (v & 1) and bit 2 (v == 4); set 1: bit 1 of the byte, nothing above it.
+static __device__ __forceinline__ uint32_t wide4_set0(uint32_t d) { return ((((d & 0x01010101u) | ((d >> 1) & 0x02020202u)) * 0x01041040u) >> 24); }
+static __device__ __forceinline__ uint32_t wide4_set1(uint32_t d) { return ((((d >> 1) & 0x01010101u) * 0x01041040u) >> 24); }
+static __device__ __forceinline__ uint32_t wide16_set0(const uint4& v) { return wide4_set0(v.x) | (wide4_set0(v.y) << 8) | (wide4_set0(v.z) << 16) | (wide4_set0(v.w) << 24); }
+static __device__ __forceinline__ uint32_t wide16_set1(const uint4& v) { return wide4_set1(v.x) | (wide4_set1(v.y) << 8) | (wide4_set1(v.z) << 16) | (wide4_set1(v.w) << 24); }
 
-// Strip records from the strip bytes (the front end writes the records itself when nothing reads the bytes: frontend.hip, bits_rows_body;
-// this kernel serves the banks and geometries that keep the byte planes — a fallback launch of k_local may follow — and the tests of both).
+// Both sets of strip records from the strip bytes (k_pack_bits's indexing: record = ((plane * NS + s) * Hd + row), 32 cells from two 16-byte rows)
 __global__ void __launch_bounds__(256)
-k_pack_bits(BitsBatch B, uint32_t sm_off0, uint32_t records, int NS, int Hd) {
-    const uint32_t i = blockIdx.x * 256u + threadIdx.x;             // record = ((plane * NS + s) * Hd + row)
+k_pack_wide(BitsBatch B, WidePlanes P, uint32_t sm_off0, uint32_t records, int NS, int Hd) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= records) return;
     const uint32_t q = i / (uint32_t)Hd, s = q % (uint32_t)NS;
     const uint8_t* src = B.strips[blockIdx.y] + sm_off0 + (size_t)i * 16;
     const uint4 a = *reinterpret_cast<const uint4*>(src);
     uint4 b = make_uint4(0, 0, 0, 0);
     if (s + 1 < (uint32_t)NS) b = *reinterpret_cast<const uint4*>(src + (size_t)Hd * 16);      // the next strip of this row
-    uint2 r;
-    r.x = pack16(a);
-    r.y = pack16(b);
-    *reinterpret_cast<uint2*>(B.bits[blockIdx.y] + (sm_off0 >> 1) + (size_t)i * 8) = r;
+    const size_t at = (sm_off0 >> 1) + (size_t)i * 8;
+    *reinterpret_cast<uint2*>(B.bits[blockIdx.y] + at) = make_uint2(wide16_set0(a), wide16_set0(b));
+    *reinterpret_cast<uint2*>(P.set1[blockIdx.y] + at) = make_uint2(wide16_set1(a), wide16_set1(b));
 }
 
-// Refinement on strip records (LL.cpp:1855-1938, similarityLocal :1366-1428).  8 lanes per candidate — lane j owns window rows 2j and 2j + 1,
-// ONE 16-byte load = their two records —, 8 candidates per wave, one feature per candidate and load instruction: a wave load serves 8
-// (candidate, feature) pairs.  Per 16 features a lane fetches two feature words and forms, ONCE for its group, their record offsets (window
-// origin, strip carry) and shift amounts; the group's lanes pick them up with two ds_bpermute per feature and add only their own row term.
-// Per lane and feature: 1 add, 2 v_alignbit, 5 adder operations (two dwords x 2.5).  Counters of kN = 4 + kHi bits: kHi = 5 serves entries
-// of up to 511 features, kHi = 10 up to 16383 (the reference allows 8191 per modality, LL.cpp:1291, 1816).
-// What bounds it (round 5, profiles/r05_local_sharing/README.txt): the number of wave loads — one takes 20-23 CU cycles whatever the lanes or addresses —, and
-// what keeps its L2 traffic down is that the 8 candidates of a wave are CONSECUTIVE candidates of one template (x-neighbours: ~5 distinct lines per wave load
-// instead of 23).  Three schemes that share loads between neighbouring candidates by regrouping them (vertical runs, interleaved pairs, same-lane pairs) were
-// built, bit-exact, and ran no faster: fewer wave loads, more L2 requests.  Hence: candidates in slot order, a grid of the resident workgroups.
-// All pyramid levels below the top are walked here (LL.cpp:1855: level by level, dropping a candidate as soon as it falls below the
-// threshold); a candidate whose windows leave their planes at some level (oversized template, features outside the frame) is marked in
-// `todo` and left, from the top, to k_local's per-candidate path.
-template <int kHi, int kWaves, int kA>
+// Refinement on two sets of strip records: k_local_bits's scheme — 8 lanes per candidate, lane j owns window rows 2j and 2j + 1, 8 consecutive
+// candidates of one template per wave, the record offsets and shifts of 16 features formed once per group and handed round with ds_bpermute —
+// with TWO 16-byte loads per lane and feature (the same offset into either arena) and THREE counters: cA / cB count set 0 of rows 2j / 2j + 1
+// (even bits: digit 0, odd bits: v == 4), cC counts digit 1 of both rows at once — set 1 has nothing in its odd bits, so row 2j + 1's window
+// goes there (one v_lshl_or_b32).  Per lane and feature: 1 add, 4 v_alignbit, 1 shift-or, 7.5 adder operations.  All levels below the top are
+// walked here; candidates whose windows leave their planes are marked in `todo` for k_local's per-candidate path, exactly as k_local_bits does.
+template <int kHi, int kWaves, int kInFlight>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kWaves, kWaves)))
-k_local_bits(FrameBatch fb, BitsBatch B, FrameGeom g, const TemplEntry* __restrict__ entries, const uint32_t* __restrict__ feat_word,
+k_local_wide(FrameBatch fb, BitsBatch B, WidePlanes P, FrameGeom g, const TemplEntry* __restrict__ entries, const uint32_t* __restrict__ feat_word,
              const int32_t* __restrict__ work_pyramids, uint32_t cand_cap, float threshold, uint32_t cap, uint32_t dedupe_cap_slots) {
-    constexpr int kN = 4 + kHi;                                     // counter bits per plane
-    constexpr int kS = kN + 3;                                      // bits of n1 + 4 n4
+    constexpr int kN = 4 + kHi;                                     // counter bits per digit
+    constexpr int kS = kN + 3;                                      // bits of n1 + 2 n2 + 4 n4
     __shared__ unsigned long long s_acc[kMaxBatch][2];
     __shared__ uint32_t s_cnt[kMaxBatch];
     const int lane = threadIdx.x & 63, grp = lane >> 3, j = lane & 7;
     const int nb = fb.nb;
-    // Frame -> XCD affinity as in k_local (an XCD's L2 holds ONE frame's planes), for ANY batch size up to 8: frame f is served by the workgroups of
-    // the XCDs x with x % nb == f — 8 / nb of them each when nb divides 8, else some frames get one XCD more than others.  (Round 3 fell back to
-    // dealing the items of all frames to all workgroups unless nb divided 8: a 5-frame launch — the first and last launches of a short stream —
-    // then cost 35 us per frame against 26 in an 8-frame launch.)
+    // frame -> XCD affinity as in k_local_bits
     int f_lo = 0, f_hi = nb;
     uint32_t w_first = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), w_step = gridDim.x * (blockDim.x >> 6);
     if (nb > 1 && nb <= 8 && (gridDim.x & 7) == 0) {
         const int xcd = (int)(blockIdx.x & 7);
         f_lo = xcd % nb; f_hi = f_lo + 1;
-        const uint32_t mine = (uint32_t)((7 - f_lo) / nb + 1);      // XCDs serving this frame: f_lo, f_lo + nb, ...
+        const uint32_t mine = (uint32_t)((7 - f_lo) / nb + 1);
         const uint32_t wpb = blockDim.x >> 6;
         w_first = ((blockIdx.x >> 3) * mine + (uint32_t)(xcd / nb)) * wpb + (threadIdx.x >> 6);
         w_step = (gridDim.x >> 3) * mine * wpb;
@@ -122,16 +85,11 @@ k_local_bits(FrameBatch fb, BitsBatch B, FrameGeom g, const TemplEntry* __restri
         const uint32_t tsize = dedupe_slots_for(s_cnt[f], dedupe_cap_slots);
         for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < tsize; i += gridDim.x * blockDim.x) table[i] = ~0ull;
     }
-    // The pair stream k_coarse_bits has just read is zeroed for the slot's next frame: the front end ORs it together (frontend.hip, top_bits_body)
-    if (B.top_clear_units)
-        for (int f = 0; f < nb; ++f)
-            for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < B.top_clear_units; i += gridDim.x * blockDim.x)
-                reinterpret_cast<uint4*>(B.top_clear[f])[i] = make_uint4(0u, 0u, 0u, 0u);
     const int src0 = (lane & ~7) << 2;                              // ds_bpermute address of the group's first lane
     const uint32_t rowoff = 16u * (uint32_t)j;                      // records of rows 2j, 2j + 1 behind the window's first row
     for (int fr = f_lo; fr < f_hi; ++fr) {
         const FrameSlot& F = fb.f[fr];
-        const BufRsrc bits = make_rsrc(B.bits[fr]);
+        const BufRsrc bits0 = make_rsrc(B.bits[fr]), bits1 = make_rsrc(P.set1[fr]);
         const uint32_t nc = s_cnt[fr], ngroups = (nc + 7u) >> 3;
         for (uint32_t gi = w_first; gi < ngroups; gi += w_step) {
             const uint32_t ci = gi * 8u + (uint32_t)grp;
@@ -149,7 +107,7 @@ k_local_bits(FrameBatch fb, BitsBatch B, FrameGeom g, const TemplEntry* __restri
                 const int T = lv.T, W = lv.W, H = lv.H, Wd = lv.Wd, Hd = lv.Hd;
                 const int border = 8 * T, offset = T / 2 + (T % 2 - 1);
                 const uint32_t HS8 = (uint32_t)Hd * 8u;
-                const uint32_t zero_off = (lv.sm_off[1] + 8u * (uint32_t)(T * T) * ((uint32_t)lv.NS * (uint32_t)Hd * 16u)) >> 1;   // the level's all-zero plane
+                const uint32_t zero_off = (lv.sm_off[1] + 8u * (uint32_t)(T * T) * ((uint32_t)lv.NS * (uint32_t)Hd * 16u)) >> 1;   // the level's all-zero plane (in either arena)
                 const TemplEntry e = entries[(size_t)pyr * g.levels + l];
                 // LL.cpp:1871-1880 (the clamp) and 1380-1381 (window origin), exactly as k_local
                 const int max_x = W - e.width - border, max_y = H - e.height - border;
@@ -171,40 +129,46 @@ k_local_bits(FrameBatch fb, BitsBatch B, FrameGeom g, const TemplEntry* __restri
                 const uint32_t Kbase = (uint32_t)(((gx >> 4) * Hd + gy) * 8);
                 const uint32_t gxl = (uint32_t)(gx & 15);
                 const uint32_t* fw = feat_word + e.feat_start;
-                uint32_t cA[kN], cB[kN];                            // bit-sliced counters of rows 2j / 2j + 1: even bits count the 1s, odd bits the 4s
+                uint32_t cA[kN], cB[kN], cC[kN];
 #pragma unroll
-                for (int k = 0; k < kN; ++k) { cA[k] = 0; cB[k] = 0; }
+                for (int k = 0; k < kN; ++k) { cA[k] = 0; cB[k] = 0; cC[k] = 0; }
                 // lane j fetches the words of features f0 + 2j, f0 + 2j + 1 (entries start at multiples of 8 words, f0 is a multiple of 16)
                 auto fetch = [&](int f0) -> uint2 {
                     uint2 w = make_uint2(0u, 0u);
                     if (f0 + 2 * j < nfp) w = *reinterpret_cast<const uint2*>(fw + f0 + 2 * j);
                     return w;
                 };
-                // a feature word (base0 | column class, lm_kernels.h) -> offset of its first record in the bit arena, 2 x the window's cell inside it
+                // a feature word (base0 | column class, lm_kernels.h) -> offset of its first record in either bit arena, 2 x the window's cell inside it
                 auto prep = [&](uint32_t w, bool on, uint32_t& off, uint32_t& s2) {
                     s2 = ((w & 15u) + gxl) << 1;
                     const uint32_t o = ((w & ~15u) >> 1) + Kbase + ((s2 >> 5) ? HS8 : 0u);
                     off = on ? o : zero_off;                        // beyond this candidate's features (or no candidate): the zero plane
                 };
                 uint32_t offx = 0, offy = 0, sx = 0, sy = 0;
-                auto batch = [&](int half, uint32_t& eA, uint32_t& eB) {           // features 8 half .. 8 half + 7 of the current 16
-                    uint4 v[8];
-                    uint32_t sh[8];
+                auto batch = [&](int half, uint32_t& eA, uint32_t& eB, uint32_t& eC) {   // features 8 half .. 8 half + 7 of the current 16
+                    uint32_t xa[8], xb[8], xc[8];
 #pragma unroll
-                    for (int u = 0; u < 8; ++u) {
-                        const int src = src0 + 4 * (4 * half + (u >> 1));          // the lane that fetched feature 8 half + u
-                        const uint32_t o = (uint32_t)__builtin_amdgcn_ds_bpermute(src, (int)((u & 1) ? offy : offx));
-                        sh[u] = (uint32_t)__builtin_amdgcn_ds_bpermute(src, (int)((u & 1) ? sy : sx));
-                        v[u] = ld_buf16(bits, o + rowoff, 0u);      // rows 2j, 2j + 1: 32 cells x 2 bits each
-                    }
-                    uint32_t xa[8], xb[8];
+                    for (int q = 0; q < 8; q += kInFlight) {        // kInFlight features x 2 sets = the loads a lane keeps in flight
+                        uint4 v[kInFlight], w[kInFlight];
+                        uint32_t sh[kInFlight];
 #pragma unroll
-                    for (int u = 0; u < 8; ++u) {
-                        xa[u] = __builtin_amdgcn_alignbit(v[u].y, v[u].x, sh[u]);      // 16 window cells of row 2j: bits 2c (is 1), 2c + 1 (is 4)
-                        xb[u] = __builtin_amdgcn_alignbit(v[u].w, v[u].z, sh[u]);      // ... of row 2j + 1
+                        for (int u = 0; u < kInFlight; ++u) {
+                            const int src = src0 + 4 * (4 * half + ((q + u) >> 1));    // the lane that fetched feature 8 half + q + u
+                            const uint32_t o = (uint32_t)__builtin_amdgcn_ds_bpermute(src, (int)(((q + u) & 1) ? offy : offx));
+                            sh[u] = (uint32_t)__builtin_amdgcn_ds_bpermute(src, (int)(((q + u) & 1) ? sy : sx));
+                            v[u] = ld_buf16(bits0, o + rowoff, 0u); // rows 2j, 2j + 1 of set 0: 32 cells x {v & 1, v == 4} each
+                            w[u] = ld_buf16(bits1, o + rowoff, 0u); // ... of set 1: 32 cells x {(v >> 1) & 1, -}
+                        }
+#pragma unroll
+                        for (int u = 0; u < kInFlight; ++u) {
+                            xa[q + u] = __builtin_amdgcn_alignbit(v[u].y, v[u].x, sh[u]);      // 16 window cells of row 2j: bits 2c (digit 0), 2c + 1 (is 4)
+                            xb[q + u] = __builtin_amdgcn_alignbit(v[u].w, v[u].z, sh[u]);      // ... of row 2j + 1
+                            xc[q + u] = __builtin_amdgcn_alignbit(w[u].y, w[u].x, sh[u]) | (__builtin_amdgcn_alignbit(w[u].w, w[u].z, sh[u]) << 1);   // digit 1: bit 2c row 2j, bit 2c + 1 row 2j + 1
+                        }
                     }
                     eA = add8(xa, cA[0], cA[1], cA[2]);
                     eB = add8(xb, cB[0], cB[1], cB[2]);
+                    eC = add8(xc, cC[0], cC[1], cC[2]);
                 };
                 uint2 wn = fetch(0);
                 for (int f0 = 0; f0 < nmax; f0 += 16) {
@@ -213,20 +177,22 @@ k_local_bits(FrameBatch fb, BitsBatch B, FrameGeom g, const TemplEntry* __restri
                     wn = fetch(f0 + 16);                            // the next 16 words while these are worked on
                     prep(w.x, on, offx, sx);
                     prep(w.y, on, offy, sy);
-                    uint32_t e1A, e1B;
-                    batch(0, e1A, e1B);
+                    uint32_t e1A, e1B, e1C;
+                    batch(0, e1A, e1B, e1C);
                     if (f0 + 8 < nmax) {                            // wave-uniform
-                        uint32_t e2A, e2B;
-                        batch(1, e2A, e2B);
+                        uint32_t e2A, e2B, e2C;
+                        batch(1, e2A, e2B, e2C);
                         add_eights2<kN>(cA, e1A, e2A);
                         add_eights2<kN>(cB, e1B, e2B);
+                        add_eights2<kN>(cC, e1C, e2C);
                     } else {
                         add_eights1<kN>(cA, e1A);
                         add_eights1<kN>(cB, e1B);
+                        add_eights1<kN>(cC, e1C);
                     }
                 }
                 // Once per candidate and level: the two rows of the lane side by side — bit 2c = row 2j, bit 2c + 1 = row 2j + 1 of window
-                // column c —, S = n1 + 4 n4 bit-sliced, the lane's maximum by a descent from the top bit, its FIRST position in raster order.
+                // column c (cC is kept that way) —, S bit-sliced, the lane's maximum by a descent from the top bit, its FIRST position in raster order.
                 uint32_t S[kS];
                 {
                     uint32_t n1[kN], n4[kN];
@@ -235,7 +201,7 @@ k_local_bits(FrameBatch fb, BitsBatch B, FrameGeom g, const TemplEntry* __restri
                         n1[k] = (cA[k] & 0x55555555u) | ((cB[k] << 1) & 0xAAAAAAAAu);
                         n4[k] = ((cA[k] >> 1) & 0x55555555u) | (cB[k] & 0xAAAAAAAAu);
                     }
-                    weighted_sum<kA, kN>(S, n1, n4);
+                    weighted_sum_wide<kN>(S, n1, cC, n4);
                 }
                 uint32_t mask = 0xFFFFFFFFu, val = 0;
 #pragma unroll
@@ -290,45 +256,36 @@ k_local_bits(FrameBatch fb, BitsBatch B, FrameGeom g, const TemplEntry* __restri
     }
 }
 
-void launch_pack_bits(const BitsBatch& B, int nb, const LevelGeom& lv, hipStream_t s) {
+void launch_pack_wide(const BitsBatch& B, const WidePlanes& P, int nb, const LevelGeom& lv, hipStream_t s) {
     const uint32_t records = (uint32_t)(2 * 8 * lv.T * lv.T) * (uint32_t)lv.NS * (uint32_t)lv.Hd;
-    hipLaunchKernelGGL(k_pack_bits, dim3((records + 255) / 256, nb), dim3(256), 0, s, B, lv.sm_off[0], records, lv.NS, lv.Hd);
+    hipLaunchKernelGGL(k_pack_wide, dim3((records + 255) / 256, nb), dim3(256), 0, s, B, P, lv.sm_off[0], records, lv.NS, lv.Hd);
 }
-void launch_local_bits(const FrameBatch& fb, const BitsBatch& B, const FrameGeom& g, const BankDev& bank, uint32_t cand_cap, float threshold,
-                       uint32_t cap, uint32_t dedupe_cap_slots, int grid_blocks, int max_features, int low_weight, hipStream_t s) {
-#define LM_LAUNCH_LOCAL_BITS(HI, A) \
-    hipLaunchKernelGGL((k_local_bits<HI, 4, A>), dim3(grid_blocks), dim3(256), 0, s, fb, B, g, bank.entries, bank.feat_word, bank.work, cand_cap, threshold, cap, dedupe_cap_slots)
-    const bool big = max_features > kBitsSmallMax;
-    if (low_weight == 2) { if (big) LM_LAUNCH_LOCAL_BITS(10, 2); else LM_LAUNCH_LOCAL_BITS(5, 2); }
-    else if (low_weight == 3) { if (big) LM_LAUNCH_LOCAL_BITS(10, 3); else LM_LAUNCH_LOCAL_BITS(5, 3); }
-    else { if (big) LM_LAUNCH_LOCAL_BITS(10, 1); else LM_LAUNCH_LOCAL_BITS(5, 1); }
-#undef LM_LAUNCH_LOCAL_BITS
+void launch_local_wide(const FrameBatch& fb, const BitsBatch& B, const WidePlanes& P, const FrameGeom& g, const BankDev& bank, uint32_t cand_cap, float threshold,
+                       uint32_t cap, uint32_t dedupe_cap_slots, int grid_blocks, int max_features, hipStream_t s) {
+#define LM_LAUNCH_LOCAL_WIDE(HI, WAVES, FLY) \
+    hipLaunchKernelGGL((k_local_wide<HI, WAVES, FLY>), dim3(grid_blocks), dim3(256), 0, s, fb, B, P, g, bank.entries, bank.feat_word, bank.work, cand_cap, threshold, cap, dedupe_cap_slots)
+    if (max_features > kBitsSmallMax) LM_LAUNCH_LOCAL_WIDE(10, 3, 4); else LM_LAUNCH_LOCAL_WIDE(5, 4, 2);   // 158 / 126 VGPRs, no spills (5, 4, 4 spills one)
+#undef LM_LAUNCH_LOCAL_WIDE
 }
 
-// ---- Coarse pass on the pair stream (LL.cpp:1284-1354 similarity + :1835-1852 scan).  A wave per template, a lane = 32 consecutive
-// positions of the template's map: a feature's load = two consecutive pairs per lane (16 bytes) at pair index (offset >> 5) + lane,
-// funnel-shifted by offset & 31 — the offset is wave-uniform, so both are scalar —, i.e. ONE wave load per feature and 2048 positions
-// (the byte kernel: one per 1008 positions and 16 bytes per position and lane).  Sums bit-sliced as in k_local_bits; the threshold test is
-// a bit-sliced comparison with the smallest raw sum that passes, so integers are formed only for the hits.  The workgroup's 4 templates
-// reserve their candidate slots with ONE atomic on the frame's counter (same-address atomics serialise in the L2: 2000 per frame cost
-// the byte kernel 16 us).  No tiles: the bit-plane refinement needs none.
+// ---- Coarse pass on two pair streams: k_coarse_bits's scheme — a wave per template, a lane = 32 consecutive positions, a feature's load =
+// two consecutive pairs per lane at a wave-uniform pair index, funnel-shifted by a wave-uniform amount — with one such load per set and
+// three counters.  The same bit-sliced threshold compare, the same hit test, the same ONE atomic per workgroup and pass for the candidate slots.
 __global__ void __launch_bounds__(256)
-k_pack_top(TopBits B, uint32_t byte0, uint32_t npairs) {
+k_pack_top_wide(TopBits B, WidePlanes P, uint32_t byte0, uint32_t npairs) {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= npairs) return;
     const uint8_t* src = B.lm[blockIdx.y] + byte0 + (size_t)i * 32;
     const uint4 a = *reinterpret_cast<const uint4*>(src), b = *reinterpret_cast<const uint4*>(src + 16);
     auto four = [](uint32_t d, int sh) -> uint32_t { return ((((d >> sh) & 0x01010101u) * 0x01020408u) >> 24) & 0xFu; };   // bit sh of 4 bytes -> 4 bits
     auto bits = [&](const uint4& v, int sh) -> uint32_t { return four(v.x, sh) | (four(v.y, sh) << 4) | (four(v.z, sh) << 8) | (four(v.w, sh) << 12); };
-    uint2 r;
-    r.x = bits(a, 0) | bits(a, 1) | ((bits(b, 0) | bits(b, 1)) << 16);   // the low plane's response a = 1, 2 or 3: bit 0 or bit 1 of the byte; response 4 = bit 2
-    r.y = bits(a, 2) | (bits(b, 2) << 16);
-    *reinterpret_cast<uint2*>(B.bits[blockIdx.y] + (size_t)i * 8) = r;
+    *reinterpret_cast<uint2*>(B.bits[blockIdx.y] + (size_t)i * 8) = make_uint2(bits(a, 0) | (bits(b, 0) << 16), bits(a, 2) | (bits(b, 2) << 16));   // v & 1, v == 4
+    *reinterpret_cast<uint2*>(P.set1[blockIdx.y] + (size_t)i * 8) = make_uint2(bits(a, 1) | (bits(b, 1) << 16), 0u);                             // (v >> 1) & 1, -
 }
 
-template <int kHi, int kWaves, int kA>
+template <int kHi, int kWaves, int kInFlight>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kWaves, kWaves)))
-k_coarse_bits(FrameBatch fb, TopBits B, LevelGeom lv, int level, int levels, const TemplEntry* __restrict__ entries, const int32_t* __restrict__ feat_off,
+k_coarse_wide(FrameBatch fb, TopBits B, WidePlanes P, LevelGeom lv, int level, int levels, const TemplEntry* __restrict__ entries, const int32_t* __restrict__ feat_off,
               const int32_t* __restrict__ work_pyramids, int num_work, float threshold, uint32_t cap, uint32_t byte0) {
     constexpr int kN = 4 + kHi, kS = kN + 3;
     __shared__ uint32_t s_tot[4];
@@ -357,47 +314,55 @@ k_coarse_bits(FrameBatch fb, TopBits B, LevelGeom lv, int level, int levels, con
     while (rmin > 0 && score_of(rmin, nf) > threshold) --rmin;
     while (rmin <= 4 * nf && !(score_of(rmin, nf) > threshold)) ++rmin;
     const bool zero_passes = score_of(0, nf) > threshold;
-    const BufRsrc bits = make_rsrc(B.bits[blockIdx.y]);
+    const BufRsrc bits0 = make_rsrc(B.bits[blockIdx.y]), bits1 = make_rsrc(P.set1[blockIdx.y]);
     for (int P0 = 0; P0 < npos; P0 += 2048) {                               // (the same number of passes for every wave of the workgroup)
         const int pos0 = P0 + 32 * lane;                                    // first position of this lane
-        uint32_t c1[kN], c4[kN];
+        uint32_t c1[kN], c2[kN], c4[kN];
 #pragma unroll
-        for (int k = 0; k < kN; ++k) { c1[k] = 0; c4[k] = 0; }
+        for (int k = 0; k < kN; ++k) { c1[k] = 0; c2[k] = 0; c4[k] = 0; }
         if (live && P0 < limit && nfp > 0 && pos0 < limit) {                // (lanes beyond the map sit the loads out)
-            auto batch = [&](int f, uint32_t& e1, uint32_t& e4) {
-                uint4 v[8];
-                uint32_t sh[8];
+            auto batch = [&](int f, uint32_t& e1, uint32_t& e2, uint32_t& e4) {
+                uint32_t x1[8], x2[8], x4[8];
 #pragma unroll
-                for (int u = 0; u < 8; ++u) {
-                    const uint32_t ob = (uint32_t)fo[f + u] - byte0 + (uint32_t)P0;      // wave-uniform -> SMEM / SALU
-                    sh[u] = ob & 31u;
-                    v[u] = ld_buf16(bits, (uint32_t)lane * 8u, (ob >> 5) * 8u);          // pairs q + lane and q + lane + 1
-                }
-                uint32_t x1[8], x4[8];
+                for (int q = 0; q < 8; q += kInFlight) {                                 // kInFlight features x 2 sets = the loads a lane keeps in flight
+                    uint4 v[kInFlight], w[kInFlight];
+                    uint32_t sh[kInFlight];
 #pragma unroll
-                for (int u = 0; u < 8; ++u) {
-                    x1[u] = __builtin_amdgcn_alignbit(v[u].z, v[u].x, sh[u]);            // bits [s, s + 32) of {is-1 of pair q + lane + 1 : pair q + lane}
-                    x4[u] = __builtin_amdgcn_alignbit(v[u].w, v[u].y, sh[u]);
+                    for (int u = 0; u < kInFlight; ++u) {
+                        const uint32_t ob = (uint32_t)fo[f + q + u] - byte0 + (uint32_t)P0;   // wave-uniform -> SMEM / SALU
+                        sh[u] = ob & 31u;
+                        v[u] = ld_buf16(bits0, (uint32_t)lane * 8u, (ob >> 5) * 8u);     // pairs p + lane and p + lane + 1 of set 0
+                        w[u] = ld_buf16(bits1, (uint32_t)lane * 8u, (ob >> 5) * 8u);     // ... of set 1
+                    }
+#pragma unroll
+                    for (int u = 0; u < kInFlight; ++u) {
+                        x1[q + u] = __builtin_amdgcn_alignbit(v[u].z, v[u].x, sh[u]);    // bits [s, s + 32) of {digit 0 of pair p + lane + 1 : pair p + lane}
+                        x4[q + u] = __builtin_amdgcn_alignbit(v[u].w, v[u].y, sh[u]);
+                        x2[q + u] = __builtin_amdgcn_alignbit(w[u].z, w[u].x, sh[u]);
+                    }
                 }
                 e1 = add8(x1, c1[0], c1[1], c1[2]);
+                e2 = add8(x2, c2[0], c2[1], c2[2]);
                 e4 = add8(x4, c4[0], c4[1], c4[2]);
             };
             for (int f = 0; f < nfp; f += 16) {
-                uint32_t a1, a4;
-                batch(f, a1, a4);
+                uint32_t a1, a2, a4;
+                batch(f, a1, a2, a4);
                 if (f + 8 < nfp) {
-                    uint32_t b1, b4;
-                    batch(f + 8, b1, b4);
+                    uint32_t b1, b2, b4;
+                    batch(f + 8, b1, b2, b4);
                     add_eights2<kN>(c1, a1, b1);
+                    add_eights2<kN>(c2, a2, b2);
                     add_eights2<kN>(c4, a4, b4);
                 } else {
                     add_eights1<kN>(c1, a1);
+                    add_eights1<kN>(c2, a2);
                     add_eights1<kN>(c4, a4);
                 }
             }
         }
         uint32_t S[kS];
-        weighted_sum<kA, kN>(S, c1, c4);
+        weighted_sum_wide<kN>(S, c1, c2, c4);
         uint32_t gt = 0, eq = 0xFFFFFFFFu;                                  // S >= rmin, bit-sliced
 #pragma unroll
         for (int k = kS - 1; k >= 0; --k) {
@@ -448,20 +413,18 @@ k_coarse_bits(FrameBatch fb, TopBits B, LevelGeom lv, int level, int levels, con
     }
 }
 
-void launch_pack_top(const TopBits& B, int nb, uint32_t byte0, uint32_t npairs, hipStream_t s) {
-    hipLaunchKernelGGL(k_pack_top, dim3((npairs + 255) / 256, nb), dim3(256), 0, s, B, byte0, npairs);
+void launch_pack_top_wide(const TopBits& B, const WidePlanes& P, int nb, uint32_t byte0, uint32_t npairs, hipStream_t s) {
+    hipLaunchKernelGGL(k_pack_top_wide, dim3((npairs + 255) / 256, nb), dim3(256), 0, s, B, P, byte0, npairs);
 }
-void launch_coarse_bits(const FrameBatch& fb, const TopBits& B, const FrameGeom& g, const BankDev& bank, int num_work, float threshold, uint32_t cap, uint32_t byte0, int max_features, int low_weight, hipStream_t s) {
+void launch_coarse_wide(const FrameBatch& fb, const TopBits& B, const WidePlanes& P, const FrameGeom& g, const BankDev& bank, int num_work, float threshold, uint32_t cap,
+                        uint32_t byte0, int max_features, hipStream_t s) {
     if (num_work <= 0 || fb.nb <= 0) return;
     const int level = g.levels - 1;
-#define LM_LAUNCH_COARSE_BITS(HI, WAVES, A) \
-    hipLaunchKernelGGL((k_coarse_bits<HI, WAVES, A>), dim3((num_work + 3) / 4, fb.nb), dim3(256), 0, s, fb, B, g.lv[level], level, g.levels, bank.entries, bank.feat_off, \
+#define LM_LAUNCH_COARSE_WIDE(HI, WAVES, FLY) \
+    hipLaunchKernelGGL((k_coarse_wide<HI, WAVES, FLY>), dim3((num_work + 3) / 4, fb.nb), dim3(256), 0, s, fb, B, P, g.lv[level], level, g.levels, bank.entries, bank.feat_off, \
                        bank.work, num_work, threshold, cap, byte0)
-    const bool big = max_features > kBitsSmallMax;
-    if (low_weight == 2) { if (big) LM_LAUNCH_COARSE_BITS(10, 5, 2); else LM_LAUNCH_COARSE_BITS(5, 6, 2); }
-    else if (low_weight == 3) { if (big) LM_LAUNCH_COARSE_BITS(10, 5, 3); else LM_LAUNCH_COARSE_BITS(5, 6, 3); }
-    else { if (big) LM_LAUNCH_COARSE_BITS(10, 5, 1); else LM_LAUNCH_COARSE_BITS(5, 6, 1); }
-#undef LM_LAUNCH_COARSE_BITS
+    if (max_features > kBitsSmallMax) LM_LAUNCH_COARSE_WIDE(10, 4, 2); else LM_LAUNCH_COARSE_WIDE(5, 5, 2);   // 109 / 89 VGPRs
+#undef LM_LAUNCH_COARSE_WIDE
 }
 
 }  // namespace lm

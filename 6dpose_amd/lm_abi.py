@@ -158,6 +158,7 @@ PROTOTYPES = {
     "lm_detector_set_response_table": (I, [P, PU8]),
     "lm_detector_get_response_table": (I, [P, PU8]),
     "lm_detector_bit_arena_bytes": (I, [P, ctypes.POINTER(U64), ctypes.POINTER(U64)]),
+    "lm_detector_wide_arena_bytes": (I, [P, ctypes.POINTER(U64), ctypes.POINTER(U64)]),
     "lm_detector_train_stats": (I, [P, ctypes.POINTER(I64)]),
     "lm_detector_set_direct_bits": (I, [P, I]),
     "lm_detector_last_timings": (I, [P, ctypes.POINTER(Timings)]),

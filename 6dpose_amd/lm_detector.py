@@ -311,16 +311,20 @@ class Detector:
         return dict(zip(k, [float(x) for x in out]))
 
     def refinesOnBitPlanes(self) -> bool:
-        """lm_detector_refines_on_bit_planes: which refinement kernel the current bank / geometry uses (valid after a match)."""
+        """lm_detector_refines_on_bit_planes: which refinement kernel the current bank / geometry uses (valid after a match).  True on
+        k_local_bits and, under "wide" with a table of three or four distinct non-zero values, on k_local_wide."""
         return bool(self._lib.lm_detector_refines_on_bit_planes(self._h))
 
-    _REFINE = {"bits": 0, "tiles": 1, "single": 2}
-    _COARSE = {"bits": 0, "bytes": 1}
+    _REFINE = {"bits": 0, "tiles": 1, "single": 2, "wide": 3}
+    _COARSE = {"bits": 0, "bytes": 1, "wide": 2}
 
     def setPaths(self, refine: str = "bits", coarse: str = "bits", direct: bool = True) -> None:
         """lm_detector_set_paths: which kernels serve the refinement ("bits" = k_local_bits, "tiles" / "single" = k_local with / without
         tiles) and the coarse pass ("bits" = k_coarse_bits, "bytes" = k_coarse); lm_detector_set_direct_bits: the front end writes the
-        bit planes itself (direct) or byte linear memories that a second kernel packs.  Results do not depend on any of it."""
+        bit planes itself (direct) or byte linear memories that a second kernel packs.  "wide" (refine, and coarse together with it) is
+        "bits" for a response table of at most two distinct non-zero values — the same kernels and memory, and getPaths() says "bits" —
+        and two sets of bit planes (k_local_wide / k_coarse_wide, packed from the byte planes whatever `direct` says) for the other
+        tables, which "bits" sends to the byte kernels.  Not on a sharded detector.  Results do not depend on any of it."""
         _check(self._lib.lm_detector_set_paths(self._h, self._REFINE[refine], self._COARSE[coarse]))
         _check(self._lib.lm_detector_set_direct_bits(self._h, int(direct)))          # True / False; tests: + 2 the top level's bit planes stay readable, + 4 / + 8 which writer of the top level (amd_linemod.h)
 
@@ -372,6 +376,13 @@ class Detector:
         """lm_detector_bit_arena_bytes: device bytes allocated for (strip records, pair stream), over all result slots (tests)."""
         a, b = ctypes.c_uint64(), ctypes.c_uint64()
         _check(self._lib.lm_detector_bit_arena_bytes(self._h, ctypes.byref(a), ctypes.byref(b)))
+        return int(a.value), int(b.value)
+
+    def wideArenaBytes(self):
+        """lm_detector_wide_arena_bytes: device bytes allocated for the second set of (strip records, pair stream) of the "wide" paths,
+        over all result slots: (0, 0) until a table of three or four distinct non-zero values has run on them."""
+        a, b = ctypes.c_uint64(), ctypes.c_uint64()
+        _check(self._lib.lm_detector_wide_arena_bytes(self._h, ctypes.byref(a), ctypes.byref(b)))
         return int(a.value), int(b.value)
 
     def getBatch(self) -> int:
@@ -541,7 +552,8 @@ class Detector:
 
     def readStage(self, level: int, kind: int) -> np.ndarray:
         """Device intermediates of the last front end run (tests): kind 0/1 quantised colour/normal,
-        2/3 linear memories colour/normal, 4 strip records of a level below the top, 5 pair stream of the top level (bit planes)."""
+        2/3 linear memories colour/normal, 4 strip records of a level below the top, 5 pair stream of the top level (bit planes),
+        6 / 7 the second set of the "wide" paths in the layout of 4 / 5 (after a match that ran on it)."""
         n = _check(self._lib.lm_detector_read_stage(self._h, level, kind, None, 0))
         buf = np.zeros(n, np.uint8)
         _check(self._lib.lm_detector_read_stage(self._h, level, kind, _ptr(buf), n))

@@ -307,15 +307,22 @@ int lm_detector_set_async_collect(lm_detector *d, int on);
  * bookkeeping, batch launches, collect: waiting for the GPU, record conversion, canonical sort + unique}; reset != 0 clears it. */
 int lm_detector_host_profile(lm_detector *d, double *out8, int reset);
 /* 1 when the local refinement (similarityLocal, LL.cpp:1366-1428) of the current bank and frame geometry runs on bit planes
- * (kernel k_local_bits), 0 when on byte planes (k_local): which kernel a profile of the match shows.  Valid after a match. */
+ * (kernel k_local_bits, or k_local_wide under refine 3 with a table of three or four distinct non-zero values), 0 when on byte
+ * planes (k_local): which kernel a profile of the match shows.  Valid after a match. */
 int lm_detector_refines_on_bit_planes(const lm_detector *d);
 /* Which kernels serve similarity (LL.cpp:1284-1354) and similarityLocal (LL.cpp:1366-1428).  Results never depend on it; tests and
  * measurements use it to run every path against the oracle in one process.
  *   refine: 0 = bit planes (k_local_bits; default, any pyramid with a level below the top), 1 = byte strip planes with tiles (k_local),
  *           2 = byte planes, every candidate on its own (k_local without tiles).
- *   coarse: 0 = bit planes (k_coarse_bits; default, used when the refinement runs on bit planes too), 1 = byte linear memories (k_coarse).
+ *           3 = wide bit planes: what 0 is for a response table of at most two distinct non-zero values (the default among them: the same
+ *           kernels, the same memory, and lm_detector_get_paths answers 0); for the other tables (4 3 2 1 0, ...) two sets of bit planes
+ *           (k_local_wide), where 0 falls back to the byte kernels.  Not on a sharded detector (lm_detector_set_shard): refused.
+ *   coarse: 0 = bit planes (k_coarse_bits; default, used when the refinement runs on bit planes too), 1 = byte linear memories (k_coarse),
+ *           2 = wide bit planes (k_coarse_wide for the tables that need it, else what 0 is); it plans no tiles, so only with refine 3.
  * Refused with frames in flight.  lm_detector_get_paths reports what the current bank and frame geometry actually use (valid after a
- * match): refine 0 / 1 / 2 and coarse 0 / 1 as above. */
+ * match): refine 0 / 1 / 2 / 3 and coarse 0 / 1 / 2 as above — 3 / 2 only when the wide kernels ran.  What sends a bank or geometry off the
+ * bit planes (a single-level pyramid, LM_BITPLANES=0, entries beyond 16383 features) does so under 3 / 2 as well.  The front end writes byte
+ * planes for a table on the wide kernels and two kernels pack both sets from them (lm_detector_set_direct_bits has no say there). */
 int lm_detector_set_paths(lm_detector *d, int refine, int coarse);
 int lm_detector_get_paths(const lm_detector *d, int *refine, int *coarse);
 /* The response table of computeResponseMaps: r[d] = the response to a feature whose label lies at cyclic distance d (0..4, eight orientations)
@@ -327,13 +334,16 @@ int lm_detector_get_paths(const lm_detector *d, int *refine, int *coarse);
  * process (lm_detector_read_stage: kinds 2 / 3 answer under the table in force — the byte planes are rebuilt from the last frame's quantised maps
  * when the table changed since —, kinds 4 / 5 show what the last match read): lm_detector_write_classes / lm_detector_write / the packed bank do not store it, training (lm_detector_add_template) does not read
  * it, and the ranks of a sharded run must each set the same one.  Tables with at most two distinct non-zero values (4 1 0 0 0, 4 2 0 0 0,
- * 4 1 1 0 0, ...) run on the bit-plane kernels; the others (4 3 2 1 0, 4 2 1 0 0, 4 3 1 0 0, ...) run on the byte kernels, which
- * lm_detector_get_paths reports.  Thresholds are not comparable between tables. */
+ * 4 1 1 0 0, ...) run on the bit-plane kernels; the others (4 3 2 1 0, 4 2 1 0 0, 4 3 1 0 0, ...) run on the byte kernels — or, when
+ * lm_detector_set_paths(d, 3, 2) asked for them, on the wide bit-plane kernels —, which lm_detector_get_paths reports.  Thresholds are not comparable between tables. */
 int lm_detector_set_response_table(lm_detector *d, const uint8_t r[5]);
 int lm_detector_get_response_table(const lm_detector *d, uint8_t r[5]);
 /* Device memory ALLOCATED for the bit planes, summed over the result slots: the strip records of the levels below the top and the pair
  * stream of the top level (tests: no response table makes them grow). */
 int lm_detector_bit_arena_bytes(const lm_detector *d, uint64_t *strip_records, uint64_t *pair_stream);
+/* The same for the SECOND set of bit planes of the wide paths (lm_detector_set_paths 3 / 2): zero until a match has run a table of three or
+ * four distinct non-zero values on them, then the sizes of the first set for every result slot that has served such a match. */
+int lm_detector_wide_arena_bytes(const lm_detector *d, uint64_t *strip_records, uint64_t *pair_stream);
 /* Which selection served the training views (lm_detector_add_template, lm_detector_add_templates_rendered[_ex]) since the detector was
  * created or lm_detector_read_params was called: out[0] views whose features the device selected (train.hip), out[1] views sent to the
  * host selection (LM_TRAIN_HOST=1, no or a grey object mask, more than 1024 features, a candidate list beyond what the kernel sorts),
@@ -358,7 +368,10 @@ int lm_detector_last_timings(const lm_detector *d, lm_timings *t);
  * records of 32 cells x {response is 1, response is 4}), 5 the pair stream of the top level ({is-1
  * dword, is-4 dword} per 32 bytes of the flat linear memories, both modality blocks with their zero
  * tails) — 4 and 5 only after a match that used them (k_local_bits / k_coarse_bits; a stream the front
- * end wrote directly is cleared by the match unless lm_detector_set_direct_bits(d, 2) was set).
+ * end wrote directly is cleared by the match unless lm_detector_set_direct_bits(d, 2) was set), 6 / 7
+ * the second set of the wide paths in the layout and size of 4 / 5 (after a match on k_local_wide /
+ * k_coarse_wide: with v the response of a cell, kinds 4 / 5 then hold {v & 1, v == 4} and kinds 6 / 7
+ * {(v >> 1) & 1, nothing}; LM_ERR_INVALID while no such match has allocated them).
  * Copies min(capacity, size) bytes, returns the full size. */
 int64_t lm_detector_read_stage(lm_detector *d, int level, int kind, uint8_t *dst, int64_t capacity);
 

@@ -193,6 +193,8 @@ struct lm_detector {
     // (round 1).  coarse: 0 = pair stream when the refinement runs on bit planes (default), 1 = byte linear memories (k_coarse).
     // refine 3 / coarse 2 = "wide": what 0 is for a table of two planes, and two sets of bit planes (match_wide.hip) for the tables that need them.
     int refine_mode = 0, coarse_mode = 0;
+    int coarse_batch = knobs().coarse_batch;        // lm_detector_set_coarse_batch: k_coarse_bits (0), k_coarse_bits_batch (1) or the launcher's rule (-1) for the coarse pass on the pair stream
+    bool coarse_batched = false;                    // the last such coarse pass ran k_coarse_bits_batch (lm_detector_get_coarse_batch)
     // Second set of bit planes of the wide paths, per result slot: allocated (and zeroed) when a batch first runs a wide table on a wide path,
     // at the sizes of bits_arena / cbits_arena; a geometry change resizes and clears the ones that exist (setup_geometry).
     DevBuf<uint8_t> wbits_arena[kSlots], wcbits_arena[kSlots];

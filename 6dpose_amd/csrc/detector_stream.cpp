@@ -465,7 +465,7 @@ static int enqueue_coarse(lm_detector* d, const Batch& B) {
     // the counters are zero on entry (reset by the slots' previous k_dedupe)
     { LM_CLOCK("launch_coarse");
     if (B.cwide) launch_coarse_wide(B.fb, B.tb, B.wt, d->geom, B.bank, B.num_work, B.threshold, d->buf_cand_cap, d->cbits_byte0, d->cbits_max_nf, B.s);
-    else if (B.cbits) launch_coarse_bits(B.fb, B.tb, d->geom, B.bank, B.num_work, B.threshold, d->buf_cand_cap, d->cbits_byte0, d->cbits_max_nf, d->resp_low_weight, B.s);
+    else if (B.cbits) d->coarse_batched = launch_coarse_bits(B.fb, B.tb, d->geom, B.bank, B.num_work, B.threshold, d->buf_cand_cap, d->cbits_byte0, d->cbits_max_nf, d->resp_low_weight, B.s, d->coarse_batch);
     else launch_coarse(B.fb, d->geom, B.bank, B.num_work, B.threshold, d->buf_cand_cap, B.tile_cap, B.s);
     }
     HIP_TRY(hipEventRecord(d->slot[B.first].ev[3], B.s));
@@ -948,6 +948,44 @@ extern "C" int lm_detector_get_paths(const lm_detector* d, int* refine, int* coa
     *refine = bits ? 0 : (d->geom.levels >= 2 && tiles_wanted(d) && tile_plan_possible(d->geom) ? 1 : 2);
     *coarse = cbits_active(d, 1) ? 0 : 1;
     return LM_OK;
+}
+
+// Which kernel serves the coarse pass on the pair stream, and which one served the last batch (tests, A/B measurements).
+extern "C" int lm_detector_set_coarse_batch(lm_detector* d, int mode) {
+    if (!d) return lm_set_error(LM_ERR_INVALID, "null detector");
+    if (mode < -1 || mode > 1) return lm_set_error(LM_ERR_INVALID, "mode must be -1 (the launcher's rule), 0 (k_coarse_bits) or 1 (k_coarse_bits_batch)");
+    int rc = lm_launch_pending(d);                      // frames waiting for their batch go out under the setting they were submitted with
+    if (rc) return rc;
+    d->coarse_batch = mode;
+    return LM_OK;
+}
+extern "C" int lm_detector_get_coarse_batch(const lm_detector* d) { return d && d->coarse_batched ? 1 : 0; }
+
+// The candidate buffers are laid out at the first frame and grow when a frame overflows them: a smaller start is for the tests of the overflow.
+extern "C" int lm_detector_set_candidate_capacity(lm_detector* d, int candidates) {
+    if (!d) return lm_set_error(LM_ERR_INVALID, "null detector");
+    if (candidates < 1024) return lm_set_error(LM_ERR_INVALID, "candidate capacity must be at least 1024, got %d", candidates);
+    if (d->buf_cand_cap) return lm_set_error(LM_ERR_INVALID, "the candidate buffers exist already (%u candidates): set the capacity before the first match", d->buf_cand_cap);
+    d->cand_cap = (uint32_t)candidates;
+    return LM_OK;
+}
+
+// The coarse candidates of a collected frame, as the coarse kernel left them in the frame's slot: {x, y, score bits, work-list index} per slot.
+extern "C" int64_t lm_detector_read_candidates(lm_detector* d, uint64_t frame_no, int32_t* dst, int64_t capacity) {
+    if (!d) return lm_set_error(LM_ERR_INVALID, "null detector");
+    if (frame_no >= d->n_collected || d->n_submitted - frame_no > (uint64_t)lm_detector::kSlots)
+        return lm_set_error(LM_ERR_INVALID, "frame %llu is not collected yet or its slot serves a later frame", (unsigned long long)frame_no);
+    const int si = (int)(frame_no % lm_detector::kSlots);
+    const lm_detector::Slot& sl = d->slot[si];
+    if (sl.cand_cap != d->buf_cand_cap || sl.cands != d->d_cands.p + (size_t)d->buf_cand_cap * si)
+        return lm_set_error(LM_ERR_INVALID, "the candidate buffers have been replaced since frame %llu", (unsigned long long)frame_no);
+    const int64_t produced = sl.num_work > 0 ? (int64_t)(sl.h_counters[0] & kCandMask) : 0;
+    const int64_t n = std::min<int64_t>(std::min<int64_t>(produced, (int64_t)sl.cand_cap), capacity);
+    if (dst && n > 0) {
+        HIP_TRY(hipSetDevice(d->device));
+        HIP_TRY(hipMemcpy(dst, sl.cands, (size_t)n * sizeof(Candidate), hipMemcpyDeviceToHost));
+    }
+    return produced;
 }
 
 extern "C" int lm_detector_flush(lm_detector* d) {

@@ -17,6 +17,7 @@ struct Knobs {
     int local_blocks = 0;          // LM_LOCAL_BLOCKS: grid of k_local (0 = default per CU count)
     int frame_batch = 0;           // LM_FRAME_BATCH: frames per matching launch in stream mode (0 = default: 8 = kMaxBatch; lm_detector_set_batch)
     int coarse_bits = 1;           // LM_COARSE_BITS=0: coarse pass on the byte linear memories (k_coarse) instead of on the pair stream (k_coarse_bits)
+    int coarse_batch = -1;         // LM_COARSE_BATCH: which kernel runs the coarse pass on the pair stream: 0 = k_coarse_bits (a wave = one template on one frame), 1 = k_coarse_bits_batch wherever a frame fits a workgroup, -1 = default: the batched kernel for batches of two frames or more whose frames leave lanes idle (lm_detector_set_coarse_batch)
     int bitplanes = 1;             // LM_BITPLANES=0: refinement on the byte strip planes with tiles (round 2-3's kernel) instead of on bit planes
     int fe_bits = 1;               // LM_FE_BITS=0: the front end always writes the byte planes and k_pack_bits / k_pack_top pack them (1: bit planes directly when nothing reads the bytes)
     int fe_bits_split = 0;         // LM_FE_BITS_SPLIT=1: k_fe_bits as two launches (strip records, pair stream) so that a profile times them apart
@@ -57,6 +58,7 @@ inline const Knobs& knobs() {
         v.fe_wgs_per_cu = geti("LM_FE_WGS_PER_CU", kFeWaves);
         v.bitplanes = geti("LM_BITPLANES", 1);
         v.coarse_bits = geti("LM_COARSE_BITS", 1);
+        v.coarse_batch = geti("LM_COARSE_BATCH", v.coarse_batch);
         v.fe_bits = geti("LM_FE_BITS", 1);
         v.fe_bits_split = geti("LM_FE_BITS_SPLIT", 0);
         v.first_batch = geti("LM_FIRST_BATCH", v.first_batch);

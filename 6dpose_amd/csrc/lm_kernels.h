@@ -163,8 +163,19 @@ void launch_local_bits(const FrameBatch& fb, const BitsBatch& B, const FrameGeom
 // nothing reads the top level's bytes (frontend.hip, top_bits_body: the stream must be zero before).
 struct TopBits { const uint8_t* lm[kMaxBatch]; uint8_t* bits[kMaxBatch]; };
 void launch_pack_top(const TopBits& B, int nb, uint32_t byte0, uint32_t npairs, hipStream_t s);
-// candidates only (no tiles); max_features = the largest nf of the bank's top-level entries
-void launch_coarse_bits(const FrameBatch& fb, const TopBits& B, const FrameGeom& g, const BankDev& bank, int num_work, float threshold, uint32_t cap, uint32_t byte0, int max_features, int low_weight, hipStream_t s);
+// candidates only (no tiles); max_features = the largest nf of the bank's top-level entries.  Two kernels: k_coarse_bits (a wave = one template on
+// one frame) and k_coarse_bits_batch (the frames of a batch share a template's waves).  batch_mode: < 0 = the batched
+// kernel when the batch has two frames or more and it issues fewer waves per template, 0 = never, > 0 = wherever a frame fits a workgroup (tests,
+// A/B runs).  Returns whether the batched kernel was launched.  Candidates, counters and the order of a template's hits inside a frame are the same.
+struct CoarseBatchPlan {
+    int L;                       // lanes per frame = ceil(positions / 32)
+    int groups, fpg;             // the batch's frames in `groups` of up to `fpg`: a group's lanes fit one workgroup
+    int Wg, tpw;                 // waves per (template, group), templates per workgroup
+    int waves, waves_per_frame_kernel;   // waves per template over the batch: this plan / k_coarse_bits
+};
+bool coarse_batch_plan(int nb, int npos, CoarseBatchPlan* p);   // false: a frame does not fit a workgroup (more than 32768 positions)
+bool launch_coarse_bits(const FrameBatch& fb, const TopBits& B, const FrameGeom& g, const BankDev& bank, int num_work, float threshold, uint32_t cap, uint32_t byte0, int max_features, int low_weight, hipStream_t s,
+                        int batch_mode = -1);
 // Wide bit planes (match_wide.hip): tables with three or four distinct non-zero values.  A response v = 0..4 is three
 // binary digits.  Set 0 lives in the arenas above with their layout: bit 2c of a strip record = v & 1 of cell c, bit 2c + 1 = (v == 4); the
 // pair stream's low dword = v & 1, its high dword = (v == 4).  Set 1 — a second arena of the same layout and size per frame — holds (v >> 1) & 1

@@ -4,6 +4,7 @@
 // 1835-1852), their launchers and the LM_LAUNCH_* macros that pick the instantiation.  The byte kernels are in match_bytes.hip,
 // what both use in match_device.h; data layout and bank: match_bytes.hip.
 #include "match_device.h"
+#include <algorithm>
 
 namespace lm {
 
@@ -448,20 +449,191 @@ k_coarse_bits(FrameBatch fb, TopBits B, LevelGeom lv, int level, int levels, con
     }
 }
 
+// ---- The coarse pass of a BATCH with the frames sharing a template's waves.  k_coarse_bits is bound by its wave loads and
+// a wave load costs the same whatever the live lanes: at VGA a frame's 1200 positions are 38 lanes, the other 26 sit every load out.  A feature's
+// offset is the same for every frame, so here the lanes of a (template, frame group) are ONE flat index g = frame * L + lane of the frame,
+// L = ceil(positions / 32), dealt to consecutive waves: a wave may straddle frames, idle lanes exist only behind a group's last frame, and a frame
+// of more than 64 lanes spans waves (no pass loop).  Only the base of a lane's loads differs — its frame's pair stream, a 64-bit address per lane:
+// the slots' streams are separate allocations —; offsets and shifts stay scalar, the arithmetic is k_coarse_bits's.
+// A workgroup = kWg waves per template x the templates that fit, on the frames [f0, f0 + fpg) of the batch (a group = as many frames as 16 waves
+// hold); it reserves the slots of each of its frames with ONE atomic, and inside them a template's hits lie together in raster order (the wave
+// scan, cut at the frame boundaries; the waves' counts per frame prefix-summed in LDS), which k_local_bits's L2 locality rests on.
+constexpr int kCoarseBatchWaves = 16;                                       // waves per workgroup at most: 1024 lanes hold a group's frames
+typedef uint32_t pair2_t __attribute__((ext_vector_type(4), aligned(8)));   // two consecutive pairs: a stream's pairs are 8-byte aligned
+template <int kHi, int kWaves, int kA>
+__global__ void __launch_bounds__(64 * kCoarseBatchWaves) __attribute__((amdgpu_waves_per_eu(kWaves, kWaves)))
+k_coarse_bits_batch(FrameBatch fb, TopBits B, LevelGeom lv, int level, int levels, const TemplEntry* __restrict__ entries, const int32_t* __restrict__ feat_off,
+                    const int32_t* __restrict__ work_pyramids, int num_work, float threshold, uint32_t cap, uint32_t byte0, int L, int fpg, int Wg) {
+    constexpr int kN = 4 + kHi, kS = kN + 3;
+    __shared__ uint32_t s_cnt[kCoarseBatchWaves][kMaxBatch];               // hits of (wave, frame of the group), then their exclusive prefix over the waves
+    __shared__ unsigned long long s_base[kMaxBatch];
+    const int lane = threadIdx.x & 63;
+    const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int nwaves = (int)(blockDim.x >> 6);
+    const int tl = wv / Wg, ww = wv - tl * Wg;                              // template of the workgroup, wave of the template
+    const int work_raw = (int)blockIdx.x * (nwaves / Wg) + tl;
+    const bool live = work_raw < num_work;
+    const int work = live ? work_raw : num_work - 1;                       // idle waves of the last workgroup shadow a real template and emit nothing
+    const int pyr = work_pyramids[work];
+    const TemplEntry e = entries[(size_t)pyr * levels + level];
+    const int nf = e.nf, nfp = e.nf_padded;
+    const int32_t* fo = feat_off + e.feat_start;
+    const int Wd = lv.Wd, Hd = lv.Hd, T = lv.T, npos = Wd * Hd;
+    const int wf = (e.width - 1) / T + 1, hf = (e.height - 1) / T + 1;      // LL.cpp:1299-1309
+    const int tp = (Hd - hf) * Wd + (Wd - wf) + 1;
+    const int offset = T / 2 + (T % 2 - 1);                                 // LL.cpp:1846
+    const int limit = tp < npos ? tp : npos;                                // positions that carry sums
+    int rmin = (int)(threshold * (float)(4 * nf) / 100.f);                  // the smallest raw sum whose score passes, as k_coarse_bits
+    if (!(rmin >= 0)) rmin = 0;
+    if (rmin > 4 * nf + 1) rmin = 4 * nf + 1;
+    while (rmin > 0 && score_of(rmin, nf) > threshold) --rmin;
+    while (rmin <= 4 * nf && !(score_of(rmin, nf) > threshold)) ++rmin;
+    const bool zero_passes = score_of(0, nf) > threshold;
+    const int f0 = (int)blockIdx.y * fpg;                                   // the group's frames
+    const int nfr = fb.nb - f0 < fpg ? fb.nb - f0 : fpg;
+    const int g = ww * 64 + lane;                                           // flat lane of the (template, group)
+    const int fl = g / L, li = g - fl * L;                                  // frame of the group, lane of the frame
+    const bool act = live && fl < nfr;                                      // (behind the group's last frame: idle)
+    const int frame = f0 + (fl < nfr ? fl : 0);
+    const int pos0 = 32 * li;                                               // first position of this lane
+    for (uint32_t i = threadIdx.x; i < (uint32_t)(kCoarseBatchWaves * kMaxBatch); i += blockDim.x) (&s_cnt[0][0])[i] = 0u;
+    uint32_t c1[kN], c4[kN];
+#pragma unroll
+    for (int k = 0; k < kN; ++k) { c1[k] = 0; c4[k] = 0; }
+    if (act && nfp > 0 && pos0 < limit) {                                   // (lanes beyond the sums sit the loads out)
+        const uint8_t* base = B.bits[frame] + (size_t)li * 8u;
+        auto batch = [&](int f, uint32_t& e1, uint32_t& e4) {
+            pair2_t v[8];
+            uint32_t sh[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                const uint32_t ob = (uint32_t)fo[f + u] - byte0;            // wave-uniform -> SMEM / SALU
+                sh[u] = ob & 31u;
+                v[u] = *reinterpret_cast<const pair2_t*>(base + (size_t)(ob >> 5) * 8u);   // pairs q + li and q + li + 1 of the lane's frame
+            }
+            uint32_t x1[8], x4[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                x1[u] = __builtin_amdgcn_alignbit(v[u].z, v[u].x, sh[u]);
+                x4[u] = __builtin_amdgcn_alignbit(v[u].w, v[u].y, sh[u]);
+            }
+            e1 = add8(x1, c1[0], c1[1], c1[2]);
+            e4 = add8(x4, c4[0], c4[1], c4[2]);
+        };
+        for (int f = 0; f < nfp; f += 16) {
+            uint32_t a1, a4;
+            batch(f, a1, a4);
+            if (f + 8 < nfp) {
+                uint32_t b1, b4;
+                batch(f + 8, b1, b4);
+                add_eights2<kN>(c1, a1, b1);
+                add_eights2<kN>(c4, a4, b4);
+            } else {
+                add_eights1<kN>(c1, a1);
+                add_eights1<kN>(c4, a4);
+            }
+        }
+    }
+    uint32_t S[kS];
+    weighted_sum<kA, kN>(S, c1, c4);
+    uint32_t gt = 0, eq = 0xFFFFFFFFu;                                      // S >= rmin, bit-sliced
+#pragma unroll
+    for (int k = kS - 1; k >= 0; --k) {
+        if ((rmin >> k) & 1) eq &= S[k];                                    // wave-uniform
+        else { gt |= eq & S[k]; eq &= ~S[k]; }
+    }
+    uint32_t hit_mask = rmin < (1 << kS) ? (gt | eq) : 0u;
+    // positions at or beyond the template's position count hold zero sums (LL.cpp:1299-1309): they are hits only if zero passes
+    const int sums = limit - pos0;
+    const uint32_t summed = sums >= 32 ? 0xFFFFFFFFu : (sums > 0 ? (1u << sums) - 1u : 0u);
+    const int inmap = npos - pos0;
+    const uint32_t mapped = inmap >= 32 ? 0xFFFFFFFFu : (inmap > 0 ? (1u << inmap) - 1u : 0u);
+    hit_mask = (hit_mask & summed) | (zero_passes ? (mapped & ~summed) : 0u);
+    if (!act) hit_mask = 0;
+    // the wave's scan, cut where a frame begins: a frame's lanes are consecutive, so its part of the scan starts at its first lane in this wave
+    int total;
+    const int mine = __popc(hit_mask);
+    const int before = wave_excl_scan(mine, lane, total);
+    const int head = lane - li > 0 ? lane - li : 0;                         // the first lane of this lane's frame in the wave
+    const int in_frame = before - __shfl(before, head, 64);                 // hits of this (template, frame) in the wave before this lane's
+    __syncthreads();                                                        // s_cnt is zero
+    if (act && (lane == 63 || li == L - 1)) s_cnt[wv][fl] = (uint32_t)(in_frame + mine);   // the last lane of the frame in the wave
+    __syncthreads();
+    if ((int)threadIdx.x < nfr) {                                           // one atomic per frame and workgroup
+        uint32_t run = 0;
+        for (int w = 0; w < nwaves; ++w) { const uint32_t c = s_cnt[w][threadIdx.x]; s_cnt[w][threadIdx.x] = run; run += c; }
+        s_base[threadIdx.x] = run ? atomicAdd(&fb.f[f0 + (int)threadIdx.x].counters[0], (unsigned long long)run) : 0ull;
+    }
+    __syncthreads();
+    if (hit_mask) {
+        Candidate* __restrict__ cands = fb.f[frame].cands;
+        unsigned long long slot = s_base[fl] + (unsigned long long)s_cnt[wv][fl] + (unsigned long long)in_frame;
+        uint32_t m = hit_mask;
+        while (m) {
+            const int b = __ffs((int)m) - 1;
+            m &= m - 1;
+            if (slot < cap) {
+                int raw = 0;
+                if ((summed >> b) & 1u) {
+#pragma unroll
+                    for (int k = 0; k < kS; ++k) raw |= (int)((S[k] >> b) & 1u) << k;
+                }
+                const int jpos = pos0 + b;
+                const int cy = jpos / Wd, cx = jpos - cy * Wd;
+                Candidate c;
+                c.x = cx * T + offset; c.y = cy * T + offset; c.score = score_of(raw, nf); c.work = work;
+                cands[slot] = c;
+            }
+            ++slot;
+        }
+    }
+}
+
 void launch_pack_top(const TopBits& B, int nb, uint32_t byte0, uint32_t npairs, hipStream_t s) {
     hipLaunchKernelGGL(k_pack_top, dim3((npairs + 255) / 256, nb), dim3(256), 0, s, B, byte0, npairs);
 }
-void launch_coarse_bits(const FrameBatch& fb, const TopBits& B, const FrameGeom& g, const BankDev& bank, int num_work, float threshold, uint32_t cap, uint32_t byte0, int max_features, int low_weight, hipStream_t s) {
-    if (num_work <= 0 || fb.nb <= 0) return;
+bool coarse_batch_plan(int nb, int npos, CoarseBatchPlan* p) {
+    const int lanes_max = 64 * kCoarseBatchWaves;
+    p->L = (npos + 31) / 32;
+    if (nb < 1 || npos < 1 || p->L > lanes_max) return false;              // a frame has to fit a workgroup (32768 positions)
+    const int fit = lanes_max / p->L;                                       // frames a workgroup holds
+    p->groups = (nb + fit - 1) / fit;
+    p->fpg = (nb + p->groups - 1) / p->groups;                              // dealt evenly: 8 frames of 150 lanes are 4 + 4, not 6 + 2
+    p->groups = (nb + p->fpg - 1) / p->fpg;
+    p->Wg = (p->fpg * p->L + 63) / 64;
+    // templates per workgroup: workgroups of about four waves, as k_coarse_bits's.  Larger ones cost more than their fewer atomics save — VGA, 8 frames,
+    // 2000 templates: 66.5 us with one template (5 waves) per workgroup, 75.5 / 75.2 us with two / three (profiles/coarse_batch_kernel_ab.txt)
+    p->tpw = std::max(1, 4 / p->Wg);
+    p->waves = 0;
+    for (int f = 0; f < nb; f += p->fpg) p->waves += (std::min(p->fpg, nb - f) * p->L + 63) / 64;
+    p->waves_per_frame_kernel = nb * ((p->L + 63) / 64);
+    return true;
+}
+bool launch_coarse_bits(const FrameBatch& fb, const TopBits& B, const FrameGeom& g, const BankDev& bank, int num_work, float threshold, uint32_t cap, uint32_t byte0, int max_features, int low_weight, hipStream_t s,
+                        int batch_mode) {
+    if (num_work <= 0 || fb.nb <= 0) return false;
     const int level = g.levels - 1;
+    const bool big = max_features > kBitsSmallMax;
+    CoarseBatchPlan p;
+    const bool can = coarse_batch_plan(fb.nb, g.lv[level].Wd * g.lv[level].Hd, &p);
+    if (can && (batch_mode > 0 || (batch_mode < 0 && fb.nb >= 2 &&p.waves < p.waves_per_frame_kernel))) {
+#define LM_LAUNCH_COARSE_BATCH(HI, WAVES, A) \
+    hipLaunchKernelGGL((k_coarse_bits_batch<HI, WAVES, A>), dim3((num_work + p.tpw - 1) / p.tpw, p.groups), dim3(64 * p.tpw * p.Wg), 0, s, fb, B, g.lv[level], level, g.levels, \
+                       bank.entries, bank.feat_off, bank.work, num_work, threshold, cap, byte0, p.L, p.fpg, p.Wg)
+        if (low_weight == 2) { if (big) LM_LAUNCH_COARSE_BATCH(10, 5, 2); else LM_LAUNCH_COARSE_BATCH(5, 6, 2); }
+        else if (low_weight == 3) { if (big) LM_LAUNCH_COARSE_BATCH(10, 5, 3); else LM_LAUNCH_COARSE_BATCH(5, 6, 3); }
+        else { if (big) LM_LAUNCH_COARSE_BATCH(10, 5, 1); else LM_LAUNCH_COARSE_BATCH(5, 6, 1); }
+#undef LM_LAUNCH_COARSE_BATCH
+        return true;
+    }
 #define LM_LAUNCH_COARSE_BITS(HI, WAVES, A) \
     hipLaunchKernelGGL((k_coarse_bits<HI, WAVES, A>), dim3((num_work + 3) / 4, fb.nb), dim3(256), 0, s, fb, B, g.lv[level], level, g.levels, bank.entries, bank.feat_off, \
                        bank.work, num_work, threshold, cap, byte0)
-    const bool big = max_features > kBitsSmallMax;
     if (low_weight == 2) { if (big) LM_LAUNCH_COARSE_BITS(10, 5, 2); else LM_LAUNCH_COARSE_BITS(5, 6, 2); }
     else if (low_weight == 3) { if (big) LM_LAUNCH_COARSE_BITS(10, 5, 3); else LM_LAUNCH_COARSE_BITS(5, 6, 3); }
     else { if (big) LM_LAUNCH_COARSE_BITS(10, 5, 1); else LM_LAUNCH_COARSE_BITS(5, 6, 1); }
 #undef LM_LAUNCH_COARSE_BITS
+    return false;
 }
 
 }  // namespace lm

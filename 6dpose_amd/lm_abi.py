@@ -161,6 +161,10 @@ PROTOTYPES = {
     "lm_detector_wide_arena_bytes": (I, [P, ctypes.POINTER(U64), ctypes.POINTER(U64)]),
     "lm_detector_train_stats": (I, [P, ctypes.POINTER(I64)]),
     "lm_detector_set_direct_bits": (I, [P, I]),
+    "lm_detector_set_coarse_batch": (I, [P, I]),
+    "lm_detector_get_coarse_batch": (I, [P]),
+    "lm_detector_set_candidate_capacity": (I, [P, I]),
+    "lm_detector_read_candidates": (I64, [P, U64, P, I64]),
     "lm_detector_last_timings": (I, [P, ctypes.POINTER(Timings)]),
     "lm_detector_read_stage": (I64, [P, I, I, P, I64]),
     # host helpers

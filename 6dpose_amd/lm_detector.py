@@ -328,6 +328,35 @@ class Detector:
         _check(self._lib.lm_detector_set_paths(self._h, self._REFINE[refine], self._COARSE[coarse]))
         _check(self._lib.lm_detector_set_direct_bits(self._h, int(direct)))          # True / False; tests: + 2 the top level's bit planes stay readable, + 4 / + 8 which writer of the top level (amd_linemod.h)
 
+    CANDIDATE_DTYPE = np.dtype([("x", np.int32), ("y", np.int32), ("score", np.float32), ("work", np.int32)])
+
+    def setCoarseBatch(self, mode) -> None:
+        """lm_detector_set_coarse_batch: the coarse pass on the pair stream by k_coarse_bits (False / 0: a wave serves one template on one
+        frame), by k_coarse_bits_batch (True / 1: the frames of a batch launch share a template's waves) or by the launcher's rule (None / -1,
+        the default unless LM_COARSE_BATCH says otherwise).  Results do not depend on it."""
+        _check(self._lib.lm_detector_set_coarse_batch(self._h, -1 if mode is None else int(mode)))
+
+    def coarseBatched(self) -> bool:
+        """lm_detector_get_coarse_batch: whether the last coarse pass on the pair stream ran k_coarse_bits_batch."""
+        return bool(self._lib.lm_detector_get_coarse_batch(self._h))
+
+    def setCandidateCapacity(self, candidates: int) -> None:
+        """lm_detector_set_candidate_capacity (tests of the overflow): coarse candidates per frame the buffers are first laid out for; before the first match."""
+        _check(self._lib.lm_detector_set_candidate_capacity(self._h, int(candidates)))
+
+    def readCandidates(self, frame_no: int):
+        """lm_detector_read_candidates: (produced, records) of collected frame `frame_no` — the frame's candidate counter and the coarse
+        candidates in slot order (CANDIDATE_DTYPE; `work` = index into the work list), min(produced, capacity) of them."""
+        n = int(self._lib.lm_detector_read_candidates(self._h, int(frame_no), None, 0))
+        if n < 0:
+            raise RuntimeError(self._lib.lm_last_error().decode("utf-8", "replace"))
+        out = np.zeros(n, self.CANDIDATE_DTYPE)
+        out["work"] = -1                                      # (a frame that overflowed its buffers: only the first `capacity` records exist)
+        got = int(self._lib.lm_detector_read_candidates(self._h, int(frame_no), out.ctypes.data_as(ctypes.c_void_p), n)) if n else 0
+        if got < 0:
+            raise RuntimeError(self._lib.lm_last_error().decode("utf-8", "replace"))
+        return n, out[out["work"] >= 0]
+
     def getPaths(self):
         """lm_detector_get_paths: (refine, coarse) the current bank and frame geometry actually use, as the names of setPaths (valid after a match)."""
         r, c = ctypes.c_int(), ctypes.c_int()

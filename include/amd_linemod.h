@@ -358,6 +358,21 @@ int lm_detector_train_stats(const lm_detector *d, int64_t out[4]);
  * the cheapest the geometry allows is used; bit 2 (on = 4 ...) forces the OR-ing writer, bit 3 (on = 8 ...) rules out the tiles (tests).
  * Results never depend on it. */
 int lm_detector_set_direct_bits(lm_detector *d, int on);
+/* The coarse pass on the pair stream has two kernels that leave the same candidates, counters and order of a template's hits inside a
+ * frame: k_coarse_bits (a wave serves one template on one frame) and k_coarse_bits_batch (the frames of a batch launch share a template's
+ * waves).  mode 0 / 1 forces the first / the second (the second wherever a frame's top level fits a workgroup: 32768 positions), -1 leaves
+ * it to the launcher's rule (the process-wide default is LM_COARSE_BATCH).  lm_detector_get_coarse_batch: 1 when the
+ * last such coarse pass ran k_coarse_bits_batch.  Results never depend on it. */
+int lm_detector_set_coarse_batch(lm_detector *d, int mode);
+int lm_detector_get_coarse_batch(const lm_detector *d);
+/* Tests: the number of coarse candidates per frame the buffers are first laid out for (default 262144, at least 1024; before the first
+ * match only).  A frame that produces more is reported by lm_detector_collect as LM_ERR_OVERFLOW and the capacity grows, as ever. */
+int lm_detector_set_candidate_capacity(lm_detector *d, int candidates);
+/* Tests: the coarse candidates of collected frame `frame_no` (counted like lm_detector_frames_submitted) as the coarse kernel left them in
+ * the frame's result slot, four words per slot: x, y, the bits of the float score, the work-list index.  Returns the number the frame
+ * PRODUCED (its counter; more than the capacity after an overflow) and copies min(produced, candidate capacity, capacity) records.
+ * LM_ERR_INVALID once the slot serves a later frame or the buffers have grown. */
+int64_t lm_detector_read_candidates(lm_detector *d, uint64_t frame_no, int32_t *dst, int64_t capacity);
 int lm_detector_last_timings(const lm_detector *d, lm_timings *t);
 
 /* Test/diagnostic access to the device-resident intermediates of the last front end run (parity

@@ -117,6 +117,42 @@ extern "C" int lm_detector_get_modalities(const lm_detector* d, const char* name
     return d->nmod;
 }
 
+extern "C" int lm_detector_set_colour_channels(lm_detector* d, int channels) {
+    if (!d) return lm_set_error(LM_ERR_INVALID, "null detector");
+    if (channels != 1 && channels != 3) return lm_set_error(LM_ERR_INVALID, "colour_channels must be 3 (interleaved colour) or 1 (grey), got %d", channels);
+    if (channels == 1 && !d->use[0]) return lm_set_error(LM_ERR_INVALID, "colour_channels = 1 on a detector without the ColorGradient modality: it takes no colour image");
+    if (d->n_submitted != d->n_collected) return lm_set_error(LM_ERR_INVALID, "frames in flight: collect them before changing colour_channels");
+    int rc = lm_launch_pending(d);
+    if (rc) return rc;
+    if (channels == d->cch) return LM_OK;
+    d->cch = channels;
+    // buffers are sized per channel count: the next frame lays the geometry out again; the resident frame and the parked ones are in the old format
+    d->frame_valid = false;
+    d->fW = d->fH = 0;
+    std::fill(d->slot_w.begin(), d->slot_w.end(), 0);
+    return LM_OK;
+}
+
+extern "C" int lm_detector_get_colour_channels(const lm_detector* d) { return d ? d->cch : lm_set_error(LM_ERR_INVALID, "null detector"); }
+
+extern "C" int lm_rgb_to_grey(int device, const uint8_t* rgb, int64_t pixels, uint8_t* grey) {
+    if (pixels < 0 || (pixels && (!rgb || !grey))) return lm_set_error(LM_ERR_INVALID, "bad argument");
+    if (!pixels) return LM_OK;
+    HIP_TRY(hipSetDevice(device));
+    DevBuf<uint8_t> in, out;
+    int rc = in.ensure((size_t)pixels * 3);
+    if (!rc) rc = out.ensure((size_t)pixels);
+    hipError_t e = hipSuccess;
+    if (!rc) {
+        e = hipMemcpy(in.p, rgb, (size_t)pixels * 3, hipMemcpyHostToDevice);
+        if (e == hipSuccess) { launch_rgb_to_grey(in.p, out.p, (size_t)pixels, nullptr); e = hipGetLastError(); }
+        if (e == hipSuccess) e = hipMemcpy(grey, out.p, (size_t)pixels, hipMemcpyDeviceToHost);   // (synchronises with the null stream)
+    }
+    in.release(); out.release();
+    if (rc) return rc;
+    return e == hipSuccess ? LM_OK : lm_set_error(LM_ERR_HIP, "lm_rgb_to_grey: %s", hipGetErrorString(e));
+}
+
 extern "C" int lm_detector_create_modalities(int num_features, const int* T, int num_levels, int device, const char* const* modalities,
                                              int num_modalities, lm_detector** out) {
     if (!out) return lm_set_error(LM_ERR_INVALID, "out is null");

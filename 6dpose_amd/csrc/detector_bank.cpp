@@ -188,13 +188,21 @@ extern "C" int lm_detector_add_template(lm_detector* d, const uint8_t* rgb, cons
 // chunk of views, not per view.  A view whose candidate lists exceed what the selection kernel sorts in LDS (very large
 // objects), or a detector with more than kTrainMaxFeatures features, takes the host selection (add_template_resident), which
 // yields the same templates; LM_TRAIN_HOST=1 forces it (tests compare the two).
+// The rasteriser's colour image of a view into the detector's frame buffer: as it is, or — a grey detector — through the fixed-point RGB2GRAY of
+// k_rgb_to_grey (what lm_rgb_to_grey gives a caller who trains from colour photographs), without leaving the device.
+static int rendered_colour_to_frame(lm_detector* d, const uint8_t* view_rgb, size_t npx, hipStream_t s) {
+    if (d->cch == 1) { launch_rgb_to_grey(view_rgb, d->frame_rgb.p, npx, s); HIP_TRY(hipGetLastError()); }
+    else HIP_TRY(hipMemcpyAsync(d->frame_rgb.p, view_rgb, npx * 3, hipMemcpyDeviceToDevice, s));
+    return LM_OK;
+}
+
 static int add_rendered_view_host(lm_detector* d, lm_mesh* m, int i, int width, int height, const char* class_id, std::vector<uint16_t>& hdepth,
                                   std::vector<uint8_t>& hmask, int32_t* box_wh_view) {
     const size_t npx = (size_t)width * height;
     d->frame_valid = false;
     d->have_mask[0] = d->have_mask[1] = false;
     d->cur_rgb = d->frame_rgb.p; d->cur_depth = d->frame_depth.p;
-    if (d->use[0]) HIP_TRY(hipMemcpyAsync(d->frame_rgb.p, m->d_rgb + (size_t)i * npx * 3, npx * 3, hipMemcpyDeviceToDevice, d->stream));
+    if (d->use[0]) { int rc = rendered_colour_to_frame(d, m->d_rgb + (size_t)i * npx * 3, npx, d->stream); if (rc) return rc; }
     if (d->use[1]) HIP_TRY(hipMemcpyAsync(d->frame_depth.p, m->d_depth + (size_t)i * npx, npx * 2, hipMemcpyDeviceToDevice, d->stream));
     HIP_TRY(hipMemcpyAsync(hdepth.data(), m->d_depth + (size_t)i * npx, npx * 2, hipMemcpyDeviceToHost, d->stream));
     HIP_TRY(hipStreamSynchronize(d->stream));
@@ -268,7 +276,7 @@ static int add_templates_rendered(lm_detector* d, lm_mesh* m, const char* class_
         for (int i = 0; i < n; ++i) {
             d->cur_rgb = d->frame_rgb.p; d->cur_depth = d->frame_depth.p;
             const uint16_t* view_depth = m->d_depth + (size_t)i * npx;    // a colour-only detector has no depth frame: the mask comes from the rasteriser's buffer
-            if (d->use[0]) HIP_TRY(hipMemcpyAsync(d->frame_rgb.p, m->d_rgb + (size_t)i * npx * 3, npx * 3, hipMemcpyDeviceToDevice, s));
+            if (d->use[0] && (rc = rendered_colour_to_frame(d, m->d_rgb + (size_t)i * npx * 3, npx, s))) return rc;
             if (d->use[1]) HIP_TRY(hipMemcpyAsync(d->frame_depth.p, view_depth, npx * 2, hipMemcpyDeviceToDevice, s));
             if ((rc = run_frontend_training(d))) return rc;
             launch_train_prep(d->use[1] ? d->frame_depth.p : view_depth, nullptr, g, strong_sq, d->extract_threshold, T.keys.p + keys_view * i, kTrainCap,

@@ -56,7 +56,7 @@ int setup_geometry(lm_detector* d, int W, int H, bool check_match_preconditions)
     const size_t n0 = (size_t)W * H;
     int rc;
     // (a modality outside the detector's set has no frame buffer and no intermediates; its arena blocks exist, stay zero and are never written)
-    if (d->use[0] && (rc = d->frame_rgb.ensure(n0 * 3))) return rc;
+    if (d->use[0] && (rc = d->frame_rgb.ensure(n0 * d->cch))) return rc;
     if (d->use[1] && (rc = d->frame_depth.ensure(n0))) return rc;
     if (d->use[1] && (rc = d->nrm_raw.ensure(n0))) return rc;
 
@@ -96,7 +96,7 @@ int setup_geometry(lm_detector* d, int W, int H, bool check_match_preconditions)
         LevelBufs& b = d->lvl[l];
         b.W = g.lv[l].W; b.H = g.lv[l].H;
         size_t n = (size_t)b.W * b.H;
-        if (d->use[0] && l > 0 && (rc = b.rgb.ensure(n * 3))) return rc;
+        if (d->use[0] && l > 0 && (rc = b.rgb.ensure(n * d->cch))) return rc;
         if (d->use[0] && (rc = b.mag.ensure(n))) return rc;
         if (d->use[0] && (rc = b.ang.ensure(n))) return rc;
         if (d->use[1] && (rc = b.nrm.ensure(n))) return rc;
@@ -120,7 +120,7 @@ int upload_frame(lm_detector* d, const uint8_t* rgb, const uint16_t* depth, int 
     d->cur_rgb = d->frame_rgb.p; d->cur_depth = d->frame_depth.p;
     const size_t n = (size_t)W * H;
     const bool m0 = masks && masks[0], m1 = masks && d->nmod == 2 && masks[1];
-    const size_t nc = d->use[0] ? n * 3 : 0, nd = d->use[1] ? n * 2 : 0;     // only the sources of the set are staged and uploaded
+    const size_t nc = d->use[0] ? n * d->cch : 0, nd = d->use[1] ? n * 2 : 0;     // only the sources of the set are staged and uploaded
     size_t bytes = nc + nd + (m0 ? n : 0) + (m1 ? n : 0);
     if ((rc = ensure_pinned(d, bytes))) return rc;
     uint8_t* st = (uint8_t*)d->pinned;
@@ -172,13 +172,13 @@ int run_frontend_training(lm_detector* d) {
         LevelBufs& b = d->lvl[l];
         const uint8_t* src = l == 0 ? d->cur_rgb : b.rgb.p;
         st.njobs = 0;                                                                                                 // (the chains of the set's modalities only)
-        if (d->use[0]) fe_job_colour(st.job[st.njobs++], src, b.mag.p, b.ang.p, b.W, b.H, thr_sq);                    // LL.cpp:367-504
+        if (d->use[0]) fe_job_colour(st.job[st.njobs++], src, b.mag.p, b.ang.p, b.W, b.H, thr_sq, d->cch);                    // LL.cpp:367-504
         if (d->use[1]) {
             if (l == 0) fe_job_normals(st.job[st.njobs++], d->cur_depth, d->nrm_raw.p, b.nrm.p, b.W, b.H, d->distance_threshold,
                                        d->difference_threshold);                                                      // LL.cpp:729-819
             else fe_job_nn_down2(st.job[st.njobs++], d->lvl[l - 1].nrm.p, b.nrm.p, d->lvl[l - 1].W, d->lvl[l - 1].H); // LL.cpp:857-880
         }
-        if (d->use[0] && l + 1 < L) fe_job_pyrdown(st.job[st.njobs++], src, d->lvl[l + 1].rgb.p, b.W, b.H);           // LL.cpp:557-581
+        if (d->use[0] && l + 1 < L) fe_job_pyrdown(st.job[st.njobs++], src, d->lvl[l + 1].rgb.p, b.W, b.H, d->cch);           // LL.cpp:557-581
         launch_fe_stage(st, s);
     }
     HIP_TRY(hipGetLastError());
@@ -202,7 +202,7 @@ extern "C" int lm_detector_store_frame(lm_detector* d, int slot, const uint8_t* 
     }
     const size_t n = (size_t)width * height;
     int rc;
-    const size_t nc = rgb ? n * 3 : 0, nd = depth ? n : 0;                   // elements of the set's sources
+    const size_t nc = rgb ? n * d->cch : 0, nd = depth ? n : 0;                   // elements of the set's sources
     if (d->slot_rgb[slot].cap < nc || d->slot_depth[slot].cap < nd)         // about to be reallocated: a frame in flight may still be
         HIP_TRY(hipStreamSynchronize(d->stream));                          // copying out of the old buffer
     if (nc && (rc = d->slot_rgb[slot].ensure(nc))) return rc;
@@ -240,7 +240,7 @@ extern "C" int lm_detector_select_frame(lm_detector* d, int slot) {
         HIP_TRY(hipStreamWaitEvent(d->stream, d->resident_reader, 0));
         d->resident_reader = nullptr;
     }
-    if (d->use[0]) HIP_TRY(hipMemcpyAsync(d->frame_rgb.p, d->slot_rgb[slot].p, n * 3, hipMemcpyDeviceToDevice, d->stream));
+    if (d->use[0]) HIP_TRY(hipMemcpyAsync(d->frame_rgb.p, d->slot_rgb[slot].p, n * d->cch, hipMemcpyDeviceToDevice, d->stream));
     if (d->use[1]) HIP_TRY(hipMemcpyAsync(d->frame_depth.p, d->slot_depth[slot].p, n * 2, hipMemcpyDeviceToDevice, d->stream));
     d->have_mask[0] = d->have_mask[1] = false;
     d->last_h2d_ms = 0.f;

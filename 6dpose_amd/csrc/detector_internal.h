@@ -81,6 +81,9 @@ struct lm_detector {
     int nmod = 2;
     int mod_kind[2] = {0, 1};
     bool use[2] = {true, true};
+    // Channels of the colour image (lm_detector_set_colour_channels): 3, or 1 for a grey camera.  Sizes every colour buffer, staging slice and upload,
+    // and selects the front end's grey job kinds; nothing downstream of the quantised maps sees it.
+    int cch = 3;
 
     // device
     int device = 0;

@@ -84,7 +84,7 @@ static int run_frontend_batch(lm_detector* d, int first, int nb, hipStream_t s, 
             LevelBufs& B = d->level_bufs(b, l);
             B.W = d->lvl[l].W; B.H = d->lvl[l].H;
             const size_t n = (size_t)B.W * B.H;
-            if (d->use[0] && l > 0 && (rc = B.rgb.ensure(n * 3))) return rc;
+            if (d->use[0] && l > 0 && (rc = B.rgb.ensure(n * d->cch))) return rc;
             if (d->use[0] && (rc = B.mag.ensure(n))) return rc;
             if (d->use[0] && (rc = B.ang.ensure(n))) return rc;
             if (d->use[1] && (rc = B.nrm.ensure(n))) return rc;
@@ -114,13 +114,13 @@ static int run_frontend_batch(lm_detector* d, int first, int nb, hipStream_t s, 
             LevelBufs& B = d->level_bufs(b, l);
             const uint8_t* src = l == 0 ? sl.in_rgb : B.rgb.p;
             room(3);
-            if (d->use[0]) fe_job_colour(st.job[st.njobs++], src, nullptr /* magnitudes: addTemplate only */, B.ang.p, B.W, B.H, thr_sq);      // LL.cpp:367-504
+            if (d->use[0]) fe_job_colour(st.job[st.njobs++], src, nullptr /* magnitudes: addTemplate only */, B.ang.p, B.W, B.H, thr_sq, d->cch);      // LL.cpp:367-504
             if (d->use[1]) {
                 if (l == 0) fe_job_normals(st.job[st.njobs++], sl.in_depth, b == 0 ? d->nrm_raw.p : d->nrm_raw_x[b - 1].p, B.nrm.p, B.W, B.H,
                                            d->distance_threshold, d->difference_threshold);                                      // LL.cpp:729-819
                 else fe_job_nn_down2(st.job[st.njobs++], d->level_bufs(b, l - 1).nrm.p, B.nrm.p, d->level_bufs(b, l - 1).W, d->level_bufs(b, l - 1).H);   // LL.cpp:857-880
             }
-            if (d->use[0] && l + 1 < L) fe_job_pyrdown(st.job[st.njobs++], src, d->level_bufs(b, l + 1).rgb.p, B.W, B.H);                     // LL.cpp:557-581
+            if (d->use[0] && l + 1 < L) fe_job_pyrdown(st.job[st.njobs++], src, d->level_bufs(b, l + 1).rgb.p, B.W, B.H, d->cch);                     // LL.cpp:557-581
         }
         if (l > 0) build_lm_jobs(l - 1);
         flush();
@@ -829,7 +829,7 @@ static int ingest_entry(lm_detector* d, int r, size_t n) {
         HIP_TRY(hipStreamCreateWithFlags(&g.stream, hipStreamNonBlocking));
         for (int i = 0; i < lm_detector::kSlots; ++i) { HIP_TRY(hipEventCreate(&g.t0[i])); HIP_TRY(hipEventCreate(&g.t1[i])); }
     }
-    g.depth_off = d->use[0] ? (n * 3 + 15) & ~(size_t)15 : 0;       // the depth image behind the colour image, 16-byte aligned (host entry and device entry alike);
+    g.depth_off = d->use[0] ? (n * d->cch + 15) & ~(size_t)15 : 0;       // the depth image behind the colour image, 16-byte aligned (host entry and device entry alike);
     const size_t bytes = g.depth_off + (d->use[1] ? n * 2 : 0);     // a detector with one modality keeps (and uploads) only that modality's image
     if (g.pinned_bytes[r] < bytes) {
         if (g.pinned[r]) (void)hipHostFree(g.pinned[r]);
@@ -887,7 +887,7 @@ extern "C" int lm_detector_submit_frame(lm_detector* d, const uint8_t* rgb, cons
     lm_detector::Ingest& g = d->ingest;
     uint8_t* st = (uint8_t*)g.pinned[r];
     const auto tp0 = std::chrono::steady_clock::now();
-    const size_t nc = d->use[0] ? n * 3 : 0, nd = d->use[1] ? n * 2 : 0;
+    const size_t nc = d->use[0] ? n * d->cch : 0, nd = d->use[1] ? n * 2 : 0;
     staged_copy(d, st, rgb, nc, st + g.depth_off, (const uint8_t*)depth, nd);  // zero-copy when the caller filled lm_detector_ingest_buffer's pointers
     const auto tp1 = std::chrono::steady_clock::now();
     if (g.reader[r]) {                                            // a resident re-match of the entry's previous frame may still read it (another slot's front end)

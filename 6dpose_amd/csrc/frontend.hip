@@ -204,6 +204,119 @@ static __device__ __forceinline__ void color_quant_body(const int bx, const int 
     }
 }
 
+// ---- the colour chain on a ONE-channel image (a detector with colour_channels = 1: kFeColourGrey) ----
+// quantizedOrientations on a frame whose three channels are equal takes channel 0 everywhere (mag1 >= mag2 && mag1 >= mag3, LL.cpp:395-412),
+// so this is color_quant_body on the replicated image, byte for byte, with what one channel allows: a byte per pixel in LDS (6.4 KB of
+// intermediates against 17.4), the horizontal pass on four pixels per thread from three dwords (two 16-bit sums per multiply-add: 256 x 255
+// fits), the vertical pass on two.  The border rule is the same — every stage evaluated at the clamped position — but taken at the other end:
+// the tile is LOADED at clamped positions, both blur passes then run on the tile's own (virtual) grid, which makes their taps regular, and
+// Sobel picks its neighbours at the clamped index.  smoothed(p) of a pixel p inside the image only ever reads clamped loads, so it is the
+// replicate-border blur; virtual positions outside the image hold values nothing reads.
+static __device__ __forceinline__ void grey_quant_body(const int bx, const int by, const uint8_t* __restrict__ img, float* __restrict__ mag,
+                                                       uint8_t* __restrict__ onehot, int W, int H, float thr_sq) {
+    constexpr int kGRow = (kCTX + 10 + 3) / 4;                                       // dwords per row of the loaded tile (42 bytes -> 11)
+    __shared__ uint32_t s_g[(kCTY + 10) * kGRow];                                    // pixels at clamp(y0-5 ..), clamp(x0-5 ..), a byte each
+    __shared__ __attribute__((aligned(8))) uint16_t s_tmp[kCTY + 10][kCTX + 4];      // horizontal pass at virtual columns x0-2 .. x0+TX+1, all halo rows
+    __shared__ __attribute__((aligned(4))) uint8_t s_sm[kCTY + 4][kCTX + 4];         // smoothed at virtual y0-2 .., x0-2 ..
+    __shared__ uint32_t s_q4[(kCTY + 2) * kQRowWords];                               // as in color_quant_body
+    __shared__ __attribute__((aligned(16))) float s_mag[kCTY][kCTX];
+    const int x0 = bx * kCTX, y0 = by * kCTY, tid = threadIdx.x;
+    const uint32_t w7[7] = {8, 28, 56, 72, 56, 28, 8};
+    for (int i = tid; i < (kCTY + 10) * (kCTX + 10); i += 256) {
+        const int ty = i / (kCTX + 10), tx = i - ty * (kCTX + 10);
+        reinterpret_cast<uint8_t*>(s_g)[ty * (kGRow * 4) + tx] = img[(size_t)clampi(y0 - 5 + ty, 0, H - 1) * W + clampi(x0 - 5 + tx, 0, W - 1)];
+    }
+    __syncthreads();
+    // horizontal pass: a thread takes four neighbouring columns 4 g .. 4 g + 3 of a row; their taps are bytes 4 g .. 4 g + 9 of the row.
+    // word k = bytes k .. k + 3: its even bytes are tap k of columns 0 and 2, its odd bytes tap k of columns 1 and 3.
+    if (tid < (kCTY + 10) * ((kCTX + 4) / 4)) {
+        const int ty = tid / ((kCTX + 4) / 4), g = tid - ty * ((kCTX + 4) / 4);
+        const uint32_t d0 = s_g[ty * kGRow + g], d1 = s_g[ty * kGRow + g + 1], d2 = s_g[ty * kGRow + g + 2];
+        const uint32_t wk[7] = {d0, __builtin_amdgcn_alignbyte(d1, d0, 1), __builtin_amdgcn_alignbyte(d1, d0, 2), __builtin_amdgcn_alignbyte(d1, d0, 3),
+                                d1, __builtin_amdgcn_alignbyte(d2, d1, 1), __builtin_amdgcn_alignbyte(d2, d1, 2)};
+        uint32_t p02 = 0, p13 = 0;
+#pragma unroll
+        for (int k = 0; k < 7; ++k) {
+            p02 += w7[k] * (wk[k] & 0x00FF00FFu);
+            p13 += w7[k] * ((wk[k] >> 8) & 0x00FF00FFu);
+        }
+        *reinterpret_cast<uint2*>(&s_tmp[ty][4 * g]) = make_uint2((p02 & 0xFFFFu) | (p13 << 16), (p02 >> 16) | (p13 & 0xFFFF0000u));
+    }
+    __syncthreads();
+    // vertical pass: two neighbouring columns per thread, a dword of two 16-bit sums per tap
+    for (int i = tid; i < (kCTY + 4) * ((kCTX + 4) / 2); i += 256) {
+        const int ty = i / ((kCTX + 4) / 2), p = i - ty * ((kCTX + 4) / 2);
+        uint32_t a0 = 0, a1 = 0;
+#pragma unroll
+        for (int k = 0; k < 7; ++k) {
+            const uint32_t t = *reinterpret_cast<const uint32_t*>(&s_tmp[ty + k][2 * p]);
+            a0 += w7[k] * (t & 0xFFFFu); a1 += w7[k] * (t >> 16);
+        }
+        *reinterpret_cast<uint16_t*>(&s_sm[ty][2 * p]) = (uint16_t)(((a0 + 32768u) >> 16) | (((a1 + 32768u) >> 16) << 8));
+    }
+    __syncthreads();
+    // Sobel + quantisation at (y0-1+ty, x0-1+tx); s_sm index of virtual (vy, vx) = (vy - y0 + 2, vx - x0 + 2), neighbours at the clamped position
+    for (int i = tid; i < (kCTY + 2) * (kCTX + 2); i += 256) {
+        const int ty = i / (kCTX + 2), tx = i - ty * (kCTX + 2);
+        const int y = y0 - 1 + ty, x = x0 - 1 + tx;
+        uint8_t q = 0;
+        if (x >= 0 && y >= 0 && x < W && y < H) {
+            const int sy = ty + 1, sx = tx + 1;
+            const int ym = y > 0 ? sy - 1 : sy, yp = y < H - 1 ? sy + 1 : sy, xm = x > 0 ? sx - 1 : sx, xp = x < W - 1 ? sx + 1 : sx;
+            const int p00 = s_sm[ym][xm], p01 = s_sm[ym][sx], p02 = s_sm[ym][xp];
+            const int p10 = s_sm[sy][xm], p12 = s_sm[sy][xp];
+            const int p20 = s_sm[yp][xm], p21 = s_sm[yp][sx], p22 = s_sm[yp][xp];
+            const int bdx = (p02 + 2 * p12 + p22) - (p00 + 2 * p10 + p20), bdy = (p20 + 2 * p21 + p22) - (p00 + 2 * p01 + p02);
+            const int bmag = bdx * bdx + bdy * bdy;
+            if (ty >= 1 && ty <= kCTY && tx >= 1 && tx <= kCTX) s_mag[ty - 1][tx - 1] = (float)bmag;
+            if (x > 0 && y > 0 && x < W - 1 && y < H - 1) {
+                const float ang = fast_atan2_deg((float)bdy, (float)bdx);
+                const float v = rintf(__fmul_rn(ang, (float)(16.0 / 360.0)));   // cvRound: half to even
+                const int iv = v < 0.f ? 0 : (v > 255.f ? 255 : (int)v);
+                q = (uint8_t)(iv & 7);
+            }
+        }
+        reinterpret_cast<uint8_t*>(s_q4)[ty * (kQRowWords * 4) + tx] = (uint8_t)(1u << q);
+    }
+    __syncthreads();
+    // hysteresisGradient's vote and the stores: color_quant_body's, statement for statement (that body stays untouched: its instructions are what
+    // every RGB detector has run since round 6)
+    if (tid < kCTY * kCTX / 4) {
+        const int ty = tid >> 3, c = tid & 7;
+        const int y = y0 + ty, x = x0 + 4 * c;
+        if (x < W && y < H) {
+            uint32_t sr[3], kr[3];
+#pragma unroll
+            for (int dy = 0; dy < 3; ++dy) {
+                const uint32_t lo = s_q4[(ty + dy) * kQRowWords + c], hi = s_q4[(ty + dy) * kQRowWords + c + 1];
+                full_add(lo, __builtin_amdgcn_alignbyte(hi, lo, 1), __builtin_amdgcn_alignbyte(hi, lo, 2), sr[dy], kr[dy]);
+            }
+            uint32_t b0, k3, u, k4;
+            full_add(sr[0], sr[1], sr[2], b0, k3);
+            full_add(kr[0], kr[1], kr[2], u, k4);
+            const uint32_t b1 = u ^ k3, k5 = u & k3;
+            const uint32_t b2 = k4 ^ k5, b3 = k4 & k5;
+            const uint32_t win = b3 | (b2 & (b1 | b0));
+            const size_t o = (size_t)y * W + x;
+            const bool yin = y > 0 && y < H - 1;
+            uint32_t keep = 0;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const float m = s_mag[ty][4 * c + q];
+                if (yin && x + q > 0 && x + q < W - 1 && m > thr_sq) keep |= 0xFFu << (8 * q);
+                if (mag && x + q < W) mag[o + q] = m;
+            }
+            const uint32_t res = win & keep;
+            if (x + 3 < W && ((reinterpret_cast<uintptr_t>(onehot) + o) & 3) == 0) *reinterpret_cast<uint32_t*>(onehot + o) = res;
+            else {
+#pragma unroll
+                for (int q = 0; q < 4; ++q)
+                    if (x + q < W) onehot[o + q] = (uint8_t)(res >> (8 * q));
+            }
+        }
+    }
+}
+
 // ---- cv::pyrDown 8UC3 (LL.cpp:566; Appendix A.6): 5x5 [1 4 6 4 1], REFLECT_101, (sum+128)>>8 ----
 static __device__ __forceinline__ int reflect101(int p, int n) {
     if (n == 1) return 0;
@@ -227,6 +340,39 @@ static __device__ __forceinline__ void pyrdown_body(const int bx, const int by, 
         s += w[j] * rs;
     }
     dst[(size_t)y * Wo * 3 + i] = (uint8_t)((s + 128) >> 8);
+}
+
+// the same on a one-channel image (kFePyrDownGrey): a thread per output pixel
+static __device__ __forceinline__ void pyrdown_grey_body(const int bx, const int by, const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, int W, int H,
+                                                         int Wo, int Ho) {
+    const int x = bx * 256 + threadIdx.x, y = by;
+    if (x >= Wo) return;
+    const int w[5] = {1, 4, 6, 4, 1};
+    int cx[5];
+#pragma unroll
+    for (int k = 0; k < 5; ++k) cx[k] = reflect101(2 * x + k - 2, W);
+    int s = 0;
+#pragma unroll
+    for (int j = 0; j < 5; ++j) {
+        const uint8_t* row = src + (size_t)reflect101(2 * y + j - 2, H) * W;
+        int rs = 0;
+#pragma unroll
+        for (int k = 0; k < 5; ++k) rs += w[k] * row[cx[k]];
+        s += w[j] * rs;
+    }
+    dst[(size_t)y * Wo + x] = (uint8_t)((s + 128) >> 8);
+}
+
+// (4899 R + 9617 G + 1868 B + 8192) >> 14: the 8-bit fixed point of OpenCV's RGB2GRAY.  UNPINNED: stated from OpenCV's documentation of the
+// conversion, not checked against an OpenCV build (none here); rgb_to_grey_ref in lm_abi.py is the same formula in numpy and the tests hold the two together.
+__global__ void __launch_bounds__(256) k_rgb_to_grey(const uint8_t* __restrict__ rgb, uint8_t* __restrict__ grey, size_t n) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const uint8_t* p = rgb + 3 * i;
+    grey[i] = (uint8_t)((4899u * p[0] + 9617u * p[1] + 1868u * p[2] + 8192u) >> 14);
+}
+void launch_rgb_to_grey(const uint8_t* rgb, uint8_t* grey, size_t pixels, hipStream_t s) {
+    if (pixels) hipLaunchKernelGGL(k_rgb_to_grey, dim3((unsigned)((pixels + 255) / 256)), dim3(256), 0, s, rgb, grey, pixels);
 }
 
 // ---- quantizedNormals (LL.cpp:729-817; Appendix A.7) + cv::medianBlur(5) (LL.cpp:818), replicate border ----------
@@ -911,6 +1057,9 @@ static __device__ __forceinline__ void bits_rows_block_body(const int blk, const
 // ~30 ns — with one workgroup per tile (10.8k for the first stage of four VGA frames) a CU held 1.3 workgroups on average and the
 // stage took as long as the dispatcher needed (42 us; profiles/r03_pmc.txt: 5 waves per CU).  A few workgroups per CU walk the
 // tiles instead (flat index + k * grid).
+// kCh = the colour image's channels: the instantiation for 3 holds the RGB colour chain and pyrDown, the one for 1 the grey ones (a detector launches
+// one of the two: the bodies' __shared__ arrays add up per kernel, and with both chains inside neither would keep kFeWaves workgroups on a CU).
+template <int kCh>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kFeWaves, kFeWaves)))   // kFeWaves persistent workgroups per CU (knobs: fe_wgs_per_cu) = as many waves per SIMD
 k_fe_stage(FeStage st, int total) {
     for (int blk = (int)blockIdx.x; blk < total; blk += (int)gridDim.x) {
@@ -921,9 +1070,15 @@ k_fe_stage(FeStage st, int total) {
         const int bz = (int)fast_div((uint32_t)local, J.m_gxgy, (uint32_t)(J.gx * J.gy)), rem = local - bz * J.gx * J.gy;
         const int by = (int)fast_div((uint32_t)rem, J.m_gx, (uint32_t)J.gx), bx = rem - by * J.gx;
         switch (J.kind) {
-            case kFeColour: color_quant_body(bx, by, (const uint8_t*)J.in, (float*)J.out0, (uint8_t*)J.out1, J.W, J.H, J.f); break;
+            case kCh == 3 ? kFeColour : kFeColourGrey:           // (the other instantiation's kinds fall to the default: nothing)
+                if (kCh == 3) color_quant_body(bx, by, (const uint8_t*)J.in, (float*)J.out0, (uint8_t*)J.out1, J.W, J.H, J.f);
+                else grey_quant_body(bx, by, (const uint8_t*)J.in, (float*)J.out0, (uint8_t*)J.out1, J.W, J.H, J.f);
+                break;
             case kFeNormals: normals_median_body(bx, by, (const uint16_t*)J.in, (uint8_t*)J.out0, (uint8_t*)J.out1, J.W, J.H, J.a, J.b); break;
-            case kFePyrDown: pyrdown_body(bx, by, (const uint8_t*)J.in, (uint8_t*)J.out0, J.W, J.H, J.a, J.b); break;
+            case kCh == 3 ? kFePyrDown : kFePyrDownGrey:
+                if (kCh == 3) pyrdown_body(bx, by, (const uint8_t*)J.in, (uint8_t*)J.out0, J.W, J.H, J.a, J.b);
+                else pyrdown_grey_body(bx, by, (const uint8_t*)J.in, (uint8_t*)J.out0, J.W, J.H, J.a, J.b);
+                break;
             case kFeNnDown: nn_down2_body(bx, by, (const uint8_t*)J.in, (uint8_t*)J.out0, J.W, J.a); break;
             case kFeBuildLm:
                 if ((J.Wd & 3) == 0) build_lm_body4(bx, by, J.lm[bz], J.W, J.H, J.a, J.Wd, J.Hd, (J.Wd + 15) >> 4, J.m_wd, J.m_t, st.resp);
@@ -961,16 +1116,16 @@ k_fe_bits(FeStage st, int total) {
     }
 }
 
-void fe_job_colour(FeJob& j, const uint8_t* rgb, float* mag, uint8_t* onehot, int W, int H, float thr_sq) {
-    j = FeJob{}; j.kind = kFeColour; j.gx = (W + kCTX - 1) / kCTX; j.gy = (H + kCTY - 1) / kCTY; j.gz = 1;
+void fe_job_colour(FeJob& j, const uint8_t* rgb, float* mag, uint8_t* onehot, int W, int H, float thr_sq, int channels) {
+    j = FeJob{}; j.kind = channels == 1 ? kFeColourGrey : kFeColour; j.gx = (W + kCTX - 1) / kCTX; j.gy = (H + kCTY - 1) / kCTY; j.gz = 1;
     j.in = rgb; j.out0 = mag; j.out1 = onehot; j.W = W; j.H = H; j.f = thr_sq;
 }
 void fe_job_normals(FeJob& j, const uint16_t* depth, uint8_t* raw, uint8_t* med, int W, int H, int dist_thr, int diff_thr) {
     j = FeJob{}; j.kind = kFeNormals; j.gx = (W + kCTX - 1) / kCTX; j.gy = (H + kCTY - 1) / kCTY; j.gz = 1;
     j.in = depth; j.out0 = raw; j.out1 = med; j.W = W; j.H = H; j.a = dist_thr; j.b = diff_thr;
 }
-void fe_job_pyrdown(FeJob& j, const uint8_t* src, uint8_t* dst, int W, int H) {
-    j = FeJob{}; j.kind = kFePyrDown; j.a = W / 2; j.b = H / 2; j.gx = (j.a * 3 + 255) / 256; j.gy = j.b; j.gz = 1;
+void fe_job_pyrdown(FeJob& j, const uint8_t* src, uint8_t* dst, int W, int H, int channels) {
+    j = FeJob{}; j.kind = channels == 1 ? kFePyrDownGrey : kFePyrDown; j.a = W / 2; j.b = H / 2; j.gx = (j.a * channels + 255) / 256; j.gy = j.b; j.gz = 1;
     j.in = src; j.out0 = dst; j.W = W; j.H = H;
 }
 void fe_job_nn_down2(FeJob& j, const uint8_t* src, uint8_t* dst, int W, int H) {
@@ -1045,7 +1200,10 @@ void launch_fe_stage(FeStage& st, hipStream_t s) {
     if (total <= 0) return;
     const int per_cu = knobs().fe_wgs_per_cu;
     const int grid = per_cu > 0 ? std::min(total, fe_cus() * per_cu) : total;
-    hipLaunchKernelGGL(k_fe_stage, dim3(grid), dim3(256), 0, s, st, total);
+    bool grey = false;                                               // the grey kinds come from a detector with colour_channels = 1, which never adds the RGB ones
+    for (int i = 0; i < st.njobs; ++i) grey = grey || st.job[i].kind == kFeColourGrey || st.job[i].kind == kFePyrDownGrey;
+    if (grey) hipLaunchKernelGGL(k_fe_stage<1>, dim3(grid), dim3(256), 0, s, st, total);
+    else hipLaunchKernelGGL(k_fe_stage<3>, dim3(grid), dim3(256), 0, s, st, total);
 }
 void launch_fe_bits(FeStage& st, hipStream_t s) {
     if (knobs().fe_bits_split) {                          // LM_FE_BITS_SPLIT=1 (measurements): the strip-record jobs and the pair-stream jobs as two launches

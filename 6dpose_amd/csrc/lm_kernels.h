@@ -34,7 +34,8 @@ void upload_normal_lut(const uint8_t lut400[400]);
 struct LmJob { const uint8_t* quant; const uint8_t* mask; uint8_t* lm; uint8_t* strips; };
 // (the bit-plane jobs reuse the two output slots — 24 jobs of a batch of 8 frames must fit the 4 KB of kernel arguments —: `lm` = the strip
 // records of the level / the top level's pair stream, `strips` = for the pair stream the flat position of the modality's block in it, as an integer)
-enum { kFeNone = 0, kFeColour, kFeNormals, kFePyrDown, kFeNnDown, kFeBuildLm, kFeBitsRows, kFeTopBits, kFeTopBitsAligned, kFeTopBitsTile, kFeBitsRowsTile };
+enum { kFeNone = 0, kFeColour, kFeNormals, kFePyrDown, kFeNnDown, kFeBuildLm, kFeBitsRows, kFeTopBits, kFeTopBitsAligned, kFeTopBitsTile, kFeBitsRowsTile,
+       kFeColourGrey, kFePyrDownGrey };   // the colour chain and pyrDown of a one-channel image: the stage kernel's grey instantiation runs them (a launch holds the RGB kinds or the grey ones, never both)
 struct FeJob {
     int kind, gx, gy, gz, first;          // job kind, its block grid, its first flat block index (set by launch_fe_stage)
     const void* in; void* out0; void* out1;
@@ -50,9 +51,10 @@ struct FeJob {
 constexpr int kFeMaxJobs = 24;            // 3-4 jobs per frame of a batch (stage 1), kMaxLevels per frame in the last stage: the struct is a kernel argument (< 4 KB)
 struct FeStage { int njobs; uint32_t resp = kRespDefault /* resp_pack: every writer of response memories of the launch */; FeJob job[kFeMaxJobs]; };
 static_assert(sizeof(FeStage) + 16 <= 4096, "FeStage is passed by value: kernel arguments are limited to 4 KB");
-void fe_job_colour(FeJob& j, const uint8_t* rgb, float* mag, uint8_t* onehot, int W, int H, float thr_sq);
+// channels: 3 = interleaved R G B (any order: the chain treats the channels alike), 1 = grey (kFeColourGrey / kFePyrDownGrey)
+void fe_job_colour(FeJob& j, const uint8_t* rgb, float* mag, uint8_t* onehot, int W, int H, float thr_sq, int channels = 3);
 void fe_job_normals(FeJob& j, const uint16_t* depth, uint8_t* raw, uint8_t* med, int W, int H, int dist_thr, int diff_thr);
-void fe_job_pyrdown(FeJob& j, const uint8_t* src, uint8_t* dst, int W, int H);
+void fe_job_pyrdown(FeJob& j, const uint8_t* src, uint8_t* dst, int W, int H, int channels = 3);
 void fe_job_nn_down2(FeJob& j, const uint8_t* src, uint8_t* dst, int W, int H);
 // The writers below take their arrays indexed by modality kind ([0] colour, [1] normals) and serve the kinds [m0, m0 + nm): (0, 2) for the
 // default set, (0, 1) or (1, 1) for a detector with one modality (gz = nm slices of blocks; the absent kind's pointers are never read).
@@ -68,6 +70,8 @@ void fe_job_top_bits(FeJob& j, const uint8_t* const quant[2], const uint8_t* con
 int fe_top_bits_kind(int W, int H, int T, const uint32_t bit0[2], int mode, int m0 = 0, int nm = 2);   // kFeTopBitsTile / kFeTopBitsAligned / kFeTopBits (the only one that needs a zeroed stream)
 void launch_fe_stage(FeStage& st, hipStream_t s);
 void launch_fe_bits(FeStage& st, hipStream_t s);      // a launch of bit-plane jobs only (fe_job_bits_rows, fe_job_top_bits)
+// grey[i] = (4899 R + 9617 G + 1868 B + 8192) >> 14 of pixel i of an interleaved R G B image (training a grey detector from renders, lm_rgb_to_grey)
+void launch_rgb_to_grey(const uint8_t* rgb, uint8_t* grey, size_t pixels, hipStream_t s);
 
 // ---- matching (match_bytes.hip, match_bits.hip): reference A8-A11, LL.cpp:1284-1428, 1788-1941 ----
 struct LevelGeom {        // one pyramid level of the current frame

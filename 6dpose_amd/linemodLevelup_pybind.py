@@ -24,16 +24,17 @@ residual == -1 convention.
 Array conventions (np2mat/ndarray_converter.cpp:159-336 is zero-copy and never checks dtypes, so a
 float depth image is silently reinterpreted — driver comment linemod_and_levelup_test.py:117):
 this wrapper validates instead: sources = [rgb uint8 HxWx3, depth uint16 HxW]; other dtypes raise.
+Detector(..., colour_channels=1) takes a grey image, uint8 HxW, in the colour slot.
 
 This file is the import name only.  The code lives in the flat modules beside it, one per subsystem: lm_abi (library loading, the
 structures, the prototype table of the C ABI), lm_detector, lm_icp, lm_render and lm_pose_error.  The loaded library is
 lm_abi._lib, set by load_library(); a global assigned after import does not travel through a re-export, so it has no alias here.
 """
 from lm_abi import (LM_ICP_POINT_TO_POINT, LM_ICP_SCENE_FROM_SCENE, MATCH_DTYPE, IcpOptions, PipelineTimings, RenderOptions, Timings,
-                    _CDetection, _CMatch, _CPoseResult, _as_depth, _as_mask, _as_rgb, _check, _ptr, _share_hip_runtime_with_torch,
-                    bind_near_device, library_path, load_library)
+                    _CDetection, _CMatch, _CPoseResult, _as_depth, _as_grey, _as_mask, _as_rgb, _check, _ptr, _share_hip_runtime_with_torch,
+                    bind_near_device, library_path, load_library, rgb_to_grey_ref)
 from lm_detector import (Comm, Detector, Match, NMSBoxes, Template, bank_file_info, bank_file_modalities, merge_matches, nms,
-                         nms_norms)
+                         nms_norms, rgb_to_grey)
 from lm_icp import (ICP_ESTIMATIONS, IcpContext, Pipeline, _icp_flags, _icp_options, _pose_dict, evaluate_registration, poseRefine,
                     pose_refine_batch)
 from lm_render import OVERLAY_MODES, SHADINGS, Mesh, _colour, add_templates_rendered, render_options

@@ -91,6 +91,9 @@ PROTOTYPES = {
     "lm_detector_create": (I, [I, PI, I, I, PP]),
     "lm_detector_create_modalities": (I, [I, PI, I, I, PS, I, PP]),
     "lm_detector_get_modalities": (I, [P, PS]),
+    "lm_detector_set_colour_channels": (I, [P, I]),
+    "lm_detector_get_colour_channels": (I, [P]),
+    "lm_rgb_to_grey": (I, [I, P, I64, P]),
     "lm_detector_destroy": (None, [P]),
     "lm_detector_add_template": (I, [P, P, P, P, I, I, S]),
     "lm_detector_read_class": (I, [P, S, S]),
@@ -277,8 +280,34 @@ def _ptr(a: Optional[np.ndarray]):
 def _as_rgb(a, what="sources[0]") -> np.ndarray:
     a = np.asarray(a)
     if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3:
-        raise RuntimeError("%s must be a uint8 HxWx3 image (got %s %s)" % (what, a.dtype, a.shape))
+        hint = " — a grey image needs a detector made with colour_channels=1" if a.dtype == np.uint8 and (a.ndim == 2 or (a.ndim == 3 and a.shape[2] == 1)) else ""
+        raise RuntimeError("%s must be a uint8 HxWx3 image (got %s %s)%s" % (what, a.dtype, a.shape, hint))
     return np.ascontiguousarray(a)
+
+
+def _as_grey(a, what="sources[0]") -> np.ndarray:
+    """The colour source of a detector with colour_channels=1: uint8 HxW (HxWx1 is taken as that)."""
+    a = np.asarray(a)
+    if a.ndim == 3 and a.shape[2] == 1:
+        a = a[:, :, 0]
+    if a.dtype != np.uint8 or a.ndim != 2:
+        hint = " — this detector was made with colour_channels=1" if a.ndim == 3 else ""
+        raise RuntimeError("%s must be a uint8 HxW grey image (got %s %s)%s" % (what, a.dtype, a.shape, hint))
+    return np.ascontiguousarray(a)
+
+
+def _rgb_last_axis(rgb) -> np.ndarray:
+    a = np.asarray(rgb)
+    if a.dtype != np.uint8 or a.ndim < 1 or a.shape[-1] != 3:
+        raise RuntimeError("rgb must be a uint8 array whose last axis holds R, G, B (got %s %s)" % (a.dtype, a.shape))
+    return a
+
+
+def rgb_to_grey_ref(rgb) -> np.ndarray:
+    """What rgb_to_grey computes, in numpy (no device): (4899 R + 9617 G + 1868 B + 8192) >> 14 per pixel of a uint8 (..., 3) array in
+    R, G, B order — the 8-bit fixed point of OpenCV's RGB2GRAY (unpinned: stated from its documentation, not checked against a build)."""
+    v = _rgb_last_axis(rgb).astype(np.int64)
+    return ((4899 * v[..., 0] + 9617 * v[..., 1] + 1868 * v[..., 2] + 8192) >> 14).astype(np.uint8)
 
 
 def _as_depth(a, what="sources[1]") -> np.ndarray:

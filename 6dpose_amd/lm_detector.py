@@ -11,7 +11,7 @@ from typing import List, Optional, Sequence
 
 import numpy as np
 
-from lm_abi import MATCH_DTYPE, Timings, _CMatch, _as_depth, _as_mask, _as_rgb, _check, _ptr, load_library
+from lm_abi import MATCH_DTYPE, Timings, _CMatch, _as_depth, _as_grey, _as_mask, _as_rgb, _check, _ptr, _rgb_last_axis, load_library
 
 
 class Match:
@@ -72,11 +72,13 @@ class Comm:
 class Detector:
     """linemodLevelup::Detector (LL.h:264-375) running on one MI355X."""
 
-    def __init__(self, *args, device: Optional[int] = None, modalities: Optional[Sequence[str]] = None):
+    def __init__(self, *args, device: Optional[int] = None, modalities: Optional[Sequence[str]] = None, colour_channels: int = 3):
         """Detector(), Detector(T), Detector(num_features, T) (pybind11.cpp:26-28).  modalities= selects the modality set, the
         counterpart of Detector(const std::vector<Ptr<Modality>>&, T) (LL.cpp:1694-1700): ("ColorGradient", "DepthNormal") — the
         default —, ("ColorGradient",) or ("DepthNormal",), with the parameters of the reference's constructors (LL.cpp:1684-1692).
-        `sources` and `masks` then carry one array per modality of the set, in its order."""
+        `sources` and `masks` then carry one array per modality of the set, in its order.  colour_channels=1 makes the colour source a grey
+        image, uint8 HxW (a mono8 camera): the results are those of the same image replicated to three channels, at a third of the upload and
+        of the colour chain's work (lm_detector_set_colour_channels)."""
         lib = load_library()
         num_features, T = 0, None
         if len(args) == 1:
@@ -103,6 +105,9 @@ class Detector:
         self._lib = lib
         self.device = device
         self._shard = (0, 1)
+        self._cch = 3
+        if colour_channels != 3:
+            self.setColourChannels(colour_channels)
 
     def __del__(self):
         h, self._h = getattr(self, "_h", None), None
@@ -113,19 +118,33 @@ class Detector:
         """The detector's modality set, names as in the class YAML (lm_detector_get_modalities)."""
         return self._mods
 
+    def setColourChannels(self, channels: int) -> None:
+        """lm_detector_set_colour_channels: 3 (uint8 HxWx3 colour sources) or 1 (uint8 HxW grey).  Refused with frames in flight and, for 1, on a
+        detector without ColorGradient; drops the resident and the stored frames.  No file stores it."""
+        if isinstance(channels, bool) or not isinstance(channels, (int, np.integer)):
+            raise RuntimeError("colour_channels must be 3 or 1, got %r" % (channels,))
+        _check(self._lib.lm_detector_set_colour_channels(self._h, int(channels)))
+        self._cch = int(channels)
+
+    def getColourChannels(self) -> int:
+        return int(self._lib.lm_detector_get_colour_channels(self._h))
+
+    def _colour(self, a):
+        return _as_grey(a) if self._cch == 1 else _as_rgb(a)
+
     def _sources(self, sources, check_len: bool = False):
         """(rgb or None, depth or None, (H, W)): one array per modality of the set, in its order."""
         if check_len and len(sources) != len(self._mods):
             raise RuntimeError("sources.size() == modalities.size() [LL.cpp:1707]")
         if len(self._mods) == 2:
-            rgb, depth = _as_rgb(sources[0]), _as_depth(sources[1])
+            rgb, depth = self._colour(sources[0]), _as_depth(sources[1])
             if rgb.shape[:2] != depth.shape:
                 raise RuntimeError("rgb and depth sizes differ")
             return rgb, depth, depth.shape
         if len(sources) != 1:
             raise RuntimeError("sources.size() == modalities.size() [LL.cpp:1707]")
         if self._mods[0] == "ColorGradient":
-            rgb = _as_rgb(sources[0])
+            rgb = self._colour(sources[0])
             return rgb, None, rgb.shape[:2]
         depth = _as_depth(sources[0], "sources[0]")
         return None, depth, depth.shape
@@ -418,7 +437,7 @@ class Detector:
         return int(self._lib.lm_detector_get_batch(self._h))
 
     def ingestBuffers(self, width: int, height: int):
-        """(rgb uint8 HxWx3, depth uint16 HxW) views of the pinned staging memory the NEXT submitFrame() will upload from
+        """(rgb uint8 HxWx3 — HxW on a detector with colour_channels=1 —, depth uint16 HxW) views of the pinned staging memory the NEXT submitFrame() will upload from
         (lm_detector_ingest_buffer): fill them in place and pass them to submitFrame — no staging copy.  Valid until that
         frame has been collected.  A detector with one modality returns a 1-tuple: the buffer of that modality."""
         pr, pd = ctypes.c_void_p(), ctypes.c_void_p()
@@ -426,7 +445,8 @@ class Detector:
         n = int(width) * int(height)
         rgb = depth = None
         if pr.value:
-            rgb = np.ctypeslib.as_array(ctypes.cast(pr, ctypes.POINTER(ctypes.c_uint8)), shape=(n * 3,)).reshape(height, width, 3)
+            rgb = np.ctypeslib.as_array(ctypes.cast(pr, ctypes.POINTER(ctypes.c_uint8)), shape=(n * self._cch,))
+            rgb = rgb.reshape(height, width) if self._cch == 1 else rgb.reshape(height, width, 3)
         if pd.value:
             depth = np.ctypeslib.as_array(ctypes.cast(pd, ctypes.POINTER(ctypes.c_uint16)), shape=(n,)).reshape(height, width)
         return tuple(b for b in (rgb, depth) if b is not None)
@@ -608,6 +628,16 @@ def bank_file_modalities(path) -> tuple:
     report ("ColorGradient", "DepthNormal")."""
     out = (ctypes.c_char_p * 2)()
     return tuple(out[i].decode() for i in range(_check(load_library().lm_bank_file_modalities(os.fspath(path).encode(), out))))
+
+
+def rgb_to_grey(rgb, device: int = 0) -> np.ndarray:
+    """The grey image a detector with colour_channels=1 trains on when add_templates_rendered feeds it a colour render, for any uint8 (..., 3)
+    array in R, G, B order: (4899 R + 9617 G + 1868 B + 8192) >> 14, computed by the same kernel (lm_rgb_to_grey).  Train a mono camera's
+    templates from colour photographs through it.  rgb_to_grey_ref is the formula in numpy."""
+    a = np.ascontiguousarray(_rgb_last_axis(rgb))
+    out = np.zeros(a.shape[:-1], np.uint8)
+    _check(load_library().lm_rgb_to_grey(int(device), _ptr(a), out.size, _ptr(out)))
+    return out
 
 
 def merge_matches(records: np.ndarray) -> np.ndarray:

@@ -105,6 +105,20 @@ int lm_detector_create(int num_features, const int *T, int num_levels, int devic
 int lm_detector_create_modalities(int num_features, const int *T, int num_levels, int device, const char *const *modalities,
                                   int num_modalities, lm_detector **out);
 int lm_detector_get_modalities(const lm_detector *d, const char *names[2]);
+/* The colour image's format: 3 interleaved channels (the default) or 1, a grey image (a mono8 camera).  Set once, after creation: anything but
+ * 1 or 3 is LM_ERR_INVALID, as are 1 on a detector without the colour modality and a change with frames in flight.  Every entry point that takes
+ * a colour pointer (lm_detector_match, _set_frame, _store_frame / _select_frame, _submit_frame, _ingest_buffer, _add_template) then reads or
+ * returns width * height * channels bytes; no signature changes.  A grey frame g gives at every pyramid level, byte for byte, what the three-channel
+ * frame with R = G = B = g gives (quantizedOrientations takes channel 0 where the three magnitudes are equal, LL.cpp:395-412; cv::pyrDown keeps
+ * equal channels equal) — by kernels that load, stage, blur and differentiate one channel.  A change drops the resident frame and the frames parked
+ * by lm_detector_store_frame.  The setting is state of this detector in this process: class files, packed banks and lm_detector_write_params do not store it,
+ * and templates are the same objects either way — a bank trained in grey loads into an RGB detector and the other way round.
+ * lm_detector_add_templates_rendered on a grey detector converts the rasteriser's colour image with lm_rgb_to_grey's arithmetic, on the device. */
+int lm_detector_set_colour_channels(lm_detector *d, int channels);
+int lm_detector_get_colour_channels(const lm_detector *d);
+/* grey[i] = (4899 R + 9617 G + 1868 B + 8192) >> 14 for the `pixels` pixels of an interleaved R, G, B image, on `device`: the 8-bit fixed point of
+ * OpenCV's RGB2GRAY (unpinned: not checked against an OpenCV build).  For training a grey detector from colour photographs. */
+int lm_rgb_to_grey(int device, const uint8_t *rgb, int64_t pixels, uint8_t *grey);
 void lm_detector_destroy(lm_detector *d);
 
 /* Detector::addTemplate (pybind11.cpp:29, LL.cpp:1943-1975).  Returns the new template_id (>=0),

@@ -1,10 +1,13 @@
-// Similarity kernels of Detector::matchClass on gfx950, on bit planes (the default): the bit-sliced
-// carry-save adders and weighted_sum, k_pack_bits / k_local_bits (strip records of the levels below the top, reference
-// similarityLocal LL.cpp:1366-1428, 1855-1938), k_pack_top / k_coarse_bits (pair stream of the top level, LL.cpp:1284-1354,
-// 1835-1852), their launchers and the LM_LAUNCH_* macros that pick the instantiation.  The byte kernels are in match_bytes.hip,
-// what both use in match_device.h; data layout and bank: match_bytes.hip.
-#include "match_device.h"
+// Similarity kernels of Detector::matchClass on gfx950, on bit planes (the default): weighted_sum, k_pack_bits /
+// k_local_bits (strip records of the levels below the top, reference similarityLocal LL.cpp:1366-1428, 1855-1938), k_pack_top / k_coarse_bits /
+// k_coarse_bits_batch (pair stream of the top level, LL.cpp:1284-1354, 1835-1852), their launchers and the dispatcher that picks the
+// instantiation.  A kernel here holds what is particular to it — its load scheme, its counters, how it reserves candidate slots —; the stages
+// it shares with match_wide.hip's kernels (template head, hit test and emission of the coarse pass; window, arg-max, update and epilogue of
+// the refinement; the packers' indexing) are in match_planes.h, the bit-sliced adders in match_device.h.  The byte kernels are in
+// match_bytes.hip; data layout and bank: match_bytes.hip.
+#include "match_planes.h"
 #include <algorithm>
+#include <type_traits>
 
 namespace lm {
 
@@ -61,17 +64,14 @@ static __device__ __forceinline__ uint32_t pack16(const uint4& v) { return pack4
 // this kernel serves the banks and geometries that keep the byte planes — a fallback launch of k_local may follow — and the tests of both).
 __global__ void __launch_bounds__(256)
 k_pack_bits(BitsBatch B, uint32_t sm_off0, uint32_t records, int NS, int Hd) {
-    const uint32_t i = blockIdx.x * 256u + threadIdx.x;             // record = ((plane * NS + s) * Hd + row)
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= records) return;
-    const uint32_t q = i / (uint32_t)Hd, s = q % (uint32_t)NS;
-    const uint8_t* src = B.strips[blockIdx.y] + sm_off0 + (size_t)i * 16;
-    const uint4 a = *reinterpret_cast<const uint4*>(src);
-    uint4 b = make_uint4(0, 0, 0, 0);
-    if (s + 1 < (uint32_t)NS) b = *reinterpret_cast<const uint4*>(src + (size_t)Hd * 16);      // the next strip of this row
+    uint4 a, b;
+    const size_t at = strip_cells(B.strips[blockIdx.y], sm_off0, i, NS, Hd, a, b);
     uint2 r;
     r.x = pack16(a);
     r.y = pack16(b);
-    *reinterpret_cast<uint2*>(B.bits[blockIdx.y] + (sm_off0 >> 1) + (size_t)i * 8) = r;
+    *reinterpret_cast<uint2*>(B.bits[blockIdx.y] + at) = r;
 }
 
 // Refinement on strip records (LL.cpp:1855-1938, similarityLocal :1366-1428).  8 lanes per candidate — lane j owns window rows 2j and 2j + 1,
@@ -97,32 +97,8 @@ k_local_bits(FrameBatch fb, BitsBatch B, FrameGeom g, const TemplEntry* __restri
     __shared__ uint32_t s_cnt[kMaxBatch];
     const int lane = threadIdx.x & 63, grp = lane >> 3, j = lane & 7;
     const int nb = fb.nb;
-    // Frame -> XCD affinity as in k_local (an XCD's L2 holds ONE frame's planes), for ANY batch size up to 8: frame f is served by the workgroups of
-    // the XCDs x with x % nb == f — 8 / nb of them each when nb divides 8, else some frames get one XCD more than others.  (Round 3 fell back to
-    // dealing the items of all frames to all workgroups unless nb divided 8: a 5-frame launch — the first and last launches of a short stream —
-    // then cost 35 us per frame against 26 in an 8-frame launch.)
-    int f_lo = 0, f_hi = nb;
-    uint32_t w_first = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), w_step = gridDim.x * (blockDim.x >> 6);
-    if (nb > 1 && nb <= 8 && (gridDim.x & 7) == 0) {
-        const int xcd = (int)(blockIdx.x & 7);
-        f_lo = xcd % nb; f_hi = f_lo + 1;
-        const uint32_t mine = (uint32_t)((7 - f_lo) / nb + 1);      // XCDs serving this frame: f_lo, f_lo + nb, ...
-        const uint32_t wpb = blockDim.x >> 6;
-        w_first = ((blockIdx.x >> 3) * mine + (uint32_t)(xcd / nb)) * wpb + (threadIdx.x >> 6);
-        w_step = (gridDim.x >> 3) * mine * wpb;
-    }
-    if ((int)threadIdx.x < nb) {
-        const unsigned long long nc = fb.f[threadIdx.x].counters[0] & kCandMask;
-        s_cnt[threadIdx.x] = nc < cand_cap ? (uint32_t)nc : cand_cap;
-        s_acc[threadIdx.x][0] = 0; s_acc[threadIdx.x][1] = 0;
-    }
-    __syncthreads();
-    for (int f = 0; f < nb; ++f) {                                  // k_dedupe's hash table, emptied here like k_local does
-        unsigned long long* table = fb.f[f].dedupe_table;
-        if (!table) continue;
-        const uint32_t tsize = dedupe_slots_for(s_cnt[f], dedupe_cap_slots);
-        for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < tsize; i += gridDim.x * blockDim.x) table[i] = ~0ull;
-    }
+    const LocalShare share = local_share(nb);
+    local_prologue(fb, s_cnt, s_acc, cand_cap, dedupe_cap_slots);
     // The pair stream k_coarse_bits has just read is zeroed for the slot's next frame: the front end ORs it together (frontend.hip, top_bits_body)
     if (B.top_clear_units)
         for (int f = 0; f < nb; ++f)
@@ -130,11 +106,11 @@ k_local_bits(FrameBatch fb, BitsBatch B, FrameGeom g, const TemplEntry* __restri
                 reinterpret_cast<uint4*>(B.top_clear[f])[i] = make_uint4(0u, 0u, 0u, 0u);
     const int src0 = (lane & ~7) << 2;                              // ds_bpermute address of the group's first lane
     const uint32_t rowoff = 16u * (uint32_t)j;                      // records of rows 2j, 2j + 1 behind the window's first row
-    for (int fr = f_lo; fr < f_hi; ++fr) {
+    for (int fr = share.f_lo; fr < share.f_hi; ++fr) {
         const FrameSlot& F = fb.f[fr];
         const BufRsrc bits = make_rsrc(B.bits[fr]);
         const uint32_t nc = s_cnt[fr], ngroups = (nc + 7u) >> 3;
-        for (uint32_t gi = w_first; gi < ngroups; gi += w_step) {
+        for (uint32_t gi = share.w_first; gi < ngroups; gi += share.w_step) {
             const uint32_t ci = gi * 8u + (uint32_t)grp;
             const bool valid = ci < nc;
             Candidate cd{0, 0, 0.f, 0};
@@ -147,46 +123,13 @@ k_local_bits(FrameBatch fb, BitsBatch B, FrameGeom g, const TemplEntry* __restri
             uint32_t evals = 0, bytes = 0;
             for (int l = g.levels - 2; l >= 0; --l) {
                 const LevelGeom& lv = g.lv[l];
-                const int T = lv.T, W = lv.W, H = lv.H, Wd = lv.Wd, Hd = lv.Hd;
-                const int border = 8 * T, offset = T / 2 + (T % 2 - 1);
-                const uint32_t HS8 = (uint32_t)Hd * 8u;
-                const uint32_t zero_off = (lv.sm_off[1] + 8u * (uint32_t)(T * T) * ((uint32_t)lv.NS * (uint32_t)Hd * 16u)) >> 1;   // the level's all-zero plane
                 const TemplEntry e = entries[(size_t)pyr * g.levels + l];
-                // LL.cpp:1871-1880 (the clamp) and 1380-1381 (window origin), exactly as k_local
-                const int max_x = W - e.width - border, max_y = H - e.height - border;
-                int x = mx * 2 + 1, y = my * 2 + 1;
-                x = x > border ? x : border;  y = y > border ? y : border;
-                x = x < max_x ? x : max_x;    y = y < max_y ? y : max_y;
-                const int gx = x / T - 8, gy = y / T - 8;
-                const int off_x = gx * T, off_y = gy * T;
-                const bool all_in = e.min_x >= 0 && e.min_y >= 0 && gx >= 0 && gy >= 0 &&
-                                    ((e.max_x + off_x) / T + 16 <= Wd) && ((e.max_y + off_y) / T + 16 <= Hd);
-                const bool want = alive && !leave;
-                if (want && !all_in) leave = true;
-                const bool run = want && all_in;
-                const int nf = e.nf, nfp = run ? (int)e.nf_padded : 0;
-                int nmax = nfp;
-#pragma unroll
-                for (int o = 32; o > 0; o >>= 1) { const int t = __shfl_xor(nmax, o, 64); nmax = t > nmax ? t : nmax; }
-                nmax = __builtin_amdgcn_readfirstlane(nmax);
-                const uint32_t Kbase = (uint32_t)(((gx >> 4) * Hd + gy) * 8);
-                const uint32_t gxl = (uint32_t)(gx & 15);
+                const LocalWindow win = local_window(lv, e, mx, my, alive, leave);
+                const int nfp = win.nfp, nmax = win.nmax;
                 const uint32_t* fw = feat_word + e.feat_start;
                 uint32_t cA[kN], cB[kN];                            // bit-sliced counters of rows 2j / 2j + 1: even bits count the 1s, odd bits the 4s
 #pragma unroll
                 for (int k = 0; k < kN; ++k) { cA[k] = 0; cB[k] = 0; }
-                // lane j fetches the words of features f0 + 2j, f0 + 2j + 1 (entries start at multiples of 8 words, f0 is a multiple of 16)
-                auto fetch = [&](int f0) -> uint2 {
-                    uint2 w = make_uint2(0u, 0u);
-                    if (f0 + 2 * j < nfp) w = *reinterpret_cast<const uint2*>(fw + f0 + 2 * j);
-                    return w;
-                };
-                // a feature word (base0 | column class, lm_kernels.h) -> offset of its first record in the bit arena, 2 x the window's cell inside it
-                auto prep = [&](uint32_t w, bool on, uint32_t& off, uint32_t& s2) {
-                    s2 = ((w & 15u) + gxl) << 1;
-                    const uint32_t o = ((w & ~15u) >> 1) + Kbase + ((s2 >> 5) ? HS8 : 0u);
-                    off = on ? o : zero_off;                        // beyond this candidate's features (or no candidate): the zero plane
-                };
                 uint32_t offx = 0, offy = 0, sx = 0, sy = 0;
                 auto batch = [&](int half, uint32_t& eA, uint32_t& eB) {           // features 8 half .. 8 half + 7 of the current 16
                     uint4 v[8];
@@ -207,13 +150,13 @@ k_local_bits(FrameBatch fb, BitsBatch B, FrameGeom g, const TemplEntry* __restri
                     eA = add8(xa, cA[0], cA[1], cA[2]);
                     eB = add8(xb, cB[0], cB[1], cB[2]);
                 };
-                uint2 wn = fetch(0);
+                uint2 wn = local_fetch(fw, 0, j, nfp);
                 for (int f0 = 0; f0 < nmax; f0 += 16) {
-                    const uint2 w = wn;
+                    const uint2 wd = wn;
                     const bool on = f0 + 2 * j < nfp;
-                    wn = fetch(f0 + 16);                            // the next 16 words while these are worked on
-                    prep(w.x, on, offx, sx);
-                    prep(w.y, on, offy, sy);
+                    wn = local_fetch(fw, f0 + 16, j, nfp);          // the next 16 words while these are worked on
+                    local_prep(wd.x, on, win.gxl, win.Kbase, win.HS8, win.zero_off, offx, sx);
+                    local_prep(wd.y, on, win.gxl, win.Kbase, win.HS8, win.zero_off, offy, sy);
                     uint32_t e1A, e1B;
                     batch(0, e1A, e1B);
                     if (f0 + 8 < nmax) {                            // wave-uniform
@@ -226,105 +169,62 @@ k_local_bits(FrameBatch fb, BitsBatch B, FrameGeom g, const TemplEntry* __restri
                         add_eights1<kN>(cB, e1B);
                     }
                 }
-                // Once per candidate and level: the two rows of the lane side by side — bit 2c = row 2j, bit 2c + 1 = row 2j + 1 of window
-                // column c —, S = n1 + 4 n4 bit-sliced, the lane's maximum by a descent from the top bit, its FIRST position in raster order.
+                // Once per candidate and level: the two rows of the lane side by side, S = n1 + 4 n4 bit-sliced, its maximum and where
                 uint32_t S[kS];
                 {
                     uint32_t n1[kN], n4[kN];
-#pragma unroll
-                    for (int k = 0; k < kN; ++k) {
-                        n1[k] = (cA[k] & 0x55555555u) | ((cB[k] << 1) & 0xAAAAAAAAu);
-                        n4[k] = ((cA[k] >> 1) & 0x55555555u) | (cB[k] & 0xAAAAAAAAu);
-                    }
+                    local_interleave<kN>(n1, n4, cA, cB);
                     weighted_sum<kA, kN>(S, n1, n4);
                 }
-                uint32_t mask = 0xFFFFFFFFu, val = 0;
-#pragma unroll
-                for (int k = kS - 1; k >= 0; --k) {
-                    const uint32_t t = mask & S[k];
-                    if (t) { mask = t; val |= 1u << k; }
-                }
-                const uint32_t upper = mask & 0x55555555u;           // positions of row 2j attaining the maximum come first in raster order
-                const uint32_t pick = upper ? upper : mask;
-                const uint32_t bitp = (uint32_t)__ffs((int)pick) - 1u;
-                const uint32_t pos = ((2u * (uint32_t)j + (bitp & 1u)) << 4) + (bitp >> 1);   // row * 16 + column
-                uint32_t key = (val << 8) | (255u - pos);
-#pragma unroll
-                for (int o = 1; o < 8; o <<= 1) { const uint32_t t = (uint32_t)__shfl_xor((int)key, o, 64); key = t > key ? t : key; }
-                const int raw = (int)(key >> 8);
-                int br = -1, bc = -1;                               // LL.cpp:1910-1911
-                float best = 0.f;
-                if (raw > 0) {
-                    const int idx = 255 - (int)(key & 0xFF);
-                    br = idx >> 4; bc = idx & 15;
-                    best = score_of(raw, nf);
-                }
-                if (run) {
-                    ++evals;
-                    bytes += 256u * (uint32_t)nf;                   // algorithmic response bytes of this 16x16 evaluation
-                    sim = best;
-                    mx = (x / T - 8 + bc) * T + offset;             // LL.cpp:1930-1931
-                    my = (y / T - 8 + br) * T + offset;
-                    if (sim < threshold) alive = false;             // LL.cpp:1935
-                }
+                int raw, br, bc;
+                local_argmax<kS>(S, j, raw, br, bc);
+                local_update(win, lv.T, raw, br, bc, threshold, sim, mx, my, alive, evals, bytes);
             }
-            if (valid && j == 0) {
-                F.todo[ci] = leave ? 1 : 0;
-                if (!leave) {
-                    if (ci < cap) {
-                        Candidate m;
-                        m.x = mx; m.y = my; m.score = sim;
-                        m.work = alive ? work : -1;
-                        F.matches_dev[ci] = m;
-                    }
-                    atomicAdd(&s_acc[fr][0], (unsigned long long)evals);
-                    atomicAdd(&s_acc[fr][1], (unsigned long long)bytes);
-                }
-            }
+            if (valid && j == 0) local_store(F, ci, leave, cap, mx, my, sim, alive, work, s_acc[fr], evals, bytes);
         }
     }
-    __syncthreads();
-    if ((int)threadIdx.x < nb && s_acc[threadIdx.x][0] != 0) {
-        unsigned long long* st = fb.f[threadIdx.x].counters + 8 + 2 * (blockIdx.x & (kStatShards - 1));
-        atomicAdd(st, s_acc[threadIdx.x][0]);
-        atomicAdd(st + 1, s_acc[threadIdx.x][1]);
-    }
+    local_flush_stats(fb, s_acc);
 }
 
 void launch_pack_bits(const BitsBatch& B, int nb, const LevelGeom& lv, hipStream_t s) {
     const uint32_t records = (uint32_t)(2 * 8 * lv.T * lv.T) * (uint32_t)lv.NS * (uint32_t)lv.Hd;
     hipLaunchKernelGGL(k_pack_bits, dim3((records + 255) / 256, nb), dim3(256), 0, s, B, lv.sm_off[0], records, lv.NS, lv.Hd);
 }
+// The instantiation for a bank and a table, for every two-plane kernel: counters of 9 bits (kHi = 5) for entries of up to kBitsSmallMax features, of
+// 14 (kHi = 10) beyond, each at the waves per SIMD the kernel declares for it; kA = the table's low weight.  launch(kHi, kWaves, kA) receives them
+// as std::integral_constants, i.e. as template arguments.
+template <int kWavesSmall, int kWavesBig, class Launch>
+static void with_bits_instance(int max_features, int low_weight, Launch launch) {
+    auto with_a = [&](auto a) {
+        if (max_features > kBitsSmallMax) launch(std::integral_constant<int, 10>(), std::integral_constant<int, kWavesBig>(), a);
+        else launch(std::integral_constant<int, 5>(), std::integral_constant<int, kWavesSmall>(), a);
+    };
+    if (low_weight == 2) with_a(std::integral_constant<int, 2>());
+    else if (low_weight == 3) with_a(std::integral_constant<int, 3>());
+    else with_a(std::integral_constant<int, 1>());
+}
 void launch_local_bits(const FrameBatch& fb, const BitsBatch& B, const FrameGeom& g, const BankDev& bank, uint32_t cand_cap, float threshold,
                        uint32_t cap, uint32_t dedupe_cap_slots, int grid_blocks, int max_features, int low_weight, hipStream_t s) {
-#define LM_LAUNCH_LOCAL_BITS(HI, A) \
-    hipLaunchKernelGGL((k_local_bits<HI, 4, A>), dim3(grid_blocks), dim3(256), 0, s, fb, B, g, bank.entries, bank.feat_word, bank.work, cand_cap, threshold, cap, dedupe_cap_slots)
-    const bool big = max_features > kBitsSmallMax;
-    if (low_weight == 2) { if (big) LM_LAUNCH_LOCAL_BITS(10, 2); else LM_LAUNCH_LOCAL_BITS(5, 2); }
-    else if (low_weight == 3) { if (big) LM_LAUNCH_LOCAL_BITS(10, 3); else LM_LAUNCH_LOCAL_BITS(5, 3); }
-    else { if (big) LM_LAUNCH_LOCAL_BITS(10, 1); else LM_LAUNCH_LOCAL_BITS(5, 1); }
-#undef LM_LAUNCH_LOCAL_BITS
+    with_bits_instance<4, 4>(max_features, low_weight, [&](auto hi, auto waves, auto a) {
+        hipLaunchKernelGGL((k_local_bits<hi(), waves(), a()>), dim3(grid_blocks), dim3(256), 0, s, fb, B, g, bank.entries, bank.feat_word, bank.work, cand_cap, threshold, cap,
+                           dedupe_cap_slots);
+    });
 }
 
 // ---- Coarse pass on the pair stream (LL.cpp:1284-1354 similarity + :1835-1852 scan).  A wave per template, a lane = 32 consecutive
 // positions of the template's map: a feature's load = two consecutive pairs per lane (16 bytes) at pair index (offset >> 5) + lane,
 // funnel-shifted by offset & 31 — the offset is wave-uniform, so both are scalar —, i.e. ONE wave load per feature and 2048 positions
-// (the byte kernel: one per 1008 positions and 16 bytes per position and lane).  Sums bit-sliced as in k_local_bits; the threshold test is
-// a bit-sliced comparison with the smallest raw sum that passes, so integers are formed only for the hits.  The workgroup's 4 templates
-// reserve their candidate slots with ONE atomic on the frame's counter (same-address atomics serialise in the L2: 2000 per frame cost
-// the byte kernel 16 us).  No tiles: the bit-plane refinement needs none.
+// (the byte kernel: one per 1008 positions and 16 bytes per position and lane).  Sums bit-sliced as in k_local_bits; template head, hit
+// test, slot reservation (one atomic per workgroup of 4 templates and pass) and emission: match_planes.h.  No tiles: the bit-plane
+// refinement needs none.
 __global__ void __launch_bounds__(256)
 k_pack_top(TopBits B, uint32_t byte0, uint32_t npairs) {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= npairs) return;
     const uint8_t* src = B.lm[blockIdx.y] + byte0 + (size_t)i * 32;
     const uint4 a = *reinterpret_cast<const uint4*>(src), b = *reinterpret_cast<const uint4*>(src + 16);
-    auto four = [](uint32_t d, int sh) -> uint32_t { return ((((d >> sh) & 0x01010101u) * 0x01020408u) >> 24) & 0xFu; };   // bit sh of 4 bytes -> 4 bits
-    auto bits = [&](const uint4& v, int sh) -> uint32_t { return four(v.x, sh) | (four(v.y, sh) << 4) | (four(v.z, sh) << 8) | (four(v.w, sh) << 12); };
-    uint2 r;
-    r.x = bits(a, 0) | bits(a, 1) | ((bits(b, 0) | bits(b, 1)) << 16);   // the low plane's response a = 1, 2 or 3: bit 0 or bit 1 of the byte; response 4 = bit 2
-    r.y = bits(a, 2) | (bits(b, 2) << 16);
-    *reinterpret_cast<uint2*>(B.bits[blockIdx.y] + (size_t)i * 8) = r;
+    // the low plane's response a = 1, 2 or 3: bit 0 or bit 1 of the byte; response 4 = bit 2
+    *reinterpret_cast<uint2*>(B.bits[blockIdx.y] + (size_t)i * 8) = make_uint2(byte_bits32(a, b, 0) | byte_bits32(a, b, 1), byte_bits32(a, b, 2));
 }
 
 template <int kHi, int kWaves, int kA>
@@ -335,29 +235,12 @@ k_coarse_bits(FrameBatch fb, TopBits B, LevelGeom lv, int level, int levels, con
     __shared__ uint32_t s_tot[4];
     __shared__ unsigned long long s_base;
     const FrameSlot& F = fb.f[blockIdx.y];
-    Candidate* __restrict__ cands = F.cands;
-    unsigned long long* __restrict__ counters = F.counters;
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int work_raw = (int)blockIdx.x * 4 + wave;                       // a wave per template
-    const bool live = work_raw < num_work;
-    const int work = live ? work_raw : num_work - 1;                       // idle waves of the last workgroup shadow a real template and emit nothing
-    const int pyr = work_pyramids[work];
-    const TemplEntry e = entries[(size_t)pyr * levels + level];
-    const int nf = e.nf, nfp = e.nf_padded;
-    const int32_t* fo = feat_off + e.feat_start;
-    const int Wd = lv.Wd, Hd = lv.Hd, T = lv.T, npos = Wd * Hd;
-    const int wf = (e.width - 1) / T + 1, hf = (e.height - 1) / T + 1;      // LL.cpp:1299-1309
-    const int tp = (Hd - hf) * Wd + (Wd - wf) + 1;
-    const int offset = T / 2 + (T % 2 - 1);                                 // LL.cpp:1846
-    const int limit = tp < npos ? tp : npos;                                // positions that carry sums
-    // the smallest raw sum whose score passes (score_of is monotone in raw): LL.cpp:1844 `> threshold`
-    int rmin = (int)(threshold * (float)(4 * nf) / 100.f);
-    if (!(rmin >= 0)) rmin = 0;
-    if (rmin > 4 * nf + 1) rmin = 4 * nf + 1;
-    while (rmin > 0 && score_of(rmin, nf) > threshold) --rmin;
-    while (rmin <= 4 * nf && !(score_of(rmin, nf) > threshold)) ++rmin;
-    const bool zero_passes = score_of(0, nf) > threshold;
+    const CoarseHead h = coarse_head((int)blockIdx.x * 4 + wave, num_work, entries, feat_off, work_pyramids, lv, level, levels, threshold);   // a wave per template
+    const bool live = h.live;
+    const int nfp = h.nfp, npos = h.npos, limit = h.limit;
+    const int32_t* fo = h.fo;
     const BufRsrc bits = make_rsrc(B.bits[blockIdx.y]);
     for (int P0 = 0; P0 < npos; P0 += 2048) {                               // (the same number of passes for every wave of the workgroup)
         const int pos0 = P0 + 32 * lane;                                    // first position of this lane
@@ -399,53 +282,13 @@ k_coarse_bits(FrameBatch fb, TopBits B, LevelGeom lv, int level, int levels, con
         }
         uint32_t S[kS];
         weighted_sum<kA, kN>(S, c1, c4);
-        uint32_t gt = 0, eq = 0xFFFFFFFFu;                                  // S >= rmin, bit-sliced
-#pragma unroll
-        for (int k = kS - 1; k >= 0; --k) {
-            if ((rmin >> k) & 1) eq &= S[k];                                // wave-uniform
-            else { gt |= eq & S[k]; eq &= ~S[k]; }
-        }
-        uint32_t hit_mask = rmin < (1 << kS) ? (gt | eq) : 0u;
-        // positions at or beyond the template's position count hold zero sums (LL.cpp:1299-1309): they are hits only if zero passes
-        const int sums = limit - pos0;                                      // positions of this lane that carry sums
-        const uint32_t summed = sums >= 32 ? 0xFFFFFFFFu : (sums > 0 ? (1u << sums) - 1u : 0u);
-        const int inmap = npos - pos0;
-        const uint32_t mapped = inmap >= 32 ? 0xFFFFFFFFu : (inmap > 0 ? (1u << inmap) - 1u : 0u);
-        hit_mask = (hit_mask & summed) | (zero_passes ? (mapped & ~summed) : 0u);
+        uint32_t summed;
+        uint32_t hit_mask = coarse_hit_mask<kS>(S, h.rmin, h.zero_passes, limit, npos, pos0, summed);
         if (!live) hit_mask = 0;
         int total;
-        const int before = wave_excl_scan(__popc(hit_mask), lane, total);
-        // one atomic per workgroup and pass
-        if (lane == 0) s_tot[wave] = (uint32_t)total;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            const unsigned long long all = (unsigned long long)s_tot[0] + s_tot[1] + s_tot[2] + s_tot[3];
-            s_base = all ? atomicAdd(&counters[0], all) : 0ull;
-        }
-        __syncthreads();
-        unsigned long long slot = s_base + (unsigned long long)before;
-        for (int w = 0; w < wave; ++w) slot += s_tot[w];
-        __syncthreads();                                                    // s_tot / s_base are rewritten by the next pass
-        if (total > 0) {                                                    // wave-uniform
-            uint32_t m = hit_mask;
-            while (m) {
-                const int b = __ffs((int)m) - 1;
-                m &= m - 1;
-                if (slot < cap) {
-                    int raw = 0;
-                    if ((summed >> b) & 1u) {
-#pragma unroll
-                        for (int k = 0; k < kS; ++k) raw |= (int)((S[k] >> b) & 1u) << k;
-                    }
-                    const int jpos = pos0 + b;
-                    const int cy = jpos / Wd, cx = jpos - cy * Wd;
-                    Candidate c;
-                    c.x = cx * T + offset; c.y = cy * T + offset; c.score = score_of(raw, nf); c.work = work;
-                    cands[slot] = c;
-                }
-                ++slot;
-            }
-        }
+        const unsigned long long slot = coarse_reserve_slots(s_tot, s_base, F.counters, hit_mask, lane, wave, total);
+        if (total > 0)                                                      // wave-uniform
+            coarse_emit<kS>(hit_mask, summed, S, slot, cap, pos0, h.Wd, h.T, h.offset, h.nf, h.work, F.cands);
     }
 }
 
@@ -454,7 +297,7 @@ k_coarse_bits(FrameBatch fb, TopBits B, LevelGeom lv, int level, int levels, con
 // offset is the same for every frame, so here the lanes of a (template, frame group) are ONE flat index g = frame * L + lane of the frame,
 // L = ceil(positions / 32), dealt to consecutive waves: a wave may straddle frames, idle lanes exist only behind a group's last frame, and a frame
 // of more than 64 lanes spans waves (no pass loop).  Only the base of a lane's loads differs — its frame's pair stream, a 64-bit address per lane:
-// the slots' streams are separate allocations —; offsets and shifts stay scalar, the arithmetic is k_coarse_bits's.
+// the slots' streams are separate allocations —; offsets and shifts stay scalar, head, hit test and emission are the shared stages of match_planes.h.
 // A workgroup = kWg waves per template x the templates that fit, on the frames [f0, f0 + fpg) of the batch (a group = as many frames as 16 waves
 // hold); it reserves the slots of each of its frames with ONE atomic, and inside them a template's hits lie together in raster order (the wave
 // scan, cut at the frame boundaries; the waves' counts per frame prefix-summed in LDS), which k_local_bits's L2 locality rests on.
@@ -471,24 +314,10 @@ k_coarse_bits_batch(FrameBatch fb, TopBits B, LevelGeom lv, int level, int level
     const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int nwaves = (int)(blockDim.x >> 6);
     const int tl = wv / Wg, ww = wv - tl * Wg;                              // template of the workgroup, wave of the template
-    const int work_raw = (int)blockIdx.x * (nwaves / Wg) + tl;
-    const bool live = work_raw < num_work;
-    const int work = live ? work_raw : num_work - 1;                       // idle waves of the last workgroup shadow a real template and emit nothing
-    const int pyr = work_pyramids[work];
-    const TemplEntry e = entries[(size_t)pyr * levels + level];
-    const int nf = e.nf, nfp = e.nf_padded;
-    const int32_t* fo = feat_off + e.feat_start;
-    const int Wd = lv.Wd, Hd = lv.Hd, T = lv.T, npos = Wd * Hd;
-    const int wf = (e.width - 1) / T + 1, hf = (e.height - 1) / T + 1;      // LL.cpp:1299-1309
-    const int tp = (Hd - hf) * Wd + (Wd - wf) + 1;
-    const int offset = T / 2 + (T % 2 - 1);                                 // LL.cpp:1846
-    const int limit = tp < npos ? tp : npos;                                // positions that carry sums
-    int rmin = (int)(threshold * (float)(4 * nf) / 100.f);                  // the smallest raw sum whose score passes, as k_coarse_bits
-    if (!(rmin >= 0)) rmin = 0;
-    if (rmin > 4 * nf + 1) rmin = 4 * nf + 1;
-    while (rmin > 0 && score_of(rmin, nf) > threshold) --rmin;
-    while (rmin <= 4 * nf && !(score_of(rmin, nf) > threshold)) ++rmin;
-    const bool zero_passes = score_of(0, nf) > threshold;
+    const CoarseHead h = coarse_head((int)blockIdx.x * (nwaves / Wg) + tl, num_work, entries, feat_off, work_pyramids, lv, level, levels, threshold);
+    const bool live = h.live;
+    const int nfp = h.nfp, limit = h.limit;
+    const int32_t* fo = h.fo;
     const int f0 = (int)blockIdx.y * fpg;                                   // the group's frames
     const int nfr = fb.nb - f0 < fpg ? fb.nb - f0 : fpg;
     const int g = ww * 64 + lane;                                           // flat lane of the (template, group)
@@ -536,19 +365,8 @@ k_coarse_bits_batch(FrameBatch fb, TopBits B, LevelGeom lv, int level, int level
     }
     uint32_t S[kS];
     weighted_sum<kA, kN>(S, c1, c4);
-    uint32_t gt = 0, eq = 0xFFFFFFFFu;                                      // S >= rmin, bit-sliced
-#pragma unroll
-    for (int k = kS - 1; k >= 0; --k) {
-        if ((rmin >> k) & 1) eq &= S[k];                                    // wave-uniform
-        else { gt |= eq & S[k]; eq &= ~S[k]; }
-    }
-    uint32_t hit_mask = rmin < (1 << kS) ? (gt | eq) : 0u;
-    // positions at or beyond the template's position count hold zero sums (LL.cpp:1299-1309): they are hits only if zero passes
-    const int sums = limit - pos0;
-    const uint32_t summed = sums >= 32 ? 0xFFFFFFFFu : (sums > 0 ? (1u << sums) - 1u : 0u);
-    const int inmap = npos - pos0;
-    const uint32_t mapped = inmap >= 32 ? 0xFFFFFFFFu : (inmap > 0 ? (1u << inmap) - 1u : 0u);
-    hit_mask = (hit_mask & summed) | (zero_passes ? (mapped & ~summed) : 0u);
+    uint32_t summed;
+    uint32_t hit_mask = coarse_hit_mask<kS>(S, h.rmin, h.zero_passes, limit, h.npos, pos0, summed);
     if (!act) hit_mask = 0;
     // the wave's scan, cut where a frame begins: a frame's lanes are consecutive, so its part of the scan starts at its first lane in this wave
     int total;
@@ -566,26 +384,8 @@ k_coarse_bits_batch(FrameBatch fb, TopBits B, LevelGeom lv, int level, int level
     }
     __syncthreads();
     if (hit_mask) {
-        Candidate* __restrict__ cands = fb.f[frame].cands;
-        unsigned long long slot = s_base[fl] + (unsigned long long)s_cnt[wv][fl] + (unsigned long long)in_frame;
-        uint32_t m = hit_mask;
-        while (m) {
-            const int b = __ffs((int)m) - 1;
-            m &= m - 1;
-            if (slot < cap) {
-                int raw = 0;
-                if ((summed >> b) & 1u) {
-#pragma unroll
-                    for (int k = 0; k < kS; ++k) raw |= (int)((S[k] >> b) & 1u) << k;
-                }
-                const int jpos = pos0 + b;
-                const int cy = jpos / Wd, cx = jpos - cy * Wd;
-                Candidate c;
-                c.x = cx * T + offset; c.y = cy * T + offset; c.score = score_of(raw, nf); c.work = work;
-                cands[slot] = c;
-            }
-            ++slot;
-        }
+        const unsigned long long slot = s_base[fl] + (unsigned long long)s_cnt[wv][fl] + (unsigned long long)in_frame;
+        coarse_emit<kS>(hit_mask, summed, S, slot, cap, pos0, h.Wd, h.T, h.offset, h.nf, h.work, fb.f[frame].cands);
     }
 }
 
@@ -613,27 +413,18 @@ bool launch_coarse_bits(const FrameBatch& fb, const TopBits& B, const FrameGeom&
                         int batch_mode) {
     if (num_work <= 0 || fb.nb <= 0) return false;
     const int level = g.levels - 1;
-    const bool big = max_features > kBitsSmallMax;
     CoarseBatchPlan p;
     const bool can = coarse_batch_plan(fb.nb, g.lv[level].Wd * g.lv[level].Hd, &p);
-    if (can && (batch_mode > 0 || (batch_mode < 0 && fb.nb >= 2 &&p.waves < p.waves_per_frame_kernel))) {
-#define LM_LAUNCH_COARSE_BATCH(HI, WAVES, A) \
-    hipLaunchKernelGGL((k_coarse_bits_batch<HI, WAVES, A>), dim3((num_work + p.tpw - 1) / p.tpw, p.groups), dim3(64 * p.tpw * p.Wg), 0, s, fb, B, g.lv[level], level, g.levels, \
-                       bank.entries, bank.feat_off, bank.work, num_work, threshold, cap, byte0, p.L, p.fpg, p.Wg)
-        if (low_weight == 2) { if (big) LM_LAUNCH_COARSE_BATCH(10, 5, 2); else LM_LAUNCH_COARSE_BATCH(5, 6, 2); }
-        else if (low_weight == 3) { if (big) LM_LAUNCH_COARSE_BATCH(10, 5, 3); else LM_LAUNCH_COARSE_BATCH(5, 6, 3); }
-        else { if (big) LM_LAUNCH_COARSE_BATCH(10, 5, 1); else LM_LAUNCH_COARSE_BATCH(5, 6, 1); }
-#undef LM_LAUNCH_COARSE_BATCH
-        return true;
-    }
-#define LM_LAUNCH_COARSE_BITS(HI, WAVES, A) \
-    hipLaunchKernelGGL((k_coarse_bits<HI, WAVES, A>), dim3((num_work + 3) / 4, fb.nb), dim3(256), 0, s, fb, B, g.lv[level], level, g.levels, bank.entries, bank.feat_off, \
-                       bank.work, num_work, threshold, cap, byte0)
-    if (low_weight == 2) { if (big) LM_LAUNCH_COARSE_BITS(10, 5, 2); else LM_LAUNCH_COARSE_BITS(5, 6, 2); }
-    else if (low_weight == 3) { if (big) LM_LAUNCH_COARSE_BITS(10, 5, 3); else LM_LAUNCH_COARSE_BITS(5, 6, 3); }
-    else { if (big) LM_LAUNCH_COARSE_BITS(10, 5, 1); else LM_LAUNCH_COARSE_BITS(5, 6, 1); }
-#undef LM_LAUNCH_COARSE_BITS
-    return false;
+    const bool batched = can && (batch_mode > 0 || (batch_mode < 0 && fb.nb >= 2 && p.waves < p.waves_per_frame_kernel));
+    with_bits_instance<6, 5>(max_features, low_weight, [&](auto hi, auto waves, auto a) {
+        if (batched)
+            hipLaunchKernelGGL((k_coarse_bits_batch<hi(), waves(), a()>), dim3((num_work + p.tpw - 1) / p.tpw, p.groups), dim3(64 * p.tpw * p.Wg), 0, s, fb, B, g.lv[level], level,
+                               g.levels, bank.entries, bank.feat_off, bank.work, num_work, threshold, cap, byte0, p.L, p.fpg, p.Wg);
+        else
+            hipLaunchKernelGGL((k_coarse_bits<hi(), waves(), a()>), dim3((num_work + 3) / 4, fb.nb), dim3(256), 0, s, fb, B, g.lv[level], level, g.levels, bank.entries,
+                               bank.feat_off, bank.work, num_work, threshold, cap, byte0);
+    });
+    return batched;
 }
 
 }  // namespace lm

@@ -1,5 +1,7 @@
 // Device helpers that the matching units share (match_bytes.hip, match_bits.hip, match_wide.hip): the score, the buffer loads of the arenas,
-// the wave's exclusive scan and the bit-sliced counters of the bit-plane kernels.  What one unit alone uses stays in that unit.  gfx950 only.
+// the wave's exclusive scan and the bit-sliced counters of the bit-plane kernels.  The STAGES that the bit-plane kernels share (template head,
+// hit test and emission of the coarse pass; window, arg-max and epilogue of the refinement; the packers' indexing) are in match_planes.h, which
+// match_bits.hip and match_wide.hip include instead of this file.  What one unit alone uses stays in that unit.  gfx950 only.
 #pragma once
 #include "lm_kernels.h"
 

@@ -1,11 +1,12 @@
 // Similarity kernels of Detector::matchClass on gfx950 for response tables of three or four distinct non-zero values (4 3 2 1 0, 4 2 1 0 0,
-// 4 3 1 0 0, ...), selected with lm_detector_set_paths(3, 2): the schemes of match_bits.hip on TWO sets of bit planes.
+// 4 3 1 0 0, ...), selected with lm_detector_set_paths(3, 2): the schemes of match_bits.hip on TWO sets of bit planes —
+// its kernels' stages through match_planes.h; here only what the second set changes: the loads, the third counter, the sum, the packing.
 // A response v = 0..4 is three binary digits: set 0 keeps the two-plane layout with bit 2c = v & 1 and bit 2c + 1 = (v == 4), set 1 — a second
 // arena of the same layout and size — holds (v >> 1) & 1 at bit 2c and nothing at bit 2c + 1, so the same v_alignbit windows cut both.  The sum of
 // a position is c0 + 2 c1 + 4 c2 with c_i = the number of features whose digit i is set there: three bit-sliced counters instead of two.
 // k_pack_wide / k_local_wide: strip records of the levels below the top; k_pack_top_wide / k_coarse_wide: pair stream of the top level.  The
 // front end writes the byte planes for such tables and these kernels pack them (the front end's own bit-plane writers know two planes).
-#include "match_device.h"
+#include "match_planes.h"
 
 namespace lm {
 
@@ -31,17 +32,13 @@ static __device__ __forceinline__ uint32_t wide4_set1(uint32_t d) { return ((((d
 static __device__ __forceinline__ uint32_t wide16_set0(const uint4& v) { return wide4_set0(v.x) | (wide4_set0(v.y) << 8) | (wide4_set0(v.z) << 16) | (wide4_set0(v.w) << 24); }
 static __device__ __forceinline__ uint32_t wide16_set1(const uint4& v) { return wide4_set1(v.x) | (wide4_set1(v.y) << 8) | (wide4_set1(v.z) << 16) | (wide4_set1(v.w) << 24); }
 
-// Both sets of strip records from the strip bytes (k_pack_bits's indexing: record = ((plane * NS + s) * Hd + row), 32 cells from two 16-byte rows)
+// Both sets of strip records from the strip bytes
 __global__ void __launch_bounds__(256)
 k_pack_wide(BitsBatch B, WidePlanes P, uint32_t sm_off0, uint32_t records, int NS, int Hd) {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= records) return;
-    const uint32_t q = i / (uint32_t)Hd, s = q % (uint32_t)NS;
-    const uint8_t* src = B.strips[blockIdx.y] + sm_off0 + (size_t)i * 16;
-    const uint4 a = *reinterpret_cast<const uint4*>(src);
-    uint4 b = make_uint4(0, 0, 0, 0);
-    if (s + 1 < (uint32_t)NS) b = *reinterpret_cast<const uint4*>(src + (size_t)Hd * 16);      // the next strip of this row
-    const size_t at = (sm_off0 >> 1) + (size_t)i * 8;
+    uint4 a, b;
+    const size_t at = strip_cells(B.strips[blockIdx.y], sm_off0, i, NS, Hd, a, b);
     *reinterpret_cast<uint2*>(B.bits[blockIdx.y] + at) = make_uint2(wide16_set0(a), wide16_set0(b));
     *reinterpret_cast<uint2*>(P.set1[blockIdx.y] + at) = make_uint2(wide16_set1(a), wide16_set1(b));
 }
@@ -61,37 +58,15 @@ k_local_wide(FrameBatch fb, BitsBatch B, WidePlanes P, FrameGeom g, const TemplE
     __shared__ unsigned long long s_acc[kMaxBatch][2];
     __shared__ uint32_t s_cnt[kMaxBatch];
     const int lane = threadIdx.x & 63, grp = lane >> 3, j = lane & 7;
-    const int nb = fb.nb;
-    // frame -> XCD affinity as in k_local_bits
-    int f_lo = 0, f_hi = nb;
-    uint32_t w_first = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), w_step = gridDim.x * (blockDim.x >> 6);
-    if (nb > 1 && nb <= 8 && (gridDim.x & 7) == 0) {
-        const int xcd = (int)(blockIdx.x & 7);
-        f_lo = xcd % nb; f_hi = f_lo + 1;
-        const uint32_t mine = (uint32_t)((7 - f_lo) / nb + 1);
-        const uint32_t wpb = blockDim.x >> 6;
-        w_first = ((blockIdx.x >> 3) * mine + (uint32_t)(xcd / nb)) * wpb + (threadIdx.x >> 6);
-        w_step = (gridDim.x >> 3) * mine * wpb;
-    }
-    if ((int)threadIdx.x < nb) {
-        const unsigned long long nc = fb.f[threadIdx.x].counters[0] & kCandMask;
-        s_cnt[threadIdx.x] = nc < cand_cap ? (uint32_t)nc : cand_cap;
-        s_acc[threadIdx.x][0] = 0; s_acc[threadIdx.x][1] = 0;
-    }
-    __syncthreads();
-    for (int f = 0; f < nb; ++f) {                                  // k_dedupe's hash table, emptied here like k_local does
-        unsigned long long* table = fb.f[f].dedupe_table;
-        if (!table) continue;
-        const uint32_t tsize = dedupe_slots_for(s_cnt[f], dedupe_cap_slots);
-        for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < tsize; i += gridDim.x * blockDim.x) table[i] = ~0ull;
-    }
+    const LocalShare share = local_share(fb.nb);
+    local_prologue(fb, s_cnt, s_acc, cand_cap, dedupe_cap_slots);
     const int src0 = (lane & ~7) << 2;                              // ds_bpermute address of the group's first lane
     const uint32_t rowoff = 16u * (uint32_t)j;                      // records of rows 2j, 2j + 1 behind the window's first row
-    for (int fr = f_lo; fr < f_hi; ++fr) {
+    for (int fr = share.f_lo; fr < share.f_hi; ++fr) {
         const FrameSlot& F = fb.f[fr];
         const BufRsrc bits0 = make_rsrc(B.bits[fr]), bits1 = make_rsrc(P.set1[fr]);
         const uint32_t nc = s_cnt[fr], ngroups = (nc + 7u) >> 3;
-        for (uint32_t gi = w_first; gi < ngroups; gi += w_step) {
+        for (uint32_t gi = share.w_first; gi < ngroups; gi += share.w_step) {
             const uint32_t ci = gi * 8u + (uint32_t)grp;
             const bool valid = ci < nc;
             Candidate cd{0, 0, 0.f, 0};
@@ -104,46 +79,13 @@ k_local_wide(FrameBatch fb, BitsBatch B, WidePlanes P, FrameGeom g, const TemplE
             uint32_t evals = 0, bytes = 0;
             for (int l = g.levels - 2; l >= 0; --l) {
                 const LevelGeom& lv = g.lv[l];
-                const int T = lv.T, W = lv.W, H = lv.H, Wd = lv.Wd, Hd = lv.Hd;
-                const int border = 8 * T, offset = T / 2 + (T % 2 - 1);
-                const uint32_t HS8 = (uint32_t)Hd * 8u;
-                const uint32_t zero_off = (lv.sm_off[1] + 8u * (uint32_t)(T * T) * ((uint32_t)lv.NS * (uint32_t)Hd * 16u)) >> 1;   // the level's all-zero plane (in either arena)
                 const TemplEntry e = entries[(size_t)pyr * g.levels + l];
-                // LL.cpp:1871-1880 (the clamp) and 1380-1381 (window origin), exactly as k_local
-                const int max_x = W - e.width - border, max_y = H - e.height - border;
-                int x = mx * 2 + 1, y = my * 2 + 1;
-                x = x > border ? x : border;  y = y > border ? y : border;
-                x = x < max_x ? x : max_x;    y = y < max_y ? y : max_y;
-                const int gx = x / T - 8, gy = y / T - 8;
-                const int off_x = gx * T, off_y = gy * T;
-                const bool all_in = e.min_x >= 0 && e.min_y >= 0 && gx >= 0 && gy >= 0 &&
-                                    ((e.max_x + off_x) / T + 16 <= Wd) && ((e.max_y + off_y) / T + 16 <= Hd);
-                const bool want = alive && !leave;
-                if (want && !all_in) leave = true;
-                const bool run = want && all_in;
-                const int nf = e.nf, nfp = run ? (int)e.nf_padded : 0;
-                int nmax = nfp;
-#pragma unroll
-                for (int o = 32; o > 0; o >>= 1) { const int t = __shfl_xor(nmax, o, 64); nmax = t > nmax ? t : nmax; }
-                nmax = __builtin_amdgcn_readfirstlane(nmax);
-                const uint32_t Kbase = (uint32_t)(((gx >> 4) * Hd + gy) * 8);
-                const uint32_t gxl = (uint32_t)(gx & 15);
+                const LocalWindow win = local_window(lv, e, mx, my, alive, leave);
+                const int nfp = win.nfp, nmax = win.nmax;
                 const uint32_t* fw = feat_word + e.feat_start;
                 uint32_t cA[kN], cB[kN], cC[kN];
 #pragma unroll
                 for (int k = 0; k < kN; ++k) { cA[k] = 0; cB[k] = 0; cC[k] = 0; }
-                // lane j fetches the words of features f0 + 2j, f0 + 2j + 1 (entries start at multiples of 8 words, f0 is a multiple of 16)
-                auto fetch = [&](int f0) -> uint2 {
-                    uint2 w = make_uint2(0u, 0u);
-                    if (f0 + 2 * j < nfp) w = *reinterpret_cast<const uint2*>(fw + f0 + 2 * j);
-                    return w;
-                };
-                // a feature word (base0 | column class, lm_kernels.h) -> offset of its first record in either bit arena, 2 x the window's cell inside it
-                auto prep = [&](uint32_t w, bool on, uint32_t& off, uint32_t& s2) {
-                    s2 = ((w & 15u) + gxl) << 1;
-                    const uint32_t o = ((w & ~15u) >> 1) + Kbase + ((s2 >> 5) ? HS8 : 0u);
-                    off = on ? o : zero_off;                        // beyond this candidate's features (or no candidate): the zero plane
-                };
                 uint32_t offx = 0, offy = 0, sx = 0, sy = 0;
                 auto batch = [&](int half, uint32_t& eA, uint32_t& eB, uint32_t& eC) {   // features 8 half .. 8 half + 7 of the current 16
                     uint32_t xa[8], xb[8], xc[8];
@@ -170,13 +112,13 @@ k_local_wide(FrameBatch fb, BitsBatch B, WidePlanes P, FrameGeom g, const TemplE
                     eB = add8(xb, cB[0], cB[1], cB[2]);
                     eC = add8(xc, cC[0], cC[1], cC[2]);
                 };
-                uint2 wn = fetch(0);
+                uint2 wn = local_fetch(fw, 0, j, nfp);
                 for (int f0 = 0; f0 < nmax; f0 += 16) {
-                    const uint2 w = wn;
+                    const uint2 wd = wn;
                     const bool on = f0 + 2 * j < nfp;
-                    wn = fetch(f0 + 16);                            // the next 16 words while these are worked on
-                    prep(w.x, on, offx, sx);
-                    prep(w.y, on, offy, sy);
+                    wn = local_fetch(fw, f0 + 16, j, nfp);          // the next 16 words while these are worked on
+                    local_prep(wd.x, on, win.gxl, win.Kbase, win.HS8, win.zero_off, offx, sx);
+                    local_prep(wd.y, on, win.gxl, win.Kbase, win.HS8, win.zero_off, offy, sy);
                     uint32_t e1A, e1B, e1C;
                     batch(0, e1A, e1B, e1C);
                     if (f0 + 8 < nmax) {                            // wave-uniform
@@ -191,69 +133,21 @@ k_local_wide(FrameBatch fb, BitsBatch B, WidePlanes P, FrameGeom g, const TemplE
                         add_eights1<kN>(cC, e1C);
                     }
                 }
-                // Once per candidate and level: the two rows of the lane side by side — bit 2c = row 2j, bit 2c + 1 = row 2j + 1 of window
-                // column c (cC is kept that way) —, S bit-sliced, the lane's maximum by a descent from the top bit, its FIRST position in raster order.
+                // Once per candidate and level: the two rows of the lane side by side (cC is kept that way), S bit-sliced, its maximum and where
                 uint32_t S[kS];
                 {
                     uint32_t n1[kN], n4[kN];
-#pragma unroll
-                    for (int k = 0; k < kN; ++k) {
-                        n1[k] = (cA[k] & 0x55555555u) | ((cB[k] << 1) & 0xAAAAAAAAu);
-                        n4[k] = ((cA[k] >> 1) & 0x55555555u) | (cB[k] & 0xAAAAAAAAu);
-                    }
+                    local_interleave<kN>(n1, n4, cA, cB);
                     weighted_sum_wide<kN>(S, n1, cC, n4);
                 }
-                uint32_t mask = 0xFFFFFFFFu, val = 0;
-#pragma unroll
-                for (int k = kS - 1; k >= 0; --k) {
-                    const uint32_t t = mask & S[k];
-                    if (t) { mask = t; val |= 1u << k; }
-                }
-                const uint32_t upper = mask & 0x55555555u;           // positions of row 2j attaining the maximum come first in raster order
-                const uint32_t pick = upper ? upper : mask;
-                const uint32_t bitp = (uint32_t)__ffs((int)pick) - 1u;
-                const uint32_t pos = ((2u * (uint32_t)j + (bitp & 1u)) << 4) + (bitp >> 1);   // row * 16 + column
-                uint32_t key = (val << 8) | (255u - pos);
-#pragma unroll
-                for (int o = 1; o < 8; o <<= 1) { const uint32_t t = (uint32_t)__shfl_xor((int)key, o, 64); key = t > key ? t : key; }
-                const int raw = (int)(key >> 8);
-                int br = -1, bc = -1;                               // LL.cpp:1910-1911
-                float best = 0.f;
-                if (raw > 0) {
-                    const int idx = 255 - (int)(key & 0xFF);
-                    br = idx >> 4; bc = idx & 15;
-                    best = score_of(raw, nf);
-                }
-                if (run) {
-                    ++evals;
-                    bytes += 256u * (uint32_t)nf;                   // algorithmic response bytes of this 16x16 evaluation
-                    sim = best;
-                    mx = (x / T - 8 + bc) * T + offset;             // LL.cpp:1930-1931
-                    my = (y / T - 8 + br) * T + offset;
-                    if (sim < threshold) alive = false;             // LL.cpp:1935
-                }
+                int raw, br, bc;
+                local_argmax<kS>(S, j, raw, br, bc);
+                local_update(win, lv.T, raw, br, bc, threshold, sim, mx, my, alive, evals, bytes);
             }
-            if (valid && j == 0) {
-                F.todo[ci] = leave ? 1 : 0;
-                if (!leave) {
-                    if (ci < cap) {
-                        Candidate m;
-                        m.x = mx; m.y = my; m.score = sim;
-                        m.work = alive ? work : -1;
-                        F.matches_dev[ci] = m;
-                    }
-                    atomicAdd(&s_acc[fr][0], (unsigned long long)evals);
-                    atomicAdd(&s_acc[fr][1], (unsigned long long)bytes);
-                }
-            }
+            if (valid && j == 0) local_store(F, ci, leave, cap, mx, my, sim, alive, work, s_acc[fr], evals, bytes);
         }
     }
-    __syncthreads();
-    if ((int)threadIdx.x < nb && s_acc[threadIdx.x][0] != 0) {
-        unsigned long long* st = fb.f[threadIdx.x].counters + 8 + 2 * (blockIdx.x & (kStatShards - 1));
-        atomicAdd(st, s_acc[threadIdx.x][0]);
-        atomicAdd(st + 1, s_acc[threadIdx.x][1]);
-    }
+    local_flush_stats(fb, s_acc);
 }
 
 void launch_pack_wide(const BitsBatch& B, const WidePlanes& P, int nb, const LevelGeom& lv, hipStream_t s) {
@@ -270,17 +164,15 @@ void launch_local_wide(const FrameBatch& fb, const BitsBatch& B, const WidePlane
 
 // ---- Coarse pass on two pair streams: k_coarse_bits's scheme — a wave per template, a lane = 32 consecutive positions, a feature's load =
 // two consecutive pairs per lane at a wave-uniform pair index, funnel-shifted by a wave-uniform amount — with one such load per set and
-// three counters.  The same bit-sliced threshold compare, the same hit test, the same ONE atomic per workgroup and pass for the candidate slots.
+// three counters.  Template head, hit test, slot reservation and emission are k_coarse_bits's, through match_planes.h.
 __global__ void __launch_bounds__(256)
 k_pack_top_wide(TopBits B, WidePlanes P, uint32_t byte0, uint32_t npairs) {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= npairs) return;
     const uint8_t* src = B.lm[blockIdx.y] + byte0 + (size_t)i * 32;
     const uint4 a = *reinterpret_cast<const uint4*>(src), b = *reinterpret_cast<const uint4*>(src + 16);
-    auto four = [](uint32_t d, int sh) -> uint32_t { return ((((d >> sh) & 0x01010101u) * 0x01020408u) >> 24) & 0xFu; };   // bit sh of 4 bytes -> 4 bits
-    auto bits = [&](const uint4& v, int sh) -> uint32_t { return four(v.x, sh) | (four(v.y, sh) << 4) | (four(v.z, sh) << 8) | (four(v.w, sh) << 12); };
-    *reinterpret_cast<uint2*>(B.bits[blockIdx.y] + (size_t)i * 8) = make_uint2(bits(a, 0) | (bits(b, 0) << 16), bits(a, 2) | (bits(b, 2) << 16));   // v & 1, v == 4
-    *reinterpret_cast<uint2*>(P.set1[blockIdx.y] + (size_t)i * 8) = make_uint2(bits(a, 1) | (bits(b, 1) << 16), 0u);                             // (v >> 1) & 1, -
+    *reinterpret_cast<uint2*>(B.bits[blockIdx.y] + (size_t)i * 8) = make_uint2(byte_bits32(a, b, 0), byte_bits32(a, b, 2));   // v & 1, v == 4
+    *reinterpret_cast<uint2*>(P.set1[blockIdx.y] + (size_t)i * 8) = make_uint2(byte_bits32(a, b, 1), 0u);                    // (v >> 1) & 1, -
 }
 
 template <int kHi, int kWaves, int kInFlight>
@@ -291,29 +183,12 @@ k_coarse_wide(FrameBatch fb, TopBits B, WidePlanes P, LevelGeom lv, int level, i
     __shared__ uint32_t s_tot[4];
     __shared__ unsigned long long s_base;
     const FrameSlot& F = fb.f[blockIdx.y];
-    Candidate* __restrict__ cands = F.cands;
-    unsigned long long* __restrict__ counters = F.counters;
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int work_raw = (int)blockIdx.x * 4 + wave;                       // a wave per template
-    const bool live = work_raw < num_work;
-    const int work = live ? work_raw : num_work - 1;                       // idle waves of the last workgroup shadow a real template and emit nothing
-    const int pyr = work_pyramids[work];
-    const TemplEntry e = entries[(size_t)pyr * levels + level];
-    const int nf = e.nf, nfp = e.nf_padded;
-    const int32_t* fo = feat_off + e.feat_start;
-    const int Wd = lv.Wd, Hd = lv.Hd, T = lv.T, npos = Wd * Hd;
-    const int wf = (e.width - 1) / T + 1, hf = (e.height - 1) / T + 1;      // LL.cpp:1299-1309
-    const int tp = (Hd - hf) * Wd + (Wd - wf) + 1;
-    const int offset = T / 2 + (T % 2 - 1);                                 // LL.cpp:1846
-    const int limit = tp < npos ? tp : npos;                                // positions that carry sums
-    // the smallest raw sum whose score passes (score_of is monotone in raw): LL.cpp:1844 `> threshold`
-    int rmin = (int)(threshold * (float)(4 * nf) / 100.f);
-    if (!(rmin >= 0)) rmin = 0;
-    if (rmin > 4 * nf + 1) rmin = 4 * nf + 1;
-    while (rmin > 0 && score_of(rmin, nf) > threshold) --rmin;
-    while (rmin <= 4 * nf && !(score_of(rmin, nf) > threshold)) ++rmin;
-    const bool zero_passes = score_of(0, nf) > threshold;
+    const CoarseHead h = coarse_head((int)blockIdx.x * 4 + wave, num_work, entries, feat_off, work_pyramids, lv, level, levels, threshold);   // a wave per template
+    const bool live = h.live;
+    const int nfp = h.nfp, npos = h.npos, limit = h.limit;
+    const int32_t* fo = h.fo;
     const BufRsrc bits0 = make_rsrc(B.bits[blockIdx.y]), bits1 = make_rsrc(P.set1[blockIdx.y]);
     for (int P0 = 0; P0 < npos; P0 += 2048) {                               // (the same number of passes for every wave of the workgroup)
         const int pos0 = P0 + 32 * lane;                                    // first position of this lane
@@ -363,53 +238,13 @@ k_coarse_wide(FrameBatch fb, TopBits B, WidePlanes P, LevelGeom lv, int level, i
         }
         uint32_t S[kS];
         weighted_sum_wide<kN>(S, c1, c2, c4);
-        uint32_t gt = 0, eq = 0xFFFFFFFFu;                                  // S >= rmin, bit-sliced
-#pragma unroll
-        for (int k = kS - 1; k >= 0; --k) {
-            if ((rmin >> k) & 1) eq &= S[k];                                // wave-uniform
-            else { gt |= eq & S[k]; eq &= ~S[k]; }
-        }
-        uint32_t hit_mask = rmin < (1 << kS) ? (gt | eq) : 0u;
-        // positions at or beyond the template's position count hold zero sums (LL.cpp:1299-1309): they are hits only if zero passes
-        const int sums = limit - pos0;                                      // positions of this lane that carry sums
-        const uint32_t summed = sums >= 32 ? 0xFFFFFFFFu : (sums > 0 ? (1u << sums) - 1u : 0u);
-        const int inmap = npos - pos0;
-        const uint32_t mapped = inmap >= 32 ? 0xFFFFFFFFu : (inmap > 0 ? (1u << inmap) - 1u : 0u);
-        hit_mask = (hit_mask & summed) | (zero_passes ? (mapped & ~summed) : 0u);
+        uint32_t summed;
+        uint32_t hit_mask = coarse_hit_mask<kS>(S, h.rmin, h.zero_passes, limit, npos, pos0, summed);
         if (!live) hit_mask = 0;
         int total;
-        const int before = wave_excl_scan(__popc(hit_mask), lane, total);
-        // one atomic per workgroup and pass
-        if (lane == 0) s_tot[wave] = (uint32_t)total;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            const unsigned long long all = (unsigned long long)s_tot[0] + s_tot[1] + s_tot[2] + s_tot[3];
-            s_base = all ? atomicAdd(&counters[0], all) : 0ull;
-        }
-        __syncthreads();
-        unsigned long long slot = s_base + (unsigned long long)before;
-        for (int w = 0; w < wave; ++w) slot += s_tot[w];
-        __syncthreads();                                                    // s_tot / s_base are rewritten by the next pass
-        if (total > 0) {                                                    // wave-uniform
-            uint32_t m = hit_mask;
-            while (m) {
-                const int b = __ffs((int)m) - 1;
-                m &= m - 1;
-                if (slot < cap) {
-                    int raw = 0;
-                    if ((summed >> b) & 1u) {
-#pragma unroll
-                        for (int k = 0; k < kS; ++k) raw |= (int)((S[k] >> b) & 1u) << k;
-                    }
-                    const int jpos = pos0 + b;
-                    const int cy = jpos / Wd, cx = jpos - cy * Wd;
-                    Candidate c;
-                    c.x = cx * T + offset; c.y = cy * T + offset; c.score = score_of(raw, nf); c.work = work;
-                    cands[slot] = c;
-                }
-                ++slot;
-            }
-        }
+        const unsigned long long slot = coarse_reserve_slots(s_tot, s_base, F.counters, hit_mask, lane, wave, total);
+        if (total > 0)                                                      // wave-uniform
+            coarse_emit<kS>(hit_mask, summed, S, slot, cap, pos0, h.Wd, h.T, h.offset, h.nf, h.work, F.cands);
     }
 }
 

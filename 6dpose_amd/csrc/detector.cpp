@@ -133,6 +133,46 @@ extern "C" int lm_detector_set_colour_channels(lm_detector* d, int channels) {
     return LM_OK;
 }
 
+// The border policy: what the matching entry points do with a frame whose size is not aligned to the T grid — the sizes
+// the reference refuses at LL.cpp:1136 and 1217-1218.  Training views are not concerned (they take any size).
+extern "C" int lm_detector_set_border(lm_detector* d, int policy) {
+    if (!d) return lm_set_error(LM_ERR_INVALID, "null detector");
+    if (policy != kBorderStrict && policy != kBorderPad && policy != kBorderCrop)
+        return lm_set_error(LM_ERR_INVALID, "unknown border policy %d: 0 (strict), 1 (pad) or 2 (crop)", policy);
+    if (d->n_submitted != d->n_collected) return lm_set_error(LM_ERR_INVALID, "frames in flight: collect them before changing the border policy");
+    d->border = policy;          // the resident frame and the parked ones stay what they are: frames of an aligned size
+    return LM_OK;
+}
+
+extern "C" int lm_detector_get_border(const lm_detector* d) { return d ? d->border : lm_set_error(LM_ERR_INVALID, "null detector"); }
+
+// The one rule (border_aligned_size, frame_border.h) for this detector's T: the size of the frame buffers a width x height source gets under
+// `policy` (-1: the detector's own).  Strict answers with the source size itself, or refuses it with the reference's asserts.
+extern "C" int lm_detector_aligned_size(const lm_detector* d, int policy, int width, int height, int* aligned_width, int* aligned_height) {
+    if (!d || !aligned_width || !aligned_height) return lm_set_error(LM_ERR_INVALID, "null argument");
+    if (policy < 0) policy = d->border;
+    if (policy != kBorderStrict && policy != kBorderPad && policy != kBorderCrop)
+        return lm_set_error(LM_ERR_INVALID, "unknown border policy %d: 0 (strict), 1 (pad) or 2 (crop)", policy);
+    if (width < 16 || height < 16 || width > 16384 || height > 16384) return lm_set_error(LM_ERR_INVALID, "unsupported frame size %dx%d", width, height);
+    const int* T = d->T_at_level.data();
+    const int L = d->pyramid_levels;
+    if (policy == kBorderStrict) {
+        for (int l = 0; l < L; ++l) {                          // setup_geometry's checks and words
+            const int w = width >> l, h = height >> l;
+            if (w < 1 || h < 1) return lm_set_error(LM_ERR_INVALID, "image too small for %d pyramid levels", L);
+            if (((long)w * h) % 16 != 0)
+                return lm_set_error(LM_ERR_INVALID, "(src.rows * src.cols) %% 16 == 0 violated at level %d (%dx%d) [LL.cpp:1136]", l, w, h);
+            if (h % T[l] != 0 || w % T[l] != 0)
+                return lm_set_error(LM_ERR_INVALID, "response_map.rows/cols %% T == 0 violated at level %d (%dx%d, T=%d) [LL.cpp:1217-1218]", l, w, h, T[l]);
+        }
+        *aligned_width = width; *aligned_height = height;
+        return LM_OK;
+    }
+    if (!border_aligned_size(T, L, policy, width, height, aligned_width, aligned_height) || *aligned_width > 16384 || *aligned_height > 16384)
+        return lm_set_error(LM_ERR_INVALID, "unsupported frame size %dx%d", width, height);
+    return LM_OK;
+}
+
 extern "C" int lm_detector_get_colour_channels(const lm_detector* d) { return d ? d->cch : lm_set_error(LM_ERR_INVALID, "null detector"); }
 
 extern "C" int lm_rgb_to_grey(int device, const uint8_t* rgb, int64_t pixels, uint8_t* grey) {
@@ -260,10 +300,10 @@ extern "C" void lm_detector_destroy(lm_detector* d) {
     for (auto& sl : d->slot) { free(sl.prep); sl.prep = nullptr; }
     (void)hipStreamSynchronize(d->stream);
     if (d->mstream) (void)hipStreamSynchronize(d->mstream);
-    d->frame_rgb.release(); d->frame_depth.release(); d->nrm_raw.release();
+    d->frame_rgb.release(); d->frame_depth.release(); d->nrm_raw.release(); d->border_src.release();
     for (int i = 0; i < lm_detector::kSlots; ++i) {
         if (d->ingest.pinned[i]) (void)hipHostFree(d->ingest.pinned[i]);
-        d->ingest.d_rgb[i].release();
+        d->ingest.d_rgb[i].release(); d->ingest.d_src[i].release();
         if (d->ingest.t0[i]) (void)hipEventDestroy(d->ingest.t0[i]);
         if (d->ingest.t1[i]) (void)hipEventDestroy(d->ingest.t1[i]);
     }

@@ -106,6 +106,16 @@ int setup_geometry(lm_detector* d, int W, int H, bool check_match_preconditions)
     return LM_OK;
 }
 
+// The aligned size of a W x H source under the detector's border policy.  Strict hands the source size on as it is: setup_geometry refuses
+// it with the reference's own asserts where it is not aligned.
+int border_resolve(const lm_detector* d, int W, int H, int* Wa, int* Ha) {
+    *Wa = W; *Ha = H;
+    if (d->border == kBorderStrict) return LM_OK;
+    if (!border_aligned_size(d->T_at_level.data(), d->pyramid_levels, d->border, W, H, Wa, Ha) || *Wa > 16384 || *Ha > 16384)
+        return lm_set_error(LM_ERR_INVALID, "unsupported frame size %dx%d", W, H);   // (crop: nothing of at least 16 x 16 fits; pad: beyond 16384)
+    return LM_OK;
+}
+
 int upload_frame(lm_detector* d, const uint8_t* rgb, const uint16_t* depth, int W, int H, const uint8_t* const* masks, bool check_match_preconditions) {
     if ((d->use[0] && !rgb) || (d->use[1] && !depth)) return lm_set_error(LM_ERR_INVALID, "rgb/depth is null");
     if ((!d->use[0] && rgb) || (!d->use[1] && depth)) return lm_set_error(LM_ERR_INVALID, "a source was given for a modality outside the detector's set");
@@ -115,10 +125,12 @@ int upload_frame(lm_detector* d, const uint8_t* rgb, const uint16_t* depth, int 
     if (d->n_submitted != d->n_collected)   // the front end's buffers (and, on a size change, the arenas) belong to the frames in flight
         return lm_set_error(LM_ERR_INVALID, "frames in flight: collect them before uploading another frame this way (lm_detector_submit_frame streams)");
     LM_DIAG_IDLE(d, "upload_frame");
-    int rc = setup_geometry(d, W, H, check_match_preconditions);
-    if (rc) return rc;
+    int rc, Wa = W, Ha = H;                 // the aligned geometry: the source's own for a training view and under the strict policy
+    if (check_match_preconditions && (rc = border_resolve(d, W, H, &Wa, &Ha))) return rc;
+    if ((rc = setup_geometry(d, Wa, Ha, check_match_preconditions))) return rc;
+    const bool bordered = Wa != W || Ha != H;
     d->cur_rgb = d->frame_rgb.p; d->cur_depth = d->frame_depth.p;
-    const size_t n = (size_t)W * H;
+    const size_t n = (size_t)W * H, na = (size_t)Wa * Ha;    // pixels of the source (staged and uploaded) and of the frame buffers
     const bool m0 = masks && masks[0], m1 = masks && d->nmod == 2 && masks[1];
     const size_t nc = d->use[0] ? n * d->cch : 0, nd = d->use[1] ? n * 2 : 0;     // only the sources of the set are staged and uploaded
     size_t bytes = nc + nd + (m0 ? n : 0) + (m1 ? n : 0);
@@ -126,9 +138,17 @@ int upload_frame(lm_detector* d, const uint8_t* rgb, const uint16_t* depth, int 
     uint8_t* st = (uint8_t*)d->pinned;
     if (nc) memcpy(st, rgb, nc);
     if (nd) memcpy(st + nc, depth, nd);
+    BorderStage bs{};
+    if (bordered && (rc = d->border_src.ensure(bytes + 16))) return rc;     // (+16: the kernel fetches the aligned dwords around a unit)
     HIP_TRY(hipEventRecord(d->ev[6], d->stream));
-    if (nc) HIP_TRY(hipMemcpyAsync(d->frame_rgb.p, st, nc, hipMemcpyHostToDevice, d->stream));
-    if (nd) HIP_TRY(hipMemcpyAsync(d->frame_depth.p, st + nc, nd, hipMemcpyHostToDevice, d->stream));
+    if (bordered) {                                          // the sources as they are, in the staging buffer's layout; the frame buffers are written by k_frame_border below
+        if (nc + nd) HIP_TRY(hipMemcpyAsync(d->border_src.p, st, nc + nd, hipMemcpyHostToDevice, d->stream));
+        if (nc) border_job(bs.job[bs.njobs++], d->border_src.p, d->frame_rgb.p, W, H, Wa, Ha, d->cch, true);
+        if (nd) border_job(bs.job[bs.njobs++], d->border_src.p + nc, d->frame_depth.p, W, H, Wa, Ha, 2, false);
+    } else {
+        if (nc) HIP_TRY(hipMemcpyAsync(d->frame_rgb.p, st, nc, hipMemcpyHostToDevice, d->stream));
+        if (nd) HIP_TRY(hipMemcpyAsync(d->frame_depth.p, st + nc, nd, hipMemcpyHostToDevice, d->stream));
+    }
     size_t off = nc + nd;
     d->have_mask[0] = d->have_mask[1] = false;
     for (int i = 0; i < d->nmod; ++i) {                      // masks[i] belongs to the set's i-th modality; the buffers are indexed by kind
@@ -136,9 +156,18 @@ int upload_frame(lm_detector* d, const uint8_t* rgb, const uint16_t* depth, int 
         d->have_mask[m] = masks && masks[i];
         if (!d->have_mask[m]) continue;
         memcpy(st + off, masks[i], n);
-        if ((rc = d->lvl[0].mask[m].ensure(n))) return rc;
-        HIP_TRY(hipMemcpyAsync(d->lvl[0].mask[m].p, st + off, n, hipMemcpyHostToDevice, d->stream));
+        if ((rc = d->lvl[0].mask[m].ensure(na))) return rc;
+        if (bordered) {                                      // a mask comes at the source size and is padded with 0 or cropped like the depth image
+            HIP_TRY(hipMemcpyAsync(d->border_src.p + off, st + off, n, hipMemcpyHostToDevice, d->stream));
+            border_job(bs.job[bs.njobs++], d->border_src.p + off, d->lvl[0].mask[m].p, W, H, Wa, Ha, 1, false);
+        } else
+            HIP_TRY(hipMemcpyAsync(d->lvl[0].mask[m].p, st + off, n, hipMemcpyHostToDevice, d->stream));
         off += n;
+    }
+    if (bordered) HIP_TRY(launch_frame_border(bs, d->stream));
+    for (int i = 0; i < d->nmod; ++i) {
+        const int m = d->mod_kind[i];
+        if (!d->have_mask[m]) continue;
         for (int l = 1; l < d->pyramid_levels; ++l) {       // resize(INTER_NEAREST), LL.cpp:573-578, 874-879
             const LevelBufs& a = d->lvl[l - 1];
             LevelBufs& b = d->lvl[l];
@@ -201,22 +230,35 @@ extern "C" int lm_detector_store_frame(lm_detector* d, int slot, const uint8_t* 
         d->slot_w.resize(slot + 1, 0); d->slot_h.resize(slot + 1, 0);
     }
     const size_t n = (size_t)width * height;
-    int rc;
+    int rc, Wa, Ha;                                                         // a parked frame has the aligned size (strict: the source's, checked when it is selected)
+    if ((rc = border_resolve(d, width, height, &Wa, &Ha))) return rc;
+    const bool bordered = Wa != width || Ha != height;
+    const size_t na = (size_t)Wa * Ha;
     const size_t nc = rgb ? n * d->cch : 0, nd = depth ? n : 0;                   // elements of the set's sources
-    if (d->slot_rgb[slot].cap < nc || d->slot_depth[slot].cap < nd)         // about to be reallocated: a frame in flight may still be
+    const size_t nca = rgb ? na * d->cch : 0, nda = depth ? na : 0;               // ... and of the parked frame
+    if (d->slot_rgb[slot].cap < nca || d->slot_depth[slot].cap < nda)       // about to be reallocated: a frame in flight may still be
         HIP_TRY(hipStreamSynchronize(d->stream));                          // copying out of the old buffer
-    if (nc && (rc = d->slot_rgb[slot].ensure(nc))) return rc;
-    if (nd && (rc = d->slot_depth[slot].ensure(nd))) return rc;
+    if (nca && (rc = d->slot_rgb[slot].ensure(nca))) return rc;
+    if (nda && (rc = d->slot_depth[slot].ensure(nda))) return rc;
     // staged through the detector's pinned buffer like every other upload (a pageable hipMemcpy stages internally, chunk by chunk)
     if ((rc = ensure_pinned(d, nc + nd * 2))) return rc;
     HIP_TRY(hipStreamSynchronize(d->stream));                              // the staging buffer is shared with upload_frame
     uint8_t* st = (uint8_t*)d->pinned;
     if (nc) memcpy(st, rgb, nc);
     if (nd) memcpy(st + nc, depth, nd * 2);
-    if (nc) HIP_TRY(hipMemcpyAsync(d->slot_rgb[slot].p, st, nc, hipMemcpyHostToDevice, d->stream));
-    if (nd) HIP_TRY(hipMemcpyAsync(d->slot_depth[slot].p, st + nc, nd * 2, hipMemcpyHostToDevice, d->stream));
+    if (bordered) {                                                        // the source as it is, then k_frame_border into the slot
+        if ((rc = d->border_src.ensure(nc + nd * 2 + 16))) return rc;
+        HIP_TRY(hipMemcpyAsync(d->border_src.p, st, nc + nd * 2, hipMemcpyHostToDevice, d->stream));
+        BorderStage bs{};
+        if (nc) border_job(bs.job[bs.njobs++], d->border_src.p, d->slot_rgb[slot].p, width, height, Wa, Ha, d->cch, true);
+        if (nd) border_job(bs.job[bs.njobs++], d->border_src.p + nc, d->slot_depth[slot].p, width, height, Wa, Ha, 2, false);
+        HIP_TRY(launch_frame_border(bs, d->stream));
+    } else {
+        if (nc) HIP_TRY(hipMemcpyAsync(d->slot_rgb[slot].p, st, nc, hipMemcpyHostToDevice, d->stream));
+        if (nd) HIP_TRY(hipMemcpyAsync(d->slot_depth[slot].p, st + nc, nd * 2, hipMemcpyHostToDevice, d->stream));
+    }
     HIP_TRY(hipStreamSynchronize(d->stream));
-    d->slot_w[slot] = width; d->slot_h[slot] = height;
+    d->slot_w[slot] = Wa; d->slot_h[slot] = Ha;
     return LM_OK;
 }
 
@@ -248,6 +290,7 @@ extern "C" int lm_detector_select_frame(lm_detector* d, int slot) {
     return LM_OK;
 }
 
+// (every stage has the ALIGNED geometry: under a border policy that is not the source's)
 extern "C" int64_t lm_detector_read_stage(lm_detector* d, int level, int kind, uint8_t* dst, int64_t capacity) {
     if (!d || level < 0 || level >= d->pyramid_levels || kind < 0 || kind > 7) return lm_set_error(LM_ERR_INVALID, "bad argument");
     if (d->fW <= 0) return lm_set_error(LM_ERR_INVALID, "no frame processed yet");

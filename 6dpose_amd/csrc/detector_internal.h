@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "../../include/amd_linemod.h"
+#include "frame_border.h"
 #include "host_templates.h"
 #include "knobs.h"
 #include "lm_kernels.h"
@@ -84,6 +85,13 @@ struct lm_detector {
     // Channels of the colour image (lm_detector_set_colour_channels): 3, or 1 for a grey camera.  Sizes every colour buffer, staging slice and upload,
     // and selects the front end's grey job kinds; nothing downstream of the quantised maps sees it.
     int cch = 3;
+
+    // Frames of any size (lm_detector_set_border): kBorderStrict refuses a source size that is not aligned (the reference's
+    // asserts), kBorderPad / kBorderCrop extend or cut it at the right and bottom to the aligned size of border_aligned_size.  Two geometries
+    // from there on: the SOURCE size is what the caller hands over, what the pinned staging and the ingest ring's host entries hold and what
+    // crosses PCIe; the ALIGNED size (fW x fH, geom) is that of the frame buffers, the arenas, the parked frames and lm_detector_read_stage.
+    int border = kBorderStrict;
+    DevBuf<uint8_t> border_src;         // the uploaded sources (and masks) of a blocking upload whose size is not aligned: k_frame_border reads them
 
     // device
     int device = 0;
@@ -166,6 +174,8 @@ struct lm_detector {
         const uint16_t* in_depth = nullptr;
         bool have_mask[2] = {false, false};         // lone frames only (Detector.match with masks)
         int ring = -1;                              // ingest ring entry holding the frame (-1: resident frame)
+        int src_w = 0, src_h = 0;                   // != 0: the ring entry holds the frame at this source size; the batch's k_frame_border writes the aligned frame the front end reads
+        bool src_in_place = false;                  // ... its rows are in the aligned buffers already (2-D copies), only the margins are missing
         // prepared by the collector thread (streamed frames): the frame's Detector::match list, ready when `ready` != 0
         bool prep_queued = false;                   // a collector job covers this frame
         std::atomic<int> ready{0};                  // 0 not yet, 1 list prepared, 2 nothing prepared (overflow: the caller's path decides)
@@ -296,6 +306,8 @@ struct lm_detector {
         DevBuf<uint8_t> d_rgb[kSlots];                 // colour image, then (16-byte aligned) the depth image: ONE upload per frame, the pinned entry has the same layout
         uint16_t* d_depth[kSlots] = {};                // = d_rgb + depth_off
         size_t depth_off = 0;
+        size_t src_depth_off = 0;                      // the same in an entry of the source size (the pinned entry and d_src; == depth_off for an aligned source)
+        DevBuf<uint8_t> d_src[kSlots];                 // the frame at its source size, where that is not aligned: the upload goes here and k_frame_border writes d_rgb / d_depth
         hipEvent_t t0[kSlots] = {}, t1[kSlots] = {};   // timing of the H2D (copy stream)
         bool used[kSlots] = {};                        // the slot's frame came in through the ring (lm_timings.h2d_ms from t0/t1)
         hipEvent_t reader[kSlots] = {};                // front end (of another slot: a resident re-match of the streamed frame) that still reads the entry
@@ -337,6 +349,7 @@ int lm_need_both(const lm_detector* d, const char* what);   // LM_OK for the def
 extern const char* const kModalityName[2];                  // "ColorGradient", "DepthNormal"
 
 // detector_frame.cpp
+int border_resolve(const lm_detector* d, int W, int H, int* Wa, int* Ha);   // the aligned size of a W x H source under the detector's policy (strict: W x H, whatever it is)
 int setup_geometry(lm_detector* d, int W, int H, bool check_match_preconditions);
 int upload_frame(lm_detector* d, const uint8_t* rgb, const uint16_t* depth, int W, int H, const uint8_t* const* masks, bool check_match_preconditions);
 int run_frontend_training(lm_detector* d);

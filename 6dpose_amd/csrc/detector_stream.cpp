@@ -250,6 +250,7 @@ static int slot_begin(lm_detector* d, float threshold, const char* const* class_
     sl.matches_dev = d->d_matches_dev.p + (size_t)d->buf_cand_cap * si;
     sl.in_rgb = rgb; sl.in_depth = depth; sl.have_mask[0] = have_mask[0]; sl.have_mask[1] = have_mask[1]; sl.ring = ring;
     sl.launched = false; sl.pending = true; sl.leader = -1; sl.batch_n = 0;
+    sl.src_w = sl.src_h = 0; sl.src_in_place = false;   // (lm_detector_submit_frame sets them for a source that is not aligned)
     if (d->pend_n == 0) { d->pend_first = si; d->pend_threshold = threshold; }
     ++d->pend_n;
     ++d->n_submitted;
@@ -372,6 +373,24 @@ static int order_batch(lm_detector* d, const Batch& B) {
     int rc;
     if ((rc = order_after_default_stream(d, B.s))) return rc;
     HIP_TRY(hipEventRecord(d->slot[B.first].ev[0], B.s));
+    return LM_OK;
+}
+
+// Streamed frames whose source size is not aligned (frame_border.h): ONE k_frame_border launch writes the aligned colour and depth images of
+// every such frame of the batch, from the source-size copies their uploads left in the ring entries, in front of the front end.
+static int enqueue_border(lm_detector* d, const Batch& B) {
+    BorderStage bs{};
+    for (int b = 0; b < B.nb; ++b) {
+        const int si = B.slot(b);
+        const lm_detector::Slot& sl = d->slot[si];
+        if (sl.ring < 0 || !sl.src_w) continue;
+        if (sl.src_in_place && d->fW <= sl.src_w && d->fH <= sl.src_h) continue;            // cropped by the 2-D copies: no margin
+        const lm_detector::Ingest& g = d->ingest;
+        if (d->use[0]) border_job(bs.job[bs.njobs++], g.d_src[si].p, g.d_rgb[si].p, sl.src_w, sl.src_h, d->fW, d->fH, d->cch, true, sl.src_in_place);
+        const size_t src_depth_off = d->use[0] ? ((size_t)sl.src_w * sl.src_h * d->cch + 15) & ~(size_t)15 : 0;   // (the entry's layout at ITS source size: another frame of the batch may have another)
+        if (d->use[1]) border_job(bs.job[bs.njobs++], g.d_src[si].p + src_depth_off, g.d_depth[si], sl.src_w, sl.src_h, d->fW, d->fH, 2, false, sl.src_in_place);
+    }
+    if (bs.njobs) HIP_TRY(launch_frame_border(bs, B.s));
     return LM_OK;
 }
 
@@ -534,7 +553,7 @@ int lm_launch_pending(lm_detector* d) {
     {
         LM_CLOCK("step waits+ev0");
         HIP_TRY(hipSetDevice(d->device));
-        if ((rc = batch_begin(d, B)) || (rc = order_batch(d, B)) || (rc = choose_bit_writers(d, B))) return rc;
+        if ((rc = batch_begin(d, B)) || (rc = order_batch(d, B)) || (rc = enqueue_border(d, B)) || (rc = choose_bit_writers(d, B))) return rc;
         if ((B.wide || B.cwide) && (rc = ensure_wide_arenas(d, B))) return rc;
     }
     { LM_CLOCK("step front end"); if ((rc = run_frontend_batch(d, B.first, B.nb, B.s, B.direct_low, B.direct_top))) return rc; }
@@ -823,7 +842,7 @@ extern "C" int lm_detector_submit(lm_detector* d, float threshold, const char* c
 // The per-frame call of a camera / dataset loop (linemod_ros/detect.py:83-138, linemod_and_levelup_test.py:314-327 hand a NEW
 // host frame to every match): stage -> H2D on the copy stream -> front end + matching of lm_detector_submit, up to kSlots
 // frames in flight; results come back through lm_detector_collect in submission order.
-static int ingest_entry(lm_detector* d, int r, size_t n) {
+static int ingest_entry(lm_detector* d, int r, size_t n, size_t nsrc) {   // pixels of the aligned frame and of the source
     lm_detector::Ingest& g = d->ingest;
     if (!g.stream) {
         HIP_TRY(hipStreamCreateWithFlags(&g.stream, hipStreamNonBlocking));
@@ -831,14 +850,19 @@ static int ingest_entry(lm_detector* d, int r, size_t n) {
     }
     g.depth_off = d->use[0] ? (n * d->cch + 15) & ~(size_t)15 : 0;       // the depth image behind the colour image, 16-byte aligned (host entry and device entry alike);
     const size_t bytes = g.depth_off + (d->use[1] ? n * 2 : 0);     // a detector with one modality keeps (and uploads) only that modality's image
-    if (g.pinned_bytes[r] < bytes) {
+    // A source that is not aligned: the pinned entry (and its copy on the device, d_src) has the same layout at the SOURCE size — only those bytes
+    // cross PCIe —, the device entry the front end reads keeps the aligned size.
+    g.src_depth_off = d->use[0] ? (nsrc * d->cch + 15) & ~(size_t)15 : 0;
+    const size_t src_bytes = g.src_depth_off + (d->use[1] ? nsrc * 2 : 0);
+    if (g.pinned_bytes[r] < src_bytes) {
         if (g.pinned[r]) (void)hipHostFree(g.pinned[r]);
         g.pinned[r] = nullptr; g.pinned_bytes[r] = 0;
-        HIP_TRY(hipHostMalloc(&g.pinned[r], bytes, hipHostMallocDefault));
-        g.pinned_bytes[r] = bytes;
+        HIP_TRY(hipHostMalloc(&g.pinned[r], src_bytes, hipHostMallocDefault));
+        g.pinned_bytes[r] = src_bytes;
     }
     int rc;
     if ((rc = g.d_rgb[r].ensure(bytes))) return rc;
+    if (nsrc != n && (rc = g.d_src[r].ensure(src_bytes + 16))) return rc;   // (+16: k_frame_border fetches the aligned dwords around a unit)
     g.d_depth[r] = d->use[1] ? reinterpret_cast<uint16_t*>(g.d_rgb[r].p + g.depth_off) : nullptr;
     return LM_OK;
 }
@@ -860,10 +884,11 @@ static int ingest_begin(lm_detector* d, int width, int height, int* r) {
     if (d->n_submitted - d->n_collected >= (uint64_t)lm_detector::kSlots)
         return lm_set_error(LM_ERR_INVALID, "%d frames already in flight: call lm_detector_collect first", lm_detector::kSlots);
     HIP_TRY(hipSetDevice(d->device));
-    int rc = ingest_geometry(d, width, height);
-    if (rc) return rc;
+    if (width < 16 || height < 16 || width > 16384 || height > 16384) return lm_set_error(LM_ERR_INVALID, "unsupported frame size %dx%d", width, height);
+    int Wa, Ha, rc = border_resolve(d, width, height, &Wa, &Ha);   // the geometry is that of the aligned size (the source's own under the strict policy)
+    if (rc || (rc = ingest_geometry(d, Wa, Ha))) return rc;
     *r = (int)(d->n_submitted % lm_detector::kSlots);
-    return ingest_entry(d, *r, (size_t)width * height);
+    return ingest_entry(d, *r, (size_t)Wa * Ha, (size_t)width * height);
 }
 
 extern "C" int lm_detector_ingest_buffer(lm_detector* d, int width, int height, uint8_t** rgb, uint16_t** depth) {
@@ -872,7 +897,7 @@ extern "C" int lm_detector_ingest_buffer(lm_detector* d, int width, int height, 
     int r, rc = ingest_begin(d, width, height, &r);
     if (rc) return rc;
     if (d->use[0]) *rgb = (uint8_t*)d->ingest.pinned[r];             // (null stays for a modality outside the set)
-    if (d->use[1]) *depth = (uint16_t*)((uint8_t*)d->ingest.pinned[r] + d->ingest.depth_off);
+    if (d->use[1]) *depth = (uint16_t*)((uint8_t*)d->ingest.pinned[r] + d->ingest.src_depth_off);
     return LM_OK;
 }
 
@@ -888,14 +913,21 @@ extern "C" int lm_detector_submit_frame(lm_detector* d, const uint8_t* rgb, cons
     uint8_t* st = (uint8_t*)g.pinned[r];
     const auto tp0 = std::chrono::steady_clock::now();
     const size_t nc = d->use[0] ? n * d->cch : 0, nd = d->use[1] ? n * 2 : 0;
-    staged_copy(d, st, rgb, nc, st + g.depth_off, (const uint8_t*)depth, nd);  // zero-copy when the caller filled lm_detector_ingest_buffer's pointers
+    const bool bordered = width != d->fW || height != d->fH;     // the source is not aligned: the entry holds it as it is, k_frame_border (enqueue_border) writes the frame the front end reads
+    const bool copy_2d = bordered && knobs().border_copy2d;      // ... or 2-D copies put its rows into the aligned frame and the kernel writes the margins only
+    staged_copy(d, st, rgb, nc, st + g.src_depth_off, (const uint8_t*)depth, nd);  // zero-copy when the caller filled lm_detector_ingest_buffer's pointers
     const auto tp1 = std::chrono::steady_clock::now();
     if (g.reader[r]) {                                            // a resident re-match of the entry's previous frame may still read it (another slot's front end)
         HIP_TRY(hipStreamWaitEvent(g.stream, g.reader[r], 0));
         g.reader[r] = nullptr;
     }
     HIP_TRY(hipEventRecord(g.t0[r], g.stream));
-    HIP_TRY(hipMemcpyAsync(g.d_rgb[r].p, st, g.depth_off + nd, hipMemcpyHostToDevice, g.stream));   // colour + depth: one copy (two cost the copy engine a second set-up: 0.061 -> ~0.05 ms, and the host a call)
+    if (copy_2d) {
+        const size_t cw = (size_t)std::min(width, d->fW), ch = (size_t)std::min(height, d->fH);
+        if (nc) HIP_TRY(hipMemcpy2DAsync(g.d_rgb[r].p, (size_t)d->fW * d->cch, st, (size_t)width * d->cch, cw * d->cch, ch, hipMemcpyHostToDevice, g.stream));
+        if (nd) HIP_TRY(hipMemcpy2DAsync(g.d_depth[r], (size_t)d->fW * 2, st + g.src_depth_off, (size_t)width * 2, cw * 2, ch, hipMemcpyHostToDevice, g.stream));
+    } else
+    HIP_TRY(hipMemcpyAsync(bordered ? g.d_src[r].p : g.d_rgb[r].p, st, g.src_depth_off + nd, hipMemcpyHostToDevice, g.stream));   // colour + depth: one copy (two cost the copy engine a second set-up: 0.061 -> ~0.05 ms, and the host a call)
     HIP_TRY(hipEventRecord(g.t1[r], g.stream));                   // the batch's front end waits for it (lm_launch_pending)
     const uint8_t* const in_rgb = d->use[0] ? g.d_rgb[r].p : nullptr;
     d->cur_rgb = in_rgb; d->cur_depth = g.d_depth[r];
@@ -907,6 +939,7 @@ extern "C" int lm_detector_submit_frame(lm_detector* d, const uint8_t* rgb, cons
     rc = slot_begin(d, threshold, class_ids, num_class_ids, in_rgb, g.d_depth[r], d->have_mask, r);
     if (rc) return rc;
     if (d->n_submitted == before + 1) g.used[r] = true;
+    if (bordered) { d->slot[r].src_w = width; d->slot[r].src_h = height; d->slot[r].src_in_place = copy_2d; }
     const auto tp3 = std::chrono::steady_clock::now();
     auto secs = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double>(b - a).count(); };
     d->host_prof[0] += 1; d->host_prof[1] += secs(tp0, tp1); d->host_prof[2] += secs(tp1, tp2); d->host_prof[3] += secs(tp2, tp3);

@@ -24,6 +24,7 @@ struct Knobs {
     int first_batch = 3;           // LM_FIRST_BATCH: frames an idle GPU waits for before a partial batch goes out WHILE THE CALLER SUBMITS IN A TIGHT LOOP (collect / flush launch what is left; sparse streams: every frame at once)
     int fe_rows_cs = 0;            // LM_FE_ROWS_CS: column phases per workgroup of the strip-record tile writer (a divisor of T: 1, 2, 4, 8 or 1, 5; 0 = default 2, or 1 where 2 does not divide T: the spread rows are built T / 2 times per row phase, for twice the workgroups)
     int nt_copy = 1;               // LM_NT_COPY=0: the staging copy of a streamed frame with memcpy instead of non-temporal AVX2 stores
+    int border_copy2d = 0;         // LM_BORDER_COPY2D=1: a streamed frame whose size is not aligned reaches its aligned buffers by 2-D copies from the pinned ring and k_frame_border writes the margins only (0: one linear copy, the kernel re-pitches; DESIGN section 2.6 has the comparison)
     int dedupe_blocks = 0;         // LM_DEDUPE_BLOCKS: workgroups per frame of k_dedupe (0 = default: one per 256 candidates of the last frame, 64 .. two per CU)
     int fe_wgs_per_cu = kFeWaves;         // LM_FE_WGS_PER_CU: persistent workgroups per CU of a front-end stage (0 = one workgroup per tile)
     int launch_slack_us = 0;       // LM_LAUNCH_SLACK_US: a partial batch goes out when the GPU's estimated backlog is shorter than this (0 = default 150)
@@ -64,6 +65,7 @@ inline const Knobs& knobs() {
         v.first_batch = geti("LM_FIRST_BATCH", v.first_batch);
         v.dedupe_blocks = geti("LM_DEDUPE_BLOCKS", 0);
         v.nt_copy = geti("LM_NT_COPY", 1);
+        v.border_copy2d = geti("LM_BORDER_COPY2D", 0);
         v.fe_rows_cs = geti("LM_FE_ROWS_CS", 0);
         v.knn_blocks = geti("LM_KNN_BLOCKS", 0);
         v.icp_splits = geti("LM_ICP_SPLITS", 0);

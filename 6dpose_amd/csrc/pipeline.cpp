@@ -18,7 +18,9 @@
 struct lm_pipeline {
     lm_detector* det = nullptr;
     lm_icp* icp = nullptr;
-    int W = 0, H = 0;
+    int W = 0, H = 0;                             // the aligned geometry: the detector's frame buffers, the ICP context, the model slots
+    int srcW = 0, srcH = 0;                       // what the caller named: the size of the frames and depth renderings it hands over (== W x H unless the detector pads or crops)
+    DevBuf<uint8_t> border_src;                   // depth renderings of the source size on their way into the model slots (k_frame_border)
     struct ClassViews { int base = 0, count = 0; };
     std::map<std::string, ClassViews> views;      // class id -> range of view slots
     int num_views = 0;                            // slots handed out
@@ -51,9 +53,11 @@ extern "C" int lm_pipeline_create(lm_detector* det, int width, int height, lm_pi
     if (int rc = lm_need_both(det, "lm_pipeline_create")) return rc;   // the ICP stage reads the scene depth of the detector's frame
     HIP_TRY(hipSetDevice(det->device));
     lm_pipeline* p = new lm_pipeline();
-    p->det = det; p->W = width; p->H = height;
-    int rc = lm_icp_create(det->device, &p->icp);
-    if (!rc) rc = lm_icp_set_geometry(p->icp, width, height);
+    p->det = det; p->srcW = width; p->srcH = height;
+    int rc = border_resolve(det, width, height, &p->W, &p->H);   // under the detector's border policy as it is now
+    if (rc) { delete p; return rc; }
+    rc = lm_icp_create(det->device, &p->icp);
+    if (!rc) rc = lm_icp_set_geometry(p->icp, p->W, p->H);
     if (rc) { if (p->icp) lm_icp_destroy(p->icp); delete p; return rc; }
     if (hipEventCreate(&p->e0) != hipSuccess || hipEventCreate(&p->e1) != hipSuccess || hipEventCreate(&p->e2) != hipSuccess) {
         lm_icp_destroy(p->icp); delete p;
@@ -70,6 +74,7 @@ extern "C" void lm_pipeline_destroy(lm_pipeline* p) {
     (void)hipStreamSynchronize(p->det->mstream);
     void* dev[] = {p->d_view_K, p->d_view_valid, p->d_view_wh, p->d_class_base, p->d_sel, p->d_nsel, p->d_scratch};
     for (void* q : dev) if (q) (void)hipFree(q);
+    p->border_src.release();
     void* pin[] = {p->h_sel, p->h_nsel, p->h_class_base};
     for (void* q : pin) if (q) (void)hipHostFree(q);
     if (p->e0) (void)hipEventDestroy(p->e0);
@@ -108,8 +113,30 @@ extern "C" int lm_pipeline_set_views(lm_pipeline* p, const char* class_id, int f
     HIP_TRY(hipStreamSynchronize(p->det->stream));                 // the slot array may be reallocated: no frame may be in flight
     HIP_TRY(hipStreamSynchronize(p->det->mstream));
     const int slot0 = it->second.base + first_template;
-    int rc = lm_icp_set_models(p->icp, slot0, count, depth_ren);
-    if (rc) return rc;
+    int rc;
+    if (p->srcW == p->W && p->srcH == p->H) {
+        if ((rc = lm_icp_set_models(p->icp, slot0, count, depth_ren))) return rc;
+    } else {
+        // depth renderings of the source size: padded with 0 or cropped into the model slots like the scene depth (k_frame_border), eight per launch
+        for (int i = 0; i < count; ++i)
+            if (!depth_ren[i]) return lm_set_error(LM_ERR_INVALID, "model depth %d is null", i);
+        if ((rc = lm_icp_ensure_slots(p->icp, slot0 + count))) return rc;
+        const size_t src_img = (size_t)p->srcW * p->srcH * sizeof(uint16_t), npx = (size_t)p->W * p->H;
+        const int chunk = 8;
+        if ((rc = p->border_src.ensure(src_img * chunk + 16))) return rc;
+        for (int c0 = 0; c0 < count; c0 += chunk) {
+            const int n = std::min(chunk, count - c0);
+            BorderStage bs{};
+            for (int i = 0; i < n; ++i) {
+                HIP_TRY(hipMemcpyAsync(p->border_src.p + (size_t)i * src_img, depth_ren[c0 + i], src_img, hipMemcpyHostToDevice, p->icp->s));
+                border_job(bs.job[bs.njobs++], p->border_src.p + (size_t)i * src_img, p->icp->d_models + ((size_t)slot0 + c0 + i) * npx, p->srcW, p->srcH, p->W, p->H, 2, false);
+            }
+            HIP_TRY(launch_frame_border(bs, p->icp->s));
+            HIP_TRY(hipStreamSynchronize(p->icp->s));              // the staging buffer serves the next eight
+        }
+        HIP_TRY(lm::launch_icp_model_boxes(p->icp->d_models, p->icp->d_model_bbox, slot0, count, p->W, p->H, p->icp->s));   // the boxes of the new images, once (LL.cpp:43-50)
+        for (int i = 0; i < count; ++i) p->icp->slot_boxed[(size_t)slot0 + i] = 1;
+    }
     HIP_TRY(hipStreamSynchronize(p->icp->s));
     memcpy(&p->view_K[(size_t)slot0 * 9], Ks, (size_t)count * 9 * sizeof(float));
     memcpy(&p->view_R[(size_t)slot0 * 9], Rs, (size_t)count * 9 * sizeof(float));

@@ -32,7 +32,7 @@ lm_abi._lib, set by load_library(); a global assigned after import does not trav
 """
 from lm_abi import (LM_ICP_POINT_TO_POINT, LM_ICP_SCENE_FROM_SCENE, MATCH_DTYPE, IcpOptions, PipelineTimings, RenderOptions, Timings,
                     _CDetection, _CMatch, _CPoseResult, _as_depth, _as_grey, _as_mask, _as_rgb, _check, _ptr, _share_hip_runtime_with_torch,
-                    bind_near_device, library_path, load_library, rgb_to_grey_ref)
+                    aligned_size, bind_near_device, library_path, load_library, rgb_to_grey_ref)
 from lm_detector import (Comm, Detector, Match, NMSBoxes, Template, bank_file_info, bank_file_modalities, merge_matches, nms,
                          nms_norms, rgb_to_grey)
 from lm_icp import (ICP_ESTIMATIONS, IcpContext, Pipeline, _icp_flags, _icp_options, _pose_dict, evaluate_registration, poseRefine,

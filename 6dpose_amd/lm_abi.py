@@ -93,6 +93,9 @@ PROTOTYPES = {
     "lm_detector_get_modalities": (I, [P, PS]),
     "lm_detector_set_colour_channels": (I, [P, I]),
     "lm_detector_get_colour_channels": (I, [P]),
+    "lm_detector_set_border": (I, [P, I]),
+    "lm_detector_get_border": (I, [P]),
+    "lm_detector_aligned_size": (I, [P, I, I, I, PI, PI]),
     "lm_rgb_to_grey": (I, [I, P, I64, P]),
     "lm_detector_destroy": (None, [P]),
     "lm_detector_add_template": (I, [P, P, P, P, I, I, S]),
@@ -308,6 +311,52 @@ def rgb_to_grey_ref(rgb) -> np.ndarray:
     R, G, B order — the 8-bit fixed point of OpenCV's RGB2GRAY (unpinned: stated from its documentation, not checked against a build)."""
     v = _rgb_last_axis(rgb).astype(np.int64)
     return ((4899 * v[..., 0] + 9617 * v[..., 1] + 1868 * v[..., 2] + 8192) >> 14).astype(np.uint8)
+
+
+BORDER_POLICIES = {"strict": 0, "pad": 1, "crop": 2}          # lm_detector_set_border
+
+
+def _border_code(border) -> int:
+    if not isinstance(border, str) or border not in BORDER_POLICIES:
+        raise RuntimeError("unknown border policy %r: one of 'strict', 'pad', 'crop'" % (border,))
+    return BORDER_POLICIES[border]
+
+
+def aligned_size(T, width: int, height: int, border: str = "pad"):
+    """(aligned width, aligned height) of a width x height source for a detector with T = T (one entry per pyramid level), in plain Python
+    — the rule of lm_detector_aligned_size, which answers the same.  A size is aligned when at every level l of the L levels
+    (W >> l) % T[l] == 0, (H >> l) % T[l] == 0, W and H are multiples of 2 ** (L - 1) and ((W >> l) * (H >> l)) % 16 == 0.  "pad": the
+    smallest aligned height >= height, then the smallest width >= width; "crop": the largest height <= height, then the largest width <=
+    width, both at least 16; "strict": the size itself.  RuntimeError where there is none ("crop": nothing of at least 16 fits; "strict":
+    the size is not aligned)."""
+    code = _border_code(border)
+    T = [int(t) for t in T]
+    L, W, H = len(T), int(width), int(height)
+    if L < 1 or any(t < 1 for t in T) or W < 16 or H < 16 or W > 16384 or H > 16384:
+        raise RuntimeError("unsupported frame size %dx%d" % (W, H))
+
+    def side_ok(v):
+        return v >= 1 and v % (1 << (L - 1)) == 0 and all((v >> l) >= 1 and (v >> l) % T[l] == 0 for l in range(L))
+
+    def area_ok(w, h):
+        return all(((w >> l) * (h >> l)) % 16 == 0 for l in range(L))
+
+    if code == 0:
+        if not (side_ok(W) and side_ok(H) and area_ok(W, H)):
+            raise RuntimeError("%dx%d is not aligned to T = %s [LL.cpp:1136, 1217-1218]" % (W, H, T))
+        return W, H
+    if code == 1:
+        h = next(v for v in range(H, 1 << 20) if side_ok(v))
+        w = next(v for v in range(W, 1 << 20) if side_ok(v) and area_ok(v, h))
+        if w > 16384 or h > 16384:
+            raise RuntimeError("unsupported frame size %dx%d" % (W, H))
+        return w, h
+    for h in range(H, 15, -1):
+        if side_ok(h):
+            for w in range(W, 15, -1):
+                if side_ok(w) and area_ok(w, h):
+                    return w, h
+    raise RuntimeError("unsupported frame size %dx%d" % (W, H))
 
 
 def _as_depth(a, what="sources[1]") -> np.ndarray:

@@ -11,7 +11,8 @@ from typing import List, Optional, Sequence
 
 import numpy as np
 
-from lm_abi import MATCH_DTYPE, Timings, _CMatch, _as_depth, _as_grey, _as_mask, _as_rgb, _check, _ptr, _rgb_last_axis, load_library
+from lm_abi import (BORDER_POLICIES, MATCH_DTYPE, Timings, _CMatch, _as_depth, _as_grey, _as_mask, _as_rgb, _border_code, _check, _ptr,
+                    _rgb_last_axis, aligned_size, load_library)
 
 
 class Match:
@@ -128,6 +129,26 @@ class Detector:
 
     def getColourChannels(self) -> int:
         return int(self._lib.lm_detector_get_colour_channels(self._h))
+
+    def setBorder(self, border: str) -> None:
+        """lm_detector_set_border: what match, setFrame, storeFrame, submitFrame / matchStream and Pipeline do with a frame whose size is not
+        aligned to the T grid (the reference's asserts at LL.cpp:1136 and 1217-1218).  "strict" (the default) refuses it; "pad" extends it at the
+        right and bottom to alignedSize() — colour by edge replication, depth and masks with 0; "crop" cuts it there.  The results are bit for
+        bit those of "strict" on the frame padded or cropped that way on the host; matches whose box reaches into the padded margin are kept.
+        Sources, masks and ingestBuffers() keep the source size; readStage() returns arrays of the aligned size.  Refused with frames in flight."""
+        _check(self._lib.lm_detector_set_border(self._h, _border_code(border)))
+
+    def getBorder(self) -> str:
+        code = _check(self._lib.lm_detector_get_border(self._h))
+        return {v: k for k, v in BORDER_POLICIES.items()}[code]
+
+    def alignedSize(self, width: int, height: int, border: Optional[str] = None):
+        """lm_detector_aligned_size: (width, height) of the frame buffers a width x height source gets under `border` (None: the detector's
+        own policy) — what the module's aligned_size(T, width, height, border) says in plain Python."""
+        w, h = ctypes.c_int(), ctypes.c_int()
+        _check(self._lib.lm_detector_aligned_size(self._h, -1 if border is None else _border_code(border), int(width), int(height),
+                                                  ctypes.byref(w), ctypes.byref(h)))
+        return int(w.value), int(h.value)
 
     def _colour(self, a):
         return _as_grey(a) if self._cch == 1 else _as_rgb(a)
@@ -599,7 +620,7 @@ class Detector:
         keeps an array of them and reads the fields afterwards)."""
         self._lib.lm_detector_last_timings(self._h, ctypes.byref(t))
 
-    def readStage(self, level: int, kind: int) -> np.ndarray:
+    def readStage(self, level: int, kind: int) -> np.ndarray:  # (arrays of the aligned geometry: alignedSize() of the source under setBorder)
         """Device intermediates of the last front end run (tests): kind 0/1 quantised colour/normal,
         2/3 linear memories colour/normal, 4 strip records of a level below the top, 5 pair stream of the top level (bit planes),
         6 / 7 the second set of the "wide" paths in the layout of 4 / 5 (after a match that ran on it)."""

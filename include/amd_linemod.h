@@ -116,6 +116,27 @@ int lm_detector_get_modalities(const lm_detector *d, const char *names[2]);
  * lm_detector_add_templates_rendered on a grey detector converts the rasteriser's colour image with lm_rgb_to_grey's arithmetic, on the device. */
 int lm_detector_set_colour_channels(lm_detector *d, int channels);
 int lm_detector_get_colour_channels(const lm_detector *d);
+/* Frames of any size.  The reference asserts (src.rows * src.cols) % 16 == 0 (LL.cpp:1136) and response_map.rows / cols % T == 0 at every
+ * pyramid level (LL.cpp:1217-1218); the border policy says what the MATCHING entry points (lm_detector_match, _set_frame, _store_frame,
+ * _submit_frame, _ingest_buffer, lm_pipeline_create / _set_views) do with a width x height that breaks them:
+ *   0 strict (the default): refused with LM_ERR_INVALID and the assert's words, as the reference does;
+ *   1 pad:   the frame is extended at the right and bottom to the aligned size — colour / grey by edge replication (what the reference's
+ *            BORDER_REPLICATE stages assume at a frame edge: no gradient appears), depth and every mask with 0 (no measurement: no normals);
+ *   2 crop:  the frame is cut at the right and bottom to the aligned size.
+ * The source's top-left pixel stays at (0, 0), so match coordinates, K and principal points keep their meaning.  Every entry point then
+ * returns bit for bit what the strict policy returns for the frame padded that way, or for frame[:Ha, :Wa], on the host; matches whose box
+ * reaches into the padded margin are kept (they are records of the padded frame).  The caller hands over — and the pinned staging holds,
+ * and PCIe carries — the SOURCE size: rgb, depth, masks and lm_detector_ingest_buffer's pointers are width x height.  The frame buffers, the
+ * frames parked by lm_detector_store_frame and lm_detector_read_stage have the ALIGNED size; a kernel on the device (k_frame_border) writes them.
+ * A size that is aligned already takes the strict path unchanged.  Training (lm_detector_add_template, _add_templates_rendered) takes any
+ * size under every policy.  A change is LM_ERR_INVALID with frames in flight.
+ * The aligned size, for pad: the smallest Ha >= height, then the smallest Wa >= width, for crop the largest Ha <= height, then the largest
+ * Wa <= width (both at least 16, else LM_ERR_INVALID "unsupported frame size"), such that at every level l of the L levels
+ * (Wa >> l) % T[l] == 0, (Ha >> l) % T[l] == 0, Wa and Ha are multiples of 2^(L-1), and ((Wa >> l) * (Ha >> l)) % 16 == 0.
+ * lm_detector_aligned_size answers for `policy` (-1: the detector's own); under 0 it returns the size itself or the strict refusal. */
+int lm_detector_set_border(lm_detector *d, int policy);
+int lm_detector_get_border(const lm_detector *d);
+int lm_detector_aligned_size(const lm_detector *d, int policy, int width, int height, int *aligned_width, int *aligned_height);
 /* grey[i] = (4899 R + 9617 G + 1868 B + 8192) >> 14 for the `pixels` pixels of an interleaved R, G, B image, on `device`: the 8-bit fixed point of
  * OpenCV's RGB2GRAY (unpinned: not checked against an OpenCV build).  For training a grey detector from colour photographs. */
 int lm_rgb_to_grey(int device, const uint8_t *rgb, int64_t pixels, uint8_t *grey);

@@ -9,6 +9,8 @@
 //     v = fy y/z + cy; pixel (i, j) is sampled at (i, j) — the convention poseRefine back-projects with;
 //   * vertices snapped to 1/256 pixel, edge functions in int64 (exact, watertight, top-left fill rule),
 //     both windings drawn (the reference does not cull);
+//   * a vertex is valid iff p_z > 0 and |rint(256 u)| < 1e9 and |rint(256 v)| < 1e9 (NaN fails); a triangle with an
+//     invalid vertex is not drawn (no near-plane clipping);
 //   * depth: perspective-correct, z = 1 / sum(lambda_i / z_i) in double, nearest fragment wins, ties go
 //     to the lower triangle index; stored as uint16 by truncation (depth.astype(np.uint16));
 //   * colour (mode 'rgb', phong): per-fragment normal / colour interpolated perspective-correctly, light at

@@ -5,7 +5,12 @@ The reference renders with OpenGL (pysixd/renderer.py:306-420), whose result dep
 is nothing bit-level to pin ("parity unpinned by the reference").  This file restates the rules render.hip
 documents — OpenCV camera, vertices snapped to 1/256 pixel, exact int64 edge functions with one fill rule,
 perspective-correct depth in float64 with a fixed operation order, nearest fragment then lower triangle index — in
-numpy, so that depth images can be compared exactly and colour images within a rounding step."""
+numpy, so that depth images can be compared exactly and colour images within a rounding step.
+
+  * a vertex is valid iff p_z > 0 and |rint(256 u)| < 1e9 and |rint(256 v)| < 1e9 (NaN fails); a triangle with an
+    invalid vertex is not drawn (no near-plane clipping).
+
+tests/render_edges_ref.py holds this file to references that do not restate the kernel."""
 import numpy as np
 
 
@@ -20,9 +25,10 @@ def _project(V, K, R, t, scale=1):
     with np.errstate(divide="ignore", invalid="ignore"):
         u = ((K[0, 0] * s) * px) / pz + K[0, 2] * s
         v = ((K[1, 1] * s) * py) / pz + K[1, 2] * s
-    valid = pz > 0
-    sx = np.where(valid, np.rint(u * 256.0), 0).astype(np.int64)
-    sy = np.where(valid, np.rint(v * 256.0), 0).astype(np.int64)
+        fu, fv = np.rint(u * 256.0), np.rint(v * 256.0)
+        valid = (pz > 0) & (np.abs(fu) < 1e9) & (np.abs(fv) < 1e9)
+    sx = np.where(valid, fu, 0).astype(np.int64)
+    sy = np.where(valid, fv, 0).astype(np.int64)
     return sx, sy, pz, valid
 
 

@@ -317,6 +317,10 @@ extern "C" void lm_detector_destroy(lm_detector* d) {
     d->d_cands.release(); d->d_counters.release(); d->d_final.release(); d->d_matches_dev.release(); d->d_hash.release(); d->d_distinct_keys.release(); d->d_tiles.release(); d->d_todo.release(); d->d_work_cls.release(); d->d_work_tid.release();
     for (int l = 0; l < kMaxLevels; ++l) { d->train.mask[l].release(); d->train.lab[l].release(); d->train.hrun[l].release(); }
     d->train.user_mask.release();
+    d->slabs.hist.release(); d->slabs.modes.release();
+    for (auto& lv : d->slabs.mask) for (auto& m : lv) m.release();
+    if (d->slabs.h_modes) (void)hipHostFree(d->slabs.h_modes);
+    if (d->slabs.modes_ready) (void)hipEventDestroy(d->slabs.modes_ready);
     d->train.keys.release(); d->train.counts.release(); d->train.bbox.release(); d->train.out.release();
     for (auto& sl : d->slot) {
         if (sl.h_matches) (void)hipHostFree(sl.h_matches);

@@ -451,6 +451,7 @@ extern "C" int lm_detector_read_params(lm_detector* d, const char* path) {
                             "LL.cpp:560; LL.cpp:632 then divides by zero)", path, nf[0], levels);
     for (int t : T) if (t < 1) return lm_set_error(LM_ERR_INVALID, "T must be >= 1");
     d->class_templates.clear();                                   // LL.cpp:2015
+    d->class_depth_range.clear();                                 // (the ranges go with their classes)
     d->bank_dirty = true; d->work_valid = false; d->frame_valid = false;
     d->pyramid_levels = levels; d->T_at_level = T;
     d->num_features = nf[0]; d->weak_threshold = weak; d->strong_threshold = strong;

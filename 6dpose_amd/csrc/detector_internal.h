@@ -1,5 +1,5 @@
 // Private view of the detector shared by the detector's translation units (detector.cpp, detector_frame.cpp, detector_bank.cpp,
-// detector_stream.cpp, host_pool.cpp, match_lists.cpp), bank_file.cpp, comm.cpp, exchange.cpp and pipeline.cpp (not part of the C ABI).
+// detector_stream.cpp, detector_slabs.cpp, host_pool.cpp, match_lists.cpp), bank_file.cpp, comm.cpp, exchange.cpp and pipeline.cpp (not part of the C ABI).
 #pragma once
 #include <algorithm>
 #include <atomic>
@@ -7,6 +7,7 @@
 #include <condition_variable>
 #include <deque>
 #include <functional>
+#include <map>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -14,6 +15,7 @@
 #include <vector>
 
 #include "../../include/amd_linemod.h"
+#include "depth_modes.h"
 #include "frame_border.h"
 #include "host_templates.h"
 #include "knobs.h"
@@ -231,7 +233,7 @@ struct lm_detector {
         LevelPtrs P{};
         P.quant[0] = q.ang.p; P.quant[1] = q.nrm.p;
         for (int m = 0; m < 2; ++m) {
-            P.mask[m] = slot[arena].have_mask[m] ? lvl[l].mask[m].p : nullptr;
+            P.mask[m] = slabs.mask_on ? slabs.mask_of[l][m] : (slot[arena].have_mask[m] ? lvl[l].mask[m].p : nullptr);
             P.lm[m] = lm_arena[arena].p + lv.lm_off[m];
             P.strips[m] = low ? sm_arena[arena].p + lv.sm_off[m] : nullptr;
             P.bits[m] = low ? bits_arena[arena].p + (lv.sm_off[m] >> 1) : nullptr;
@@ -240,6 +242,19 @@ struct lm_detector {
         P.top_stream = cbits_arena[arena].p;
         return P;
     }
+    // Depth slabs (detector_slabs.cpp).  The histogram, the mode records and the slab masks live on the device; a pass of
+    // lm_detector_match_slabs under a slab sets mask_on, and the front end's writers then take mask_of[level][kind] — the slab ANDed with the
+    // user's mask of that modality, or the slab alone — instead of the resident frame's own masks, which are never written.  quantised: the
+    // quantised maps of lvl[] are those of the resident frame already, so the front end of a lone frame only builds its response memories.
+    struct Slabs {
+        DevBuf<uint32_t> hist, modes;               // kDepthMaxBins counts; kDepthModeWords words of mode records
+        uint32_t* h_modes = nullptr;                // pinned copy of the mode records
+        hipEvent_t modes_ready = nullptr;
+        DevBuf<uint8_t> mask[kMaxLevels][3];        // [level][0 / 1: slab & user mask of that kind, 2: the slab alone]
+        const uint8_t* mask_of[kMaxLevels][2] = {};
+        bool mask_on = false, quantised = false;
+    } slabs;
+    std::map<std::string, std::pair<int, int>> class_depth_range;   // lm_detector_set_class_depth_range: host state, stored in no file
     bool cbits_clean[kSlots] = {};                  // the slot's pair stream is all zero (what the front end's OR-ing writer needs)
     uint64_t n_submitted = 0, n_collected = 0, n_launched = 0;
     // frames submitted but not launched yet: slots pend_first .. pend_first + pend_n - 1 (modulo kSlots), same threshold and work list
@@ -362,6 +377,7 @@ int build_work(lm_detector* d, const char* const* class_ids, int num_class_ids);
 int lm_submit_frame(lm_detector* d, float threshold, const char* const* class_ids, int num_class_ids);
 int lm_collect_frame(lm_detector* d, int sort_unique, lm_match** out, size_t* n_out);   // sort_unique < 0: discard the records
 int lm_launch_pending(lm_detector* d);                                                  // launches the frames waiting for their batch to fill
+int lm_quantise_resident(lm_detector* d);                                               // the quantising stages of the resident frame alone, on `stream` (depth slabs)
 
 // host_pool.cpp: the helper threads of the streamed path (HostPool above) and the staging copy they share with the caller
 bool pool_ready(lm_detector* d);

@@ -75,7 +75,9 @@ struct LaunchClock {                                          // LM_LAUNCH_PROF:
 #else
 #define LM_CLOCK(n)
 #endif
-static int run_frontend_batch(lm_detector* d, int first, int nb, hipStream_t s, bool direct_low, bool direct_top) {
+// stages: bit 0 = quantise, bit 1 = the response memories (a slab pass of lm_detector_match_slabs runs 2 alone: the maps do not depend on masks).
+enum { kFeQuantise = 1, kFeMemories = 2 };
+static int run_frontend_batch(lm_detector* d, int first, int nb, hipStream_t s, bool direct_low, bool direct_top, int stages = kFeQuantise | kFeMemories) {
     const int L = d->pyramid_levels;
     const float thr_sq = d->weak_threshold * d->weak_threshold;
     int rc;
@@ -97,6 +99,7 @@ static int run_frontend_batch(lm_detector* d, int first, int nb, hipStream_t s, 
     auto flush = [&]() { if (st.njobs) { LM_CLOCK("launch_fe_stage"); launch_fe_stage(st, s); } st.njobs = 0; };
     auto room = [&](int jobs) { if (st.njobs + jobs > kFeMaxJobs) flush(); };
     auto build_lm_jobs = [&](int l) {                        // linear memories of level l of every frame (its quantised maps are complete)
+        if (!(stages & kFeMemories)) return;
         if (l < L - 1 ? direct_low : direct_top) return;    // bit planes only: fe_bits_jobs below
         for (int b = 0; b < nb; ++b) {
             const LevelPtrs P = d->level_ptrs(b, l, (first + b) % lm_detector::kSlots);
@@ -109,7 +112,7 @@ static int run_frontend_batch(lm_detector* d, int first, int nb, hipStream_t s, 
     // the quantisation of the small levels, and the last launch is a quarter of what it was.)
     for (int l = 0; l < L; ++l) {
         st.njobs = 0;
-        for (int b = 0; b < nb; ++b) {
+        for (int b = 0; b < nb && (stages & kFeQuantise); ++b) {
             const lm_detector::Slot& sl = d->slot[(first + b) % lm_detector::kSlots];
             LevelBufs& B = d->level_bufs(b, l);
             const uint8_t* src = l == 0 ? sl.in_rgb : B.rgb.p;
@@ -127,6 +130,7 @@ static int run_frontend_batch(lm_detector* d, int first, int nb, hipStream_t s, 
     }
     build_lm_jobs(L - 1);
     flush();
+    if (!(stages & kFeMemories)) { HIP_TRY(hipGetLastError()); return LM_OK; }
     if (direct_low || direct_top) {                      // the bit planes of every frame in one launch
         st.njobs = 0;
         auto flush_bits = [&]() { if (st.njobs) { LM_CLOCK("launch_fe_bits"); launch_fe_bits(st, s); } st.njobs = 0; };
@@ -556,13 +560,25 @@ int lm_launch_pending(lm_detector* d) {
         if ((rc = batch_begin(d, B)) || (rc = order_batch(d, B)) || (rc = enqueue_border(d, B)) || (rc = choose_bit_writers(d, B))) return rc;
         if ((B.wide || B.cwide) && (rc = ensure_wide_arenas(d, B))) return rc;
     }
-    { LM_CLOCK("step front end"); if ((rc = run_frontend_batch(d, B.first, B.nb, B.s, B.direct_low, B.direct_top))) return rc; }
+    const int stages = d->slabs.quantised && B.nb == 1 ? kFeMemories : kFeQuantise | kFeMemories;
+    { LM_CLOCK("step front end"); if ((rc = run_frontend_batch(d, B.first, B.nb, B.s, B.direct_low, B.direct_top, stages))) return rc; }
     { LM_CLOCK("step bits tables+ev1"); pack_bit_planes(d, B); if ((rc = record_front_end(d, B))) return rc; }
     { LM_CLOCK("step coarse"); if ((rc = enqueue_coarse(d, B))) return rc; }
     { LM_CLOCK("step refine"); if ((rc = enqueue_match(d, B))) return rc; }
     { LM_CLOCK("step dedupe+done"); if ((rc = enqueue_dedupe(d, B))) return rc; }
     batch_launched(d, B);
     return LM_OK;
+}
+
+// The quantising stages of the resident frame into lvl[], on the frame stream, with nothing in flight (lm_detector_match_slabs: its passes
+// follow with kFeMemories alone, ordered behind this by order_after_default_stream).
+int lm_quantise_resident(lm_detector* d) {
+    if (!d->frame_valid) return lm_set_error(LM_ERR_INVALID, "no frame resident: call lm_detector_set_frame / select_frame first");
+    if (d->n_submitted != d->n_collected) return lm_set_error(LM_ERR_INVALID, "frames in flight: collect them first");
+    LM_DIAG_IDLE(d, "lm_quantise_resident");
+    const int si = (int)(d->n_submitted % lm_detector::kSlots);      // the slot the next submit takes: it reads the same frame
+    d->slot[si].in_rgb = d->cur_rgb; d->slot[si].in_depth = d->cur_depth;
+    return run_frontend_batch(d, si, 1, d->stream, false, false, kFeQuantise);
 }
 
 // The detector's current frame (lm_detector_set_frame / select_frame, or the frame a previous submit_frame left current) as a

@@ -69,6 +69,22 @@ class RenderOptions(ctypes.Structure):
                 ("clip_near", ctypes.c_float), ("clip_far", ctypes.c_float)]
 
 
+class DepthModeOptions(ctypes.Structure):
+    """lm_depth_mode_options (include/amd_linemod_depth.h)."""
+    _fields_ = [("bin_mm", ctypes.c_int32), ("near_mm", ctypes.c_int32), ("far_mm", ctypes.c_int32), ("window", ctypes.c_int32),
+                ("min_pixels", ctypes.c_int32), ("max_modes", ctypes.c_int32)]
+
+
+class _CDepthMode(ctypes.Structure):
+    _fields_ = [("bin", ctypes.c_int32), ("depth_mm", ctypes.c_int32), ("pixels", ctypes.c_uint32)]
+
+
+class _CSlab(ctypes.Structure):
+    _fields_ = [("depth_mm", ctypes.c_int32), ("pixels", ctypes.c_uint32), ("lo_mm", ctypes.c_int32), ("hi_mm", ctypes.c_int32),
+                ("first_class", ctypes.c_int32), ("num_classes", ctypes.c_int32), ("records", ctypes.c_int64)]
+
+
+DEPTH_MODE_DTYPE = np.dtype([("bin", np.int32), ("depth_mm", np.int32), ("pixels", np.uint32)])
 MATCH_DTYPE = np.dtype([("x", np.int32), ("y", np.int32), ("similarity", np.float32),
                         ("class_index", np.int32), ("template_id", np.int32)])
 LM_ICP_SCENE_FROM_SCENE = 1
@@ -81,6 +97,7 @@ P, I, F, D, S = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_double, 
 Z, U64, I64 = ctypes.c_size_t, ctypes.c_uint64, ctypes.c_int64
 PP, PI, PS, PZ = ctypes.POINTER(P), ctypes.POINTER(I), ctypes.POINTER(S), ctypes.POINTER(Z)
 PM, PPM, PU8 = ctypes.POINTER(_CMatch), ctypes.POINTER(ctypes.POINTER(_CMatch)), ctypes.POINTER(ctypes.c_uint8)
+PDMO = ctypes.POINTER(DepthModeOptions)
 PPOSE, PICPO, PRO = ctypes.POINTER(_CPoseResult), ctypes.POINTER(IcpOptions), ctypes.POINTER(RenderOptions)
 PROTOTYPES = {
     "lm_last_error": (S, []),
@@ -163,6 +180,11 @@ PROTOTYPES = {
     "lm_detector_get_paths": (I, [P, PI, PI]),
     "lm_detector_set_response_table": (I, [P, PU8]),
     "lm_detector_get_response_table": (I, [P, PU8]),
+    "lm_depth_mode_options_init": (None, [PDMO]),
+    "lm_detector_depth_modes": (I, [P, PDMO, P, I, PI]),
+    "lm_detector_set_class_depth_range": (I, [P, S, I, I, I]),
+    "lm_detector_get_class_depth_range": (I, [P, S, PI, PI]),
+    "lm_detector_match_slabs": (I, [P, F, PS, I, I, PDMO, PPM, PZ, ctypes.POINTER(_CSlab), I, PI, ctypes.POINTER(ctypes.POINTER(ctypes.c_int32))]),
     "lm_detector_bit_arena_bytes": (I, [P, ctypes.POINTER(U64), ctypes.POINTER(U64)]),
     "lm_detector_wide_arena_bytes": (I, [P, ctypes.POINTER(U64), ctypes.POINTER(U64)]),
     "lm_detector_train_stats": (I, [P, ctypes.POINTER(I64)]),

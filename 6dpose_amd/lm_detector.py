@@ -11,8 +11,8 @@ from typing import List, Optional, Sequence
 
 import numpy as np
 
-from lm_abi import (BORDER_POLICIES, MATCH_DTYPE, Timings, _CMatch, _as_depth, _as_grey, _as_mask, _as_rgb, _border_code, _check, _ptr,
-                    _rgb_last_axis, aligned_size, load_library)
+from lm_abi import (BORDER_POLICIES, DEPTH_MODE_DTYPE, MATCH_DTYPE, DepthModeOptions, Timings, _CMatch, _CSlab, _as_depth, _as_grey, _as_mask,
+                    _as_rgb, _border_code, _check, _ptr, _rgb_last_axis, aligned_size, load_library)
 
 
 class Match:
@@ -609,6 +609,80 @@ class Detector:
         # column lists first: indexing a structured array record by record costs ~5 us per match
         cols = [recs[f].tolist() for f in ("x", "y", "similarity", "class_index", "template_id")]
         return [Match(x, y, s, names[c], t) for x, y, s, c, t in zip(*cols)]
+
+    # ---- depth slabs: template scales from the scene's depth histogram ----------------------------
+    @staticmethod
+    def _mode_options(bin_mm=25, near_mm=300, far_mm=4000, window=2, min_pixels=1000, max_modes=8) -> DepthModeOptions:
+        vals = (bin_mm, near_mm, far_mm, window, min_pixels, max_modes)
+        if any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) or abs(int(v)) > 2 ** 30 for v in vals):
+            raise RuntimeError("depth modes: bin_mm, near_mm, far_mm, window, min_pixels and max_modes are integers, got %r" % (vals,))
+        return DepthModeOptions(*[int(v) for v in vals])
+
+    def depthModes(self, **mode_options) -> np.ndarray:
+        """lm_detector_depth_modes: the primary depths of the resident frame (setFrame / selectFrame, in the aligned geometry of setBorder) as
+        DEPTH_MODE_DTYPE records (bin, depth_mm, pixels), most pixels first.  Options: bin_mm=25, near_mm=300, far_mm=4000, window=2,
+        min_pixels=1000, max_modes=8.  A pixel with near_mm <= d < far_mm counts in bin (d - near_mm) // bin_mm; bin b is a mode iff
+        h[b] >= min_pixels, h[b] > h[j] for j in [b - window, b) and h[b] >= h[j] for j in (b, b + window]; depth_mm is the bin's centre
+        near_mm + b * bin_mm + bin_mm // 2.  Exact: tests/depth_slabs_ref.py says the same in numpy."""
+        opt = self._mode_options(**mode_options)
+        out = np.zeros(16, DEPTH_MODE_DTYPE)
+        n = ctypes.c_int()
+        _check(self._lib.lm_detector_depth_modes(self._h, ctypes.byref(opt), _ptr(out), len(out), ctypes.byref(n)))
+        return out[:n.value].copy()
+
+    def setClassDepthRange(self, class_id: str, lo_mm, hi_mm) -> None:
+        """lm_detector_set_class_depth_range: the band of scene depths [lo_mm, hi_mm] at which this class's templates are valid — for a class
+        rendered at radius r, say 0.85 r .. 1.15 r.  (None, None) clears it.  Host state of this detector: no file stores it, readClasses and
+        readBank produce classes without a range."""
+        if lo_mm is None and hi_mm is None:
+            _check(self._lib.lm_detector_set_class_depth_range(self._h, class_id.encode(), 0, 0, 1))
+            return
+        if any(v is None or isinstance(v, bool) or not isinstance(v, (int, np.integer)) or abs(int(v)) > 2 ** 30 for v in (lo_mm, hi_mm)):
+            raise RuntimeError("a depth range is two integers lo_mm <= hi_mm (mm), or None, None; got %r" % ((lo_mm, hi_mm),))
+        _check(self._lib.lm_detector_set_class_depth_range(self._h, class_id.encode(), int(lo_mm), int(hi_mm), 0))
+
+    def getClassDepthRange(self, class_id: str):
+        """(lo_mm, hi_mm) of setClassDepthRange, or None for a class without a range."""
+        lo, hi = ctypes.c_int(), ctypes.c_int()
+        have = _check(self._lib.lm_detector_get_class_depth_range(self._h, class_id.encode(), ctypes.byref(lo), ctypes.byref(hi)))
+        return (int(lo.value), int(hi.value)) if have else None
+
+    def matchSlabsResident(self, threshold: float, class_ids: Sequence[str] = (), masks=(), slab_mm: int = 150, **mode_options):
+        """lm_detector_match_slabs on the resident frame: every class with a depth range is matched once per primary depth p of the scene
+        (depthModes(**mode_options)) inside its range, under the slab mask "d != 0 and p - slab_mm <= d <= p + slab_mm" ANDed with the frame's own
+        masks; classes without a range are matched once, without a slab.  Returns (records, slabs): the canonical merge of all passes
+        (MATCH_DTYPE, class_index as in matchArray) and one dict per mode, in mode order — depth_mm, pixels, lo_mm, hi_mm, class_ids, records
+        (before the merge; 0 with class_ids == [] for a slab no class wanted) — plus a last one with depth_mm None for the pass of the classes
+        without a range.  The masks of the resident frame are those given to setFrame: `masks` must be empty here (matchSlabs takes them)."""
+        if masks is not None and len(masks):
+            raise RuntimeError("matchSlabsResident matches the resident frame under the masks setFrame was given: pass masks to setFrame or matchSlabs")
+        if isinstance(slab_mm, bool) or not isinstance(slab_mm, (int, np.integer)) or abs(int(slab_mm)) > 2 ** 30:
+            raise RuntimeError("slab_mm must be an integer (mm), got %r" % (slab_mm,))
+        opt = self._mode_options(**mode_options)
+        carr, n, names = self._class_args(class_ids)
+        out, cnt = ctypes.POINTER(_CMatch)(), ctypes.c_size_t()
+        slabs = (_CSlab * 17)()
+        ns, cls = ctypes.c_int(), ctypes.POINTER(ctypes.c_int32)()
+        _check(self._lib.lm_detector_match_slabs(self._h, float(threshold), carr, n, int(slab_mm), ctypes.byref(opt), ctypes.byref(out),
+                                                 ctypes.byref(cnt), slabs, len(slabs), ctypes.byref(ns), ctypes.byref(cls)))
+        try:
+            info = []
+            for s in slabs[:ns.value]:
+                ids = [names[cls[i]] for i in range(s.first_class, s.first_class + s.num_classes)]
+                free = s.depth_mm < 0
+                info.append({"depth_mm": None if free else int(s.depth_mm), "pixels": None if free else int(s.pixels),
+                             "lo_mm": None if free else int(s.lo_mm), "hi_mm": None if free else int(s.hi_mm), "class_ids": ids,
+                             "records": int(s.records)})
+        finally:
+            self._lib.lm_free(cls)
+        return self._take(out, cnt.value), info
+
+    def matchSlabs(self, sources, threshold: float, class_ids: Sequence[str] = (), masks=(), slab_mm: int = 150, **mode_options):
+        """setFrame(sources, masks) followed by matchSlabsResident(threshold, class_ids, slab_mm=slab_mm, **mode_options)."""
+        self._sources(sources, True)
+        self._mode_options(**mode_options)                    # (refuse bad options before the upload)
+        self.setFrame(sources, masks)
+        return self.matchSlabsResident(threshold, class_ids, (), slab_mm, **mode_options)
 
     def lastTimings(self) -> dict:
         t = Timings()

@@ -26,6 +26,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "amd_linemod_depth.h"   /* lm_depth_mode_options, lm_depth_mode, lm_slab */
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -373,6 +375,45 @@ int lm_detector_get_paths(const lm_detector *d, int *refine, int *coarse);
  * lm_detector_set_paths(d, 3, 2) asked for them, on the wide bit-plane kernels —, which lm_detector_get_paths reports.  Thresholds are not comparable between tables. */
 int lm_detector_set_response_table(lm_detector *d, const uint8_t r[5]);
 int lm_detector_get_response_table(const lm_detector *d, uint8_t r[5]);
+/* Depth slabs: template scales chosen from the scene's depth histogram (the reference's "use depth histogram and 1D nms to find some primary
+ * scales", linemodLevelup/readme.md:29-34, notes.md: train each scale as a class of its own and match it only where the scene has that depth).
+ *
+ * lm_detector_depth_modes: the primary depths of the RESIDENT frame (lm_detector_set_frame / select_frame; the aligned geometry of
+ * lm_detector_set_border, whose padding is depth 0 and counts nowhere).  Integers only, so the result is exact:
+ *   nbins = ceil((far_mm - near_mm) / bin_mm); a pixel with near_mm <= d < far_mm counts in bin (d - near_mm) / bin_mm;
+ *   bin b is a mode iff h[b] >= min_pixels, h[b] > h[j] for j in [b - window, b) and h[b] >= h[j] for j in (b, b + window] (bins outside
+ *   [0, nbins) do not exist; on a plateau the lowest bin wins); depth_mm = near_mm + b * bin_mm + bin_mm / 2;
+ *   the max_modes modes with the most pixels are returned, most pixels first, ties towards the smaller depth.
+ * options NULL = the defaults of lm_depth_mode_options_init.  out has room for `capacity` >= max_modes records; *n receives the count.
+ * LM_ERR_INVALID: options outside the limits stated in amd_linemod_depth.h, a detector without DepthNormal, no resident frame, frames in flight.
+ *
+ * lm_detector_set_class_depth_range: the band of scene depths [lo_mm, hi_mm] at which the templates of a class are valid (for a class
+ * rendered at radius r, for example 0.85 r .. 1.15 r); clear != 0 removes it.  lo_mm > hi_mm is LM_ERR_INVALID, an unknown class
+ * LM_ERR_NOT_FOUND.  Host state of this detector: no class file, bank file or parameter file stores it, lm_detector_read_class / _read_bank
+ * produce classes without a range and lm_detector_read_params drops every range with the classes.  lm_detector_get_class_depth_range returns 1 and the range,
+ * 0 when the class has none.
+ *
+ * lm_detector_match_slabs, on the resident frame, with modes = lm_detector_depth_modes(options):
+ *   the requested classes are class_ids in their order (NULL / 0: every class, sorted); unknown names are skipped;
+ *   for mode k of depth p: slab S_k = the pixels with d != 0 and p - slab_mm <= d <= p + slab_mm; classes_k = the requested classes whose
+ *   range holds p.  classes_k empty: the slab is skipped (reported with no class and 0 records).  Otherwise its records are those of
+ *   lm_detector_match of classes_k under the masks S_k AND the frame's own mask of each modality (lm_detector_set_frame's `masks`);
+ *   the requested classes without a range are matched once under the frame's own masks only;
+ *   *out = the canonical merge (lm_merge_matches) of all of it, class_index = the position in the requested list; lm_free(*out).
+ * slabs[0 .. *num_slabs): one lm_slab per mode, in mode order, then one with depth_mm = -1 for the classes without a range when there are
+ * any; slab_capacity >= max_modes + 1.  *slab_classes (lm_free) holds the slabs' class positions.
+ * The histogram, the modes, the slab masks and their pyramid are made on the device from the resident depth image: per slab nothing crosses
+ * PCIe but the records, the frame is quantised once per call, and the frame's own masks are left as they are.  Response table, paths,
+ * border policy, colour_channels and a depth-only modality set apply as in lm_detector_match.  LM_ERR_INVALID: a detector without
+ * DepthNormal, a sharded detector (lm_detector_set_shard), slab_mm < 0, no resident frame, frames in flight.  The streamed calls
+ * (lm_detector_submit_frame) and lm_pipeline_run do not know slabs. */
+void lm_depth_mode_options_init(lm_depth_mode_options *options);
+int lm_detector_depth_modes(lm_detector *d, const lm_depth_mode_options *options, lm_depth_mode *out, int capacity, int *n);
+int lm_detector_set_class_depth_range(lm_detector *d, const char *class_id, int lo_mm, int hi_mm, int clear);
+int lm_detector_get_class_depth_range(const lm_detector *d, const char *class_id, int *lo_mm, int *hi_mm);
+int lm_detector_match_slabs(lm_detector *d, float threshold, const char *const *class_ids, int num_class_ids, int slab_mm,
+                            const lm_depth_mode_options *options, lm_match **out, size_t *n, lm_slab *slabs, int slab_capacity,
+                            int *num_slabs, int32_t **slab_classes);
 /* Device memory ALLOCATED for the bit planes, summed over the result slots: the strip records of the levels below the top and the pair
  * stream of the top level (tests: no response table makes them grow). */
 int lm_detector_bit_arena_bytes(const lm_detector *d, uint64_t *strip_records, uint64_t *pair_stream);

@@ -292,10 +292,10 @@ extern "C" int lm_detector_select_frame(lm_detector* d, int slot) {
 
 // (every stage has the ALIGNED geometry: under a border policy that is not the source's)
 extern "C" int64_t lm_detector_read_stage(lm_detector* d, int level, int kind, uint8_t* dst, int64_t capacity) {
-    if (!d || level < 0 || level >= d->pyramid_levels || kind < 0 || kind > 7) return lm_set_error(LM_ERR_INVALID, "bad argument");
+    if (!d || level < 0 || level >= d->pyramid_levels || kind < 0 || kind > 8) return lm_set_error(LM_ERR_INVALID, "bad argument");
     if (d->fW <= 0) return lm_set_error(LM_ERR_INVALID, "no frame processed yet");
-    if (kind < 4 && !d->use[kind & 1])            // kinds 0, 2: colour; 1, 3: normals
-        return lm_set_error(LM_ERR_INVALID, "stage %d belongs to %s, which is not in the detector's modality set", kind, kModalityName[kind & 1]);
+    if ((kind < 4 || kind == 8) && !d->use[kind == 8 ? 1 : kind & 1])            // kinds 0, 2: colour; 1, 3, 8: normals
+        return lm_set_error(LM_ERR_INVALID, "stage %d belongs to %s, which is not in the detector's modality set", kind, kModalityName[kind == 8 ? 1 : kind & 1]);
     const LevelBufs& b = d->lvl[level];
     const LevelGeom& lv = d->geom.lv[level];
     const uint8_t* src = nullptr;
@@ -316,6 +316,9 @@ extern "C" int64_t lm_detector_read_stage(lm_detector* d, int level, int kind, u
             if (level == d->pyramid_levels - 1) return lm_set_error(LM_ERR_INVALID, "the top level has no strip records");
             if (!d->wbits_arena[d->last_arena].cap) return lm_set_error(LM_ERR_INVALID, "no second set of strip records: the last match did not refine on the wide path");
             src = d->wbits_arena[d->last_arena].p + (lv.sm_off[d->mod_kind[0]] >> 1); size = (int64_t)d->nmod * 8 * lv.T * lv.T * lv.NS * lv.Hd * 8; break;
+        case 8:       // the normals of level 0 before the median, as the synchronous front end (a training view, a lone match, frame 0 of a batch) left them
+            if (level != 0) return lm_set_error(LM_ERR_INVALID, "only level 0 has normals before the median");
+            src = d->nrm_raw.p; size = (int64_t)b.W * b.H; break;
         default:      // the second pair stream (k_coarse_wide reads kinds 5 and 7): the layout and size of kind 5
             if (level != d->pyramid_levels - 1) return lm_set_error(LM_ERR_INVALID, "only the top level has a pair stream");
             if (!d->wcbits_arena[d->last_arena].cap) return lm_set_error(LM_ERR_INVALID, "no second pair stream: the last match did not run its coarse pass on the wide path");

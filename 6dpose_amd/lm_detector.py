@@ -697,7 +697,8 @@ class Detector:
     def readStage(self, level: int, kind: int) -> np.ndarray:  # (arrays of the aligned geometry: alignedSize() of the source under setBorder)
         """Device intermediates of the last front end run (tests): kind 0/1 quantised colour/normal,
         2/3 linear memories colour/normal, 4 strip records of a level below the top, 5 pair stream of the top level (bit planes),
-        6 / 7 the second set of the "wide" paths in the layout of 4 / 5 (after a match that ran on it)."""
+        6 / 7 the second set of the "wide" paths in the layout of 4 / 5 (after a match that ran on it), 8 the quantised normals of level 0
+        before the 5x5 median (level 0 only; of the last synchronous front end: addTemplate, a lone match, the first frame of a batch)."""
         n = _check(self._lib.lm_detector_read_stage(self._h, level, kind, None, 0))
         buf = np.zeros(n, np.uint8)
         _check(self._lib.lm_detector_read_stage(self._h, level, kind, _ptr(buf), n))

@@ -462,7 +462,9 @@ int lm_detector_last_timings(const lm_detector *d, lm_timings *t);
  * end wrote directly is cleared by the match unless lm_detector_set_direct_bits(d, 2) was set), 6 / 7
  * the second set of the wide paths in the layout and size of 4 / 5 (after a match on k_local_wide /
  * k_coarse_wide: with v the response of a cell, kinds 4 / 5 then hold {v & 1, v == 4} and kinds 6 / 7
- * {(v >> 1) & 1, nothing}; LM_ERR_INVALID while no such match has allocated them).
+ * {(v >> 1) & 1, nothing}; LM_ERR_INVALID while no such match has allocated them), 8 the quantised
+ * normals of level 0 BEFORE the 5x5 median (W_0*H_0 bytes, 0 or one-hot; level 0 only): what the last
+ * synchronous front end — a training view, a lone match, the first frame of a batch — left there.
  * Copies min(capacity, size) bytes, returns the full size. */
 int64_t lm_detector_read_stage(lm_detector *d, int level, int kind, uint8_t *dst, int64_t capacity);
 

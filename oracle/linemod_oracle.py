@@ -119,10 +119,11 @@ def fast_atan2_deg(y: np.ndarray, x: np.ndarray) -> np.ndarray:
     return a
 
 
-def quantized_orientations(src: np.ndarray, weak_threshold: float) -> Tuple[np.ndarray, np.ndarray]:
+def quantized_orientations(src: np.ndarray, weak_threshold: float, parts: Optional[dict] = None) -> Tuple[np.ndarray, np.ndarray]:
     """quantizedOrientations + hysteresisGradient (LL.cpp:350-505).
 
-    src: (H,W,3) u8 in caller's channel order.  Returns (magnitude f32 (squared), one-hot u8)."""
+    src: (H,W,3) u8 in caller's channel order.  Returns (magnitude f32 (squared), one-hot u8).  parts (optional dict) receives the
+    intermediates: smoothed, dx3, dy3, mag3 (per channel), idx (the channel taken), dx, dy, angle, thr_sq and hysteresis_gradient's."""
     smoothed = gaussian_blur7(src)
     dx3, dy3 = sobel3(smoothed)
     dx3 = dx3.astype(np.int32)
@@ -136,11 +137,14 @@ def quantized_orientations(src: np.ndarray, weak_threshold: float) -> Tuple[np.n
     dy = np.take_along_axis(dy3, idx[..., None], 2)[..., 0]
     mag = np.take_along_axis(mag3, idx[..., None], 2)[..., 0].astype(f32)
     angle = fast_atan2_deg(dy, dx)
-    return mag, hysteresis_gradient(mag, angle, f32(weak_threshold) * f32(weak_threshold))
+    if parts is not None:
+        parts.update(smoothed=smoothed, dx3=dx3, dy3=dy3, mag3=mag3, idx=idx, dx=dx, dy=dy, angle=angle, thr_sq=f32(weak_threshold) * f32(weak_threshold))
+    return mag, hysteresis_gradient(mag, angle, f32(weak_threshold) * f32(weak_threshold), parts)
 
 
-def hysteresis_gradient(mag: np.ndarray, angle: np.ndarray, threshold_sq) -> np.ndarray:
-    """hysteresisGradient (LL.cpp:427-505); Appendix A.4-5."""
+def hysteresis_gradient(mag: np.ndarray, angle: np.ndarray, threshold_sq, parts: Optional[dict] = None) -> np.ndarray:
+    """hysteresisGradient (LL.cpp:427-505); Appendix A.4-5.  parts (optional dict) receives q (the codes the vote reads, (H, W)) and, of
+    the interior (H - 2, W - 2), max_votes and index."""
     H, W = angle.shape
     q = np.rint((angle * f32(16.0 / 360.0)).astype(f32))
     q = np.clip(q, 0, 255).astype(np.uint8)           # saturate_cast<uchar>
@@ -159,6 +163,8 @@ def hysteresis_gradient(mag: np.ndarray, angle: np.ndarray, threshold_sq) -> np.
                 hist[b] += (patch == b)
     max_votes = hist.max(axis=0)
     index = hist.argmax(axis=0)                        # first maximum (strict '<' at LL.cpp:491)
+    if parts is not None:
+        parts.update(q=q, max_votes=max_votes, index=index)
     ok = (mag[1:-1, 1:-1] > f32(threshold_sq)) & (max_votes >= 5)
     out[1:-1, 1:-1] = np.where(ok, (1 << index).astype(np.uint8), 0)
     return out
@@ -179,9 +185,10 @@ def nn_down2(img: np.ndarray) -> np.ndarray:
     return np.ascontiguousarray(img[0:2 * (H // 2):2, 0:2 * (W // 2):2])
 
 
-def quantized_normals(depth: np.ndarray, distance_threshold: int, difference_threshold: int) -> np.ndarray:
-    """quantizedNormals (LL.cpp:729-819); Appendix A.7.  depth: (H,W) u16."""
-    from scipy.ndimage import median_filter
+def quantized_normals_raw(depth: np.ndarray, distance_threshold: int, difference_threshold: int, parts: Optional[dict] = None) -> np.ndarray:
+    """quantizedNormals up to the median (LL.cpp:729-817); Appendix A.7.  depth: (H,W) u16.  parts (optional dict) receives the
+    intermediates of the interior [5, H - 6] x [5, W - 6]: c, deltas and counted (8 taps each, in the reference's order), A0, A1, A3, b0, b1, det, ddx,
+    ddy (int64), valid, v1, v2, v3."""
     H, W = depth.shape
     r = 5
     d = depth.astype(np.int64)
@@ -192,10 +199,12 @@ def quantized_normals(depth: np.ndarray, distance_threshold: int, difference_thr
     c = d[y0:y1, x0:x1]
     A0 = np.zeros_like(c); A1 = np.zeros_like(c); A3 = np.zeros_like(c)
     b0 = np.zeros_like(c); b1 = np.zeros_like(c)
+    deltas, counted = [], []
     for (i, j) in [(-r, -r), (0, -r), (r, -r), (-r, 0), (r, 0), (-r, r), (0, r), (r, r)]:
         nb = d[y0 + j:y1 + j, x0 + i:x1 + i]
         delta = nb - c
         f = (np.abs(delta) < difference_threshold).astype(np.int64)
+        deltas.append(delta); counted.append(f)
         fi, fj = f * i, f * j
         A0 += fi * i; A1 += fi * j; A3 += fj * j
         b0 += fi * delta; b1 += fj * delta
@@ -223,7 +232,15 @@ def quantized_normals(depth: np.ndarray, distance_threshold: int, difference_thr
     # any dimension (the reference's out-of-table corner, Appendix A.7) wraps modulo 400/8000.
     flat = (v3 * 400 + v2 * 20 + v1) % 8000
     dst[y0:y1, x0:x1] = np.where(valid, lut[flat], 0)
-    return median_filter(dst, size=5, mode="nearest")
+    if parts is not None:
+        parts.update(c=c, deltas=np.stack(deltas), counted=np.stack(counted), A0=A0, A1=A1, A3=A3, b0=b0, b1=b1, det=det, ddx=ddx, ddy=ddy, valid=valid, v1=v1, v2=v2, v3=v3)
+    return dst
+
+
+def quantized_normals(depth: np.ndarray, distance_threshold: int, difference_threshold: int) -> np.ndarray:
+    """quantizedNormals (LL.cpp:729-819): the raw normals, then cv::medianBlur(5) (replicate border)."""
+    from scipy.ndimage import median_filter
+    return median_filter(quantized_normals_raw(depth, distance_threshold, difference_threshold), size=5, mode="nearest")
 
 
 # --------------------------------------------------------------------------------------

@@ -995,7 +995,6 @@ constexpr int kKnnLanes = 8;       // lanes per point
 constexpr int kKnnSlabPts = 2048;  // target points staged per workgroup (32-byte records, 64 KiB: two workgroups per CU)
 constexpr int kKnnRuns = 16;       // x columns of a ring kept as separate runs (R <= 7; wider rings take whole x columns)
 constexpr int kKnnHard = 512;      // points per round of a workgroup, any of which may be handed to a whole wave
-constexpr int kKnnFarMax = 256;    // points per hypothesis k_icp_knn_far takes (more than that stay with their wave)
 constexpr int kKnnFarBlocks = 96;  // ... with this many workgroups per hypothesis
 constexpr int kKnnFew = 4;         // distinct distances a lane sorts in registers in a collecting pass
 
@@ -1316,8 +1315,10 @@ k_icp_knn(IcpBuffers B, int knn) {
             int slot = 0;
             if (lane == 0) slot = atomicAdd(&B.st[h].n_far, 1);
             slot = __shfl(slot, 0, 64);
-            if (slot < kKnnFarMax) { if (lane == 0) far_list[slot] = pos; }
-            else (void)knn_point<64>(pos, lane, runs, k, gx > gy ? gx : gy, INT_MAX, s_tgt, p0, np, T, rec, orig, cs, cov, gx, gy, minx, miny, inv, cell);
+            // (the list holds every target: 2 * cap2 keys of scratch per hypothesis.  It was cut at 256 entries once, the points beyond summed by
+            // their wave: which ones depended on the order the waves arrived, and a run did not repeat bit for bit — 64 lanes and 512 threads
+            // group the same 30 terms differently)
+            if (lane == 0 && slot < nt) far_list[slot] = pos;       // (a point is handed over once, so slot < nt)
         }
         __syncthreads();
         if (threadIdx.x == 0) {
@@ -1347,9 +1348,10 @@ k_icp_knn_far(IcpBuffers B, int knn) {
     const int h = blockIdx.y;
     const IcpState& S = B.st[h];
     if (S.status != 0 || S.n_tgt == 0) return;
-    const int nfar = S.n_far < kKnnFarMax ? S.n_far : kKnnFarMax;
+    const int nt_all = S.n_tgt;
+    const int nfar = S.n_far < nt_all ? S.n_far : nt_all;
     if ((int)blockIdx.x >= nfar) return;
-    const int nt = S.n_tgt;
+    const int nt = nt_all;
     const int big = S.gx > S.gy ? S.gx : S.gy;
     // (kKnnFarBlocks workgroups per cloud walk the list: a workgroup per possible entry was 4096 workgroups to dispatch for 16 clouds — 11 us
     // when the lists are empty, as they are for clouds without depth outliers)

@@ -440,6 +440,10 @@ extern "C" int64_t lm_icp_read_debug(lm_icp* c, int hypothesis, int kind, double
             tmp.push_back((double)st.n_model); tmp.push_back((double)st.n_scene);
             for (int k = 0; k < 16; ++k) tmp.push_back((double)st.sort_clk[k]);
             tmp.push_back((double)st.team_size); tmp.push_back((double)st.resume_it); tmp.push_back((double)st.build);
+            // which kernels prepared the clouds: groups of the wide sorts that finished (kIcpSortGroups = the one-workgroup kernel had nothing
+            // to do), points k_icp_knn handed to k_icp_knn_far and points that list had no room for (none: it holds every target)
+            tmp.push_back((double)st.vox_done[0]); tmp.push_back((double)st.vox_done[1]); tmp.push_back((double)st.grid_done);
+            tmp.push_back((double)std::min(st.n_far, st.n_tgt)); tmp.push_back((double)std::max(st.n_far - st.n_tgt, 0));
             n = (int64_t)tmp.size();
             break;
         }
@@ -447,6 +451,14 @@ extern "C" int64_t lm_icp_read_debug(lm_icp* c, int hypothesis, int kind, double
             n = (int64_t)st.n_tgt * kIcpCovStride; tmp.resize((size_t)n);
             if (n && hipMemcpy(tmp.data(), c->B.cov + off * kIcpCovStride, (size_t)n * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
                 return lm_set_error(LM_ERR_HIP, "read-back failed");
+            break;
+        }
+        case 6: {   // original (voxel-order) index of the target point at every sorted position [n_tgt]: the row order of kind 5
+            n = (int64_t)st.n_tgt; tmp.resize((size_t)n);
+            std::vector<int> orig((size_t)n);
+            if (n && hipMemcpy(orig.data(), c->B.tgt_orig + off, (size_t)n * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess)
+                return lm_set_error(LM_ERR_HIP, "read-back failed");
+            for (int64_t p = 0; p < n; ++p) tmp[(size_t)p] = (double)orig[(size_t)p];
             break;
         }
         case 4: {   // the slices' partial sums of the last two evaluations, [2][kIcpMaxSplit][32] (slots 29..31: shader cycles of the slice)

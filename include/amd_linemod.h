@@ -562,9 +562,12 @@ int lm_icp_run(lm_icp *c, int count, const int32_t *model_slots, const float *mo
  * cloud, 1 target cloud, 2 target normals (xyz triples, voxel order), 3 {init_guess t[3], T[16],
  * n_model, n_scene, grid_x, grid_y, cell, iterations, 8 phase cycle counts, team_note[4], n_source, n_target, 4 kNN cycle counts,
  * 4 voxel cycle counts, n_model, n_scene, 16 sort cycle counts, team_size, resume_it, build (the k_icp_team build that finished the
- * hypothesis, KP * 4 + SLAB * 2 + slabbed: 4 <1,false>, 6 / 7 <1,true>, 10 / 11 <2,true>, 22 / 23 <5,true>; 0 the sliced launches)}, 4 the slices' partial sums of
+ * hypothesis, KP * 4 + SLAB * 2 + slabbed: 4 <1,false>, 6 / 7 <1,true>, 10 / 11 <2,true>, 22 / 23 <5,true>; 0 the sliced launches),
+ * groups of the eight-workgroup voxel sort that finished the model cloud, the scene cloud, of the eight-workgroup grid sort (8: that path
+ * prepared the cloud, less: the one-workgroup kernel did), target points handed to the whole-cloud kNN search, points its list had no room for (0: it holds every target)}, 4 the slices' partial sums of
  * the last two evaluations [2][64][32] (slots 29-31 of a slice: its shader cycles, search cycles, queued points), 5 the cumulants of the
- * k nearest neighbours per sorted target position [n_target][12].  Copies min(capacity, size) doubles, returns the size. */
+ * k nearest neighbours per sorted target position [n_target][12], 6 the original (voxel-order) index of the target point at every sorted
+ * position [n_target].  Copies min(capacity, size) doubles, returns the size. */
 int64_t lm_icp_read_debug(lm_icp *c, int hypothesis, int kind, double *dst, int64_t capacity);
 
 /* ---- per-frame pipeline --------------------------------------------------------

@@ -12,6 +12,11 @@ K_CAM = np.array([572.4114, 0, 325.2611, 0, 573.57043, 242.04899, 0, 0, 1], np.f
 
 # entries of IcpContext.read_debug(h, 3) (lm_icp_read_debug kind 3, pose_refine.cpp)
 DBG3_TEAM_NOTE, DBG3_TEAM_SIZE, DBG3_RESUME_IT, DBG3_BUILD = 33, 65, 66, 67
+# which kernels prepared the clouds: groups of k_icp_voxel_wide that finished the model / scene cloud and of k_icp_grid_wide (SORT_GROUPS: the
+# wide path did the cloud; less: k_icp_voxel / k_icp_grid did), points handed to k_icp_knn_far, points its list had no room for (its list holds
+# every target, so 0)
+DBG3_VOX_DONE_MODEL, DBG3_VOX_DONE_SCENE, DBG3_GRID_DONE, DBG3_KNN_FAR, DBG3_KNN_FAR_REFUSED = 68, 69, 70, 71, 72
+SORT_GROUPS = 8                                                   # kIcpSortGroups (icp_kernels.h)
 
 
 def load_bgr(name):

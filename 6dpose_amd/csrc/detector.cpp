@@ -1,7 +1,7 @@
 // libamdlinemod.so — host orchestration + C ABI (include/amd_linemod.h) of the MI355X LINE-MOD
 // detector.  Mirrors linemodLevelup::Detector (LL.cpp:1663-2146): bank bookkeeping and the greedy
 // template extraction on the host, every per-pixel / per-template stage in HIP kernels
-// (frontend.hip, match_bytes.hip, match_bits.hip).  No CPU fallback: creation fails without a HIP device.
+// (fe_quant.hip, fe_bits.hip, match_bytes.hip, match_bits.hip).  No CPU fallback: creation fails without a HIP device.
 // This file: errors, thread binding, creation / destruction and the small setters and getters.  The frame and the training front
 // end are in detector_frame.cpp, the template bank in detector_bank.cpp, the streamed matching path in detector_stream.cpp (its
 // helper threads: host_pool.cpp), the host-side result lists and NMS in match_lists.cpp.

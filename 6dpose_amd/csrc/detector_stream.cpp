@@ -57,7 +57,7 @@ static int bits_grid(lm_detector* d, int nb) {
 // that carries the jobs of all frames of the batch.  Frame b keeps its intermediates in level_bufs(b, l) and writes the arenas of its
 // own result slot.  7 launches per frame (round 2's per-slot graph) -> 3 per batch.
 // direct_low / direct_top: nothing will read the byte planes of the levels below the top / of the top level — the bit planes are written
-// straight from the quantised maps by one k_fe_bits launch at the end (frontend.hip) and the byte planes not at all.
+// straight from the quantised maps by one k_fe_bits launch at the end (fe_bits.hip) and the byte planes not at all.
 #ifdef LM_DIAG
 struct LaunchClock {                                          // LM_LAUNCH_PROF: host time of the steps of a batch launch and of individual HIP calls in them; LM_LAUNCH_SERIES: the first 80 of each, one by one
     const char* name; double t0;

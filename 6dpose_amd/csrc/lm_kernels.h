@@ -1,5 +1,5 @@
 // Internal interface between the host orchestration (detector*.cpp, pose_refine.cpp) and the HIP
-// kernels (frontend.hip, match_bytes.hip, match_bits.hip, match_wide.hip, icp*.hip).  gfx950 only.  Not part of the public C ABI.
+// kernels (fe_quant.hip, fe_bits.hip, match_bytes.hip, match_bits.hip, match_wide.hip, icp*.hip).  gfx950 only.  Not part of the public C ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -23,10 +23,10 @@ inline uint32_t resp_pack(const uint8_t r[5]) {
 inline int resp_low_weight(const uint8_t r[5]) { const uint32_t p = resp_pack(r), kh = (p >> 20) & 7u, kl = (p >> 24) & 7u; return kl > kh ? r[kl] : 1; }   // a (1 when the low plane is empty)
 inline bool resp_two_planes(const uint8_t r[5]) { const uint32_t kl = (resp_pack(r) >> 24) & 7u; return kl == 4 || r[kl + 1] == 0; }          // nothing non-zero beyond the second value
 
-// ---- front end (frontend.hip): reference A1-A7, LL.cpp:350-505, 557-581, 729-880, 1026-1243 ----
+// ---- front end (fe_quant.hip, fe_bits.hip): reference A1-A7, LL.cpp:350-505, 557-581, 729-880, 1026-1243 ----
 void upload_normal_lut(const uint8_t lut400[400]);
 
-// Every job of the front end goes through one job table: several independent jobs in one launch (frontend.hip, k_fe_stage).
+// Every job of the front end goes through one job table: several independent jobs in one launch (fe_quant.hip, k_fe_stage).
 // The jobs: the colour chain (blur7 + sobel_quant + hysteresis) and the normal chain (normals + median5) as tiled passes, the pyramid
 // steps (dst = (W/2, H/2)), and build_lm: spread (T x T OR) -> 8 response maps -> linearised layout LM[8][T*T][(W/T)*(H/T)] for both
 // modalities of a level ([0] colour, [1] normals); mask[m] may be null; `strips[m]` (may be null) receives the strip-major copy used
@@ -60,7 +60,7 @@ void fe_job_nn_down2(FeJob& j, const uint8_t* src, uint8_t* dst, int W, int H);
 // default set, (0, 1) or (1, 1) for a detector with one modality (gz = nm slices of blocks; the absent kind's pointers are never read).
 void fe_job_build_lm(FeJob& j, const uint8_t* const quant[2], const uint8_t* const mask[2], uint8_t* const lm[2], uint8_t* const strips[2],
                      int W, int H, int T, int m0 = 0, int nm = 2);
-// the bit planes straight from the quantised maps, when nothing reads the byte planes (frontend.hip)
+// the bit planes straight from the quantised maps, when nothing reads the byte planes (fe_bits.hip)
 bool fe_bits_rows_possible(int W, int T);     // the level's rows fit the stage's LDS
 void fe_job_bits_rows(FeJob& j, const uint8_t* const quant[2], const uint8_t* const mask[2], uint8_t* const bits[2], int W, int H, int T, bool tiles, int m0 = 0, int nm = 2);   // tiles: from pixel tiles where the geometry allows (T = 4, 5 or 8, the row fits the LDS pool)
 // (the writer of whole dwords when the label planes start on 64-position boundaries — fe_top_bits_kind —, else, or when forced, the one that ORs
@@ -164,7 +164,7 @@ void launch_local_bits(const FrameBatch& fb, const BitsBatch& B, const FrameGeom
                        uint32_t cap, uint32_t dedupe_cap_slots, int grid_blocks, int max_features, int low_weight /* a: the sum is a n_a + 4 n_4 */, hipStream_t s);
 // Coarse pass on bit planes: per frame of a batch the flat arena and the pair stream of bytes [byte0, byte0 + 32 npairs) of it (the top
 // level's blocks of both modalities with their zero tails): launch_pack_top packs it from the bytes, the front end writes it directly when
-// nothing reads the top level's bytes (frontend.hip, top_bits_body: the stream must be zero before).
+// nothing reads the top level's bytes (fe_bits.hip, top_bits_body: the stream must be zero before).
 struct TopBits { const uint8_t* lm[kMaxBatch]; uint8_t* bits[kMaxBatch]; };
 void launch_pack_top(const TopBits& B, int nb, uint32_t byte0, uint32_t npairs, hipStream_t s);
 // candidates only (no tiles); max_features = the largest nf of the bank's top-level entries.  Two kernels: k_coarse_bits (a wave = one template on

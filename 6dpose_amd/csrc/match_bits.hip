@@ -60,7 +60,7 @@ static __device__ __forceinline__ uint32_t pack4(uint32_t d) {
 }
 static __device__ __forceinline__ uint32_t pack16(const uint4& v) { return pack4(v.x) | (pack4(v.y) << 8) | (pack4(v.z) << 16) | (pack4(v.w) << 24); }
 
-// Strip records from the strip bytes (the front end writes the records itself when nothing reads the bytes: frontend.hip, bits_rows_body;
+// Strip records from the strip bytes (the front end writes the records itself when nothing reads the bytes: fe_bits.hip, bits_rows_body;
 // this kernel serves the banks and geometries that keep the byte planes — a fallback launch of k_local may follow — and the tests of both).
 __global__ void __launch_bounds__(256)
 k_pack_bits(BitsBatch B, uint32_t sm_off0, uint32_t records, int NS, int Hd) {
@@ -99,7 +99,7 @@ k_local_bits(FrameBatch fb, BitsBatch B, FrameGeom g, const TemplEntry* __restri
     const int nb = fb.nb;
     const LocalShare share = local_share(nb);
     local_prologue(fb, s_cnt, s_acc, cand_cap, dedupe_cap_slots);
-    // The pair stream k_coarse_bits has just read is zeroed for the slot's next frame: the front end ORs it together (frontend.hip, top_bits_body)
+    // The pair stream k_coarse_bits has just read is zeroed for the slot's next frame: the front end ORs it together (fe_bits.hip, top_bits_body)
     if (B.top_clear_units)
         for (int f = 0; f < nb; ++f)
             for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < B.top_clear_units; i += gridDim.x * blockDim.x)

@@ -7,7 +7,7 @@
 // Cache; the byte kernels (k_coarse, k_local) are bound by the vector-L1 access rate (see "Gather discipline" below), the bit-plane refinement
 // (k_local_bits, the default) by the number of 16-byte wave loads it issues — not by HBM and not by arithmetic.
 //
-// Data layout (built by frontend.hip / detector_frame.cpp, offsets in FrameGeom):
+// Data layout (built by fe_quant.hip, fe_bits.hip / detector_frame.cpp, offsets in FrameGeom):
 //   LM arena: per level, per modality: u8 [8 labels][T*T phases][(W/T)*(H/T)] + zero tail.
 //   Bank:     TemplEntry per (pyramid, level).  Its features (both modalities) are sorted by alignment
 //             class and padded to a multiple of kFeatBatch with entries that read zeros, so the inner

@@ -1,6 +1,6 @@
 // Template extraction on the device: Detector::addTemplate's feature selection for rendered views —
 // ColorGradientPyramid::extractTemplate (LL.cpp:589-643), DepthNormalPyramid::extractTemplate (LL.cpp:888-966) and
-// QuantizedPyramid::selectScatteredFeatures (LL.cpp:279-318) — after the quantisers of frontend.hip.  gfx950 only.
+// QuantizedPyramid::selectScatteredFeatures (LL.cpp:279-318) — after the quantisers of fe_quant.hip.  gfx950 only.
 //
 // Per view (pixel-parallel, on the detector's stream right after the view's front end):
 //   k_train_mask   object mask = rendered depth > 0 (or the caller's object_mask != 0: single-image addTemplate), its nearest-neighbour pyramid (LL.cpp:576, 877), bounding box

@@ -1,5 +1,5 @@
 """numpy model of the bit-level tricks of the front end: the 8 x 8 bit-matrix transposes that turn per-cell response bytes into strip records
-(bits_rows_block_body), and the two bit-sliced window counts (csrc/frontend.hip, round 4): the 3x3 majority vote of
+(bits_rows_block_body), and the two bit-sliced window counts (csrc/fe_quant.hip, round 4): the 3x3 majority vote of
 hysteresisGradient (LL.cpp:457-504) and cv::medianBlur(5) of the quantised normals (LL.cpp:818).  A tap is a BYTE of predicates per pixel
 (the kernel packs four neighbouring pixels into a word: the operations are bitwise, so a byte array states the same algorithm), a tree of
 full adders counts the taps per predicate, a bit-sliced comparison picks the result.  `python profiles/frontend_bitslice_model.py` checks
@@ -62,7 +62,7 @@ def median5_bitsliced(raw):
 
 
 def transpose8x8(x):
-    """8 x 8 bit-matrix transpose of uint64 words (byte i bit j <-> byte j bit i): three shift-xor-mask steps (csrc/frontend.hip)."""
+    """8 x 8 bit-matrix transpose of uint64 words (byte i bit j <-> byte j bit i): three shift-xor-mask steps (csrc/fe_bits.hip)."""
     x = x.astype(np.uint64)
     for sh, mask in ((7, 0x00AA00AA00AA00AA), (14, 0x0000CCCC0000CCCC), (28, 0x00000000F0F0F0F0)):
         t = (x ^ (x >> np.uint64(sh))) & np.uint64(mask)

@@ -1,4 +1,4 @@
-"""Seeded frames that put the front end (csrc/frontend.hip) on its edges, each with the modality parameters it needs and a CONDITION
+"""Seeded frames that put the front end (csrc/fe_quant.hip, csrc/fe_bits.hip) on its edges, each with the modality parameters it needs and a CONDITION
 function: given the oracle's intermediates (the `parts` of quantized_orientations / quantized_normals_raw) it counts the pixels that sit on
 the edge the case is about.  tests/test_frontend_cases.py asserts those counts and holds the oracle to the scalar restatement
 (frontend_scalar_ref.py) on every frame; tests/test_gpu_frontend_edges.py runs the same frames through the kernels.

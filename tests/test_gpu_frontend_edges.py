@@ -1,4 +1,4 @@
-"""GPU tests (`-m gpu`) of the front end (csrc/frontend.hip) away from the default modality parameters and on the frames of frontend_cases.py:
+"""GPU tests (`-m gpu`) of the front end (csrc/fe_quant.hip, csrc/fe_bits.hip) away from the default modality parameters and on the frames of frontend_cases.py:
 every comparison is exact, against the oracle that test_frontend_cases.py holds to the scalar restatement on the same frames.
 
 The parameters are set the way a user sets them: the detector writes its parameter file, the values are replaced in the text, Detector.read()

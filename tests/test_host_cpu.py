@@ -296,7 +296,7 @@ def test_nms_norms_and_nmsboxes_equal_the_oracle(lib):
 
 
 def test_magic_division_with_one_correction_is_exact():
-    """frontend.hip fast_div: q = umulhi(n, ceil(2^32 / d)) is floor(n / d) or one more for EVERY 32-bit n (the excess n e / (d 2^32) with
+    """fe_device.h fast_div: q = umulhi(n, ceil(2^32 / d)) is floor(n / d) or one more for EVERY 32-bit n (the excess n e / (d 2^32) with
     e = m d - 2^32 < d stays below 1), so `q - (q d > n)` is exact — also where n d passes 2^32 (8000 x 6000 frames: ADVICE r03; the bare
     product was wrong there).  Checked here on the index ranges the front end divides (flat block index / blocks of a job, linear-memory
     index / row length) up to 16384 x 16384 frames and on random 31-bit values."""

@@ -532,8 +532,55 @@ extern "C" int lm_detector_set_shard(lm_detector* d, int rank, int world) {
     if (!d || world < 1 || rank < 0 || rank >= world) return lm_set_error(LM_ERR_INVALID, "bad shard (%d of %d)", rank, world);
     if (int rc = lm_need_both(d, "lm_detector_set_shard")) return rc;
     if (world > 1 && d->refine_mode == 3) return lm_set_error(LM_ERR_INVALID, "the wide paths are not available on a sharded detector: lm_detector_set_paths first");
+    if (world > 1 && d->part_min_parts > 0) return lm_set_error(LM_ERR_INVALID, "part matching is not available on a sharded detector (%d ranks)", world);
     d->shard_rank = rank; d->shard_world = world;
     return LM_OK;
+}
+
+// ---- part-based matching (match_parts.hip) ----------------------------------------------------------------------
+// The part table of one template entry, on the host alone: feature i at (xs[i], ys[i]) belongs to part (2 x >= width) + 2 (2 y >= height); part p
+// owns the slots [start[p], start[p] + npad[p]) of the part-ordered feature arrays, its n[p] features first in their original order, then
+// padding up to a multiple of kFeatBatch; it is eligible iff n[p] >= min_part_features.  out16 = start[4], n[4], npad[4], eligible[4] (start
+// counted from the entry's first slot); order (may be null; room for n + 28) = per slot the feature's index, -1 for padding.
+extern "C" int lm_part_table(int width, int height, const int32_t* xs, const int32_t* ys, int n, int min_part_features, int32_t* out16, int32_t* order) {
+    if (n < 0 || (n && (!xs || !ys)) || !out16) return lm_set_error(LM_ERR_INVALID, "null argument");
+    if (min_part_features < 1) return lm_set_error(LM_ERR_INVALID, "min_part_features must be at least 1, got %d", min_part_features);
+    int cnt[4] = {0, 0, 0, 0};
+    auto part_of = [&](int i) { return (2 * (long)xs[i] >= width ? 1 : 0) + (2 * (long)ys[i] >= height ? 2 : 0); };
+    for (int i = 0; i < n; ++i) ++cnt[part_of(i)];
+    int at = 0;
+    for (int p = 0; p < 4; ++p) {
+        const int npad = (cnt[p] + kFeatBatch - 1) / kFeatBatch * kFeatBatch;
+        out16[p] = at; out16[4 + p] = cnt[p]; out16[8 + p] = npad; out16[12 + p] = cnt[p] >= min_part_features ? 1 : 0;
+        if (order) {
+            int w = at;
+            for (int i = 0; i < n; ++i) if (part_of(i) == p) order[w++] = i;
+            while (w < at + npad) order[w++] = -1;
+        }
+        at += npad;
+    }
+    return LM_OK;
+}
+
+extern "C" int lm_detector_set_part_matching(lm_detector* d, int min_parts, int min_part_features) {
+    if (!d) return lm_set_error(LM_ERR_INVALID, "null detector");
+    if (min_parts < 0 || min_parts > 4) return lm_set_error(LM_ERR_INVALID, "min_parts must be 0 (off) or 1..4, got %d", min_parts);
+    if (min_part_features < 1) return lm_set_error(LM_ERR_INVALID, "min_part_features must be at least 1, got %d", min_part_features);
+    if (min_parts > 0 && d->shard_world > 1) return lm_set_error(LM_ERR_INVALID, "part matching is not available on a sharded detector (%d ranks)", d->shard_world);
+    if (d->n_submitted != d->n_collected) return lm_set_error(LM_ERR_INVALID, "frames in flight: collect them before changing part matching");
+    int rc = lm_launch_pending(d);
+    if (rc) return rc;
+    if ((min_parts > 0) != (d->part_min_parts > 0) || (min_parts > 0 && min_part_features != d->part_min_features)) d->bank_dirty = true;   // the part tables come and go with the bank's device image
+    d->part_min_parts = min_parts; d->part_min_features = min_part_features;
+    return LM_OK;
+}
+extern "C" int lm_detector_get_part_matching(const lm_detector* d, int* min_parts, int* min_part_features) {
+    if (!d || !min_parts || !min_part_features) return lm_set_error(LM_ERR_INVALID, "null argument");
+    *min_parts = d->part_min_parts; *min_part_features = d->part_min_features;
+    return LM_OK;
+}
+int lm_parts_refused(const lm_detector* d, const char* what) {
+    return d->part_min_parts > 0 ? lm_set_error(LM_ERR_INVALID, "%s is not available under part matching: lm_detector_set_part_matching(d, 0, .) first", what) : LM_OK;
 }
 
 static inline int floordiv(int a, int b) { int q = a / b; return (a % b != 0 && ((a < 0) != (b < 0))) ? q - 1 : q; }
@@ -552,6 +599,10 @@ int upload_bank(lm_detector* d) {
     std::vector<uint32_t> xy;
     std::vector<uint32_t> word, rmask;          // levels below the top: feat_word per feature, run_mask per 8 features (lm_kernels.h)
     const uint32_t pad_xy = 0x80008000u;   // x = y = -32768: never inside an image
+    const bool with_parts = d->part_min_parts > 0;
+    std::vector<PartEntry> ptab;                // part matching: the part table per entry and the part-ordered copies of off / word
+    std::vector<int32_t> poff, pxs, pys, porder;
+    std::vector<uint32_t> pword;
     int flat = 0;
     for (auto& kv : d->class_templates) {
         d->bank_classes.push_back(kv.first);
@@ -603,6 +654,27 @@ int upload_bank(lm_detector* d) {
                     }
                 if (e.nf == 0) mnx = mny = mxx = mxy = 0;
                 e.min_x = (int16_t)mnx; e.min_y = (int16_t)mny; e.max_x = (int16_t)mxx; e.max_y = (int16_t)mxy;
+                if (with_parts) {                        // the features in their own order, part by part; padding reads zeros as in the holistic arrays
+                    pxs.clear(); pys.clear();
+                    for (int i = 0; i < nm; ++i)
+                        for (const Feature& f : tp[(size_t)nm * l + i].features) { pxs.push_back(f.x); pys.push_back(f.y); }
+                    porder.assign(recs.size() + 4 * kFeatBatch, -1);
+                    int32_t t16[16];
+                    if (int rc = lm_part_table(e.width, e.height, pxs.data(), pys.data(), (int)recs.size(), d->part_min_features, t16, porder.data())) return rc;
+                    PartEntry pe{};
+                    const uint32_t first = (uint32_t)poff.size();
+                    for (int p = 0; p < 4; ++p) {
+                        pe.start[p] = first + (uint32_t)t16[p]; pe.n[p] = (uint16_t)t16[4 + p]; pe.npad[p] = (uint16_t)t16[8 + p];
+                        pe.eligible |= (uint32_t)t16[12 + p] << p;
+                    }
+                    const int slots = t16[3] + t16[11];
+                    for (int k = 0; k < slots; ++k) {
+                        const int i = porder[k];
+                        poff.push_back(i >= 0 ? recs[i].off : (int32_t)zero16);
+                        pword.push_back(i >= 0 ? ((recs[i].base0 & ~15u) | (uint32_t)recs[i].cls) : (szero & ~15u));
+                    }
+                    ptab.push_back(pe);
+                }
                 std::stable_sort(recs.begin(), recs.end(), [](const Rec& a, const Rec& b) { return a.cls < b.cls; });
                 std::vector<uint8_t> starts;             // per feature of this entry: 1 = first of a class run
                 auto push_feat = [&](int32_t o, uint32_t pxy, uint32_t base0, int cls, bool start) {
@@ -646,6 +718,15 @@ int upload_bank(lm_detector* d) {
         HIP_TRY(hipMemcpy(d->d_feat_xy.p, xy.data(), xy.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(d->d_feat_word.p, word.data(), word.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(d->d_run_mask.p, rmask.data(), rmask.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    }
+    if (with_parts) {
+        if ((rc = d->d_parts.ensure(std::max<size_t>(1, ptab.size()))) || (rc = d->d_part_off.ensure(std::max<size_t>(1, poff.size()))) ||
+            (rc = d->d_part_word.ensure(std::max<size_t>(1, pword.size())))) return rc;
+        if (!ptab.empty()) HIP_TRY(hipMemcpy(d->d_parts.p, ptab.data(), ptab.size() * sizeof(PartEntry), hipMemcpyHostToDevice));
+        if (!poff.empty()) {
+            HIP_TRY(hipMemcpy(d->d_part_off.p, poff.data(), poff.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+            HIP_TRY(hipMemcpy(d->d_part_word.p, pword.data(), pword.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+        }
     }
     // counter widths of the bit-plane kernels: the largest entry at the top level (k_coarse_bits) and below it (k_local_bits)
     d->bits_max_nf = 0; d->cbits_max_nf = 0;

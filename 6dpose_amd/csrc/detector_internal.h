@@ -140,6 +140,12 @@ struct lm_detector {
     DevBuf<int32_t> d_feat_off;
     DevBuf<uint32_t> d_feat_xy;
     DevBuf<uint32_t> d_feat_word, d_run_mask;       // refinement levels: feature words + class-run masks (lm_kernels.h)
+    // Part-based matching (lm_detector_set_part_matching; match_parts.hip): off while part_min_parts == 0.  Switched on, upload_bank
+    // also builds the part table of every entry and the part-ordered copies of feat_off / feat_word (one index space, like the holistic arrays).
+    int part_min_parts = 0, part_min_features = 8;
+    DevBuf<PartEntry> d_parts;
+    DevBuf<int32_t> d_part_off;
+    DevBuf<uint32_t> d_part_word;
     // work list
     std::vector<int32_t> work_pyr;
     std::shared_ptr<std::vector<int32_t>> work_cls, work_tid;   // shared with in-flight result slots
@@ -371,6 +377,7 @@ int run_frontend_training(lm_detector* d);
 
 // detector_bank.cpp
 int upload_bank(lm_detector* d);
+int lm_parts_refused(const lm_detector* d, const char* what);   // LM_OK while part matching is off, else LM_ERR_INVALID "<what> is not available under part matching"
 int build_work(lm_detector* d, const char* const* class_ids, int num_class_ids);
 
 // detector_stream.cpp

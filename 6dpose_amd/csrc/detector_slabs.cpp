@@ -165,6 +165,7 @@ extern "C" int lm_detector_match_slabs(lm_detector* d, float threshold, const ch
     int nbins = 0, rc;
     if ((rc = depth_frame_ready(d, "lm_detector_match_slabs"))) return rc;
     if (d->shard_world > 1) return lm_set_error(LM_ERR_INVALID, "lm_detector_match_slabs is not available on a sharded detector (%d ranks)", d->shard_world);
+    if ((rc = lm_parts_refused(d, "lm_detector_match_slabs"))) return rc;
     if (slab_mm < 0) return lm_set_error(LM_ERR_INVALID, "slab_mm must not be negative, got %d", slab_mm);
     if ((rc = mode_options(options, &o, &nbins))) return rc;
     if (slab_capacity < o.max_modes + 1) return lm_set_error(LM_ERR_INVALID, "room for %d slabs, max_modes + 1 = %d may be reported", slab_capacity, o.max_modes + 1);

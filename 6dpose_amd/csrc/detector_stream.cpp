@@ -173,6 +173,23 @@ static bool wide_active(const lm_detector* d, int num_work) {
 static bool cwide_active(const lm_detector* d, int num_work) {
     return wide_active(d, num_work) && knobs().coarse_bits && d->coarse_mode == 2 && d->cbits_max_nf <= kWideMaxFeatures;
 }
+// Part-based matching (match_parts.hip): k_coarse_parts / k_local_parts in place of k_coarse_bits / k_local_bits, for any
+// pyramid (with a single level the coarse pass's verdict is final and k_local_parts only hands the candidates on).
+static bool parts_active(const lm_detector* d, int num_work) { return d->part_min_parts > 0 && num_work > 0; }
+// Nothing is silently holistic: whatever would send a part-mode frame to another kernel is refused when the frame is submitted.
+static int parts_check(const lm_detector* d, float threshold) {
+    if (d->part_min_parts <= 0) return LM_OK;
+    if (!(threshold >= 0.f)) return lm_set_error(LM_ERR_INVALID, "part matching needs a threshold >= 0 (a part without responses must not pass), got %g", (double)threshold);
+    if (d->shard_world > 1) return lm_set_error(LM_ERR_INVALID, "part matching is not available on a sharded detector (%d ranks)", d->shard_world);
+    if (d->refine_mode != 0 || d->coarse_mode != 0 || !knobs().bitplanes || !knobs().coarse_bits)
+        return lm_set_error(LM_ERR_INVALID, "part matching runs on the bit-plane kernels only: lm_detector_set_paths(d, 0, 0)");
+    if (!d->resp_two_planes) return lm_set_error(LM_ERR_INVALID, "part matching needs a response table of at most two distinct non-zero values (the bit-plane kernels)");
+    if (d->bits_max_nf > 16383 || d->cbits_max_nf > 16383) return lm_set_error(LM_ERR_INVALID, "part matching: a template entry has more than 16383 features");
+    if (!d->bits_all_in)
+        return lm_set_error(LM_ERR_INVALID, "part matching needs every refinement window inside its planes: a template of this bank has features outside its box, "
+                                            "or is too large for the frame (width + 16 T > frame width)");
+    return LM_OK;
+}
 // Device pointers of result slot `si` (everything a frame in flight owns).
 static int frame_slot(lm_detector* d, int si, bool tiled, uint32_t tile_cap, FrameSlot* out) {
     lm_detector::Slot& sl = d->slot[si];
@@ -215,6 +232,7 @@ static int slot_begin(lm_detector* d, float threshold, const char* const* class_
         if (d->pend_n && (!same || threshold != d->pend_threshold) && (rc = lm_launch_pending(d))) return rc;
     }
     if ((rc = build_work(d, class_ids, num_class_ids))) return rc;
+    if ((rc = parts_check(d, threshold))) return rc;
     const int num_work = (int)d->work_pyr.size();
     const int K = lm_detector::kSlots;
     if (d->buf_cand_cap < d->cand_cap) {
@@ -236,7 +254,7 @@ static int slot_begin(lm_detector* d, float threshold, const char* const* class_
         HIP_TRY(hipMemset(d->d_final.p, 0, 8 * (size_t)K * sizeof(unsigned long long)));
     }
     // tile refinement (match_bytes.hip): two-level pyramids with a tileable geometry; the buffers exist per result slot
-    const bool tiled = (tiles_wanted(d) && num_work > 0 && tile_plan_possible(d->geom)) || bits_active(d, num_work) || wide_active(d, num_work);   // (the bit-plane paths use the todo bytes)
+    const bool tiled = (tiles_wanted(d) && num_work > 0 && tile_plan_possible(d->geom)) || bits_active(d, num_work) || wide_active(d, num_work) || parts_active(d, num_work);   // (the bit-plane paths use the todo bytes)
     const uint32_t tile_cap = d->buf_cand_cap / 2;      // a tile has at least two members
     if (tiled && (d->d_tiles.cap < (size_t)tile_cap * K || d->d_todo.cap < (size_t)d->buf_cand_cap * K)) {
         if ((rc = lm_launch_pending(d))) return rc;
@@ -332,6 +350,7 @@ struct Batch {
     float threshold;
     bool bits, cbits, tiled;                  // refinement on bit planes / coarse pass on the pair stream / tile refinement
     bool wide, cwide;                         // ... on two sets of bit planes (match_wide.hip): bits / cbits are set as well
+    bool parts;                               // ... under the part rule (match_parts.hip): bits / cbits are set as well
     bool direct_low, direct_top, top_ored;    // the front end writes the bit planes below the top / of the top level itself; ... by OR-ing into a zeroed pair stream
     uint32_t tile_cap, cap;
     hipStream_t s;                            // every kernel of a batch on the matching stream (one queue; the end of a stage is the start of the next)
@@ -340,6 +359,7 @@ struct Batch {
     TopBits tb;
     WidePlanes wb, wt;                        // the second set of strip records / of the pair stream
     BankDev bank;                             // the device bank and work list, as the matching launchers take them
+    PartsDev pd;                              // ... and its part tables
     int slot(int b) const { return (first + b) % lm_detector::kSlots; }
 };
 
@@ -352,14 +372,16 @@ static int batch_begin(lm_detector* d, Batch& B) {
     B.threshold = lead.threshold;
     B.wide = wide_active(d, B.num_work);
     B.cwide = cwide_active(d, B.num_work);
-    B.bits = B.wide || bits_active(d, B.num_work);
-    B.cbits = B.cwide || cbits_active(d, B.num_work);
+    B.parts = parts_active(d, B.num_work);               // (slot_begin has refused what the part kernels do not serve: no wide table, ("bits", "bits"))
+    B.bits = B.wide || B.parts || bits_active(d, B.num_work);
+    B.cbits = B.cwide || B.parts || cbits_active(d, B.num_work);
     B.tiled = !B.bits && tiles_wanted(d) && B.num_work > 0 && tile_plan_possible(d->geom);
     B.tile_cap = d->buf_cand_cap / 2;
     B.cap = std::min<uint32_t>(lead.match_cap, d->buf_cand_cap);
     B.s = d->mstream;
     B.fb.nb = B.nb;
     B.bank = BankDev{d->d_entries.p, d->d_feat_off.p, d->d_feat_word.p, d->d_run_mask.p, d->d_feat_xy.p, d->d_work.p};
+    B.pd = PartsDev{d->d_parts.p, d->d_part_off.p, d->d_part_word.p, d->part_min_parts};
     int rc;
     for (int b = 0; b < B.nb; ++b)
         if ((rc = frame_slot(d, B.slot(b), B.tiled, B.tile_cap, &B.fb.f[b]))) return rc;
@@ -488,6 +510,7 @@ static int enqueue_coarse(lm_detector* d, const Batch& B) {
     // the counters are zero on entry (reset by the slots' previous k_dedupe)
     { LM_CLOCK("launch_coarse");
     if (B.cwide) launch_coarse_wide(B.fb, B.tb, B.wt, d->geom, B.bank, B.num_work, B.threshold, d->buf_cand_cap, d->cbits_byte0, d->cbits_max_nf, B.s);
+    else if (B.parts) { launch_coarse_parts(B.fb, B.tb, d->geom, B.bank, B.pd, B.num_work, B.threshold, d->buf_cand_cap, d->cbits_byte0, d->cbits_max_nf, d->resp_low_weight, B.s); d->coarse_batched = false; }
     else if (B.cbits) d->coarse_batched = launch_coarse_bits(B.fb, B.tb, d->geom, B.bank, B.num_work, B.threshold, d->buf_cand_cap, d->cbits_byte0, d->cbits_max_nf, d->resp_low_weight, B.s, d->coarse_batch);
     else launch_coarse(B.fb, d->geom, B.bank, B.num_work, B.threshold, d->buf_cand_cap, B.tile_cap, B.s);
     }
@@ -503,6 +526,7 @@ static int enqueue_match(lm_detector* d, const Batch& B) {
     if (B.bits) {
         { LM_CLOCK("launch_local_bits");
         if (B.wide) launch_local_wide(B.fb, B.bb, B.wb, d->geom, B.bank, d->buf_cand_cap, B.threshold, B.cap, dedupe_slots, bits_grid(d, B.nb), d->bits_max_nf, B.s);
+        else if (B.parts) launch_local_parts(B.fb, B.bb, d->geom, B.bank, B.pd, d->buf_cand_cap, B.threshold, B.cap, dedupe_slots, bits_grid(d, B.nb), d->bits_max_nf, d->resp_low_weight, B.s);
         else launch_local_bits(B.fb, B.bb, d->geom, B.bank, d->buf_cand_cap, B.threshold, B.cap, dedupe_slots, bits_grid(d, B.nb), d->bits_max_nf, d->resp_low_weight, B.s); }
         if (B.bb.top_clear_units)     // the pair streams this launch zeroes again are clean for their slots' next frames
             for (int b = 0; b < B.nb; ++b)

@@ -51,6 +51,7 @@ extern "C" uint64_t lm_detector_frames_collected(const lm_detector* d) { return 
 extern "C" int lm_detector_exchange_pack_group(lm_detector* d, uint64_t first, int n, void* send_blocks, int capacity) {
     if (!d || !send_blocks || n < 1 || n > kMaxBatch) return lm_set_error(LM_ERR_INVALID, "bad argument");
     if (int rc = lm_need_both(d, "the multi-GPU exchange")) return rc;
+    if (int rc = lm_parts_refused(d, "the multi-GPU exchange")) return rc;
     if (!valid_capacity(capacity)) return lm_set_error(LM_ERR_INVALID, "capacity must be a power of two in [256, %u]", kXchgMaxCapacity);
     if (first < d->n_collected || first + (uint64_t)n > d->n_launched)
         return lm_set_error(LM_ERR_INVALID, "frames %llu..%llu are not all in flight on the device (collected %llu, launched %llu, submitted %llu)", (unsigned long long)first,
@@ -147,6 +148,7 @@ extern "C" int lm_detector_exchange_merge_frame(lm_detector* d, uint64_t frame_n
 extern "C" int lm_detector_exchange_pack(lm_detector* d, void* send_block, int capacity) {
     if (!d) return lm_set_error(LM_ERR_INVALID, "null argument");
     if (int rc = lm_need_both(d, "the multi-GPU exchange")) return rc;
+    if (int rc = lm_parts_refused(d, "the multi-GPU exchange")) return rc;
     if (d->n_submitted == d->n_collected) return lm_set_error(LM_ERR_INVALID, "no frame in flight: call lm_detector_submit first");
     int rc = lm_launch_pending(d);                                                   // the exchange follows the frame's kernels in stream order
     if (rc) return rc;

@@ -1,5 +1,5 @@
 // Internal interface between the host orchestration (detector*.cpp, pose_refine.cpp) and the HIP
-// kernels (fe_quant.hip, fe_bits.hip, match_bytes.hip, match_bits.hip, match_wide.hip, icp*.hip).  gfx950 only.  Not part of the public C ABI.
+// kernels (fe_quant.hip, fe_bits.hip, match_bytes.hip, match_bits.hip, match_wide.hip, match_parts.hip, icp*.hip).  gfx950 only.  Not part of the public C ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -194,6 +194,24 @@ void launch_local_wide(const FrameBatch& fb, const BitsBatch& B, const WidePlane
                        uint32_t cap, uint32_t dedupe_cap_slots, int grid_blocks, int max_features, hipStream_t s);
 void launch_coarse_wide(const FrameBatch& fb, const TopBits& B, const WidePlanes& P, const FrameGeom& g, const BankDev& bank, int num_work, float threshold, uint32_t cap,
                         uint32_t byte0, int max_features, hipStream_t s);
+// Part-based matching (match_parts.hip): a template entry is cut into 4 quadrants — a feature at (x, y) belongs to part
+// (2 x >= width) + 2 (2 y >= height), both modalities pooled — and a position is accepted when at least min_parts eligible parts pass the threshold
+// on their own; the score stays the holistic one.  Per entry (indexed like TemplEntry) the part table, and part-ordered copies of the feature
+// arrays the two bit-plane kernels read: part p owns features [start[p], start[p] + npad[p]) of feat_off (top level) / feat_word (below), n[p] of
+// them real, the rest padding that reads the zero tail / zero plane.  Built by the host when part matching is switched on (lm_part_table).
+struct PartEntry {
+    uint32_t start[4];    // index into the part-ordered arrays (a multiple of kFeatBatch)
+    uint16_t n[4];        // features of the part (the denominator of its score)
+    uint16_t npad[4];     // n rounded up to a multiple of kFeatBatch
+    uint32_t eligible;    // bit p: n[p] >= min_part_features
+    uint32_t pad[3];
+};
+struct PartsDev { const PartEntry* table; const int32_t* feat_off; const uint32_t* feat_word; int min_parts; };
+// as launch_coarse_bits (k_coarse_bits's grid: a wave per template, (templates / 4, frames)) and launch_local_bits, under the part rule; threshold >= 0
+void launch_coarse_parts(const FrameBatch& fb, const TopBits& B, const FrameGeom& g, const BankDev& bank, const PartsDev& parts, int num_work, float threshold, uint32_t cap,
+                         uint32_t byte0, int max_features, int low_weight, hipStream_t s);
+void launch_local_parts(const FrameBatch& fb, const BitsBatch& B, const FrameGeom& g, const BankDev& bank, const PartsDev& parts, uint32_t cand_cap, float threshold,
+                        uint32_t cap, uint32_t dedupe_cap_slots, int grid_blocks, int max_features, int low_weight, hipStream_t s);
 bool tile_plan_possible(const FrameGeom& g);
 size_t coarse_plan_lds_bytes(int Wd, int Hd);
 // Per frame of the batch: counters[0] = number of candidates produced (may exceed cap: nothing is written past cap); with tiles

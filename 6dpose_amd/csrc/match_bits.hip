@@ -1,4 +1,4 @@
-// Similarity kernels of Detector::matchClass on gfx950, on bit planes (the default): weighted_sum, k_pack_bits /
+// Similarity kernels of Detector::matchClass on gfx950, on bit planes (the default): k_pack_bits /
 // k_local_bits (strip records of the levels below the top, reference similarityLocal LL.cpp:1366-1428, 1855-1938), k_pack_top / k_coarse_bits /
 // k_coarse_bits_batch (pair stream of the top level, LL.cpp:1284-1354, 1835-1852), their launchers and the dispatcher that picks the
 // instantiation.  A kernel here holds what is particular to it — its load scheme, its counters, how it reserves candidate slots —; the stages
@@ -24,33 +24,7 @@ namespace lm {
 // every feature — 30 VALU instructions per lane and feature at 0.92 of the issue slots)
 // The top level ("pair stream", read by k_coarse_bits): the flat linear memories [label][phase][position] as one pair {is-1 dword, is-4
 // dword} per 32 consecutive arena bytes, so the reference's reads that run from one plane into the next stay what they are.
-// (the carry-save adders and the Harley-Seal counters: match_device.h — match_wide.hip counts three planes with them)
-// The bit-sliced sum S = a n_a + 4 n_4 of two bit-sliced counts (kA = a: the weight of the low plane, lm_kernels.h resp_pack; 1 for the
-// default table 4 1 0 0 0, whose instantiation is the code it always was).  n_a + n_4 <= features, so kN + 3 bits hold any of them.
-template <int kA, int kN>
-static __device__ __forceinline__ void weighted_sum(uint32_t (&S)[kN + 3], const uint32_t (&na)[kN], const uint32_t (&n4)[kN]) {
-    constexpr int kS = kN + 3;
-    uint32_t carry = 0;
-    if (kA == 1) {
-        S[0] = na[0]; S[1] = na[1];
-#pragma unroll
-        for (int k = 2; k < kS; ++k) csa(S[k], carry, k < kN ? na[k] : 0u, k - 2 < kN ? n4[k - 2] : 0u, carry);
-    } else if (kA == 2) {
-        S[0] = 0u; S[1] = na[0];
-#pragma unroll
-        for (int k = 2; k < kS; ++k) csa(S[k], carry, k - 1 < kN ? na[k - 1] : 0u, k - 2 < kN ? n4[k - 2] : 0u, carry);
-    } else {                                                        // 3 n_a = n_a + 2 n_a first (kN + 2 bits), then + 4 n_4
-        uint32_t t[kN + 2];
-        t[0] = na[0];
-#pragma unroll
-        for (int k = 1; k < kN + 2; ++k) csa(t[k], carry, k < kN ? na[k] : 0u, k - 1 < kN ? na[k - 1] : 0u, carry);
-        carry = 0;
-        S[0] = t[0]; S[1] = t[1];
-#pragma unroll
-        for (int k = 2; k < kS; ++k) csa(S[k], carry, k < kN + 2 ? t[k] : 0u, k - 2 < kN ? n4[k - 2] : 0u, carry);
-    }
-}
-
+// (the carry-save adders, the Harley-Seal counters and weighted_sum: match_device.h — match_wide.hip counts three planes with them)
 // 4 response bytes -> 8 bits, cell k at bits 2k (is 1 = bit 0 of the byte) and 2k + 1 (is 4 = bit 2 of the byte); the multiply gathers the
 // four 2-bit fields into the top byte (partial products land on distinct bits: no carries)
 // (any table of two planes: the bytes are 0, a or 4 with a = 1, 2 or 3 — "is a" = bit 0 or bit 1 of the byte)
@@ -189,19 +163,6 @@ k_local_bits(FrameBatch fb, BitsBatch B, FrameGeom g, const TemplEntry* __restri
 void launch_pack_bits(const BitsBatch& B, int nb, const LevelGeom& lv, hipStream_t s) {
     const uint32_t records = (uint32_t)(2 * 8 * lv.T * lv.T) * (uint32_t)lv.NS * (uint32_t)lv.Hd;
     hipLaunchKernelGGL(k_pack_bits, dim3((records + 255) / 256, nb), dim3(256), 0, s, B, lv.sm_off[0], records, lv.NS, lv.Hd);
-}
-// The instantiation for a bank and a table, for every two-plane kernel: counters of 9 bits (kHi = 5) for entries of up to kBitsSmallMax features, of
-// 14 (kHi = 10) beyond, each at the waves per SIMD the kernel declares for it; kA = the table's low weight.  launch(kHi, kWaves, kA) receives them
-// as std::integral_constants, i.e. as template arguments.
-template <int kWavesSmall, int kWavesBig, class Launch>
-static void with_bits_instance(int max_features, int low_weight, Launch launch) {
-    auto with_a = [&](auto a) {
-        if (max_features > kBitsSmallMax) launch(std::integral_constant<int, 10>(), std::integral_constant<int, kWavesBig>(), a);
-        else launch(std::integral_constant<int, 5>(), std::integral_constant<int, kWavesSmall>(), a);
-    };
-    if (low_weight == 2) with_a(std::integral_constant<int, 2>());
-    else if (low_weight == 3) with_a(std::integral_constant<int, 3>());
-    else with_a(std::integral_constant<int, 1>());
 }
 void launch_local_bits(const FrameBatch& fb, const BitsBatch& B, const FrameGeom& g, const BankDev& bank, uint32_t cand_cap, float threshold,
                        uint32_t cap, uint32_t dedupe_cap_slots, int grid_blocks, int max_features, int low_weight, hipStream_t s) {

@@ -64,6 +64,63 @@ static __device__ __forceinline__ void add_eights1(uint32_t (&c)[kN], uint32_t e
     for (int k = 4; k < kN; ++k) { const uint32_t t = c[k] & k16; c[k] ^= k16; k16 = t; }
 }
 
+// The bit-sliced sum S = a n_a + 4 n_4 of two bit-sliced counts (kA = a: the weight of the low plane, lm_kernels.h resp_pack; 1 for the
+// default table 4 1 0 0 0, whose instantiation is the code it always was).  n_a + n_4 <= features, so kN + 3 bits hold any of them.
+template <int kA, int kN>
+static __device__ __forceinline__ void weighted_sum(uint32_t (&S)[kN + 3], const uint32_t (&na)[kN], const uint32_t (&n4)[kN]) {
+    constexpr int kS = kN + 3;
+    uint32_t carry = 0;
+    if (kA == 1) {
+        S[0] = na[0]; S[1] = na[1];
+#pragma unroll
+        for (int k = 2; k < kS; ++k) csa(S[k], carry, k < kN ? na[k] : 0u, k - 2 < kN ? n4[k - 2] : 0u, carry);
+    } else if (kA == 2) {
+        S[0] = 0u; S[1] = na[0];
+#pragma unroll
+        for (int k = 2; k < kS; ++k) csa(S[k], carry, k - 1 < kN ? na[k - 1] : 0u, k - 2 < kN ? n4[k - 2] : 0u, carry);
+    } else {                                                        // 3 n_a = n_a + 2 n_a first (kN + 2 bits), then + 4 n_4
+        uint32_t t[kN + 2];
+        t[0] = na[0];
+#pragma unroll
+        for (int k = 1; k < kN + 2; ++k) csa(t[k], carry, k < kN ? na[k] : 0u, k - 1 < kN ? na[k - 1] : 0u, carry);
+        carry = 0;
+        S[0] = t[0]; S[1] = t[1];
+#pragma unroll
+        for (int k = 2; k < kS; ++k) csa(S[k], carry, k < kN + 2 ? t[k] : 0u, k - 2 < kN ? n4[k - 2] : 0u, carry);
+    }
+}
+
+// ---- what the part kernels add (match_parts.hip): sums of sums, comparisons against a per-lane bound, a small counter of passes ----
+// S += A, both bit-sliced (a ripple of carry-save adders; the caller knows that kS bits hold the sum)
+template <int kS>
+static __device__ __forceinline__ void sliced_add(uint32_t (&S)[kS], const uint32_t (&A)[kS]) {
+    uint32_t carry = 0;
+#pragma unroll
+    for (int k = 0; k < kS; ++k) csa(S[k], carry, S[k], A[k], carry);
+}
+// the positions whose bit-sliced value is >= r, r per lane (coarse_hit_mask, match_planes.h, does it for a wave-uniform r); r >= 2^kS: none
+template <int kS>
+static __device__ __forceinline__ uint32_t sliced_ge(const uint32_t (&S)[kS], int r) {
+    uint32_t gt = 0, eq = 0xFFFFFFFFu;
+#pragma unroll
+    for (int k = kS - 1; k >= 0; --k) {
+        const uint32_t b = 0u - (((uint32_t)r >> k) & 1u);          // all ones where bit k of r is set
+        gt |= eq & S[k] & ~b;
+        eq &= ~(S[k] ^ b);
+    }
+    return r < (1 << kS) ? (gt | eq) : 0u;
+}
+// a bit-sliced counter 0..4 of one-bit inputs {q0, q1, q2}: += x; and the positions whose count is >= m (m = 1..4)
+static __device__ __forceinline__ void count3_add(uint32_t& q0, uint32_t& q1, uint32_t& q2, uint32_t x) {
+    const uint32_t t = q0 & x;
+    q0 ^= x;
+    q2 ^= q1 & t;
+    q1 ^= t;
+}
+static __device__ __forceinline__ uint32_t count3_ge(uint32_t q0, uint32_t q1, uint32_t q2, int m) {
+    return m <= 1 ? (q0 | q1 | q2) : m == 2 ? (q1 | q2) : m == 3 ? (q2 | (q1 & q0)) : q2;
+}
+
 // exclusive prefix of `mine` over the lanes of the wave; total = the wave's sum
 static __device__ __forceinline__ int wave_excl_scan(int mine, int lane, int& total) {
     int incl = mine;

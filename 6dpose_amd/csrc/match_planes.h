@@ -1,10 +1,11 @@
 // The stages that the bit-plane kernels share (match_bits.hip: k_coarse_bits, k_coarse_bits_batch, k_local_bits, k_pack_*; match_wide.hip:
-// k_coarse_wide, k_local_wide, k_pack_*_wide; DESIGN.md sections 3.1, 3.1.2, 3.1.3), each once: every one of them states a rule of the
+// k_coarse_wide, k_local_wide, k_pack_*_wide; match_parts.hip: k_coarse_parts, k_local_parts; DESIGN.md sections 3.1, 3.1.2, 3.1.3, 3.1.4), each once: every one of them states a rule of the
 // reference (LL.cpp:1299-1309, 1842-1852, 1871-1880, 1910-1935), so a change to a rule is made here and reaches every kernel.  What differs
 // between the kernels stays in them: how a lane finds its loads, how many counters it keeps (two or three) and, in the coarse pass, how the
 // candidate slots are reserved.  Everything is __forceinline__ and takes values: the kernels keep their registers, LDS and launch bounds.
 #pragma once
 #include "match_device.h"
+#include <type_traits>
 
 namespace lm {
 
@@ -17,6 +18,16 @@ static __device__ __forceinline__ int coarse_rmin(float threshold, int nf) {
     if (rmin > 4 * nf + 1) rmin = 4 * nf + 1;
     while (rmin > 0 && score_of(rmin, nf) > threshold) --rmin;
     while (rmin <= 4 * nf && !(score_of(rmin, nf) > threshold)) ++rmin;
+    return rmin;
+}
+
+// ... and the smallest raw sum whose score is >= threshold, the test a refined candidate must not fail (LL.cpp:1935 drops `sim < threshold`)
+static __device__ __forceinline__ int local_rmin(float threshold, int nf) {
+    int rmin = (int)(threshold * (float)(4 * nf) / 100.f);
+    if (!(rmin >= 0)) rmin = 0;
+    if (rmin > 4 * nf + 1) rmin = 4 * nf + 1;
+    while (rmin > 0 && score_of(rmin - 1, nf) >= threshold) --rmin;
+    while (rmin <= 4 * nf && !(score_of(rmin, nf) >= threshold)) ++rmin;
     return rmin;
 }
 
@@ -304,6 +315,22 @@ static __device__ __forceinline__ size_t strip_cells(const uint8_t* strips, uint
     b = make_uint4(0, 0, 0, 0);
     if (s + 1 < (uint32_t)NS) b = *reinterpret_cast<const uint4*>(src + (size_t)Hd * 16);      // the next strip of this row
     return (sm_off0 >> 1) + (size_t)i * 8;
+}
+
+// ============================================================ launching ============================================================
+
+// The instantiation for a bank and a table, for every two-plane kernel: counters of 9 bits (kHi = 5) for entries of up to kBitsSmallMax features, of
+// 14 (kHi = 10) beyond, each at the waves per SIMD the kernel declares for it; kA = the table's low weight.  launch(kHi, kWaves, kA) receives them
+// as std::integral_constants, i.e. as template arguments.
+template <int kWavesSmall, int kWavesBig, class Launch>
+static void with_bits_instance(int max_features, int low_weight, Launch launch) {
+    auto with_a = [&](auto a) {
+        if (max_features > kBitsSmallMax) launch(std::integral_constant<int, 10>(), std::integral_constant<int, kWavesBig>(), a);
+        else launch(std::integral_constant<int, 5>(), std::integral_constant<int, kWavesSmall>(), a);
+    };
+    if (low_weight == 2) with_a(std::integral_constant<int, 2>());
+    else if (low_weight == 3) with_a(std::integral_constant<int, 3>());
+    else with_a(std::integral_constant<int, 1>());
 }
 
 }  // namespace lm

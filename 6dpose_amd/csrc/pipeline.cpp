@@ -51,6 +51,7 @@ extern "C" int lm_pipeline_create(lm_detector* det, int width, int height, lm_pi
     if (!det || !out || width <= 0 || height <= 0) return lm_set_error(LM_ERR_INVALID, "null argument");
     *out = nullptr;
     if (int rc = lm_need_both(det, "lm_pipeline_create")) return rc;   // the ICP stage reads the scene depth of the detector's frame
+    if (int rc = lm_parts_refused(det, "lm_pipeline_create")) return rc; // (a part-mode record's similarity may lie below the threshold: the NMS chain has not been held to that)
     HIP_TRY(hipSetDevice(det->device));
     lm_pipeline* p = new lm_pipeline();
     p->det = det; p->srcW = width; p->srcH = height;
@@ -262,6 +263,7 @@ extern "C" int lm_pipeline_run(lm_pipeline* p, float threshold, const char* cons
     *n_out = 0;
     lm_detector* d = p->det;
     if (d->n_submitted != d->n_collected) return lm_set_error(LM_ERR_INVALID, "a frame is in flight on the detector: collect it first");
+    if (int rc = lm_parts_refused(d, "lm_pipeline_run")) return rc;
     if (!d->frame_valid || d->fW != p->W || d->fH != p->H)
         return lm_set_error(LM_ERR_INVALID, "the detector's resident frame is not %dx%d", p->W, p->H);
     HIP_TRY(hipSetDevice(d->device));

@@ -180,6 +180,9 @@ PROTOTYPES = {
     "lm_detector_get_paths": (I, [P, PI, PI]),
     "lm_detector_set_response_table": (I, [P, PU8]),
     "lm_detector_get_response_table": (I, [P, PU8]),
+    "lm_detector_set_part_matching": (I, [P, I, I]),
+    "lm_detector_get_part_matching": (I, [P, PI, PI]),
+    "lm_part_table": (I, [I, I, P, P, I, I, P, P]),
     "lm_depth_mode_options_init": (None, [PDMO]),
     "lm_detector_depth_modes": (I, [P, PDMO, P, I, PI]),
     "lm_detector_set_class_depth_range": (I, [P, S, I, I, I]),

@@ -434,6 +434,21 @@ class Detector:
         _check(self._lib.lm_detector_get_response_table(self._h, out))
         return tuple(int(v) for v in out)
 
+    def setPartMatching(self, min_parts: int = 0, min_part_features: int = 8) -> None:
+        """lm_detector_set_part_matching: accept a template when at least `min_parts` of its 4 quadrants (a feature at (x, y) belongs to part
+        (2x >= width) + 2 (2y >= height)) pass the threshold on their own; quadrants of fewer than `min_part_features` features never pass.
+        0 switches it off (the default), 2 tolerates half the object hidden, 4 is stricter than the holistic rule.  The similarity of a
+        record stays the holistic score, so it may lie below the threshold.  Runs on the ("bits", "bits") paths with a response table of at
+        most two distinct non-zero values and a threshold >= 0; anything else, a sharded detector, the exchange, matchSlabs and a Pipeline
+        are refused, never matched holistically in silence.  Refused with frames in flight."""
+        _check(self._lib.lm_detector_set_part_matching(self._h, int(min_parts), int(min_part_features)))
+
+    def partMatching(self):
+        """lm_detector_get_part_matching: (min_parts, min_part_features); min_parts 0 = off."""
+        a, b = ctypes.c_int(), ctypes.c_int()
+        _check(self._lib.lm_detector_get_part_matching(self._h, ctypes.byref(a), ctypes.byref(b)))
+        return int(a.value), int(b.value)
+
     def trainStats(self):
         """lm_detector_train_stats: training views since creation or read() as (selected on the device, sent to the host selection,
         failed with -1, empty).  The two selections give the same templates; this is how a test sees which one ran."""

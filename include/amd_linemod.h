@@ -375,6 +375,27 @@ int lm_detector_get_paths(const lm_detector *d, int *refine, int *coarse);
  * lm_detector_set_paths(d, 3, 2) asked for them, on the wide bit-plane kernels —, which lm_detector_get_paths reports.  Thresholds are not comparable between tables. */
 int lm_detector_set_response_table(lm_detector *d, const uint8_t r[5]);
 int lm_detector_get_response_table(const lm_detector *d, uint8_t r[5]);
+/* Part-based matching: accept a template when min_parts of its 4 quadrants match, the reference author's first answer to occlusion
+ * (linemodLevelup/notes.md:1-9: "cut template to 4 parts ... if half of the obj is hidden, original holistic match's average response will drop
+ * to 50%, while part-based match keeps 100%").  Off by default (min_parts 0); 1..4 switches it on.  The rule, per template entry (pyramid, level):
+ *   a feature at (x, y) belongs to part (2 x >= width) + 2 (2 y >= height), both modalities pooled; a part of n_p features is eligible iff
+ *   n_p >= min_part_features (>= 1; parts too small to mean anything never pass);
+ *   top level: a position below the template's position count is a candidate iff at least min_parts eligible parts have
+ *   (raw_p * 100.f) / (4 * n_p) > threshold (the expression and strict comparison of LL.cpp:1842-1844); its score is the holistic one;
+ *   levels below: window, clamp, arg-max (first maximum of the holistic sum) and position update as always (LL.cpp:1871-1931); the candidate
+ *   stays iff at least min_parts eligible parts have (raw_p at the arg-max position * 100.f) / (4 * n_p) >= threshold (LL.cpp:1935 drops `<`).
+ * lm_match.similarity stays the HOLISTIC score at level 0, so under part matching it may lie below the threshold.  Record format, duplicate
+ * removal and both result orders are unchanged; min_parts 4 is stricter than the holistic rule, 2 tolerates half the object hidden.
+ * Refused (LM_ERR_INVALID), at the set or when a frame is submitted — nothing is matched holistically in silence: frames in flight at the set; a
+ * threshold < 0; paths other than lm_detector_set_paths(d, 0, 0); a response table of more than two distinct non-zero values; a bank whose
+ * refinement windows can leave their planes (features outside the template's box, a template wider than the frame minus 16 T); a sharded
+ * detector and the multi-GPU exchange; lm_detector_match_slabs; lm_pipeline_create / lm_pipeline_run on such a detector.
+ * lm_part_table is the host's part table of one entry, callable without a GPU: out16 = start[4], n[4], npad[4] (n rounded up to 8: the part's
+ * slots in the part-ordered feature arrays, from start), eligible[4]; order (may be NULL; room for n + 28 entries) = per slot the index of its
+ * feature, -1 for padding. */
+int lm_detector_set_part_matching(lm_detector *d, int min_parts, int min_part_features);
+int lm_detector_get_part_matching(const lm_detector *d, int *min_parts, int *min_part_features);
+int lm_part_table(int width, int height, const int32_t *xs, const int32_t *ys, int n, int min_part_features, int32_t *out16, int32_t *order);
 /* Depth slabs: template scales chosen from the scene's depth histogram (the reference's "use depth histogram and 1D nms to find some primary
  * scales", linemodLevelup/readme.md:29-34, notes.md: train each scale as a class of its own and match it only where the scene has that depth).
  *

@@ -1,0 +1,234 @@
+// lm_pso — pose refinement by particle swarm over rendered depth (kernels and the rule: pso.hip).
+// A call enqueues, on the context's own stream, k_pso_init and then per generation k_pso_views, k_project, k_raster,
+// k_pso_cost and k_pso_step; nothing is read back before the copy of the results.  The swarm renders into scratch of its
+// own (projected vertices, z-buffer): the mesh is only read, so lm_mesh_render returns what it did before.
+#include <math.h>
+#include <string.h>
+
+#include <algorithm>
+#include <vector>
+
+#include "pso_kernels.h"
+#include "render_internal.h"
+
+using namespace lm;
+
+struct lm_pso {
+    int device = 0;
+    hipStream_t s = nullptr;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    // the scene
+    uint16_t* d_scene = nullptr;
+    size_t cap_scene = 0;
+    int W = 0, H = 0;
+    double K[9] = {0};
+    // swarm state, render scratch and the record of the last run
+    PsoHyp* d_hyp = nullptr;
+    ViewParams* d_views = nullptr;
+    ProjVtx* d_pv = nullptr;
+    unsigned long long* d_zbuf = nullptr;
+    PsoState st{};
+    size_t cap_hyp = 0, cap_views = 0, cap_pv = 0, cap_zbuf = 0, cap_x = 0, cap_v = 0, cap_pbx = 0, cap_pbc = 0, cap_sum = 0, cap_nr = 0, cap_best = 0,
+           cap_rx = 0, cap_rc = 0, cap_rs = 0, cap_rn = 0, cap_rb = 0, cap_res = 0;
+    std::vector<PsoHyp> h_hyp;            // live until the call's synchronisation
+    std::vector<PsoResultDev> h_res;
+    int last_H = 0, last_P = 0, last_G = -1;
+};
+
+extern "C" void lm_pso_options_init(lm_pso_options* o) {
+    if (!o) return;
+    memset(o, 0, sizeof(*o));
+    o->size = (uint32_t)sizeof(*o);
+    o->particles = 64; o->generations = 30; o->tau = 20; o->cover_pixels = 0; o->seed = 0;
+    o->trans_range_mm = 20.0; o->rot_range = tan(10.0 * M_PI / 180.0 / 2.0);
+    o->inertia = 0.7298; o->c1 = 1.49618; o->c2 = 1.49618;
+    o->clip_near = 10.0; o->clip_far = 10000.0;
+}
+
+extern "C" int lm_pso_create(int device, lm_pso** out) {
+    if (!out) return lm_set_error(LM_ERR_INVALID, "null argument");
+    *out = nullptr;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+        return lm_set_error(LM_ERR_NO_DEVICE, "no HIP device visible; libamdlinemod has no CPU fallback");
+    if (device < 0 || device >= ndev) return lm_set_error(LM_ERR_INVALID, "device %d out of range", device);
+    HIP_TRY(hipSetDevice(device));
+    lm_pso* c = new lm_pso();
+    c->device = device;
+    if (hipStreamCreateWithFlags(&c->s, hipStreamNonBlocking) != hipSuccess || hipEventCreate(&c->ev0) != hipSuccess ||
+        hipEventCreate(&c->ev1) != hipSuccess) {
+        lm_pso_destroy(c);
+        return lm_set_error(LM_ERR_HIP, "stream / event creation failed");
+    }
+    *out = c;
+    return LM_OK;
+}
+
+extern "C" void lm_pso_destroy(lm_pso* c) {
+    if (!c) return;
+    (void)hipSetDevice(c->device);
+    if (c->s) (void)hipStreamSynchronize(c->s);
+    void* p[] = {c->d_scene, c->d_hyp, c->d_views, c->d_pv, c->d_zbuf, c->st.x, c->st.v, c->st.pbest_x, c->st.pbest_cost, c->st.sum, c->st.n_r,
+                 c->st.best, c->st.rec_x, c->st.rec_cost, c->st.rec_sum, c->st.rec_nr, c->st.rec_best, c->st.result};
+    for (void* q : p) if (q) (void)hipFree(q);
+    if (c->ev0) (void)hipEventDestroy(c->ev0);
+    if (c->ev1) (void)hipEventDestroy(c->ev1);
+    if (c->s) (void)hipStreamDestroy(c->s);
+    delete c;
+}
+
+static int ensure(void** p, size_t& cap, size_t bytes) {
+    if (bytes <= cap) return LM_OK;
+    if (*p) (void)hipFree(*p);
+    *p = nullptr; cap = 0;
+    HIP_TRY(hipMalloc(p, bytes));
+    cap = bytes;
+    return LM_OK;
+}
+
+extern "C" int lm_pso_set_scene(lm_pso* c, const uint16_t* scene_depth, int width, int height, const double* K) {
+    if (!c || !scene_depth || !K) return lm_set_error(LM_ERR_INVALID, "null argument");
+    if (width <= 0 || height <= 0 || width > 16384 || height > 16384) return lm_set_error(LM_ERR_INVALID, "unsupported frame size %dx%d", width, height);
+    for (int k = 0; k < 9; ++k)
+        if (!isfinite(K[k])) return lm_set_error(LM_ERR_INVALID, "K is not finite");
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->s));
+    const size_t bytes = (size_t)width * height * sizeof(uint16_t);
+    int rc = ensure((void**)&c->d_scene, c->cap_scene, bytes);
+    if (rc) { c->W = c->H = 0; return rc; }
+    HIP_TRY(hipMemcpy(c->d_scene, scene_depth, bytes, hipMemcpyHostToDevice));
+    c->W = width; c->H = height;
+    memcpy(c->K, K, sizeof(c->K));
+    return LM_OK;
+}
+
+extern "C" int lm_pso_run(lm_pso* c, lm_mesh* mesh, int count, const double* Rs, const double* ts, const int32_t* windows_xy, int w, int h,
+                          const lm_pso_options* options, lm_pso_result* results, float* device_ms) {
+    if (!c || !mesh || !Rs || !ts || !windows_xy || !results) return lm_set_error(LM_ERR_INVALID, "null argument");
+    lm_pso_options o;
+    if (options) {
+        if (options->size != sizeof(lm_pso_options))
+            return lm_set_error(LM_ERR_INVALID, "lm_pso_options.size is %u, this library expects %u", options->size, (unsigned)sizeof(lm_pso_options));
+        o = *options;
+    } else lm_pso_options_init(&o);
+    if (o.particles < 1 || o.particles > 256) return lm_set_error(LM_ERR_INVALID, "particles must be in 1..256 (got %d)", o.particles);
+    if (count < 1 || (long long)count * o.particles > 4096)
+        return lm_set_error(LM_ERR_INVALID, "hypotheses x particles must be in 1..4096 (got %d x %d)", count, o.particles);
+    if (w < 8 || w > 256 || h < 8 || h > 256) return lm_set_error(LM_ERR_INVALID, "the window must be 8..256 on each side (got %dx%d)", w, h);
+    if (o.generations < 0 || o.generations > 256) return lm_set_error(LM_ERR_INVALID, "generations must be in 0..256 (got %d)", o.generations);
+    if (o.tau < 1 || o.tau > 65535) return lm_set_error(LM_ERR_INVALID, "tau must be in 1..65535 (got %d)", o.tau);
+    if (o.cover_pixels < 0) return lm_set_error(LM_ERR_INVALID, "cover_pixels must be >= 0 (got %d)", o.cover_pixels);
+    if (!(isfinite(o.trans_range_mm) && o.trans_range_mm > 0.0)) return lm_set_error(LM_ERR_INVALID, "trans_range_mm must be finite and > 0");
+    if (!(isfinite(o.rot_range) && o.rot_range > 0.0)) return lm_set_error(LM_ERR_INVALID, "rot_range must be finite and > 0");
+    if (!isfinite(o.inertia) || !isfinite(o.c1) || !isfinite(o.c2)) return lm_set_error(LM_ERR_INVALID, "inertia, c1 and c2 must be finite");
+    if (!isfinite(o.clip_near) || !isfinite(o.clip_far)) return lm_set_error(LM_ERR_INVALID, "the clip planes must be finite");
+    if (mesh->nf <= 0 || mesh->nv <= 0) return lm_set_error(LM_ERR_INVALID, "the mesh has no faces");
+    if (mesh->device != c->device) return lm_set_error(LM_ERR_INVALID, "the mesh lives on device %d, the context on %d", mesh->device, c->device);
+    if (!c->d_scene || c->W <= 0) return lm_set_error(LM_ERR_INVALID, "no scene depth set (lm_pso_set_scene)");
+    for (size_t k = 0; k < (size_t)count * 9; ++k)
+        if (!isfinite(Rs[k])) return lm_set_error(LM_ERR_INVALID, "a hypothesis' R is not finite");
+    for (size_t k = 0; k < (size_t)count * 3; ++k)
+        if (!isfinite(ts[k])) return lm_set_error(LM_ERR_INVALID, "a hypothesis' t is not finite");
+    for (int i = 0; i < 2 * count; ++i)
+        if (windows_xy[i] < -(1 << 20) || windows_xy[i] > (1 << 20)) return lm_set_error(LM_ERR_INVALID, "window origin %d out of range", windows_xy[i]);
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->s));                                  // h_hyp / h_res of an earlier call that failed half way
+
+    PsoParams prm{};
+    memcpy(prm.K, c->K, sizeof(prm.K));
+    for (int d = 0; d < 3; ++d) { prm.range[d] = o.trans_range_mm; prm.range[3 + d] = o.rot_range; }
+    prm.inertia = o.inertia; prm.c1 = o.c1; prm.c2 = o.c2; prm.seed = o.seed;
+    prm.G = o.generations;
+    prm.P = prm.G == 0 ? 1 : o.particles;                                 // evaluate-only: the given pose alone
+    prm.w = w; prm.h = h; prm.W = c->W; prm.H = c->H; prm.tau = o.tau; prm.cover_pixels = o.cover_pixels;
+    const int H = count, P = prm.P, G = prm.G;
+    const size_t HP = (size_t)H * P, npx = (size_t)w * h, gen = (size_t)G + 1;
+
+    int rc;
+    PsoState& st = c->st;
+    if ((rc = ensure((void**)&c->d_hyp, c->cap_hyp, H * sizeof(PsoHyp)))) return rc;
+    if ((rc = ensure((void**)&c->d_views, c->cap_views, HP * sizeof(ViewParams)))) return rc;
+    if ((rc = ensure((void**)&c->d_pv, c->cap_pv, HP * mesh->nv * sizeof(ProjVtx)))) return rc;
+    if ((rc = ensure((void**)&c->d_zbuf, c->cap_zbuf, HP * npx * sizeof(unsigned long long)))) return rc;
+    if ((rc = ensure((void**)&st.x, c->cap_x, HP * 6 * sizeof(double)))) return rc;
+    if ((rc = ensure((void**)&st.v, c->cap_v, HP * 6 * sizeof(double)))) return rc;
+    if ((rc = ensure((void**)&st.pbest_x, c->cap_pbx, HP * 6 * sizeof(double)))) return rc;
+    if ((rc = ensure((void**)&st.pbest_cost, c->cap_pbc, HP * sizeof(double)))) return rc;
+    if ((rc = ensure((void**)&st.sum, c->cap_sum, HP * sizeof(unsigned long long)))) return rc;
+    if ((rc = ensure((void**)&st.n_r, c->cap_nr, HP * sizeof(unsigned int)))) return rc;
+    if ((rc = ensure((void**)&st.best, c->cap_best, H * sizeof(PsoBest)))) return rc;
+    if ((rc = ensure((void**)&st.rec_x, c->cap_rx, gen * HP * 6 * sizeof(double)))) return rc;
+    if ((rc = ensure((void**)&st.rec_cost, c->cap_rc, gen * HP * sizeof(double)))) return rc;
+    if ((rc = ensure((void**)&st.rec_sum, c->cap_rs, gen * HP * sizeof(unsigned long long)))) return rc;
+    if ((rc = ensure((void**)&st.rec_nr, c->cap_rn, gen * HP * sizeof(unsigned int)))) return rc;
+    if ((rc = ensure((void**)&st.rec_best, c->cap_rb, gen * H * 2 * sizeof(int)))) return rc;
+    if ((rc = ensure((void**)&st.result, c->cap_res, H * sizeof(PsoResultDev)))) return rc;
+    c->last_G = -1;
+
+    c->h_hyp.resize(H);
+    c->h_res.resize(H);
+    for (int i = 0; i < H; ++i) {
+        memcpy(c->h_hyp[i].R0, Rs + 9 * (size_t)i, 9 * sizeof(double));
+        memcpy(c->h_hyp[i].t0, ts + 3 * (size_t)i, 3 * sizeof(double));
+        c->h_hyp[i].x0 = windows_xy[2 * i]; c->h_hyp[i].y0 = windows_xy[2 * i + 1];
+    }
+    MeshDev M{mesh->d_v, mesh->d_n, mesh->d_c, mesh->d_f, mesh->nv, mesh->nf};
+    HIP_TRY(hipEventRecord(c->ev0, c->s));
+    HIP_TRY(hipMemcpyAsync(c->d_hyp, c->h_hyp.data(), H * sizeof(PsoHyp), hipMemcpyHostToDevice, c->s));
+    launch_pso_init(prm, H, st, c->s);
+    for (int g = 0; g <= G; ++g) {
+        launch_pso_views(prm, H, c->d_hyp, st.x, c->d_views, c->s);
+        launch_project(M, c->d_views, (int)HP, 1, c->d_pv, c->s);
+        launch_raster(M, c->d_pv, (int)HP, w, h, o.clip_near, o.clip_far, c->d_zbuf, c->s);
+        launch_pso_cost(prm, H, c->d_hyp, c->d_zbuf, c->d_scene, st.sum, st.n_r, c->s);
+        launch_pso_step(prm, H, g, c->d_hyp, st, c->s);
+    }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(c->h_res.data(), st.result, H * sizeof(PsoResultDev), hipMemcpyDeviceToHost, c->s));
+    HIP_TRY(hipEventRecord(c->ev1, c->s));
+    HIP_TRY(hipStreamSynchronize(c->s));
+    if (device_ms) HIP_TRY(hipEventElapsedTime(device_ms, c->ev0, c->ev1));
+    for (int i = 0; i < H; ++i) {
+        const PsoResultDev& r = c->h_res[i];
+        memcpy(results[i].R, r.R, sizeof(r.R));
+        memcpy(results[i].t, r.t, sizeof(r.t));
+        results[i].cost = r.cost; results[i].initial_cost = r.initial_cost;
+        results[i].n_rendered = r.n_rendered; results[i].n_initial = r.n_initial;
+        results[i].best_particle = r.best_particle; results[i].best_generation = r.best_generation;
+    }
+    c->last_H = H; c->last_P = P; c->last_G = G;
+    return LM_OK;
+}
+
+extern "C" int64_t lm_pso_read_debug(lm_pso* c, int hypothesis, int kind, double* dst, int64_t capacity) {
+    if (!c) return lm_set_error(LM_ERR_INVALID, "null argument");
+    if (c->last_G < 0) return lm_set_error(LM_ERR_INVALID, "no run to read back");
+    if (hypothesis < 0 || hypothesis >= c->last_H) return lm_set_error(LM_ERR_INVALID, "hypothesis %d out of range", hypothesis);
+    if (kind < 0 || kind > 3) return lm_set_error(LM_ERR_INVALID, "unknown kind %d", kind);
+    const size_t H = c->last_H, P = c->last_P, gen = (size_t)c->last_G + 1, HP = H * P;
+    const size_t per = kind == 0 ? P * 6 : kind == 1 ? P : 2 * (kind == 2 ? P : 1);
+    const int64_t size = (int64_t)(gen * per);
+    if (!dst || capacity <= 0) return size;
+    HIP_TRY(hipSetDevice(c->device));
+    std::vector<double> out(gen * per);
+    const PsoState& st = c->st;
+    if (kind == 0 || kind == 1) {                                         // doubles, bit for bit
+        const double* src = kind == 0 ? st.rec_x : st.rec_cost;
+        HIP_TRY(hipMemcpy2D(out.data(), per * sizeof(double), src + (size_t)hypothesis * per, HP * (per / P) * sizeof(double), per * sizeof(double), gen,
+                            hipMemcpyDeviceToHost));
+    } else if (kind == 2) {
+        std::vector<unsigned long long> sum(gen * P);
+        std::vector<unsigned int> nr(gen * P);
+        HIP_TRY(hipMemcpy2D(sum.data(), P * sizeof(unsigned long long), st.rec_sum + (size_t)hypothesis * P, HP * sizeof(unsigned long long),
+                            P * sizeof(unsigned long long), gen, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy2D(nr.data(), P * sizeof(unsigned int), st.rec_nr + (size_t)hypothesis * P, HP * sizeof(unsigned int), P * sizeof(unsigned int), gen,
+                            hipMemcpyDeviceToHost));
+        for (size_t k = 0; k < gen * P; ++k) { out[2 * k] = (double)sum[k]; out[2 * k + 1] = (double)nr[k]; }
+    } else {
+        std::vector<int> best(gen * 2);
+        HIP_TRY(hipMemcpy2D(best.data(), 2 * sizeof(int), st.rec_best + (size_t)hypothesis * 2, H * 2 * sizeof(int), 2 * sizeof(int), gen, hipMemcpyDeviceToHost));
+        for (size_t k = 0; k < gen * 2; ++k) out[k] = (double)best[k];
+    }
+    memcpy(dst, out.data(), (size_t)std::min<int64_t>(capacity, size) * sizeof(double));
+    return size;
+}

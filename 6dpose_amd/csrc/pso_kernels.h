@@ -1,0 +1,55 @@
+// Internal interface between pso.cpp (host) and pso.hip (kernels).  gfx950 only.
+#pragma once
+#include "render_kernels.h"
+
+namespace lm {
+
+struct PsoHyp {              // one hypothesis: the start pose and the origin of its window in the frame
+    double R0[9], t0[3];
+    int x0, y0;
+};
+struct PsoParams {           // the same for every hypothesis of a call
+    double K[9];             // the scene's camera
+    double range[6];         // +-range per dimension: trans_range_mm x 3, rot_range x 3
+    double inertia, c1, c2;
+    unsigned long long seed;
+    int P, G;                // particles per hypothesis, generations
+    int w, h;                // window size
+    int W, H;                // frame size
+    int tau;
+    int cover_pixels;        // > 0: n_0 is this instead of the initial pose's rendered pixels
+};
+struct PsoBest {             // the global best of one hypothesis
+    double x[6];
+    double cost, initial_cost;
+    int particle, generation, n_r, n_0;
+};
+struct PsoResultDev {        // lm_pso_result as the last k_pso_step writes it
+    double R[9], t[3];
+    double cost, initial_cost;
+    int n_rendered, n_initial, best_particle, best_generation;
+};
+struct PsoState {            // [HP] unless stated
+    double* x;               // [HP][6]
+    double* v;               // [HP][6]
+    double* pbest_x;         // [HP][6]
+    double* pbest_cost;
+    unsigned long long* sum;
+    unsigned int* n_r;
+    PsoBest* best;           // [H]
+    // the record of every generation for lm_pso_read_debug
+    double* rec_x;           // [G + 1][HP][6]
+    double* rec_cost;        // [G + 1][HP]
+    unsigned long long* rec_sum;   // [G + 1][HP]
+    unsigned int* rec_nr;    // [G + 1][HP]
+    int* rec_best;           // [G + 1][H][2]: particle, generation of the global best after the generation
+    PsoResultDev* result;    // [H]
+};
+
+void launch_pso_init(const PsoParams& p, int H, const PsoState& st, hipStream_t s);
+void launch_pso_views(const PsoParams& p, int H, const PsoHyp* hyp, const double* x, ViewParams* views, hipStream_t s);
+void launch_pso_cost(const PsoParams& p, int H, const PsoHyp* hyp, const unsigned long long* zbuf, const uint16_t* scene,
+                     unsigned long long* sum, unsigned int* n_r, hipStream_t s);
+void launch_pso_step(const PsoParams& p, int H, int g, const PsoHyp* hyp, const PsoState& st, hipStream_t s);
+
+}  // namespace lm

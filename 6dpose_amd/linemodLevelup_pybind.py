@@ -27,7 +27,7 @@ this wrapper validates instead: sources = [rgb uint8 HxWx3, depth uint16 HxW]; o
 Detector(..., colour_channels=1) takes a grey image, uint8 HxW, in the colour slot.
 
 This file is the import name only.  The code lives in the flat modules beside it, one per subsystem: lm_abi (library loading, the
-structures, the prototype table of the C ABI), lm_detector, lm_icp, lm_render and lm_pose_error.  The loaded library is
+structures, the prototype table of the C ABI), lm_detector, lm_icp, lm_pso, lm_render and lm_pose_error.  The loaded library is
 lm_abi._lib, set by load_library(); a global assigned after import does not travel through a re-export, so it has no alias here.
 """
 from lm_abi import (DEPTH_MODE_DTYPE, LM_ICP_POINT_TO_POINT, LM_ICP_SCENE_FROM_SCENE, MATCH_DTYPE, DepthModeOptions, IcpOptions, PipelineTimings, RenderOptions, Timings,
@@ -37,9 +37,10 @@ from lm_detector import (Comm, Detector, Match, NMSBoxes, Template, bank_file_in
                          nms_norms, rgb_to_grey)
 from lm_icp import (ICP_ESTIMATIONS, IcpContext, Pipeline, _icp_flags, _icp_options, _pose_dict, evaluate_registration, poseRefine,
                     pose_refine_batch)
+from lm_pso import PSO_DEBUG_KINDS, PsoContext, derive_windows, pso_options, pso_refine
 from lm_render import OVERLAY_MODES, SHADINGS, Mesh, _colour, add_templates_rendered, render_options
 from lm_pose_error import (POSE_METRICS, POSE_METRICS_SYM, _pose_batch, _scene_mm, bop19_thresholds, gt_stats, match_poses, pose_errors,
                            recall, symmetry_transforms)
 
 __all__ = ["Detector", "Match", "poseRefine", "IcpContext", "Pipeline", "Mesh", "Template", "library_path", "load_library", "nms",
-           "pose_errors", "gt_stats", "symmetry_transforms", "match_poses", "recall", "bop19_thresholds"]
+           "pose_errors", "gt_stats", "symmetry_transforms", "match_poses", "recall", "bop19_thresholds", "PsoContext", "pso_refine"]

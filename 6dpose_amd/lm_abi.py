@@ -84,6 +84,20 @@ class _CSlab(ctypes.Structure):
                 ("first_class", ctypes.c_int32), ("num_classes", ctypes.c_int32), ("records", ctypes.c_int64)]
 
 
+class PsoOptions(ctypes.Structure):
+    """lm_pso_options (include/amd_linemod_pso.h)."""
+    _fields_ = [("size", ctypes.c_uint32), ("particles", ctypes.c_int32), ("generations", ctypes.c_int32), ("tau", ctypes.c_int32),
+                ("cover_pixels", ctypes.c_int32), ("reserved", ctypes.c_int32), ("seed", ctypes.c_uint64), ("trans_range_mm", ctypes.c_double),
+                ("rot_range", ctypes.c_double), ("inertia", ctypes.c_double), ("c1", ctypes.c_double), ("c2", ctypes.c_double),
+                ("clip_near", ctypes.c_double), ("clip_far", ctypes.c_double)]
+
+
+class _CPsoResult(ctypes.Structure):
+    """lm_pso_result (include/amd_linemod_pso.h)."""
+    _fields_ = [("R", ctypes.c_double * 9), ("t", ctypes.c_double * 3), ("cost", ctypes.c_double), ("initial_cost", ctypes.c_double),
+                ("n_rendered", ctypes.c_int32), ("n_initial", ctypes.c_int32), ("best_particle", ctypes.c_int32), ("best_generation", ctypes.c_int32)]
+
+
 DEPTH_MODE_DTYPE = np.dtype([("bin", np.int32), ("depth_mm", np.int32), ("pixels", np.uint32)])
 MATCH_DTYPE = np.dtype([("x", np.int32), ("y", np.int32), ("similarity", np.float32),
                         ("class_index", np.int32), ("template_id", np.int32)])
@@ -99,6 +113,7 @@ PP, PI, PS, PZ = ctypes.POINTER(P), ctypes.POINTER(I), ctypes.POINTER(S), ctypes
 PM, PPM, PU8 = ctypes.POINTER(_CMatch), ctypes.POINTER(ctypes.POINTER(_CMatch)), ctypes.POINTER(ctypes.c_uint8)
 PDMO = ctypes.POINTER(DepthModeOptions)
 PPOSE, PICPO, PRO = ctypes.POINTER(_CPoseResult), ctypes.POINTER(IcpOptions), ctypes.POINTER(RenderOptions)
+PPSOO = ctypes.POINTER(PsoOptions)
 PROTOTYPES = {
     "lm_last_error": (S, []),
     "lm_version": (S, []),
@@ -242,6 +257,13 @@ PROTOTYPES = {
     "lm_pose_sym_tile": (I, []),
     "lm_mesh_gt_stats": (I, [P, I, P, P, P, I, I, P, D, D, D, P, P, P, P]),
     "lm_mesh_diameter": (I, [P, ctypes.POINTER(D)]),
+    # the particle-swarm refiner
+    "lm_pso_options_init": (None, [PPSOO]),
+    "lm_pso_create": (I, [I, PP]),
+    "lm_pso_destroy": (None, [P]),
+    "lm_pso_set_scene": (I, [P, P, I, I, P]),
+    "lm_pso_run": (I, [P, P, I, P, P, P, I, I, PPSOO, ctypes.POINTER(_CPsoResult), ctypes.POINTER(F)]),
+    "lm_pso_read_debug": (I64, [P, I, I, P, I64]),
 }
 
 

@@ -1,0 +1,137 @@
+"""Pose refinement by particle swarm over rendered depth (lm_pso_*): the refiner the reference's author left as a todo
+(linemodLevelup/readme.md:41-46).  Correspondence-free, so it needs neither a start inside ICP's correspondence radius nor the
+depth rendering of the matched template view: a Mesh, the scene depth and the hypotheses are enough."""
+from __future__ import annotations
+
+import ctypes
+import math
+
+import numpy as np
+
+from lm_abi import PsoOptions, _as_depth, _check, _CPsoResult, _ptr, load_library
+from lm_render import Mesh
+
+PSO_DEBUG_KINDS = {"x": 0, "cost": 1, "sum_n_r": 2, "best": 3}
+
+
+def pso_options(particles=64, generations=30, tau=20, trans_range_mm=20.0, rot_range_deg=10.0, seed=0, inertia=0.7298, c1=1.49618, c2=1.49618,
+                clip_near=10.0, clip_far=10000.0, cover_pixels=0, rot_range=None) -> PsoOptions:
+    """lm_pso_options.  rot_range_deg: the largest rotation about an axis; the library takes rot_range = tan(radians(rot_range_deg) / 2),
+    the bound on a Cayley component (rot_range= passes that number itself).  The limits are checked by lm_pso_run."""
+    for name, v in (("particles", particles), ("generations", generations), ("tau", tau), ("cover_pixels", cover_pixels), ("seed", seed)):
+        if int(v) != v:
+            raise RuntimeError("%s must be an integer (got %r)" % (name, v))
+    if not 0 <= int(seed) < 2 ** 64:
+        raise RuntimeError("seed must be in 0..2**64 - 1 (got %r)" % (seed,))
+    for name, v in (("particles", particles), ("generations", generations), ("tau", tau), ("cover_pixels", cover_pixels)):
+        if not -2 ** 31 <= int(v) < 2 ** 31:
+            raise RuntimeError("%s out of range (got %r)" % (name, v))
+    o = PsoOptions()
+    load_library().lm_pso_options_init(ctypes.byref(o))
+    o.particles, o.generations, o.tau, o.cover_pixels, o.seed = int(particles), int(generations), int(tau), int(cover_pixels), int(seed)
+    o.trans_range_mm = float(trans_range_mm)
+    o.rot_range = float(rot_range) if rot_range is not None else math.tan(math.radians(float(rot_range_deg)) / 2.0)
+    o.inertia, o.c1, o.c2, o.clip_near, o.clip_far = float(inertia), float(c1), float(c2), float(clip_near), float(clip_far)
+    return o
+
+
+def _result_dict(r):
+    return {"R": np.array(r.R, np.float64).reshape(3, 3), "t": np.array(r.t, np.float64), "cost": float(r.cost), "initial_cost": float(r.initial_cost),
+            "n_rendered": int(r.n_rendered), "n_initial": int(r.n_initial), "best_particle": int(r.best_particle),
+            "best_generation": int(r.best_generation)}
+
+
+def derive_windows(K, ts, radius_mm, window_size=None):
+    """The windows of pso_refine(windows=None): per hypothesis the projection of the sphere of radius_mm around t0, rounded outwards to
+    whole pixels; one size for the call, the largest extent rounded up to a multiple of 8 and clamped to 8..256 (or window_size), every
+    window centred on its sphere.  Returns (int32 [n][2] origins, (w, h))."""
+    K = np.asarray(K, np.float64).reshape(3, 3); ts = np.asarray(ts, np.float64).reshape(-1, 3)
+    boxes = []
+    for t in ts:
+        z = max(float(t[2]) - float(radius_mm), 1.0)                     # the sphere's nearest point bounds its image
+        cu, cv = K[0, 0] * t[0] / t[2] + K[0, 2], K[1, 1] * t[1] / t[2] + K[1, 2]
+        ru, rv = K[0, 0] * radius_mm / z, K[1, 1] * radius_mm / z
+        boxes.append((math.floor(cu - ru), math.ceil(cu + ru), math.floor(cv - rv), math.ceil(cv + rv)))
+    if window_size is None:
+        w = max(b[1] - b[0] + 1 for b in boxes); h = max(b[3] - b[2] + 1 for b in boxes)
+        w, h = (min(max(-(-int(v) // 8) * 8, 8), 256) for v in (w, h))
+    else:
+        w, h = int(window_size[0]), int(window_size[1])
+    xy = np.array([[(b[0] + b[1] + 1 - w) // 2, (b[2] + b[3] + 1 - h) // 2] for b in boxes], np.int32).reshape(-1, 2)
+    return xy, (w, h)
+
+
+class PsoContext:
+    """lm_pso (include/amd_linemod.h): set_scene(depth, K) once per frame, then run(mesh, Rs, ts, windows, window_size, **options) any
+    number of times.  run returns (list of dict(R, t, cost, initial_cost, n_rendered, n_initial, best_particle, best_generation),
+    device_ms); options: see pso_options."""
+
+    def __init__(self, device: int = 0):
+        self._lib = load_library()
+        self._h = ctypes.c_void_p()
+        _check(self._lib.lm_pso_create(int(device), ctypes.byref(self._h)))
+        self.K = None
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            self._lib.lm_pso_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    __del__ = close
+
+    def set_scene(self, scene_depth, scene_K):
+        sd = _as_depth(scene_depth, "scene_depth")
+        K = np.ascontiguousarray(np.asarray(scene_K, np.float64).reshape(9))
+        _check(self._lib.lm_pso_set_scene(self._h, _ptr(sd), sd.shape[1], sd.shape[0], _ptr(K)))
+        self.K, self.shape = K.reshape(3, 3), sd.shape
+
+    def run(self, mesh: Mesh, Rs, ts, windows=None, window_size=None, **options):
+        opts = pso_options(**options)
+        Rs = np.ascontiguousarray(np.asarray(Rs, np.float64).reshape(-1, 9))
+        n = len(Rs)
+        ts = np.ascontiguousarray(np.asarray(ts, np.float64).reshape(n, 3))
+        if windows is None:
+            if self.K is None:
+                raise RuntimeError("no scene depth set (set_scene)")
+            windows, window_size = derive_windows(self.K, ts, mesh.diameter() / 2.0 + opts.trans_range_mm, window_size)
+        elif window_size is None:
+            raise RuntimeError("windows need a window_size")
+        xy = np.ascontiguousarray(np.asarray(windows, np.int32).reshape(n, 2))
+        res = (_CPsoResult * max(n, 1))()
+        ms = ctypes.c_float()
+        _check(self._lib.lm_pso_run(self._h, mesh._h, n, _ptr(Rs), _ptr(ts), _ptr(xy), int(window_size[0]), int(window_size[1]), ctypes.byref(opts),
+                                    res, ctypes.byref(ms)))
+        return [_result_dict(res[i]) for i in range(n)], float(ms.value)
+
+    def read_debug(self, hypothesis: int, kind):
+        """The record of the last run for one hypothesis, generation 0 (the initial swarm) to `generations`.  kind 'x': float64 (G+1, P, 6)
+        positions evaluated; 'cost': (G+1, P); 'sum_n_r': int64 (G+1, P, 2); 'best': int64 (G+1, 2) particle and generation of the global
+        best after each generation."""
+        k = PSO_DEBUG_KINDS[kind] if isinstance(kind, str) else int(kind)
+        f = self._lib.lm_pso_read_debug
+        n = f(self._h, int(hypothesis), k, None, 0)
+        if n < 0:
+            _check(int(n))
+        out = np.zeros(int(n), np.float64)
+        if n:
+            f(self._h, int(hypothesis), k, _ptr(out), int(n))
+        gens = int(f(self._h, int(hypothesis), 3, None, 0)) // 2         # kind 3 is [G + 1][2]
+        if k == 0:
+            return out.reshape(gens, -1, 6)
+        if k == 1:
+            return out.reshape(gens, -1)
+        if k == 2:
+            return out.astype(np.int64).reshape(gens, -1, 2)
+        return out.astype(np.int64).reshape(gens, 2)
+
+
+def pso_refine(mesh: Mesh, scene_depth, K, Rs, ts, windows=None, window_size=None, device: int = 0, **options):
+    """One call: a context of its own, set_scene, run.  Returns (list of dict, device_ms) like PsoContext.run.  With windows=None the
+    window of each hypothesis is derived on the host (derive_windows) from the sphere around t0 of radius Mesh.diameter() / 2 +
+    trans_range_mm."""
+    ctx = PsoContext(device)
+    try:
+        ctx.set_scene(scene_depth, K)
+        return ctx.run(mesh, Rs, ts, windows, window_size, **options)
+    finally:
+        ctx.close()

@@ -27,6 +27,7 @@
 #include <stdint.h>
 
 #include "amd_linemod_depth.h"   /* lm_depth_mode_options, lm_depth_mode, lm_slab */
+#include "amd_linemod_pso.h"     /* lm_pso_options, lm_pso_result */
 
 #ifdef __cplusplus
 extern "C" {
@@ -752,6 +753,33 @@ int lm_mesh_gt_stats(lm_mesh *m, int n_gt, const double *R_gt, const double *t_g
                      double *visib_fract, int32_t *bbox_obj, int32_t *bbox_visib);
 /* misc.calc_pts_diameter: the largest vertex-to-vertex distance (mm). */
 int lm_mesh_diameter(lm_mesh *m, double *diameter);
+
+/* ---- pose refinement by particle swarm over rendered depth (linemodLevelup/readme.md:41-46, the author's todo) ----------
+ * Correspondence-free: each of `count` hypotheses (R0, t0) gets P particles x = (dt[3] mm, a[3]), a a Cayley rotation
+ * vector, dR(a) = ((1 - a.a) I + 2 a a^T + 2 [a]x) / (1 + a.a); the particle's pose is R = dR(a) R0, t = t0 + dt.  Every
+ * particle is rendered depth-only (the rasteriser of lm_mesh_render) into a w x h window of the frame whose origin is the
+ * hypothesis' windows_xy, and scored against the scene depth there: over pixels with rendered depth r > 0 (n_r of them) the
+ * sum of tau where the scene depth s is 0 and min(|r - s|, tau) elsewhere; cost = sum / n_r when n_r >= (n_0 + 1) / 2 and
+ * n_r > 0, else +inf (n_0: the n_r of the given pose, so that a particle cannot win by leaving the view).  Window pixels
+ * outside the frame read s = 0.  The swarm, its random numbers and every operation's order are stated in numpy by
+ * tests/pso_ref.py, which is this refiner's specification; the device follows it bit for bit, so a call is repeatable and
+ * depends on the seed alone.  A call is one enqueue on the context's stream with no host synchronisation before the copy
+ * of the results.  LM_ERR_INVALID: the limits stated in amd_linemod_pso.h, 8 <= w, h <= 256, count x P <= 4096, a mesh on
+ * another device, no scene set. */
+typedef struct lm_pso lm_pso;
+void lm_pso_options_init(lm_pso_options *options);
+int lm_pso_create(int device, lm_pso **out);
+void lm_pso_destroy(lm_pso *c);
+/* The scene depth (uint16 [height][width], mm, 0 = no measurement) and its camera K (float64 row-major 3x3); stays in HBM. */
+int lm_pso_set_scene(lm_pso *c, const uint16_t *scene_depth, int width, int height, const double *K);
+/* Rs [count][9], ts [count][3] float64; windows_xy [count][2] int32 (may leave the frame); options NULL = the defaults. */
+int lm_pso_run(lm_pso *c, lm_mesh *mesh, int count, const double *Rs, const double *ts, const int32_t *windows_xy /*[count][2]*/,
+               int w, int h, const lm_pso_options *options, lm_pso_result *results, float *device_ms);
+/* Test/diagnostic read-back of the last run's record of one hypothesis, generation 0 (the initial swarm) to `generations`.
+ * kind: 0 the positions evaluated x [G + 1][P][6], 1 their costs [G + 1][P], 2 (sum, n_r) [G + 1][P][2], 3 (particle,
+ * generation) of the global best after each generation [G + 1][2].  Integers are returned as doubles, doubles bit for bit.
+ * Copies min(capacity, size) doubles, returns the size. */
+int64_t lm_pso_read_debug(lm_pso *c, int hypothesis, int kind, double *dst, int64_t capacity);
 
 #ifdef __cplusplus
 }

@@ -319,6 +319,7 @@ extern "C" void lm_detector_destroy(lm_detector* d) {
     for (int l = 0; l < kMaxLevels; ++l) { d->train.mask[l].release(); d->train.lab[l].release(); d->train.hrun[l].release(); }
     d->train.user_mask.release();
     d->slabs.hist.release(); d->slabs.modes.release();
+    d->scaled.probe.release(); d->scaled.table.release(); d->scaled.entries.release(); d->scaled.train.release(); d->scaled.cands.release(); d->scaled.counter.release();
     for (auto& lv : d->slabs.mask) for (auto& m : lv) m.release();
     if (d->slabs.h_modes) (void)hipHostFree(d->slabs.h_modes);
     if (d->slabs.modes_ready) (void)hipEventDestroy(d->slabs.modes_ready);

@@ -452,6 +452,7 @@ extern "C" int lm_detector_read_params(lm_detector* d, const char* path) {
     for (int t : T) if (t < 1) return lm_set_error(LM_ERR_INVALID, "T must be >= 1");
     d->class_templates.clear();                                   // LL.cpp:2015
     d->class_depth_range.clear();                                 // (the ranges go with their classes)
+    d->class_train_depth.clear();                                 // (and the training depths)
     d->bank_dirty = true; d->work_valid = false; d->frame_valid = false;
     d->pyramid_levels = levels; d->T_at_level = T;
     d->num_features = nf[0]; d->weak_threshold = weak; d->strong_threshold = strong;
@@ -748,6 +749,7 @@ int upload_bank(lm_detector* d) {
                          lv.W - e.width - 16 * lv.T >= 0 && lv.H - e.height - 16 * lv.T >= 0 && lv.W % lv.T == 0 && lv.H % lv.T == 0;
     }
     d->bank_dirty = false;
+    ++d->bank_generation;
     d->bank_geom_W = d->fW; d->bank_geom_H = d->fH;
     return LM_OK;
 }

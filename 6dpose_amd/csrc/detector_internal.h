@@ -1,5 +1,5 @@
 // Private view of the detector shared by the detector's translation units (detector.cpp, detector_frame.cpp, detector_bank.cpp,
-// detector_stream.cpp, detector_slabs.cpp, host_pool.cpp, match_lists.cpp), bank_file.cpp, comm.cpp, exchange.cpp and pipeline.cpp (not part of the C ABI).
+// detector_stream.cpp, detector_slabs.cpp, detector_scaled.cpp, host_pool.cpp, match_lists.cpp), bank_file.cpp, comm.cpp, exchange.cpp and pipeline.cpp (not part of the C ABI).
 #pragma once
 #include <algorithm>
 #include <atomic>
@@ -20,6 +20,7 @@
 #include "host_templates.h"
 #include "knobs.h"
 #include "lm_kernels.h"
+#include "scaled_kernels.h"
 
 int lm_set_error(int code, const char* fmt, ...);
 
@@ -261,6 +262,26 @@ struct lm_detector {
         bool mask_on = false, quantised = false;
     } slabs;
     std::map<std::string, std::pair<int, int>> class_depth_range;   // lm_detector_set_class_depth_range: host state, stored in no file
+    // Depth-scaled matching (detector_scaled.cpp; match_scaled.hip): the training depth of a class (host state, stored in no
+    // file, like the depth ranges), and what a call keeps between calls: the probe map, the K-row tables of the selected classes — cached per
+    // (bank generation, ladder, selection) — and candidate buffers of its own (`cap` starts at cand_cap and grows when a call overflows it).
+    std::map<std::string, int> class_train_depth;
+    uint64_t bank_generation = 0;                   // counts upload_bank: a bank or geometry change
+    int pipelines = 0;                              // lm_pipeline objects created on this detector and not destroyed
+    struct Scaled {
+        DevBuf<uint16_t> probe;
+        DevBuf<ScaledFeat> table;
+        DevBuf<ScaledEntry> entries;
+        DevBuf<int32_t> train;
+        DevBuf<ScaledCand> cands;
+        DevBuf<unsigned int> counter;
+        uint32_t cap = 0;
+        bool table_valid = false;
+        uint64_t key_generation = 0;
+        std::vector<int32_t> key_ladder;
+        std::vector<std::string> key_classes;
+        int max_nf_top = 0;
+    } scaled;
     bool cbits_clean[kSlots] = {};                  // the slot's pair stream is all zero (what the front end's OR-ing writer needs)
     uint64_t n_submitted = 0, n_collected = 0, n_launched = 0;
     // frames submitted but not launched yet: slots pend_first .. pend_first + pend_n - 1 (modulo kSlots), same threshold and work list
@@ -385,6 +406,8 @@ int lm_submit_frame(lm_detector* d, float threshold, const char* const* class_id
 int lm_collect_frame(lm_detector* d, int sort_unique, lm_match** out, size_t* n_out);   // sort_unique < 0: discard the records
 int lm_launch_pending(lm_detector* d);                                                  // launches the frames waiting for their batch to fill
 int lm_quantise_resident(lm_detector* d);                                               // the quantising stages of the resident frame alone, on `stream` (depth slabs)
+// the whole front end of the resident frame with BYTE linear memories at every level, on `stream`; *arena = the set written (depth-scaled matching)
+int lm_byte_memories_resident(lm_detector* d, int* arena);
 
 // host_pool.cpp: the helper threads of the streamed path (HostPool above) and the staging copy they share with the caller
 bool pool_ready(lm_detector* d);

@@ -605,6 +605,19 @@ int lm_quantise_resident(lm_detector* d) {
     return run_frontend_batch(d, si, 1, d->stream, false, false, kFeQuantise);
 }
 
+// The whole front end of the resident frame with the byte linear memories of every level (what lm_detector_set_paths' "bytes" paths and
+// lm_detector_read_stage kinds 2 and 3 build), on the frame stream, with nothing in flight: depth-scaled matching reads them (detector_scaled.cpp).
+int lm_byte_memories_resident(lm_detector* d, int* arena) {
+    if (!d->frame_valid) return lm_set_error(LM_ERR_INVALID, "no frame resident: call lm_detector_set_frame / select_frame first");
+    if (d->n_submitted != d->n_collected) return lm_set_error(LM_ERR_INVALID, "frames in flight: collect them first");
+    LM_DIAG_IDLE(d, "lm_byte_memories_resident");
+    const int si = (int)(d->n_submitted % lm_detector::kSlots);
+    lm_detector::Slot& sl = d->slot[si];
+    sl.in_rgb = d->cur_rgb; sl.in_depth = d->cur_depth; sl.have_mask[0] = d->have_mask[0]; sl.have_mask[1] = d->have_mask[1];
+    *arena = si;
+    return run_frontend_batch(d, si, 1, d->stream, false, false);
+}
+
 // The detector's current frame (lm_detector_set_frame / select_frame, or the frame a previous submit_frame left current) as a
 // batch of one, launched at once.
 int lm_submit_frame(lm_detector* d, float threshold, const char* const* class_ids, int num_class_ids) {

@@ -64,12 +64,14 @@ extern "C" int lm_pipeline_create(lm_detector* det, int width, int height, lm_pi
         lm_icp_destroy(p->icp); delete p;
         return lm_set_error(LM_ERR_HIP, "could not create the pipeline events");
     }
+    ++det->pipelines;                                            // (depth-scaled matching refuses a detector that serves a pipeline)
     *out = p;
     return LM_OK;
 }
 
 extern "C" void lm_pipeline_destroy(lm_pipeline* p) {
     if (!p) return;
+    --p->det->pipelines;
     (void)hipSetDevice(p->det->device);
     (void)hipStreamSynchronize(p->det->stream);
     (void)hipStreamSynchronize(p->det->mstream);

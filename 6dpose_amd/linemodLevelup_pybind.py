@@ -30,11 +30,11 @@ This file is the import name only.  The code lives in the flat modules beside it
 structures, the prototype table of the C ABI), lm_detector, lm_icp, lm_pso, lm_render and lm_pose_error.  The loaded library is
 lm_abi._lib, set by load_library(); a global assigned after import does not travel through a re-export, so it has no alias here.
 """
-from lm_abi import (DEPTH_MODE_DTYPE, LM_ICP_POINT_TO_POINT, LM_ICP_SCENE_FROM_SCENE, MATCH_DTYPE, DepthModeOptions, IcpOptions, PipelineTimings, RenderOptions, Timings,
+from lm_abi import (DEPTH_MODE_DTYPE, LM_ICP_POINT_TO_POINT, LM_ICP_SCENE_FROM_SCENE, MATCH_DTYPE, SCALED_MATCH_DTYPE, DepthModeOptions, ScaledOptions, IcpOptions, PipelineTimings, RenderOptions, Timings,
                     _CDetection, _CMatch, _CPoseResult, _as_depth, _as_grey, _as_mask, _as_rgb, _check, _ptr, _share_hip_runtime_with_torch,
                     aligned_size, bind_near_device, library_path, load_library, rgb_to_grey_ref)
-from lm_detector import (Comm, Detector, Match, NMSBoxes, Template, bank_file_info, bank_file_modalities, merge_matches, nms,
-                         nms_norms, rgb_to_grey)
+from lm_detector import (DEFAULT_SCALES, Comm, Detector, Match, NMSBoxes, Template, bank_file_info, bank_file_modalities, merge_matches, nms,
+                         nms_norms, rgb_to_grey, scale_q10, scaled_box, scaled_features, scaled_options)
 from lm_icp import (ICP_ESTIMATIONS, IcpContext, Pipeline, _icp_flags, _icp_options, _pose_dict, evaluate_registration, poseRefine,
                     pose_refine_batch)
 from lm_pso import PSO_DEBUG_KINDS, PsoContext, derive_windows, pso_options, pso_refine

@@ -84,6 +84,18 @@ class _CSlab(ctypes.Structure):
                 ("first_class", ctypes.c_int32), ("num_classes", ctypes.c_int32), ("records", ctypes.c_int64)]
 
 
+class ScaledOptions(ctypes.Structure):
+    """lm_scaled_options (include/amd_linemod_scaled.h)."""
+    _fields_ = [("num_scales", ctypes.c_int32), ("scales_q10", ctypes.c_int32 * 16), ("min_scale_q10", ctypes.c_int32),
+                ("max_scale_q10", ctypes.c_int32), ("probe", ctypes.c_int32)]
+
+
+class _CScaledMatch(ctypes.Structure):
+    """lm_scaled_match (include/amd_linemod_scaled.h)."""
+    _fields_ = [("x", ctypes.c_int32), ("y", ctypes.c_int32), ("similarity", ctypes.c_float), ("class_index", ctypes.c_int32),
+                ("template_id", ctypes.c_int32), ("scale_index", ctypes.c_int32), ("depth_mm", ctypes.c_int32)]
+
+
 class PsoOptions(ctypes.Structure):
     """lm_pso_options (include/amd_linemod_pso.h)."""
     _fields_ = [("size", ctypes.c_uint32), ("particles", ctypes.c_int32), ("generations", ctypes.c_int32), ("tau", ctypes.c_int32),
@@ -101,6 +113,8 @@ class _CPsoResult(ctypes.Structure):
 DEPTH_MODE_DTYPE = np.dtype([("bin", np.int32), ("depth_mm", np.int32), ("pixels", np.uint32)])
 MATCH_DTYPE = np.dtype([("x", np.int32), ("y", np.int32), ("similarity", np.float32),
                         ("class_index", np.int32), ("template_id", np.int32)])
+SCALED_MATCH_DTYPE = np.dtype([("x", np.int32), ("y", np.int32), ("similarity", np.float32), ("class_index", np.int32),
+                               ("template_id", np.int32), ("scale_index", np.int32), ("depth_mm", np.int32)])
 LM_ICP_SCENE_FROM_SCENE = 1
 LM_ICP_POINT_TO_POINT = 2
 
@@ -203,6 +217,11 @@ PROTOTYPES = {
     "lm_detector_set_class_depth_range": (I, [P, S, I, I, I]),
     "lm_detector_get_class_depth_range": (I, [P, S, PI, PI]),
     "lm_detector_match_slabs": (I, [P, F, PS, I, I, PDMO, PPM, PZ, ctypes.POINTER(_CSlab), I, PI, ctypes.POINTER(ctypes.POINTER(ctypes.c_int32))]),
+    "lm_scaled_options_init": (None, [ctypes.POINTER(ScaledOptions)]),
+    "lm_detector_set_class_train_depth": (I, [P, S, I]),
+    "lm_detector_get_class_train_depth": (I, [P, S, PI]),
+    "lm_detector_match_scaled": (I, [P, F, PS, I, ctypes.POINTER(ScaledOptions), ctypes.POINTER(ctypes.POINTER(_CScaledMatch)), PZ]),
+    "lm_scaled_features": (I, [I, I, P, P, I, I, P, P]),
     "lm_detector_bit_arena_bytes": (I, [P, ctypes.POINTER(U64), ctypes.POINTER(U64)]),
     "lm_detector_wide_arena_bytes": (I, [P, ctypes.POINTER(U64), ctypes.POINTER(U64)]),
     "lm_detector_train_stats": (I, [P, ctypes.POINTER(I64)]),

@@ -11,8 +11,10 @@ from typing import List, Optional, Sequence
 
 import numpy as np
 
-from lm_abi import (BORDER_POLICIES, DEPTH_MODE_DTYPE, MATCH_DTYPE, DepthModeOptions, Timings, _CMatch, _CSlab, _as_depth, _as_grey, _as_mask,
+from lm_abi import (BORDER_POLICIES, DEPTH_MODE_DTYPE, MATCH_DTYPE, SCALED_MATCH_DTYPE, DepthModeOptions, ScaledOptions, Timings, _CMatch, _CScaledMatch, _CSlab, _as_depth, _as_grey, _as_mask,
                     _as_rgb, _border_code, _check, _ptr, _rgb_last_axis, aligned_size, load_library)
+
+DEFAULT_SCALES = tuple(2.0 ** (i / 4.0 - 1.0) for i in range(9))     # 0.5 .. 2 in quarter octaves: the ladder of lm_scaled_options_init
 
 
 class Match:
@@ -699,6 +701,50 @@ class Detector:
         self.setFrame(sources, masks)
         return self.matchSlabsResident(threshold, class_ids, (), slab_mm, **mode_options)
 
+    # ---- depth-scaled matching: every template scaled, per position, to the scene depth found there ----
+    def setClassTrainDepth(self, class_id: str, depth_mm: int) -> None:
+        """lm_detector_set_class_train_depth: the distance (mm, 1..65535) at which the templates of this class were made.  Host state of this
+        detector: no file stores it, readClasses and readBank produce classes without one."""
+        if isinstance(depth_mm, bool) or not isinstance(depth_mm, (int, np.integer)) or abs(int(depth_mm)) > 2 ** 30:
+            raise RuntimeError("a training depth is an integer (mm), got %r" % (depth_mm,))
+        _check(self._lib.lm_detector_set_class_train_depth(self._h, class_id.encode(), int(depth_mm)))
+
+    def classTrainDepth(self, class_id: str):
+        """The depth of setClassTrainDepth, or None for a class without one."""
+        v = ctypes.c_int()
+        have = _check(self._lib.lm_detector_get_class_train_depth(self._h, class_id.encode(), ctypes.byref(v)))
+        return int(v.value) if have else None
+
+    def matchScaledResident(self, threshold: float, class_ids: Sequence[str] = (), scales=DEFAULT_SCALES, min_scale=None, max_scale=None,
+                            probe: int = 2) -> np.ndarray:
+        """lm_detector_match_scaled on the resident frame: at every top-level position the template is scaled by the entry of `scales` nearest to
+        d_train / d, d the smallest non-zero depth of the (2 probe + 1)^2 level-0 pixels under the template's centre and d_train the class's
+        setClassTrainDepth; positions where d is 0 or d_train / d lies outside [min_scale, max_scale] (default: the first and last scale) are
+        not matched.  `scales`, `min_scale` and `max_scale` are floats, converted to Q10 by scale_q10 (floor(1024 s + 0.5)); 1 to 16 strictly
+        ascending scales in [0.5, 2].  Returns SCALED_MATCH_DTYPE records (x, y, similarity, class_index, template_id, scale_index, depth_mm): x,
+        y, similarity as matchArray gives them (scaled_box turns a record into the object's box), ordered by similarity descending, then
+        class_index, template_id, y, x, scale_index, depth_mm.  The rule is stated in numpy in tests/scaled_match_ref.py.  A cell outside the
+        level reads 0 here (no wrap into the next row): the one departure from match().  Refused: a detector without DepthNormal, a sharded
+        detector, part matching, a detector with a Pipeline, frames in flight, no resident frame, a bad ladder, a class without a training depth."""
+        opt = scaled_options(scales, min_scale, max_scale, probe)
+        carr, n, _names = self._class_args(class_ids)
+        out, cnt = ctypes.POINTER(_CScaledMatch)(), ctypes.c_size_t()
+        _check(self._lib.lm_detector_match_scaled(self._h, float(threshold), carr, n, ctypes.byref(opt), ctypes.byref(out), ctypes.byref(cnt)))
+        try:
+            arr = np.empty(cnt.value, SCALED_MATCH_DTYPE)
+            if cnt.value:
+                ctypes.memmove(arr.ctypes.data, out, cnt.value * ctypes.sizeof(_CScaledMatch))
+            return arr
+        finally:
+            self._lib.lm_free(out)
+
+    def matchScaled(self, sources, threshold: float, class_ids: Sequence[str] = (), masks=(), **scaled) -> np.ndarray:
+        """setFrame(sources, masks) followed by matchScaledResident(threshold, class_ids, **scaled)."""
+        self._sources(sources, True)
+        scaled_options(scaled.get("scales", DEFAULT_SCALES), scaled.get("min_scale"), scaled.get("max_scale"), scaled.get("probe", 2))   # (refuse a bad ladder before the upload)
+        self.setFrame(sources, masks)
+        return self.matchScaledResident(threshold, class_ids, **scaled)
+
     def lastTimings(self) -> dict:
         t = Timings()
         _check(self._lib.lm_detector_last_timings(self._h, ctypes.byref(t)))
@@ -718,6 +764,53 @@ class Detector:
         buf = np.zeros(n, np.uint8)
         _check(self._lib.lm_detector_read_stage(self._h, level, kind, _ptr(buf), n))
         return buf
+
+
+def scale_q10(scale) -> int:
+    """A scale as the Q10 integer the matcher uses: floor(1024 * scale + 0.5) (1024 is scale 1)."""
+    if isinstance(scale, bool) or not isinstance(scale, (int, float, np.integer, np.floating)) or not np.isfinite(scale) or abs(scale) > 2 ** 20:
+        raise RuntimeError("a scale is a finite number, got %r" % (scale,))
+    return int(np.floor(1024.0 * float(scale) + 0.5))
+
+
+def scaled_options(scales=DEFAULT_SCALES, min_scale=None, max_scale=None, probe: int = 2) -> ScaledOptions:
+    """lm_scaled_options of a ladder of float scales (scale_q10 each), optional float bounds and the probe radius; the library checks the values."""
+    q = [scale_q10(s) for s in scales]
+    if not 1 <= len(q) <= 16:
+        raise RuntimeError("scaled matching: the ladder has 1..16 scales, got %d" % len(q))
+    if isinstance(probe, bool) or not isinstance(probe, (int, np.integer)) or abs(int(probe)) > 2 ** 30:
+        raise RuntimeError("probe must be an integer, got %r" % (probe,))
+    lo = 0 if min_scale is None else scale_q10(min_scale)
+    hi = 0 if max_scale is None else scale_q10(max_scale)
+    if (min_scale is not None and lo < 1) or (max_scale is not None and hi < 1):
+        raise RuntimeError("scaled matching: bad scale bounds %r, %r" % (min_scale, max_scale))
+    opt = ScaledOptions()
+    opt.num_scales = len(q)
+    for i, v in enumerate(q):
+        opt.scales_q10[i] = v
+    opt.min_scale_q10, opt.max_scale_q10, opt.probe = lo, hi, int(probe)
+    return opt
+
+
+def scaled_features(width: int, height: int, xs, ys, scale_q10_value: int):
+    """lm_scaled_features (no detector, no GPU): the features (xs, ys) of an entry of box (width, height) scaled about its centre (width // 2,
+    height // 2) by the Q10 scale: c + sign(v - c) * ((|v - c| * s + 512) >> 10).  Returns (xs, ys) as int32 arrays."""
+    lib = load_library()
+    xs = np.ascontiguousarray(xs, np.int32); ys = np.ascontiguousarray(ys, np.int32)
+    if xs.shape != ys.shape or xs.ndim != 1:
+        raise RuntimeError("xs and ys are 1-D arrays of one length")
+    ox, oy = np.empty_like(xs), np.empty_like(ys)
+    _check(lib.lm_scaled_features(int(width), int(height), _ptr(xs), _ptr(ys), len(xs), int(scale_q10_value), _ptr(ox), _ptr(oy)))
+    return ox, oy
+
+
+def scaled_box(record, template, scales=DEFAULT_SCALES):
+    """The object's box (x0, y0, width, height), floats, of a SCALED_MATCH_DTYPE record: centre (x + w0 // 2, y + h0 // 2) of the level-0
+    template (anything with .width and .height, or a (w0, h0) pair), size s_k * (w0, h0), s_k = scale_q10(scales[scale_index]) / 1024."""
+    w0, h0 = (template.width, template.height) if hasattr(template, "width") else template
+    s = scale_q10(scales[int(record["scale_index"])]) / 1024.0
+    cx, cy = int(record["x"]) + int(w0) // 2, int(record["y"]) + int(h0) // 2
+    return cx - s * w0 / 2.0, cy - s * h0 / 2.0, s * w0, s * h0
 
 
 def bank_file_info(path) -> dict:

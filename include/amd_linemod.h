@@ -28,6 +28,7 @@
 
 #include "amd_linemod_depth.h"   /* lm_depth_mode_options, lm_depth_mode, lm_slab */
 #include "amd_linemod_pso.h"     /* lm_pso_options, lm_pso_result */
+#include "amd_linemod_scaled.h"  /* lm_scaled_match, lm_scaled_options */
 
 #ifdef __cplusplus
 extern "C" {
@@ -436,6 +437,38 @@ int lm_detector_get_class_depth_range(const lm_detector *d, const char *class_id
 int lm_detector_match_slabs(lm_detector *d, float threshold, const char *const *class_ids, int num_class_ids, int slab_mm,
                             const lm_depth_mode_options *options, lm_match **out, size_t *n, lm_slab *slabs, int slab_capacity,
                             int *num_slabs, int32_t **slab_classes);
+/* Depth-scaled matching: every template scaled, per matching position, to the scene depth found there (the reference author's "at each matching
+ * pos, scale template depth to scene depth", linemodLevelup/notes.md:1-2, 25-31, readme.md:24: the best detector of those notes, dropped for its
+ * CPU cost).  A class trained at d_train mm (lm_detector_set_class_train_depth; host state of this detector like the depth ranges, stored in no
+ * file; 1..65535) is found at other distances without a class per scale: the bank is not multiplied.  The rule, on the RESIDENT frame, is the
+ * holistic rule of lm_detector_match with one change, where a feature is sampled:
+ *   probe map P: the smallest non-zero depth of the (2 probe + 1)^2 window of level-0 pixels around a pixel, clipped to the aligned frame; 0 if none;
+ *   top level, entry (pyramid, L - 1) of box (w, h), step T, Wd = W / T: every cell (i, j) whose raster position lies below the template's
+ *   position count (of the unscaled box) is looked at; d = P at the level-0 pixel ((i T + w / 2) << (L - 1), (j T + h / 2) << (L - 1)) clamped into
+ *   the frame; no candidate if d = 0, d_train 1024 < min_scale_q10 d or d_train 1024 > max_scale_q10 d; else k = argmin |s_k d - d_train 1024| in
+ *   64-bit integers, a tie to the lower k; k is carried through every lower level, the depth is not probed again;
+ *   a feature (fx, fy) of an entry with centre c = (w / 2, h / 2) is sampled at sx = cx + sign(fx - cx) ((|fx - cx| s_k + 512) >> 10), sy alike
+ *   (lm_scaled_features: the host's statement, callable without a GPU); labels, the feature count and the score's denominator stay, features
+ *   that coincide after scaling count twice; its response at a position origin (ox, oy), a multiple of T, is the byte of its modality's linear
+ *   memories at pixel (ox + sx, oy + sy), and 0 when that pixel's cell lies outside [0, Wd) x [0, Hd);
+ *   candidates ((raw 100.f) / (4 nf) > threshold), windows, clamps (of the unscaled box), first-maximum arg-max, position updates and the drop
+ *   below the threshold are those of lm_detector_match (LL.cpp:1835-1938).
+ * The one DEPARTURE from the reference's reads: a cell outside the level reads 0, there is no wrap into the next row or the next linear memory
+ * (with the ladder {1024} the records are those of lm_detector_match wherever no template's reads wrap).
+ * Records (lm_scaled_match; lm_free(*out)): x, y, similarity of the unscaled convention, scale_index k, depth_mm d; exact duplicates removed;
+ * ordered by similarity descending, then class_index, template_id, y, x, scale_index, depth_mm ascending.  options NULL = lm_scaled_options_init.
+ * Candidate buffers of its own start at the detector's candidate capacity and grow (the call reruns) on an overflow: no candidate is dropped.
+ * Every response table, grey colour frames, a depth-only modality set and the border policies work (the padding's depth is 0).
+ * Refused (LM_ERR_INVALID), never matched unscaled in silence: a detector without DepthNormal; a sharded detector; part matching switched on;
+ * a detector that serves a pipeline; frames in flight; no resident frame; a ladder that is not 1..16 strictly ascending values in [512, 2048];
+ * bounds with min > max; probe outside 0..4; a requested class without a training depth; a ladder whose table (scales x the largest top-level
+ * feature count x 8 bytes) exceeds 160 KB.  The call leaves no frame in flight, so the multi-GPU exchange has nothing to pack. */
+void lm_scaled_options_init(lm_scaled_options *options);
+int lm_detector_set_class_train_depth(lm_detector *d, const char *class_id, int depth_mm);
+int lm_detector_get_class_train_depth(const lm_detector *d, const char *class_id, int *depth_mm);
+int lm_detector_match_scaled(lm_detector *d, float threshold, const char *const *class_ids, int num_class_ids, const lm_scaled_options *options,
+                             lm_scaled_match **out, size_t *n);
+int lm_scaled_features(int width, int height, const int32_t *xs, const int32_t *ys, int n, int scale_q10, int32_t *out_xs, int32_t *out_ys);
 /* Device memory ALLOCATED for the bit planes, summed over the result slots: the strip records of the levels below the top and the pair
  * stream of the top level (tests: no response table makes them grow). */
 int lm_detector_bit_arena_bytes(const lm_detector *d, uint64_t *strip_records, uint64_t *pair_stream);

@@ -3,8 +3,9 @@
 // template extraction on the host, every per-pixel / per-template stage in HIP kernels
 // (fe_quant.hip, fe_bits.hip, match_bytes.hip, match_bits.hip).  No CPU fallback: creation fails without a HIP device.
 // This file: errors, thread binding, creation / destruction and the small setters and getters.  The frame and the training front
-// end are in detector_frame.cpp, the template bank in detector_bank.cpp, the streamed matching path in detector_stream.cpp (its
-// helper threads: host_pool.cpp), the host-side result lists and NMS in match_lists.cpp.
+// end are in detector_frame.cpp, the template bank in detector_bank.cpp, the streamed matching path in detector_frontend.cpp,
+// detector_launch.cpp, detector_collect.cpp and detector_ingest.cpp (when a partial batch goes out: launch_model.h; the helper threads:
+// host_pool.cpp), the host-side result lists and NMS in match_lists.cpp.
 #include <math.h>
 #include <stdarg.h>
 #include <stdio.h>
@@ -274,9 +275,10 @@ extern "C" int lm_detector_create_modalities(int num_features, const int* T, int
     }
     d->work_cls = std::make_shared<std::vector<int32_t>>();
     d->work_tid = std::make_shared<std::vector<int32_t>>();
-    if (knobs().frame_batch > 0) d->batch_max = std::min(knobs().frame_batch, kMaxBatch);
-    if (knobs().batch_queue > 0) d->keep_queued = knobs().batch_queue;
-    if (knobs().launch_slack_us > 0) d->launch_slack_ms = knobs().launch_slack_us * 1e-3f;
+    if (knobs().frame_batch > 0) d->launch.batch_max = std::min(knobs().frame_batch, kMaxBatch);
+    if (knobs().batch_queue > 0) d->launch.keep_queued = knobs().batch_queue;
+    if (knobs().launch_slack_us > 0) d->launch.launch_slack_ms = knobs().launch_slack_us * 1e-3f;
+    d->launch.first_batch = knobs().first_batch;
     if (const char* ac = getenv("LM_ASYNC_COLLECT")) d->async_collect = ac[0] && ac[0] != '0';
     if (const char* ht = getenv("LM_HOST_THREADS")) d->pool.threads = std::max(0, std::min(8, atoi(ht)));
     if (const char* tl = getenv("LM_TILES")) d->use_tiles = tl[0] && tl[0] != '0';
@@ -434,11 +436,11 @@ extern "C" int lm_detector_set_batch(lm_detector* d, int frames) {
     if (frames < 1 || frames > kMaxBatch) return lm_set_error(LM_ERR_INVALID, "frames per launch must be in [1, %d]", kMaxBatch);
     int rc = lm_launch_pending(d);
     if (rc) return rc;
-    d->batch_max = frames;
+    d->launch.batch_max = frames;
     return LM_OK;
 }
 
-extern "C" int lm_detector_get_batch(const lm_detector* d) { return d ? d->batch_max : 0; }
+extern "C" int lm_detector_get_batch(const lm_detector* d) { return d ? d->launch.batch_max : 0; }
 
 extern "C" int lm_detector_host_profile(lm_detector* d, double* out8, int reset) {
     if (!d || !out8) return lm_set_error(LM_ERR_INVALID, "null argument");
@@ -455,7 +457,7 @@ extern "C" int lm_detector_set_async_collect(lm_detector* d, int on) {
 extern "C" int lm_detector_set_batch_queue(lm_detector* d, int batches) {
     if (!d) return lm_set_error(LM_ERR_INVALID, "null detector");
     if (batches < 0 || batches > lm_detector::kSlots) return lm_set_error(LM_ERR_INVALID, "batches queued on the GPU must be in [0, %d]", lm_detector::kSlots);
-    d->keep_queued = batches;
+    d->launch.keep_queued = batches;
     return LM_OK;
 }
 

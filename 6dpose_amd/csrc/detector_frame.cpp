@@ -1,6 +1,6 @@
 // The detector's frame: geometry and arenas, the blocking upload, frames parked in HBM, the front end of the training views
 // and the stage read-back of the tests (lm_detector_read_stage).  The front end of the matching path is run_frontend_batch
-// (detector_stream.cpp).
+// (detector_frontend.cpp).
 #include <string.h>
 
 #include "detector_internal.h"
@@ -83,7 +83,7 @@ int setup_geometry(lm_detector* d, int W, int H, bool check_match_preconditions)
             if ((rc = d->bits_arena[a].ensure(bbytes))) return rc;
             if (realloc_bits || d->fW != W || d->fH != H) HIP_TRY(hipMemsetAsync(d->bits_arena[a].p, 0, d->bits_arena[a].cap, d->stream));
         }
-        // the second set of the wide paths follows the first where a wide match has allocated it (detector_stream.cpp, ensure_wide_arenas)
+        // the second set of the wide paths follows the first where a wide match has allocated it (detector_launch.cpp, ensure_wide_arenas)
         for (DevBuf<uint8_t>* w : {&d->wbits_arena[a], &d->wcbits_arena[a]}) {
             if (!w->cap) continue;
             const size_t bytes = w == &d->wbits_arena[a] ? d->bits_arena[a].cap : d->cbits_arena[a].cap;

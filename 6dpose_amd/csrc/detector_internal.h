@@ -1,5 +1,6 @@
 // Private view of the detector shared by the detector's translation units (detector.cpp, detector_frame.cpp, detector_bank.cpp,
-// detector_stream.cpp, detector_slabs.cpp, detector_scaled.cpp, host_pool.cpp, match_lists.cpp), bank_file.cpp, comm.cpp, exchange.cpp and pipeline.cpp (not part of the C ABI).
+// detector_frontend.cpp, detector_launch.cpp, detector_collect.cpp, detector_ingest.cpp, detector_slabs.cpp, detector_scaled.cpp, host_pool.cpp,
+// match_lists.cpp), bank_file.cpp, comm.cpp, exchange.cpp and pipeline.cpp (not part of the C ABI).
 #pragma once
 #include <algorithm>
 #include <atomic>
@@ -19,6 +20,7 @@
 #include "frame_border.h"
 #include "host_templates.h"
 #include "knobs.h"
+#include "launch_model.h"
 #include "lm_kernels.h"
 #include "scaled_kernels.h"
 
@@ -285,33 +287,11 @@ struct lm_detector {
     bool cbits_clean[kSlots] = {};                  // the slot's pair stream is all zero (what the front end's OR-ing writer needs)
     uint64_t n_submitted = 0, n_collected = 0, n_launched = 0;
     // frames submitted but not launched yet: slots pend_first .. pend_first + pend_n - 1 (modulo kSlots), same threshold and work list
-    int batch_max = 8;                              // frames per launch in stream mode (lm_detector_set_batch, LM_FRAME_BATCH; <= kMaxBatch).  8 since round 4: 0.074 against 0.089 ms per frame over 200 steps, the same at 20 (profiles/r04_stream_ab.txt)
     int pend_first = 0, pend_n = 0;
     float pend_threshold = 0.f;
-    // Launched batches the GPU may still be working on, oldest first.  When does a streamed frame that does not fill its batch go
-    // out?  The GPU must never wait for a batch to fill, and a batch launched early is a small one (a lone frame costs ~2.5x its
-    // share of a batch of four).  The detector therefore keeps an estimate of when the GPU will have finished what it was given
-    // (`gpu_free_at`: launch times + the measured duration of batches of each size, corrected whenever a collect sees a batch
-    // finish) and launches a partial batch when that moment is closer than `launch_slack_ms` — the enqueue latency of a batch —
-    // either at a submit or just before a collect blocks.  Without a measured duration yet the rule is the backlog in batches:
-    // launch while fewer than `keep_queued` are unfinished.  keep_queued = 0 switches both off (batches of exactly batch_max frames;
-    // flush / collect launch what is left).
-    struct QueuedBatch {
-        uint64_t first_frame;                       // index of the batch's first frame
-        int slot, frames;                           // its leader slot, its size
-        double launched_at;                         // host clock (seconds, steady_clock)
-        bool gpu_idle_at_launch;                    // nothing unfinished before it: it started when it was launched
-    };
-    std::vector<QueuedBatch> queued;
-    int keep_queued = 2;                            // LM_BATCH_QUEUE
-    float batch_ms[kMaxBatch + 1] = {};             // measured GPU time of a batch of n frames (moving average); 0 = not seen yet
-    double gpu_free_at = 0.0;                       // estimate, host clock
-    double last_done_at = -1.0;                     // when the most recently collected batch finished, if a collect saw it happen (-1: unknown)
-    uint64_t last_done_end = 0;                     // index of the frame after that batch
-    float launch_slack_ms = 0.15f;                  // LM_LAUNCH_SLACK_US
-    double last_submit_at = 0.0;                    // lm_detector_submit_frame: host clock of the previous call,
-    float submit_gap_ms = 0.f;                      // moving average of the gap between calls (0 = no second call yet: treated as sparse),
-    float launch_cost_ms = 0.1f;                    // and of the host time one lm_launch_pending takes
+    // When a streamed frame that does not fill its batch goes out (launch_model.h): the queue of launched batches, the clocks and moving
+    // averages, and the knobs batch_max (lm_detector_set_batch), keep_queued (lm_detector_set_batch_queue), first_batch and launch_slack_ms.
+    LaunchModel launch;
     // Helper threads of the streamed path (one pool per detector, started with the first job; LM_HOST_THREADS, default 3, 0 = none).  They
     // never call into the HIP runtime — a second thread inside the runtime made every HIP call of the calling thread take ~0.1 ms (round 3:
     // the collector thread that waited on events) — and do two things:
@@ -334,7 +314,6 @@ struct lm_detector {
     // [3] slot bookkeeping, [4] batch launches, [5] collect: waiting for the GPU, [6] record conversion, [7] canonical sort + unique
     double host_prof[8] = {};
     uint64_t ncand_hint = 0;                        // coarse candidates of the last collected frame: sizes k_dedupe's grid
-    bool early_batch_used = false;                  // the burst's one early (partial) batch of a tight stream has gone out (partial_batch_due)
     bool async_collect = true;                      // lm_detector_set_async_collect / LM_ASYNC_COLLECT=0: the lists of a batch's later frames are prepared by the helper threads
 
     // Live-stream ingest (lm_detector_submit_frame): one ring entry per result slot.  The host frame is staged in the entry's
@@ -401,13 +380,40 @@ int upload_bank(lm_detector* d);
 int lm_parts_refused(const lm_detector* d, const char* what);   // LM_OK while part matching is off, else LM_ERR_INVALID "<what> is not available under part matching"
 int build_work(lm_detector* d, const char* const* class_ids, int num_class_ids);
 
-// detector_stream.cpp
-int lm_submit_frame(lm_detector* d, float threshold, const char* const* class_ids, int num_class_ids);
-int lm_collect_frame(lm_detector* d, int sort_unique, lm_match** out, size_t* n_out);   // sort_unique < 0: discard the records
-int lm_launch_pending(lm_detector* d);                                                  // launches the frames waiting for their batch to fill
+// What the units of the streamed path share among themselves (hidden: the library's dynamic symbols stay what they were).
+#pragma GCC visibility push(hidden)
+// detector_frontend.cpp.  stages: bit 0 = quantise, bit 1 = the response memories (a slab pass of lm_detector_match_slabs runs 2 alone: the maps do not depend on masks).
+enum { kFeQuantise = 1, kFeMemories = 2 };
+int run_frontend_batch(lm_detector* d, int first, int nb, hipStream_t s, bool direct_low, bool direct_top, int stages = kFeQuantise | kFeMemories);
+int lm_need_resident(const lm_detector* d, bool nothing_in_flight);                     // LM_OK, or LM_ERR_INVALID "no frame resident ..." / "frames in flight: collect them first"
+// detector_launch.cpp
+int slot_begin(lm_detector* d, float threshold, const char* const* class_ids, int num_class_ids, const uint8_t* rgb, const uint16_t* depth,
+               const bool have_mask[2], int ring);                                      // the next result slot for a frame; nothing is launched
+#pragma GCC visibility pop
+
+// detector_frontend.cpp
 int lm_quantise_resident(lm_detector* d);                                               // the quantising stages of the resident frame alone, on `stream` (depth slabs)
 // the whole front end of the resident frame with BYTE linear memories at every level, on `stream`; *arena = the set written (depth-scaled matching)
 int lm_byte_memories_resident(lm_detector* d, int* arena);
+
+// detector_launch.cpp
+int lm_submit_frame(lm_detector* d, float threshold, const char* const* class_ids, int num_class_ids);
+int lm_launch_pending(lm_detector* d);                                                  // launches the frames waiting for their batch to fill
+
+// detector_collect.cpp
+int lm_collect_frame(lm_detector* d, int sort_unique, lm_match** out, size_t* n_out);   // sort_unique < 0: discard the records
+
+// The host clock of the streamed path (steady_clock): seconds from a to b, and seconds since the clock's epoch — what the launch-timing model counts in.
+static inline double seconds_between(std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double>(b - a).count(); }
+static inline double host_seconds(std::chrono::steady_clock::time_point t) { return seconds_between({}, t); }
+
+// What the launch-timing model asks of the GPU (launch_model.h): has the batch launched from leader slot `slot` finished?
+struct BatchEvents {
+    lm_detector* d;
+    bool finished(int slot) const { return hipEventQuery(d->slot[slot].done) == hipSuccess; }
+    void queries_end() const { (void)hipGetLastError(); }                               // hipErrorNotReady is not an error
+};
+static_assert(LaunchModel::kMaxFrames == kMaxBatch, "the launch-timing model keeps a measured time per batch size");
 
 // host_pool.cpp: the helper threads of the streamed path (HostPool above) and the staging copy they share with the caller
 bool pool_ready(lm_detector* d);
@@ -429,6 +435,19 @@ lm_match* reference_order_list(const Candidate* recs, const Candidate* coarse, u
 #ifdef LM_DIAG
 #include <stdio.h>
 #include <stdlib.h>
+struct LaunchClock {                                          // LM_LAUNCH_PROF: host time of the steps of a batch launch and of individual HIP calls in them; LM_LAUNCH_SERIES: the first 80 of each, one by one
+    const char* name; double t0;
+    static double now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+    explicit LaunchClock(const char* n) : name(n), t0(now()) {}
+    ~LaunchClock() {
+        static std::map<std::string, std::pair<double, long>> acc;
+        const double dt = now() - t0;
+        auto& a = acc[name]; a.first += dt; ++a.second;
+        if (getenv("LM_LAUNCH_SERIES") && a.second <= 80) fprintf(stderr, "  %s #%ld: %.0f us\n", name, a.second, 1e6 * dt);
+        if (getenv("LM_LAUNCH_PROF") && a.second % 64 == 0) fprintf(stderr, "  call %-22s %.1f us (n=%ld)\n", name, 1e6 * a.first / a.second, a.second);
+    }
+};
+#define LM_CLOCK(n) LaunchClock lm_clock_##__LINE__(n)
 #define LM_DIAG_IDLE(d, what)                                                                                                    \
     do {                                                                                                                         \
         if ((d)->n_launched != (d)->n_collected) {                                                                               \
@@ -438,5 +457,6 @@ lm_match* reference_order_list(const Candidate* recs, const Candidate* coarse, u
         }                                                                                                                        \
     } while (0)
 #else
+#define LM_CLOCK(n)
 #define LM_DIAG_IDLE(d, what) do { } while (0)
 #endif

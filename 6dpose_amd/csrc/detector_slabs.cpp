@@ -1,7 +1,7 @@
 // Depth slabs (the reference's "use depth histogram and 1D nms to find some primary scales", linemodLevelup/readme.md:29-34):
 // the primary depths of the resident frame (lm_detector_depth_modes), the depth range a class's templates are valid at
 // (lm_detector_set_class_depth_range) and the match that runs every class under the slabs of the primary depths inside its range
-// (lm_detector_match_slabs).  Kernels: depth_modes.hip; the passes are ordinary lone frames of detector_stream.cpp.
+// (lm_detector_match_slabs).  Kernels: depth_modes.hip; the passes are ordinary lone frames of detector_launch.cpp.
 #include <stdlib.h>
 #include <string.h>
 

@@ -123,7 +123,7 @@ constexpr unsigned long long kCandMask = (1ull << kCandBits) - 1ull;
 // A 2k-template shard does not fill the chip: k_coarse runs at twice, k_local at 1.3x the per-unit cost they reach on a 16k bank
 // (launch / drain latency, one partial wave of workgroups).  In stream mode the matching kernels therefore serve a BATCH of up
 // to kMaxBatch consecutive frames per launch: every frame of the batch owns its arenas, candidate / record buffers, counters and
-// hash table (the per-slot buffers of detector_stream.cpp), the kernels index them by blockIdx.y (k_coarse, k_dedupe) or through the
+// hash table (the per-slot buffers of detector_launch.cpp), the kernels index them by blockIdx.y (k_coarse, k_dedupe) or through the
 // flat work-item index (k_local).  A lone frame is a batch of one.
 constexpr int kMaxBatch = 8;
 constexpr int kCounterWords = 64;             // working counters per result slot: [0] candidates | tiles << kCandBits (k_coarse), [1] distinct,

@@ -295,6 +295,23 @@ def test_nms_norms_and_nmsboxes_equal_the_oracle(lib):
     assert mod.NMSBoxes(rects, np.array([90, 95, 80, 85], np.float32), 0.0, 0.4) == [1, 3, 2]   # by score: 95 kept, 90 overlaps it (IoU 0.78), 85 and 80 kept
 
 
+def test_launch_model_decides_as_stated(tmp_path):
+    """tests/cpp/launch_model_cases.cpp: the launch-timing model of the streamed path (csrc/launch_model.h) alone, under ASan + UBSan, with a
+    table in place of the GPU: the estimate of a batch's time, the moving averages of the submit gap and the launch cost with their clamps,
+    when a partial batch is due (never / sparse / tight, the one early batch per burst, and that the GPU is asked only where the answer is
+    needed), the bookkeeping of a launch and of a collect's wait.  Host code, no GPU."""
+    import shutil
+    cxx = shutil.which("c++") or shutil.which("g++") or shutil.which("clang++")
+    assert cxx, "no host C++ compiler"
+    exe = str(tmp_path / "launch_model_cases")
+    cmd = [cxx, "-std=c++17", "-g", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+           "-I" + os.path.join(ROOT, "6dpose_amd", "csrc"), os.path.join(ROOT, "tests", "cpp", "launch_model_cases.cpp"), "-o", exe]
+    if subprocess.call(cmd + ["-static-libasan", "-static-libubsan"], stderr=subprocess.DEVNULL) != 0:   # gcc: the runtimes inside the program
+        subprocess.check_call(cmd)
+    out = subprocess.run([exe], capture_output=True, text=True, timeout=60)
+    assert out.returncode == 0 and out.stdout.strip().endswith("ok"), out.stdout + out.stderr
+
+
 def test_magic_division_with_one_correction_is_exact():
     """fe_device.h fast_div: q = umulhi(n, ceil(2^32 / d)) is floor(n / d) or one more for EVERY 32-bit n (the excess n e / (d 2^32) with
     e = m d - 2^32 < d stays below 1), so `q - (q d > n)` is exact — also where n d passes 2^32 (8000 x 6000 frames: ADVICE r03; the bare

@@ -177,8 +177,7 @@ static int exchange_collect(lm_detector* d, lm_match* dst, size_t dst_capacity, 
     if (rc == 1 && !(flags & kXchgCandOverflow))
         return lm_set_error(LM_ERR_HIP, "candidate overflow seen by the host but not by the exchange");
     if (flags) {                                                                     // every rank reads the same flags: all fall back together
-        int need = 0;
-        for (int j = 0; j < h[2] && j < kXchgHeaderWords - 8; ++j) need = std::max(need, h[8 + j]);
+        const int need = h[4];                                                       // the largest count of ALL ranks (the header lists only the first 248)
         *failed = (flags & kXchgRunOverflow) ? std::max(need, 1) : -(int)flags;
         return LM_OK;
     }

@@ -164,27 +164,28 @@ k_exchange_merge256(XchgGroup G, uint32_t cand_cap, uint32_t cap) {
 __global__ void __launch_bounds__(kWG)
 k_exchange_merge(XchgGroup G, int W, uint32_t cap, uint32_t block_words) {
     __shared__ RankLds L;
-    __shared__ uint32_t s_or, s_total;
+    __shared__ uint32_t s_or, s_total, s_max;
     const uint32_t* __restrict__ blocks = G.f[blockIdx.z].recv;           // grid (chunks, ranks, frames of the group)
     int32_t* __restrict__ merged = G.f[blockIdx.z].merged;
     const int self = blockIdx.y;
     const uint32_t b = blockIdx.x;
-    if (threadIdx.x == 0) { s_or = 0; s_total = 0; }
+    if (threadIdx.x == 0) { s_or = 0; s_total = 0; s_max = 0; }
     __syncthreads();
     {
-        uint32_t f = 0, cnt = 0;
+        uint32_t f = 0, cnt = 0, big = 0;
         for (int j = threadIdx.x; j < W; j += kWG) {
             const uint32_t* h = blocks + (size_t)j * block_words;
             f |= h[1] | (h[2] != cap ? kXchgRunOverflow : 0u);
             cnt += h[0];
+            big = max(big, h[0]);
         }
         if (f) atomicOr(&s_or, f);
-        if (cnt) atomicAdd(&s_total, cnt);
+        if (cnt) { atomicAdd(&s_total, cnt); atomicMax(&s_max, big); }
     }
     __syncthreads();
     const uint32_t flags = s_or;
     if (b == 0 && self == 0) {
-        if (threadIdx.x == 0) { merged[0] = flags ? 0 : (int32_t)s_total; merged[1] = (int32_t)flags; merged[2] = W; merged[3] = (int32_t)cap; }
+        if (threadIdx.x == 0) { merged[0] = flags ? 0 : (int32_t)s_total; merged[1] = (int32_t)flags; merged[2] = W; merged[3] = (int32_t)cap; merged[4] = (int32_t)s_max; }
         for (int j = threadIdx.x; j < W && j < kXchgHeaderWords - 8; j += kWG) merged[8 + j] = (int32_t)blocks[(size_t)j * block_words];
     }
     if (flags) return;

@@ -27,10 +27,9 @@ def visib_mask(d_test, d_model, delta):
     return (diff <= np.float32(delta)) & valid
 
 
-def vsd_counts(depth_est, depth_gt, depth_test, K, delta, tau):
-    """The quantities behind pose_error.vsd (pose_error.py:41-78): |union|, |inter|, the step cost count and the tlinear cost
-    sum over the intersection."""
-    dt, dg, de = dist_image(depth_test, K), dist_image(depth_gt, K), dist_image(depth_est, K)
+def vsd_counts_dist(dt, dg, de, delta, tau):
+    """vsd_counts on distance images already built (dist_image of the scene, the GT render and the estimate's render): the same
+    statements, so that a table of many pairs builds each pose's distance image once."""
     vg = visib_mask(dt, dg, delta)                                       # visibility.py:23-25
     ve = visib_mask(dt, de, delta) | (vg & (de > 0))                     # visibility.py:27-30
     inter, union = vg & ve, vg | ve
@@ -39,13 +38,24 @@ def vsd_counts(depth_est, depth_gt, depth_test, K, delta, tau):
             "tlinear": float(np.minimum(cost * (1.0 / tau), 1.0).sum())}
 
 
-def vsd(depth_est, depth_gt, depth_test, K, delta=15.0, tau=20.0, cost="step"):
-    """pose_error.vsd (pose_error.py:12-81) on given renders."""
-    c = vsd_counts(depth_est, depth_gt, depth_test, K, delta, tau)
+def vsd_counts(depth_est, depth_gt, depth_test, K, delta, tau):
+    """The quantities behind pose_error.vsd (pose_error.py:41-78): |union|, |inter|, the step cost count and the tlinear cost
+    sum over the intersection."""
+    return vsd_counts_dist(dist_image(depth_test, K), dist_image(depth_gt, K), dist_image(depth_est, K), delta, tau)
+
+
+def vsd_of_counts(c, cost="step"):
+    """pose_error.py:74-81: the mean of the costs over the union, the pixels outside the intersection counting 1; 1.0 for an
+    empty union."""
     if c["union"] == 0:
         return 1.0
     costs = c["step"] if cost == "step" else c["tlinear"]
     return (costs + (c["union"] - c["inter"])) / float(c["union"])
+
+
+def vsd(depth_est, depth_gt, depth_test, K, delta=15.0, tau=20.0, cost="step"):
+    """pose_error.vsd (pose_error.py:12-81) on given renders."""
+    return vsd_of_counts(vsd_counts(depth_est, depth_gt, depth_test, K, delta, tau), cost)
 
 
 def cou_counts(depth_est, depth_gt):

@@ -74,6 +74,25 @@ def errors(eR, et, gR, gt, K, pts, Rs, ts):
     return out
 
 
+def errors_batched(eR, et, gR, gt, K, pts, Rs, ts):
+    """errors() with the loop over the symmetries folded into array operations, for sets of thousands of transformations:
+    the same formulas, the products summed in numpy's order instead (differences of a few ulp, far below the tests' 1e-9)."""
+    pts = np.asarray(pts, np.float64)
+    Rs, ts = np.asarray(Rs, np.float64), np.asarray(ts, np.float64)
+    K = np.asarray(K, np.float64).reshape(3, 3)
+    sym = np.einsum("sij,vj->svi", Rs, pts) + ts[:, None, :]                 # (S, V, 3): R_s v + t_s
+    out = {"mssd": np.zeros((len(eR), len(gR))), "mspd": np.zeros((len(eR), len(gR)))}
+    for g in range(len(gR)):
+        pg = sym @ np.asarray(gR[g], np.float64).T + np.asarray(gt[g], np.float64).reshape(1, 1, 3)
+        wg = pg @ K.T
+        ug = wg[..., :2] / wg[..., 2:3]
+        for e in range(len(eR)):
+            pe = transform(eR[e], et[e], pts)
+            out["mssd"][e, g] = np.linalg.norm(pe[None] - pg, axis=2).max(1).min()
+            out["mspd"][e, g] = np.linalg.norm(project(K, pe)[None] - ug, axis=2).max(1).min()
+    return out
+
+
 def cube_rotations():
     """The 24 rotations of the cube: signed permutation matrices of determinant +1, the identity first."""
     out = []

@@ -1,4 +1,5 @@
-// lm_pso — pose refinement by particle swarm over rendered depth (kernels and the rule: pso.hip).
+// lm_pso — pose refinement by particle swarm over rendered depth (kernels and the rule: pso.hip), and over the
+// scene's edges for cameras without depth (§5.3.1; pso_edges.hip): the same swarm with k_pso_edge_cost in k_pso_cost's place.
 // A call enqueues, on the context's own stream, k_pso_init and then per generation k_pso_views, k_project, k_raster,
 // k_pso_cost and k_pso_step; nothing is read back before the copy of the results.  The swarm renders into scratch of its
 // own (projected vertices, z-buffer): the mesh is only read, so lm_mesh_render returns what it did before.
@@ -22,6 +23,12 @@ struct lm_pso {
     size_t cap_scene = 0;
     int W = 0, H = 0;
     double K[9] = {0};
+    // the edge scene (lm_pso_set_scene_edges): the map, its row distances g and the truncated squared distance D2; a frame and K of its own
+    uint8_t *d_edges = nullptr, *d_g = nullptr;
+    uint16_t* d_d2 = nullptr;
+    size_t cap_edges = 0, cap_g = 0, cap_d2 = 0;
+    int eW = 0, eH = 0, eM = 0;
+    double eK[9] = {0};
     // swarm state, render scratch and the record of the last run
     PsoHyp* d_hyp = nullptr;
     ViewParams* d_views = nullptr;
@@ -68,7 +75,7 @@ extern "C" void lm_pso_destroy(lm_pso* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     if (c->s) (void)hipStreamSynchronize(c->s);
-    void* p[] = {c->d_scene, c->d_hyp, c->d_views, c->d_pv, c->d_zbuf, c->st.x, c->st.v, c->st.pbest_x, c->st.pbest_cost, c->st.sum, c->st.n_r,
+    void* p[] = {c->d_scene, c->d_edges, c->d_g, c->d_d2, c->d_hyp, c->d_views, c->d_pv, c->d_zbuf, c->st.x, c->st.v, c->st.pbest_x, c->st.pbest_cost, c->st.sum, c->st.n_r,
                  c->st.best, c->st.rec_x, c->st.rec_cost, c->st.rec_sum, c->st.rec_nr, c->st.rec_best, c->st.result};
     for (void* q : p) if (q) (void)hipFree(q);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
@@ -102,8 +109,44 @@ extern "C" int lm_pso_set_scene(lm_pso* c, const uint16_t* scene_depth, int widt
     return LM_OK;
 }
 
-extern "C" int lm_pso_run(lm_pso* c, lm_mesh* mesh, int count, const double* Rs, const double* ts, const int32_t* windows_xy, int w, int h,
-                          const lm_pso_options* options, lm_pso_result* results, float* device_ms) {
+extern "C" int lm_pso_set_scene_edges(lm_pso* c, const uint8_t* edges, int width, int height, const double* K, int max_dist) {
+    if (!c || !edges || !K) return lm_set_error(LM_ERR_INVALID, "null argument");
+    if (width <= 0 || height <= 0 || width > 16384 || height > 16384) return lm_set_error(LM_ERR_INVALID, "unsupported frame size %dx%d", width, height);
+    if (max_dist < 1 || max_dist > 255) return lm_set_error(LM_ERR_INVALID, "max_dist must be in 1..255 (got %d)", max_dist);
+    for (int k = 0; k < 9; ++k)
+        if (!isfinite(K[k])) return lm_set_error(LM_ERR_INVALID, "K is not finite");
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->s));
+    const size_t n = (size_t)width * height;
+    c->eW = c->eH = 0;                                                    // until D2 stands
+    int rc;
+    if ((rc = ensure((void**)&c->d_edges, c->cap_edges, n))) return rc;
+    if ((rc = ensure((void**)&c->d_g, c->cap_g, n))) return rc;
+    if ((rc = ensure((void**)&c->d_d2, c->cap_d2, n * sizeof(uint16_t)))) return rc;
+    HIP_TRY(hipMemcpyAsync(c->d_edges, edges, n, hipMemcpyHostToDevice, c->s));
+    launch_edt(c->d_edges, width, height, max_dist, c->d_g, c->d_d2, c->s);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(c->s));                                  // `edges` is the caller's again
+    c->eW = width; c->eH = height; c->eM = max_dist;
+    memcpy(c->eK, K, sizeof(c->eK));
+    return LM_OK;
+}
+
+extern "C" int64_t lm_pso_read_edge_distance(lm_pso* c, uint16_t* dst, int64_t capacity) {
+    if (!c) return lm_set_error(LM_ERR_INVALID, "null argument");
+    if (c->eW <= 0) return lm_set_error(LM_ERR_INVALID, "no scene edges set (lm_pso_set_scene_edges)");
+    const int64_t size = (int64_t)c->eW * c->eH;
+    if (!dst || capacity <= 0) return size;
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipMemcpy(dst, c->d_d2, (size_t)std::min<int64_t>(capacity, size) * sizeof(uint16_t), hipMemcpyDeviceToHost));
+    return size;
+}
+
+// The body of lm_pso_run and lm_pso_run_edges.  edge_step < 0: the depth cost against the scene depth; >= 0: the edge cost against D2
+// with that edge_step_mm, tau in pixels, the frame and K of the edge scene.
+static int run_swarm(lm_pso* c, lm_mesh* mesh, int count, const double* Rs, const double* ts, const int32_t* windows_xy, int w, int h,
+                     const lm_pso_options* options, int edge_step, lm_pso_result* results, float* device_ms) {
+    const bool edges = edge_step >= 0;
     if (!c || !mesh || !Rs || !ts || !windows_xy || !results) return lm_set_error(LM_ERR_INVALID, "null argument");
     lm_pso_options o;
     if (options) {
@@ -124,7 +167,9 @@ extern "C" int lm_pso_run(lm_pso* c, lm_mesh* mesh, int count, const double* Rs,
     if (!isfinite(o.clip_near) || !isfinite(o.clip_far)) return lm_set_error(LM_ERR_INVALID, "the clip planes must be finite");
     if (mesh->nf <= 0 || mesh->nv <= 0) return lm_set_error(LM_ERR_INVALID, "the mesh has no faces");
     if (mesh->device != c->device) return lm_set_error(LM_ERR_INVALID, "the mesh lives on device %d, the context on %d", mesh->device, c->device);
-    if (!c->d_scene || c->W <= 0) return lm_set_error(LM_ERR_INVALID, "no scene depth set (lm_pso_set_scene)");
+    if (!edges && (!c->d_scene || c->W <= 0)) return lm_set_error(LM_ERR_INVALID, "no scene depth set (lm_pso_set_scene)");
+    if (edges && c->eW <= 0) return lm_set_error(LM_ERR_INVALID, "no scene edges set (lm_pso_set_scene_edges)");
+    if (edges && o.tau > c->eM) return lm_set_error(LM_ERR_INVALID, "tau must be <= max_dist for the edge cost (got %d > %d)", o.tau, c->eM);
     for (size_t k = 0; k < (size_t)count * 9; ++k)
         if (!isfinite(Rs[k])) return lm_set_error(LM_ERR_INVALID, "a hypothesis' R is not finite");
     for (size_t k = 0; k < (size_t)count * 3; ++k)
@@ -135,12 +180,12 @@ extern "C" int lm_pso_run(lm_pso* c, lm_mesh* mesh, int count, const double* Rs,
     HIP_TRY(hipStreamSynchronize(c->s));                                  // h_hyp / h_res of an earlier call that failed half way
 
     PsoParams prm{};
-    memcpy(prm.K, c->K, sizeof(prm.K));
+    memcpy(prm.K, edges ? c->eK : c->K, sizeof(prm.K));
     for (int d = 0; d < 3; ++d) { prm.range[d] = o.trans_range_mm; prm.range[3 + d] = o.rot_range; }
     prm.inertia = o.inertia; prm.c1 = o.c1; prm.c2 = o.c2; prm.seed = o.seed;
     prm.G = o.generations;
     prm.P = prm.G == 0 ? 1 : o.particles;                                 // evaluate-only: the given pose alone
-    prm.w = w; prm.h = h; prm.W = c->W; prm.H = c->H; prm.tau = o.tau; prm.cover_pixels = o.cover_pixels;
+    prm.w = w; prm.h = h; prm.W = edges ? c->eW : c->W; prm.H = edges ? c->eH : c->H; prm.tau = o.tau; prm.cover_pixels = o.cover_pixels;
     const int H = count, P = prm.P, G = prm.G;
     const size_t HP = (size_t)H * P, npx = (size_t)w * h, gen = (size_t)G + 1;
 
@@ -180,7 +225,8 @@ extern "C" int lm_pso_run(lm_pso* c, lm_mesh* mesh, int count, const double* Rs,
         launch_pso_views(prm, H, c->d_hyp, st.x, c->d_views, c->s);
         launch_project(M, c->d_views, (int)HP, 1, c->d_pv, c->s);
         launch_raster(M, c->d_pv, (int)HP, w, h, o.clip_near, o.clip_far, c->d_zbuf, c->s);
-        launch_pso_cost(prm, H, c->d_hyp, c->d_zbuf, c->d_scene, st.sum, st.n_r, c->s);
+        if (edges) launch_pso_edge_cost(prm, H, edge_step, c->d_hyp, c->d_zbuf, c->d_d2, st.sum, st.n_r, c->s);
+        else launch_pso_cost(prm, H, c->d_hyp, c->d_zbuf, c->d_scene, st.sum, st.n_r, c->s);
         launch_pso_step(prm, H, g, c->d_hyp, st, c->s);
     }
     HIP_TRY(hipGetLastError());
@@ -198,6 +244,17 @@ extern "C" int lm_pso_run(lm_pso* c, lm_mesh* mesh, int count, const double* Rs,
     }
     c->last_H = H; c->last_P = P; c->last_G = G;
     return LM_OK;
+}
+
+extern "C" int lm_pso_run(lm_pso* c, lm_mesh* mesh, int count, const double* Rs, const double* ts, const int32_t* windows_xy, int w, int h,
+                          const lm_pso_options* options, lm_pso_result* results, float* device_ms) {
+    return run_swarm(c, mesh, count, Rs, ts, windows_xy, w, h, options, -1, results, device_ms);
+}
+
+extern "C" int lm_pso_run_edges(lm_pso* c, lm_mesh* mesh, int count, const double* Rs, const double* ts, const int32_t* windows_xy, int w, int h,
+                                const lm_pso_options* options, int edge_step_mm, lm_pso_result* results, float* device_ms) {
+    if (edge_step_mm < 0 || edge_step_mm > 65535) return lm_set_error(LM_ERR_INVALID, "edge_step_mm must be in 0..65535 (got %d)", edge_step_mm);
+    return run_swarm(c, mesh, count, Rs, ts, windows_xy, w, h, options, edge_step_mm, results, device_ms);
 }
 
 extern "C" int64_t lm_pso_read_debug(lm_pso* c, int hypothesis, int kind, double* dst, int64_t capacity) {

@@ -52,4 +52,10 @@ void launch_pso_cost(const PsoParams& p, int H, const PsoHyp* hyp, const unsigne
                      unsigned long long* sum, unsigned int* n_r, hipStream_t s);
 void launch_pso_step(const PsoParams& p, int H, int g, const PsoHyp* hyp, const PsoState& st, hipStream_t s);
 
+// pso_edges.hip: the edge cost.  launch_edt: k_edt_rows (edges -> g, uint8) and k_edt_cols (g -> d2, uint16), 1 <= M <= 255.
+// launch_pso_edge_cost: p.W, p.H are the edge frame's, p.tau is in pixels (<= M); it writes what launch_pso_cost writes.
+void launch_edt(const uint8_t* edges, int W, int H, int M, uint8_t* g, uint16_t* d2, hipStream_t s);
+void launch_pso_edge_cost(const PsoParams& p, int H, int edge_step, const PsoHyp* hyp, const unsigned long long* zbuf, const uint16_t* d2,
+                          unsigned long long* sum, unsigned int* n_r, hipStream_t s);
+
 }  // namespace lm

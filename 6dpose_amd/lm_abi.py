@@ -283,6 +283,9 @@ PROTOTYPES = {
     "lm_pso_set_scene": (I, [P, P, I, I, P]),
     "lm_pso_run": (I, [P, P, I, P, P, P, I, I, PPSOO, ctypes.POINTER(_CPsoResult), ctypes.POINTER(F)]),
     "lm_pso_read_debug": (I64, [P, I, I, P, I64]),
+    "lm_pso_set_scene_edges": (I, [P, P, I, I, P, I]),
+    "lm_pso_read_edge_distance": (I64, [P, P, I64]),
+    "lm_pso_run_edges": (I, [P, P, I, P, P, P, I, I, PPSOO, I, ctypes.POINTER(_CPsoResult), ctypes.POINTER(F)]),
 }
 
 

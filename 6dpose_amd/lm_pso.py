@@ -1,6 +1,7 @@
 """Pose refinement by particle swarm over rendered depth (lm_pso_*): the refiner the reference's author left as a todo
 (linemodLevelup/readme.md:41-46).  Correspondence-free, so it needs neither a start inside ICP's correspondence radius nor the
-depth rendering of the matched template view: a Mesh, the scene depth and the hypotheses are enough."""
+depth rendering of the matched template view: a Mesh, the scene depth and the hypotheses are enough.  For a camera without depth the
+same swarm scores the rendered contour against the scene's edges instead (set_scene_edges, run(cost="edges"), pso_refine_edges)."""
 from __future__ import annotations
 
 import ctypes
@@ -63,14 +64,15 @@ def derive_windows(K, ts, radius_mm, window_size=None):
 
 class PsoContext:
     """lm_pso (include/amd_linemod.h): set_scene(depth, K) once per frame, then run(mesh, Rs, ts, windows, window_size, **options) any
-    number of times.  run returns (list of dict(R, t, cost, initial_cost, n_rendered, n_initial, best_particle, best_generation),
+    number of times; set_scene_edges(edges, K) and run(..., cost="edges") score against an edge map instead, and a context may hold
+    both scenes.  run returns (list of dict(R, t, cost, initial_cost, n_rendered, n_initial, best_particle, best_generation),
     device_ms); options: see pso_options."""
 
     def __init__(self, device: int = 0):
         self._lib = load_library()
         self._h = ctypes.c_void_p()
         _check(self._lib.lm_pso_create(int(device), ctypes.byref(self._h)))
-        self.K = None
+        self.K = self.edge_K = None
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
@@ -85,22 +87,70 @@ class PsoContext:
         _check(self._lib.lm_pso_set_scene(self._h, _ptr(sd), sd.shape[1], sd.shape[0], _ptr(K)))
         self.K, self.shape = K.reshape(3, 3), sd.shape
 
+    def set_scene_edges(self, edges, K, max_dist=32):
+        """The edge scene of run(cost="edges"): a uint8 or bool H x W array (an edge where it is not 0) and its camera.  Computes the
+        squared distance to the nearest edge, truncated at max_dist pixels (1..255), once; independent of set_scene's depth."""
+        e = np.asarray(edges)
+        if e.dtype not in (np.uint8, np.bool_) or e.ndim != 2 or e.size == 0:
+            raise RuntimeError("edges must be a uint8 or bool HxW edge map (got %s %s)" % (e.dtype, e.shape))
+        if int(max_dist) != max_dist or not -2 ** 31 <= int(max_dist) < 2 ** 31:
+            raise RuntimeError("max_dist must be an integer in 1..255 (got %r)" % (max_dist,))
+        e = np.ascontiguousarray(e).view(np.uint8)
+        K = np.ascontiguousarray(np.asarray(K, np.float64).reshape(9))
+        self.edge_K = None
+        _check(self._lib.lm_pso_set_scene_edges(self._h, _ptr(e), e.shape[1], e.shape[0], _ptr(K), int(max_dist)))
+        self.edge_K, self.edge_shape = K.reshape(3, 3), e.shape
+
+    def set_scene_from_detector(self, det, K, size, level=0, max_dist=32):
+        """set_scene_edges with LINE-MOD's own edge pixels of the detector's last front end run: det.readStage(level, 0) != 0, i.e. the
+        colour gradients that survived blur, Sobel, the strongest channel and the hysteresis vote, the very pixels the templates were
+        matched on.  size: (width, height) of the source frame of that run (the detector does not report it); the map has
+        det.alignedSize(width, height) >> level, and K is the camera of that pyramid level.  The map makes a host round trip of one
+        byte per pixel (device -> host in readStage, host -> device here)."""
+        w, h = (int(v) >> int(level) for v in det.alignedSize(int(size[0]), int(size[1])))
+        q = det.readStage(int(level), 0)
+        if q.size != w * h:
+            raise RuntimeError("the detector's stage has %d pixels, a %dx%d frame has %dx%d at level %d" % (q.size, size[0], size[1], w, h, level))
+        self.set_scene_edges((q != 0).reshape(h, w), K, max_dist)
+
+    def edge_distance(self) -> np.ndarray:
+        """The uint16 H x W truncated squared distance set_scene_edges computed (tests)."""
+        n = self._lib.lm_pso_read_edge_distance(self._h, None, 0)
+        if n < 0:
+            _check(int(n))
+        out = np.zeros(self.edge_shape, np.uint16)
+        assert out.size == n
+        self._lib.lm_pso_read_edge_distance(self._h, _ptr(out), int(n))
+        return out
+
     def run(self, mesh: Mesh, Rs, ts, windows=None, window_size=None, **options):
+        """cost="depth" (the default) scores against set_scene's depth; cost="edges" against set_scene_edges' map, tau in pixels
+        (<= max_dist), with edge_step_mm (0..65535; 0 = the silhouette only) the depth jump of the rendered model that counts as a
+        contour.  The other keywords: pso_options."""
+        cost, edge_step_mm = options.pop("cost", "depth"), options.pop("edge_step_mm", 0)
+        if cost not in ("depth", "edges"):
+            raise RuntimeError("cost must be 'depth' or 'edges' (got %r)" % (cost,))
+        if int(edge_step_mm) != edge_step_mm or not 0 <= int(edge_step_mm) <= 65535:
+            raise RuntimeError("edge_step_mm must be an integer in 0..65535 (got %r)" % (edge_step_mm,))
+        scene_K = self.edge_K if cost == "edges" else self.K
         opts = pso_options(**options)
         Rs = np.ascontiguousarray(np.asarray(Rs, np.float64).reshape(-1, 9))
         n = len(Rs)
         ts = np.ascontiguousarray(np.asarray(ts, np.float64).reshape(n, 3))
         if windows is None:
-            if self.K is None:
-                raise RuntimeError("no scene depth set (set_scene)")
-            windows, window_size = derive_windows(self.K, ts, mesh.diameter() / 2.0 + opts.trans_range_mm, window_size)
+            if scene_K is None:
+                raise RuntimeError("no scene edges set (set_scene_edges)" if cost == "edges" else "no scene depth set (set_scene)")
+            windows, window_size = derive_windows(scene_K, ts, mesh.diameter() / 2.0 + opts.trans_range_mm, window_size)
         elif window_size is None:
             raise RuntimeError("windows need a window_size")
         xy = np.ascontiguousarray(np.asarray(windows, np.int32).reshape(n, 2))
         res = (_CPsoResult * max(n, 1))()
         ms = ctypes.c_float()
-        _check(self._lib.lm_pso_run(self._h, mesh._h, n, _ptr(Rs), _ptr(ts), _ptr(xy), int(window_size[0]), int(window_size[1]), ctypes.byref(opts),
-                                    res, ctypes.byref(ms)))
+        head = (self._h, mesh._h, n, _ptr(Rs), _ptr(ts), _ptr(xy), int(window_size[0]), int(window_size[1]), ctypes.byref(opts))
+        if cost == "edges":
+            _check(self._lib.lm_pso_run_edges(*head, int(edge_step_mm), res, ctypes.byref(ms)))
+        else:
+            _check(self._lib.lm_pso_run(*head, res, ctypes.byref(ms)))
         return [_result_dict(res[i]) for i in range(n)], float(ms.value)
 
     def read_debug(self, hypothesis: int, kind):
@@ -133,5 +183,16 @@ def pso_refine(mesh: Mesh, scene_depth, K, Rs, ts, windows=None, window_size=Non
     try:
         ctx.set_scene(scene_depth, K)
         return ctx.run(mesh, Rs, ts, windows, window_size, **options)
+    finally:
+        ctx.close()
+
+
+def pso_refine_edges(mesh: Mesh, edges, K, Rs, ts, windows=None, window_size=None, device: int = 0, max_dist=32, edge_step_mm=0, **options):
+    """pso_refine for a camera without depth: a context of its own, set_scene_edges(edges, K, max_dist), run(cost="edges").  tau is in
+    pixels here (<= max_dist); the cost is the mean squared distance in px^2 from the rendered contour to the nearest scene edge."""
+    ctx = PsoContext(device)
+    try:
+        ctx.set_scene_edges(edges, K, max_dist)
+        return ctx.run(mesh, Rs, ts, windows, window_size, cost="edges", edge_step_mm=edge_step_mm, **options)
     finally:
         ctx.close()

@@ -813,6 +813,26 @@ int lm_pso_run(lm_pso *c, lm_mesh *mesh, int count, const double *Rs, const doub
  * generation) of the global best after each generation [G + 1][2].  Integers are returned as doubles, doubles bit for bit.
  * Copies min(capacity, size) doubles, returns the size. */
 int64_t lm_pso_read_debug(lm_pso *c, int hypothesis, int kind, double *dst, int64_t capacity);
+/* ---- the same swarm scored against the scene's edges: for cameras without depth (chamfer cost) ---------------------------
+ * The scene is an edge map (uint8 [height][width], a pixel is an edge where it is not 0) with a camera K of its own.
+ * lm_pso_set_scene_edges uploads it and computes, once, D2 [height][width] uint16: the squared distance in pixels to the
+ * nearest edge pixel, truncated at max_dist (1..255; 32 is a sound default): D2 = min(max_dist^2, (x - x')^2 + (y - y')^2),
+ * max_dist^2 everywhere on a map without edges.  The edge scene and the depth scene of lm_pso_set_scene are independent:
+ * a context may hold either or both, of different sizes, and neither call disturbs the other. */
+int lm_pso_set_scene_edges(lm_pso *c, const uint8_t *edges, int width, int height, const double *K, int max_dist);
+/* Test/diagnostic read-back of D2.  Copies min(capacity, width x height) values, returns width x height. */
+int64_t lm_pso_read_edge_distance(lm_pso *c, uint16_t *dst, int64_t capacity);
+/* lm_pso_run with the edge cost; arguments, options, limits and the record for lm_pso_read_debug as there.  A pixel of a
+ * particle's rendered window is a contour pixel iff its depth r > 0 and one of its four neighbours n inside the window has
+ * n == 0 or, with edge_step_mm > 0, n - r > edge_step_mm (the near side of a depth jump of the model, so a self-occlusion
+ * edge counts once; 0 = the silhouette only).  Neighbours outside the window are ignored.  A contour pixel adds
+ * min(D2, tau^2) at its place in the frame, tau^2 outside the frame; options->tau is read as pixels, 1 <= tau <= max_dist.
+ * cost = sum / n_c (px^2) over the n_c contour pixels, under the same cover floor with contour counts: n_rendered and
+ * n_initial of the results are contour pixel counts, and kind 2 of lm_pso_read_debug is (sum, n_c).  The rule is stated in
+ * numpy by tests/pso_edges_ref.py and followed bit for bit.  LM_ERR_INVALID in addition: no edges set, tau > max_dist,
+ * edge_step_mm outside 0..65535. */
+int lm_pso_run_edges(lm_pso *c, lm_mesh *mesh, int count, const double *Rs, const double *ts, const int32_t *windows_xy /*[count][2]*/,
+                     int w, int h, const lm_pso_options *options, int edge_step_mm, lm_pso_result *results, float *device_ms);
 
 #ifdef __cplusplus
 }

@@ -202,9 +202,9 @@ static int add_rendered_view_host(lm_detector* d, lm_mesh* m, int i, int width, 
     d->frame_valid = false;
     d->have_mask[0] = d->have_mask[1] = false;
     d->cur_rgb = d->frame_rgb.p; d->cur_depth = d->frame_depth.p;
-    if (d->use[0]) { int rc = rendered_colour_to_frame(d, m->d_rgb + (size_t)i * npx * 3, npx, d->stream); if (rc) return rc; }
-    if (d->use[1]) HIP_TRY(hipMemcpyAsync(d->frame_depth.p, m->d_depth + (size_t)i * npx, npx * 2, hipMemcpyDeviceToDevice, d->stream));
-    HIP_TRY(hipMemcpyAsync(hdepth.data(), m->d_depth + (size_t)i * npx, npx * 2, hipMemcpyDeviceToHost, d->stream));
+    if (d->use[0]) { int rc = rendered_colour_to_frame(d, m->d_rgb.p + (size_t)i * npx * 3, npx, d->stream); if (rc) return rc; }
+    if (d->use[1]) HIP_TRY(hipMemcpyAsync(d->frame_depth.p, m->d_depth.p + (size_t)i * npx, npx * 2, hipMemcpyDeviceToDevice, d->stream));
+    HIP_TRY(hipMemcpyAsync(hdepth.data(), m->d_depth.p + (size_t)i * npx, npx * 2, hipMemcpyDeviceToHost, d->stream));
     HIP_TRY(hipStreamSynchronize(d->stream));
     int x0 = width, y0 = height, x1 = -1, y1 = -1;
     for (int y = 0; y < height; ++y)
@@ -275,8 +275,8 @@ static int add_templates_rendered(lm_detector* d, lm_mesh* m, const char* class_
         const int mods = (d->use[0] ? 1 : 0) | (d->use[1] ? 2 : 0);
         for (int i = 0; i < n; ++i) {
             d->cur_rgb = d->frame_rgb.p; d->cur_depth = d->frame_depth.p;
-            const uint16_t* view_depth = m->d_depth + (size_t)i * npx;    // a colour-only detector has no depth frame: the mask comes from the rasteriser's buffer
-            if (d->use[0] && (rc = rendered_colour_to_frame(d, m->d_rgb + (size_t)i * npx * 3, npx, s))) return rc;
+            const uint16_t* view_depth = m->d_depth.p + (size_t)i * npx;  // a colour-only detector has no depth frame: the mask comes from the rasteriser's buffer
+            if (d->use[0] && (rc = rendered_colour_to_frame(d, m->d_rgb.p + (size_t)i * npx * 3, npx, s))) return rc;
             if (d->use[1]) HIP_TRY(hipMemcpyAsync(d->frame_depth.p, view_depth, npx * 2, hipMemcpyDeviceToDevice, s));
             if ((rc = run_frontend_training(d))) return rc;
             launch_train_prep(d->use[1] ? d->frame_depth.p : view_depth, nullptr, g, strong_sq, d->extract_threshold, T.keys.p + keys_view * i, kTrainCap,

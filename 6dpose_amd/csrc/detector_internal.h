@@ -17,6 +17,7 @@
 
 #include "../../include/amd_linemod.h"
 #include "depth_modes.h"
+#include "dev_buf.h"
 #include "frame_border.h"
 #include "host_templates.h"
 #include "knobs.h"
@@ -24,34 +25,8 @@
 #include "lm_kernels.h"
 #include "scaled_kernels.h"
 
-int lm_set_error(int code, const char* fmt, ...);
-
-#define HIP_TRY(expr)                                                                                         \
-    do {                                                                                                      \
-        hipError_t _e = (expr);                                                                               \
-        if (_e != hipSuccess) return lm_set_error(LM_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), \
-                                                  __FILE__, __LINE__);                                        \
-    } while (0)
-
-
 namespace lm {}
 using namespace lm;
-
-// ---- device buffer helper ---------------------------------------------------------------------
-template <typename T>
-struct DevBuf {
-    T* p = nullptr;
-    size_t cap = 0;   // elements
-    int ensure(size_t n) {
-        if (n <= cap) return LM_OK;
-        if (p) (void)hipFree(p);
-        p = nullptr; cap = 0;
-        HIP_TRY(hipMalloc((void**)&p, n * sizeof(T)));
-        cap = n;
-        return LM_OK;
-    }
-    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
-};
 
 struct LevelBufs {
     int W = 0, H = 0;

@@ -190,7 +190,7 @@ extern "C" int lm_pipeline_set_views_rendered(lm_pipeline* p, lm_mesh* m, const 
         if ((rc = lm_mesh_render_device(m, n, p->W, p->H, Ks + 9 * (size_t)c0, Rs + 9 * (size_t)c0, ts + 3 * (size_t)c0, clip_near, clip_far, 0.f,
                                         1, true, false)))
             return rc;
-        HIP_TRY(hipMemcpyAsync(p->icp->d_models + ((size_t)slot0 + c0) * npx, m->d_depth, (size_t)n * npx * sizeof(uint16_t),
+        HIP_TRY(hipMemcpyAsync(p->icp->d_models + ((size_t)slot0 + c0) * npx, m->d_depth.p, (size_t)n * npx * sizeof(uint16_t),
                                hipMemcpyDeviceToDevice, m->s));
         HIP_TRY(lm::launch_icp_model_boxes(p->icp->d_models, p->icp->d_model_bbox, slot0 + c0, n, p->W, p->H, m->s));   // the boxes of the new views, once (LL.cpp:43-50)
         for (int i = 0; i < n; ++i) p->icp->slot_boxed[(size_t)slot0 + c0 + i] = 1;

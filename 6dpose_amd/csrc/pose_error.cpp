@@ -34,15 +34,6 @@ constexpr int kMaxViewsPerRender = 256;              // keeps the pair grid (vie
 constexpr int kMaxPtsPairs = 16384;                  // pairs per k_pose_pts / k_pose_sym launch
 constexpr size_t kSymPartialBudget = (size_t)256 << 20;   // bytes of k_pose_sym partials per launch (one pair may exceed it)
 
-int ensure(void** p, size_t& cap, size_t bytes) {
-    if (bytes <= cap) return LM_OK;
-    if (*p) (void)hipFree(*p);
-    *p = nullptr; cap = 0;
-    HIP_TRY(hipMalloc(p, bytes));
-    cap = bytes;
-    return LM_OK;
-}
-
 bool inv3(const double* A, double* B) {
     const double c00 = A[4] * A[8] - A[5] * A[7], c01 = A[5] * A[6] - A[3] * A[8], c02 = A[3] * A[7] - A[4] * A[6];
     const double det = A[0] * c00 + A[1] * c01 + A[2] * c02;
@@ -92,10 +83,10 @@ int check_image(const double* K, int W, int H) {
 }
 
 int upload_scene(lm_mesh* m, const float* scene, int W, int H) {
-    const size_t bytes = (size_t)W * H * sizeof(float);
-    int rc = ensure((void**)&m->d_scene, m->cap_scene, bytes);
+    const size_t n = (size_t)W * H;
+    int rc = m->d_scene.ensure(n);
     if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(m->d_scene, scene, bytes, hipMemcpyHostToDevice, m->s));
+    HIP_TRY(hipMemcpyAsync(m->d_scene.p, scene, n * sizeof(float), hipMemcpyHostToDevice, m->s));
     return LM_OK;
 }
 
@@ -108,13 +99,13 @@ int run_pts(lm_mesh* m, const std::vector<PtsPair>& pairs, int mode, std::vector
     for (int p0 = 0; p0 < npairs; p0 += kMaxPtsPairs) {
         const int np = std::min(kMaxPtsPairs, npairs - p0);
         int rc;
-        if ((rc = ensure(&m->d_pe_pairs, m->cap_pe_pairs, (size_t)np * sizeof(PtsPair)))) return rc;
-        if ((rc = ensure(&m->d_pe_partial, m->cap_pe_partial, (size_t)np * chunks * sizeof(PtsPartial)))) return rc;
-        HIP_TRY(hipMemcpyAsync(m->d_pe_pairs, pairs.data() + p0, (size_t)np * sizeof(PtsPair), hipMemcpyHostToDevice, m->s));
-        launch_pose_pts(m->d_v, m->nv, (const PtsPair*)m->d_pe_pairs, np, mode, (PtsPartial*)m->d_pe_partial, m->s);
+        if ((rc = m->d_pe_pairs.ensure((size_t)np * sizeof(PtsPair)))) return rc;
+        if ((rc = m->d_pe_partial.ensure((size_t)np * chunks * sizeof(PtsPartial)))) return rc;
+        HIP_TRY(hipMemcpyAsync(m->d_pe_pairs.p, pairs.data() + p0, (size_t)np * sizeof(PtsPair), hipMemcpyHostToDevice, m->s));
+        launch_pose_pts(m->d_v.p, m->nv, (const PtsPair*)m->d_pe_pairs.p, np, mode, (PtsPartial*)m->d_pe_partial.p, m->s);
         HIP_TRY(hipGetLastError());
         part.resize((size_t)np * chunks);
-        HIP_TRY(hipMemcpyAsync(part.data(), m->d_pe_partial, part.size() * sizeof(PtsPartial), hipMemcpyDeviceToHost, m->s));
+        HIP_TRY(hipMemcpyAsync(part.data(), m->d_pe_partial.p, part.size() * sizeof(PtsPartial), hipMemcpyDeviceToHost, m->s));
         HIP_TRY(hipStreamSynchronize(m->s));
         for (int p = 0; p < np; ++p) {
             double a = 0.0, b = 0.0;
@@ -235,12 +226,12 @@ extern "C" int lm_mesh_pose_errors(lm_mesh* m, int n_est, const double* R_est, c
                                        t_est + 3 * (size_t)e0, ne, clip_near, clip_far)))
                     return rc;
                 const size_t np = (size_t)ng * ne;
-                if ((rc = ensure(&m->d_pe_partial, m->cap_pe_partial, np * nblk * sizeof(VsdPartial)))) return rc;
-                launch_vsd(m->d_zbuf, 0, ng, ng, ne, want_vsd ? m->d_scene : nullptr, width, height, cam, (float)delta, 1.0 / tau, tau,
-                           (VsdPartial*)m->d_pe_partial, m->s);
+                if ((rc = m->d_pe_partial.ensure(np * nblk * sizeof(VsdPartial)))) return rc;
+                launch_vsd(m->d_zbuf.p, 0, ng, ng, ne, want_vsd ? m->d_scene.p : nullptr, width, height, cam, (float)delta, 1.0 / tau, tau,
+                           (VsdPartial*)m->d_pe_partial.p, m->s);
                 HIP_TRY(hipGetLastError());
                 part.resize(np * nblk);
-                HIP_TRY(hipMemcpyAsync(part.data(), m->d_pe_partial, part.size() * sizeof(VsdPartial), hipMemcpyDeviceToHost, m->s));
+                HIP_TRY(hipMemcpyAsync(part.data(), m->d_pe_partial.p, part.size() * sizeof(VsdPartial), hipMemcpyDeviceToHost, m->s));
                 HIP_TRY(hipStreamSynchronize(m->s));
                 for (size_t p = 0; p < np; ++p) {
                     const int g = g0 + (int)(p / ne), e = e0 + (int)(p % ne);
@@ -319,15 +310,15 @@ extern "C" int lm_mesh_pose_errors_sym(lm_mesh* m, int n_est, const double* R_es
         }
         // one buffer holds the transforms and then the pairs; one holds the partials and then the results
         int rc;
-        if ((rc = ensure(&m->d_pe_pairs, m->cap_pe_pairs, xf_bytes + np * sizeof(SymPair)))) return rc;
-        if ((rc = ensure(&m->d_pe_partial, m->cap_pe_partial, (np * per_pair + np * nm) * sizeof(double)))) return rc;
-        SymXf* d_xf = (SymXf*)m->d_pe_pairs;
-        SymPair* d_pairs = (SymPair*)((char*)m->d_pe_pairs + xf_bytes);
-        double* d_partial = (double*)m->d_pe_partial;
+        if ((rc = m->d_pe_pairs.ensure(xf_bytes + np * sizeof(SymPair)))) return rc;
+        if ((rc = m->d_pe_partial.ensure((np * per_pair + np * nm) * sizeof(double)))) return rc;
+        SymXf* d_xf = (SymXf*)m->d_pe_pairs.p;
+        SymPair* d_pairs = (SymPair*)(m->d_pe_pairs.p + xf_bytes);
+        double* d_partial = (double*)m->d_pe_partial.p;
         double* d_out = d_partial + np * per_pair;
         HIP_TRY(hipMemcpyAsync(d_xf, xf.data(), xf_bytes, hipMemcpyHostToDevice, m->s));   // again after ensure() may have moved the buffer
         HIP_TRY(hipMemcpyAsync(d_pairs, pairs.data(), np * sizeof(SymPair), hipMemcpyHostToDevice, m->s));
-        launch_pose_sym(m->d_v, m->nv, d_pairs, (int)np, d_xf, n_sym, cam, mssd, mspd, d_partial, d_out, m->s);
+        launch_pose_sym(m->d_v.p, m->nv, d_pairs, (int)np, d_xf, n_sym, cam, mssd, mspd, d_partial, d_out, m->s);
         HIP_TRY(hipGetLastError());
         res.resize(np * nm);
         HIP_TRY(hipMemcpyAsync(res.data(), d_out, res.size() * sizeof(double), hipMemcpyDeviceToHost, m->s));
@@ -360,11 +351,11 @@ extern "C" int lm_mesh_gt_stats(lm_mesh* m, int n_gt, const double* R_gt, const 
         const int ng = std::min(cap, n_gt - g0);
         if ((rc = render_views(m, width, height, K, R_gt + 9 * (size_t)g0, t_gt + 3 * (size_t)g0, ng, nullptr, nullptr, 0, clip_near, clip_far)))
             return rc;
-        if ((rc = ensure(&m->d_pe_partial, m->cap_pe_partial, (size_t)ng * nblk * sizeof(GtPartial)))) return rc;
-        launch_gt_stats(m->d_zbuf, ng, m->d_scene, width, height, cam, (float)delta, (GtPartial*)m->d_pe_partial, m->s);
+        if ((rc = m->d_pe_partial.ensure((size_t)ng * nblk * sizeof(GtPartial)))) return rc;
+        launch_gt_stats(m->d_zbuf.p, ng, m->d_scene.p, width, height, cam, (float)delta, (GtPartial*)m->d_pe_partial.p, m->s);
         HIP_TRY(hipGetLastError());
         part.resize((size_t)ng * nblk);
-        HIP_TRY(hipMemcpyAsync(part.data(), m->d_pe_partial, part.size() * sizeof(GtPartial), hipMemcpyDeviceToHost, m->s));
+        HIP_TRY(hipMemcpyAsync(part.data(), m->d_pe_partial.p, part.size() * sizeof(GtPartial), hipMemcpyDeviceToHost, m->s));
         HIP_TRY(hipStreamSynchronize(m->s));
         for (int i = 0; i < ng; ++i) {
             const int g = g0 + i;
@@ -384,7 +375,7 @@ extern "C" int lm_mesh_gt_stats(lm_mesh* m, int n_gt, const double* R_gt, const 
     }
     // bbox_obj: misc.calc_pose_2d_bbox (projection of the model points, np.round, no clipping)
     std::vector<float> V((size_t)m->nv * 3);
-    HIP_TRY(hipMemcpy(V.data(), m->d_v, V.size() * sizeof(float), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(V.data(), m->d_v.p, V.size() * sizeof(float), hipMemcpyDeviceToHost));
     for (int g = 0; g < n_gt; ++g) {
         const double* R = R_gt + 9 * (size_t)g;
         const double* t = t_gt + 3 * (size_t)g;

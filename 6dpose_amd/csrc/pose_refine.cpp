@@ -15,17 +15,9 @@
 
 #include "../../include/amd_linemod.h"
 #include "icp_internal.h"
+#include "lm_error.h"
 
 using namespace lm;
-
-int lm_set_error(int code, const char* fmt, ...);   // detector.cpp
-
-#define HIP_TRY(expr)                                                                                         \
-    do {                                                                                                      \
-        hipError_t _e = (expr);                                                                               \
-        if (_e != hipSuccess) return lm_set_error(LM_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), \
-                                                  __FILE__, __LINE__);                                        \
-    } while (0)
 
 namespace {
 constexpr double kVoxel = 0.0025;     // LL.cpp:106

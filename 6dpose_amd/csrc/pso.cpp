@@ -19,24 +19,28 @@ struct lm_pso {
     hipStream_t s = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     // the scene
-    uint16_t* d_scene = nullptr;
-    size_t cap_scene = 0;
+    DevBuf<uint16_t> d_scene;
     int W = 0, H = 0;
     double K[9] = {0};
     // the edge scene (lm_pso_set_scene_edges): the map, its row distances g and the truncated squared distance D2; a frame and K of its own
-    uint8_t *d_edges = nullptr, *d_g = nullptr;
-    uint16_t* d_d2 = nullptr;
-    size_t cap_edges = 0, cap_g = 0, cap_d2 = 0;
+    DevBuf<uint8_t> d_edges, d_g;
+    DevBuf<uint16_t> d_d2;
     int eW = 0, eH = 0, eM = 0;
     double eK[9] = {0};
     // swarm state, render scratch and the record of the last run
-    PsoHyp* d_hyp = nullptr;
-    ViewParams* d_views = nullptr;
-    ProjVtx* d_pv = nullptr;
-    unsigned long long* d_zbuf = nullptr;
-    PsoState st{};
-    size_t cap_hyp = 0, cap_views = 0, cap_pv = 0, cap_zbuf = 0, cap_x = 0, cap_v = 0, cap_pbx = 0, cap_pbc = 0, cap_sum = 0, cap_nr = 0, cap_best = 0,
-           cap_rx = 0, cap_rc = 0, cap_rs = 0, cap_rn = 0, cap_rb = 0, cap_res = 0;
+    DevBuf<PsoHyp> d_hyp;
+    DevBuf<ViewParams> d_views;
+    DevBuf<ProjVtx> d_pv;
+    DevBuf<unsigned long long> d_zbuf;
+    DevBuf<double> x, v, pbest_x, pbest_cost, rec_x, rec_cost;   // what PsoState points to (pso_kernels.h: the sizes)
+    DevBuf<unsigned long long> sum, rec_sum;
+    DevBuf<unsigned int> n_r, rec_nr;
+    DevBuf<PsoBest> best;
+    DevBuf<int> rec_best;
+    DevBuf<PsoResultDev> result;
+    PsoState state() const {                 // the kernels' view of the buffers: taken after the run's ensure() calls
+        return PsoState{x.p, v.p, pbest_x.p, pbest_cost.p, sum.p, n_r.p, best.p, rec_x.p, rec_cost.p, rec_sum.p, rec_nr.p, rec_best.p, result.p};
+    }
     std::vector<PsoHyp> h_hyp;            // live until the call's synchronisation
     std::vector<PsoResultDev> h_res;
     int last_H = 0, last_P = 0, last_G = -1;
@@ -75,22 +79,12 @@ extern "C" void lm_pso_destroy(lm_pso* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     if (c->s) (void)hipStreamSynchronize(c->s);
-    void* p[] = {c->d_scene, c->d_edges, c->d_g, c->d_d2, c->d_hyp, c->d_views, c->d_pv, c->d_zbuf, c->st.x, c->st.v, c->st.pbest_x, c->st.pbest_cost, c->st.sum, c->st.n_r,
-                 c->st.best, c->st.rec_x, c->st.rec_cost, c->st.rec_sum, c->st.rec_nr, c->st.rec_best, c->st.result};
-    for (void* q : p) if (q) (void)hipFree(q);
-    if (c->ev0) (void)hipEventDestroy(c->ev0);
-    if (c->ev1) (void)hipEventDestroy(c->ev1);
-    if (c->s) (void)hipStreamDestroy(c->s);
-    delete c;
-}
-
-static int ensure(void** p, size_t& cap, size_t bytes) {
-    if (bytes <= cap) return LM_OK;
-    if (*p) (void)hipFree(*p);
-    *p = nullptr; cap = 0;
-    HIP_TRY(hipMalloc(p, bytes));
-    cap = bytes;
-    return LM_OK;
+    hipStream_t s = c->s;
+    hipEvent_t ev0 = c->ev0, ev1 = c->ev1;
+    delete c;                                                             // every buffer: device selected, stream idle and still alive
+    if (ev0) (void)hipEventDestroy(ev0);
+    if (ev1) (void)hipEventDestroy(ev1);
+    if (s) (void)hipStreamDestroy(s);
 }
 
 extern "C" int lm_pso_set_scene(lm_pso* c, const uint16_t* scene_depth, int width, int height, const double* K) {
@@ -100,10 +94,10 @@ extern "C" int lm_pso_set_scene(lm_pso* c, const uint16_t* scene_depth, int widt
         if (!isfinite(K[k])) return lm_set_error(LM_ERR_INVALID, "K is not finite");
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipStreamSynchronize(c->s));
-    const size_t bytes = (size_t)width * height * sizeof(uint16_t);
-    int rc = ensure((void**)&c->d_scene, c->cap_scene, bytes);
+    const size_t n = (size_t)width * height;
+    int rc = c->d_scene.ensure(n);
     if (rc) { c->W = c->H = 0; return rc; }
-    HIP_TRY(hipMemcpy(c->d_scene, scene_depth, bytes, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(c->d_scene.p, scene_depth, n * sizeof(uint16_t), hipMemcpyHostToDevice));
     c->W = width; c->H = height;
     memcpy(c->K, K, sizeof(c->K));
     return LM_OK;
@@ -120,11 +114,11 @@ extern "C" int lm_pso_set_scene_edges(lm_pso* c, const uint8_t* edges, int width
     const size_t n = (size_t)width * height;
     c->eW = c->eH = 0;                                                    // until D2 stands
     int rc;
-    if ((rc = ensure((void**)&c->d_edges, c->cap_edges, n))) return rc;
-    if ((rc = ensure((void**)&c->d_g, c->cap_g, n))) return rc;
-    if ((rc = ensure((void**)&c->d_d2, c->cap_d2, n * sizeof(uint16_t)))) return rc;
-    HIP_TRY(hipMemcpyAsync(c->d_edges, edges, n, hipMemcpyHostToDevice, c->s));
-    launch_edt(c->d_edges, width, height, max_dist, c->d_g, c->d_d2, c->s);
+    if ((rc = c->d_edges.ensure(n))) return rc;
+    if ((rc = c->d_g.ensure(n))) return rc;
+    if ((rc = c->d_d2.ensure(n))) return rc;
+    HIP_TRY(hipMemcpyAsync(c->d_edges.p, edges, n, hipMemcpyHostToDevice, c->s));
+    launch_edt(c->d_edges.p, width, height, max_dist, c->d_g.p, c->d_d2.p, c->s);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(c->s));                                  // `edges` is the caller's again
     c->eW = width; c->eH = height; c->eM = max_dist;
@@ -138,7 +132,7 @@ extern "C" int64_t lm_pso_read_edge_distance(lm_pso* c, uint16_t* dst, int64_t c
     const int64_t size = (int64_t)c->eW * c->eH;
     if (!dst || capacity <= 0) return size;
     HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipMemcpy(dst, c->d_d2, (size_t)std::min<int64_t>(capacity, size) * sizeof(uint16_t), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(dst, c->d_d2.p, (size_t)std::min<int64_t>(capacity, size) * sizeof(uint16_t), hipMemcpyDeviceToHost));
     return size;
 }
 
@@ -167,7 +161,7 @@ static int run_swarm(lm_pso* c, lm_mesh* mesh, int count, const double* Rs, cons
     if (!isfinite(o.clip_near) || !isfinite(o.clip_far)) return lm_set_error(LM_ERR_INVALID, "the clip planes must be finite");
     if (mesh->nf <= 0 || mesh->nv <= 0) return lm_set_error(LM_ERR_INVALID, "the mesh has no faces");
     if (mesh->device != c->device) return lm_set_error(LM_ERR_INVALID, "the mesh lives on device %d, the context on %d", mesh->device, c->device);
-    if (!edges && (!c->d_scene || c->W <= 0)) return lm_set_error(LM_ERR_INVALID, "no scene depth set (lm_pso_set_scene)");
+    if (!edges && (!c->d_scene.p || c->W <= 0)) return lm_set_error(LM_ERR_INVALID, "no scene depth set (lm_pso_set_scene)");
     if (edges && c->eW <= 0) return lm_set_error(LM_ERR_INVALID, "no scene edges set (lm_pso_set_scene_edges)");
     if (edges && o.tau > c->eM) return lm_set_error(LM_ERR_INVALID, "tau must be <= max_dist for the edge cost (got %d > %d)", o.tau, c->eM);
     for (size_t k = 0; k < (size_t)count * 9; ++k)
@@ -190,24 +184,24 @@ static int run_swarm(lm_pso* c, lm_mesh* mesh, int count, const double* Rs, cons
     const size_t HP = (size_t)H * P, npx = (size_t)w * h, gen = (size_t)G + 1;
 
     int rc;
-    PsoState& st = c->st;
-    if ((rc = ensure((void**)&c->d_hyp, c->cap_hyp, H * sizeof(PsoHyp)))) return rc;
-    if ((rc = ensure((void**)&c->d_views, c->cap_views, HP * sizeof(ViewParams)))) return rc;
-    if ((rc = ensure((void**)&c->d_pv, c->cap_pv, HP * mesh->nv * sizeof(ProjVtx)))) return rc;
-    if ((rc = ensure((void**)&c->d_zbuf, c->cap_zbuf, HP * npx * sizeof(unsigned long long)))) return rc;
-    if ((rc = ensure((void**)&st.x, c->cap_x, HP * 6 * sizeof(double)))) return rc;
-    if ((rc = ensure((void**)&st.v, c->cap_v, HP * 6 * sizeof(double)))) return rc;
-    if ((rc = ensure((void**)&st.pbest_x, c->cap_pbx, HP * 6 * sizeof(double)))) return rc;
-    if ((rc = ensure((void**)&st.pbest_cost, c->cap_pbc, HP * sizeof(double)))) return rc;
-    if ((rc = ensure((void**)&st.sum, c->cap_sum, HP * sizeof(unsigned long long)))) return rc;
-    if ((rc = ensure((void**)&st.n_r, c->cap_nr, HP * sizeof(unsigned int)))) return rc;
-    if ((rc = ensure((void**)&st.best, c->cap_best, H * sizeof(PsoBest)))) return rc;
-    if ((rc = ensure((void**)&st.rec_x, c->cap_rx, gen * HP * 6 * sizeof(double)))) return rc;
-    if ((rc = ensure((void**)&st.rec_cost, c->cap_rc, gen * HP * sizeof(double)))) return rc;
-    if ((rc = ensure((void**)&st.rec_sum, c->cap_rs, gen * HP * sizeof(unsigned long long)))) return rc;
-    if ((rc = ensure((void**)&st.rec_nr, c->cap_rn, gen * HP * sizeof(unsigned int)))) return rc;
-    if ((rc = ensure((void**)&st.rec_best, c->cap_rb, gen * H * 2 * sizeof(int)))) return rc;
-    if ((rc = ensure((void**)&st.result, c->cap_res, H * sizeof(PsoResultDev)))) return rc;
+    if ((rc = c->d_hyp.ensure(H))) return rc;
+    if ((rc = c->d_views.ensure(HP))) return rc;
+    if ((rc = c->d_pv.ensure(HP * mesh->nv))) return rc;
+    if ((rc = c->d_zbuf.ensure(HP * npx))) return rc;
+    if ((rc = c->x.ensure(HP * 6))) return rc;
+    if ((rc = c->v.ensure(HP * 6))) return rc;
+    if ((rc = c->pbest_x.ensure(HP * 6))) return rc;
+    if ((rc = c->pbest_cost.ensure(HP))) return rc;
+    if ((rc = c->sum.ensure(HP))) return rc;
+    if ((rc = c->n_r.ensure(HP))) return rc;
+    if ((rc = c->best.ensure(H))) return rc;
+    if ((rc = c->rec_x.ensure(gen * HP * 6))) return rc;
+    if ((rc = c->rec_cost.ensure(gen * HP))) return rc;
+    if ((rc = c->rec_sum.ensure(gen * HP))) return rc;
+    if ((rc = c->rec_nr.ensure(gen * HP))) return rc;
+    if ((rc = c->rec_best.ensure(gen * H * 2))) return rc;
+    if ((rc = c->result.ensure(H))) return rc;
+    const PsoState st = c->state();
     c->last_G = -1;
 
     c->h_hyp.resize(H);
@@ -217,17 +211,17 @@ static int run_swarm(lm_pso* c, lm_mesh* mesh, int count, const double* Rs, cons
         memcpy(c->h_hyp[i].t0, ts + 3 * (size_t)i, 3 * sizeof(double));
         c->h_hyp[i].x0 = windows_xy[2 * i]; c->h_hyp[i].y0 = windows_xy[2 * i + 1];
     }
-    MeshDev M{mesh->d_v, mesh->d_n, mesh->d_c, mesh->d_f, mesh->nv, mesh->nf};
+    MeshDev M{mesh->d_v.p, mesh->d_n.p, mesh->d_c.p, mesh->d_f.p, mesh->nv, mesh->nf};
     HIP_TRY(hipEventRecord(c->ev0, c->s));
-    HIP_TRY(hipMemcpyAsync(c->d_hyp, c->h_hyp.data(), H * sizeof(PsoHyp), hipMemcpyHostToDevice, c->s));
+    HIP_TRY(hipMemcpyAsync(c->d_hyp.p, c->h_hyp.data(), H * sizeof(PsoHyp), hipMemcpyHostToDevice, c->s));
     launch_pso_init(prm, H, st, c->s);
     for (int g = 0; g <= G; ++g) {
-        launch_pso_views(prm, H, c->d_hyp, st.x, c->d_views, c->s);
-        launch_project(M, c->d_views, (int)HP, 1, c->d_pv, c->s);
-        launch_raster(M, c->d_pv, (int)HP, w, h, o.clip_near, o.clip_far, c->d_zbuf, c->s);
-        if (edges) launch_pso_edge_cost(prm, H, edge_step, c->d_hyp, c->d_zbuf, c->d_d2, st.sum, st.n_r, c->s);
-        else launch_pso_cost(prm, H, c->d_hyp, c->d_zbuf, c->d_scene, st.sum, st.n_r, c->s);
-        launch_pso_step(prm, H, g, c->d_hyp, st, c->s);
+        launch_pso_views(prm, H, c->d_hyp.p, st.x, c->d_views.p, c->s);
+        launch_project(M, c->d_views.p, (int)HP, 1, c->d_pv.p, c->s);
+        launch_raster(M, c->d_pv.p, (int)HP, w, h, o.clip_near, o.clip_far, c->d_zbuf.p, c->s);
+        if (edges) launch_pso_edge_cost(prm, H, edge_step, c->d_hyp.p, c->d_zbuf.p, c->d_d2.p, st.sum, st.n_r, c->s);
+        else launch_pso_cost(prm, H, c->d_hyp.p, c->d_zbuf.p, c->d_scene.p, st.sum, st.n_r, c->s);
+        launch_pso_step(prm, H, g, c->d_hyp.p, st, c->s);
     }
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(c->h_res.data(), st.result, H * sizeof(PsoResultDev), hipMemcpyDeviceToHost, c->s));
@@ -268,7 +262,7 @@ extern "C" int64_t lm_pso_read_debug(lm_pso* c, int hypothesis, int kind, double
     if (!dst || capacity <= 0) return size;
     HIP_TRY(hipSetDevice(c->device));
     std::vector<double> out(gen * per);
-    const PsoState& st = c->st;
+    const PsoState st = c->state();
     if (kind == 0 || kind == 1) {                                         // doubles, bit for bit
         const double* src = kind == 0 ? st.rec_x : st.rec_cost;
         HIP_TRY(hipMemcpy2D(out.data(), per * sizeof(double), src + (size_t)hypothesis * per, HP * (per / P) * sizeof(double), per * sizeof(double), gen,

@@ -28,20 +28,18 @@ extern "C" int lm_mesh_create(int device, const float* vertices, const float* no
     HIP_TRY(hipSetDevice(device));
     lm_mesh* m = new lm_mesh();
     m->device = device; m->nv = nv; m->nf = nf;
-    auto fail = [&](const char* what) { lm_mesh_destroy(m); return lm_set_error(LM_ERR_HIP, "%s failed", what); };
-    if (hipStreamCreateWithFlags(&m->s, hipStreamNonBlocking) != hipSuccess) return fail("hipStreamCreate");
-    if (hipMalloc((void**)&m->d_v, (size_t)nv * 3 * sizeof(float)) != hipSuccess) return fail("hipMalloc");
-    if (hipMalloc((void**)&m->d_f, (size_t)nf * 3 * sizeof(int32_t)) != hipSuccess) return fail("hipMalloc");
-    if (hipMemcpy(m->d_v, vertices, (size_t)nv * 3 * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) return fail("hipMemcpy");
-    if (hipMemcpy(m->d_f, faces, (size_t)nf * 3 * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess) return fail("hipMemcpy");
-    if (normals) {
-        if (hipMalloc((void**)&m->d_n, (size_t)nv * 3 * sizeof(float)) != hipSuccess) return fail("hipMalloc");
-        if (hipMemcpy(m->d_n, normals, (size_t)nv * 3 * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) return fail("hipMemcpy");
-    }
-    if (colors) {
-        if (hipMalloc((void**)&m->d_c, (size_t)nv * 3) != hipSuccess) return fail("hipMalloc");
-        if (hipMemcpy(m->d_c, colors, (size_t)nv * 3, hipMemcpyHostToDevice) != hipSuccess) return fail("hipMemcpy");
-    }
+    auto upload = [](auto& buf, const auto* src, size_t n) -> int {
+        int rc = buf.ensure(n);
+        if (rc) return rc;
+        HIP_TRY(hipMemcpy(buf.p, src, n * sizeof(*src), hipMemcpyHostToDevice));
+        return LM_OK;
+    };
+    int rc = hipStreamCreateWithFlags(&m->s, hipStreamNonBlocking) == hipSuccess ? LM_OK : lm_set_error(LM_ERR_HIP, "hipStreamCreate failed");
+    if (!rc) rc = upload(m->d_v, vertices, (size_t)nv * 3);
+    if (!rc) rc = upload(m->d_f, faces, (size_t)nf * 3);
+    if (!rc && normals) rc = upload(m->d_n, normals, (size_t)nv * 3);
+    if (!rc && colors) rc = upload(m->d_c, colors, (size_t)nv * 3);
+    if (rc) { lm_mesh_destroy(m); return rc; }                        // the message is the failed step's
     *out = m;
     return LM_OK;
 }
@@ -50,11 +48,9 @@ extern "C" void lm_mesh_destroy(lm_mesh* m) {
     if (!m) return;
     (void)hipSetDevice(m->device);
     if (m->s) (void)hipStreamSynchronize(m->s);
-    void* p[] = {m->d_v, m->d_n, m->d_c, m->d_f, m->d_views, m->d_pv, m->d_zbuf, m->d_depth, m->d_rgb, m->d_scene, m->d_pe_pairs, m->d_pe_partial,
-                 m->d_uv, m->d_tex, m->d_view_surf, m->d_ov_layers, m->d_ov_frame, m->d_ov_scene, m->d_ov_rgb, m->d_ov_index};
-    for (void* q : p) if (q) (void)hipFree(q);
-    if (m->s) (void)hipStreamDestroy(m->s);
-    delete m;
+    hipStream_t s = m->s;
+    delete m;                                                         // every buffer: device selected, stream idle and still alive
+    if (s) (void)hipStreamDestroy(s);
 }
 
 extern "C" int lm_mesh_counts(const lm_mesh* m, int* nv, int* nf) {
@@ -229,8 +225,9 @@ extern "C" int lm_mesh_set_texcoords(lm_mesh* m, const float* uv, int count) {
     if (count != m->nv) return lm_set_error(LM_ERR_INVALID, "%d texture coordinates for %d vertices", count, m->nv);
     HIP_TRY(hipSetDevice(m->device));
     HIP_TRY(hipStreamSynchronize(m->s));
-    if (!m->d_uv) HIP_TRY(hipMalloc((void**)&m->d_uv, (size_t)m->nv * 2 * sizeof(float)));
-    HIP_TRY(hipMemcpy(m->d_uv, uv, (size_t)m->nv * 2 * sizeof(float), hipMemcpyHostToDevice));
+    int rc = m->d_uv.ensure((size_t)m->nv * 2);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpy(m->d_uv.p, uv, (size_t)m->nv * 2 * sizeof(float), hipMemcpyHostToDevice));
     return LM_OK;
 }
 
@@ -242,16 +239,17 @@ extern "C" int lm_mesh_set_texture(lm_mesh* m, const uint8_t* rgb, int width, in
     const size_t n = (size_t)width * height;
     std::vector<uint32_t> texels(n);                                   // 4-byte texels: one dword load per lookup
     for (size_t i = 0; i < n; ++i) texels[i] = (uint32_t)rgb[3 * i] | ((uint32_t)rgb[3 * i + 1] << 8) | ((uint32_t)rgb[3 * i + 2] << 16);
-    if (m->d_tex) { (void)hipFree(m->d_tex); m->d_tex = nullptr; m->tex_w = m->tex_h = 0; }
-    HIP_TRY(hipMalloc((void**)&m->d_tex, n * sizeof(uint32_t)));
-    HIP_TRY(hipMemcpy(m->d_tex, texels.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice));
+    m->d_tex.release(); m->tex_w = m->tex_h = 0;                      // exactly this size, not a grown buffer
+    int rc = m->d_tex.ensure(n);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpy(m->d_tex.p, texels.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice));
     m->tex_w = width; m->tex_h = height;
     return LM_OK;
 }
 
 extern "C" int lm_mesh_texture_info(const lm_mesh* m, int* has_texcoords, int* width, int* height) {
     if (!m) return lm_set_error(LM_ERR_INVALID, "null mesh");
-    if (has_texcoords) *has_texcoords = m->d_uv != nullptr;
+    if (has_texcoords) *has_texcoords = m->d_uv.p != nullptr;
     if (width) *width = m->tex_w;
     if (height) *height = m->tex_h;
     return LM_OK;
@@ -282,7 +280,7 @@ int lm_parse_render_options(const lm_mesh* m, const lm_render_options* o, lm_sha
     lm_shade_opts r;
     r.flat = o->shading == LM_SHADING_FLAT;
     r.use_texture = o->use_texture != 0;
-    if (r.use_texture && (!m->d_uv || !m->d_tex)) return lm_set_error(LM_ERR_INVALID, "texture requested but the mesh has %s", !m->d_uv ? "no texture coordinates" : "no texture image");
+    if (r.use_texture && (!m->d_uv.p || !m->d_tex.p)) return lm_set_error(LM_ERR_INVALID, "texture requested but the mesh has %s", !m->d_uv.p ? "no texture coordinates" : "no texture image");
     r.has_surf = o->has_surf_color != 0;
     if (r.has_surf && !pack_colour(o->surf_color, &r.surf)) return lm_set_error(LM_ERR_INVALID, "surf_color outside [0, 1]");
     if (!pack_colour(o->bg_color, &r.bg) || !(o->bg_color[3] >= 0.f && o->bg_color[3] <= 1.f)) return lm_set_error(LM_ERR_INVALID, "bg_color outside [0, 1]");
@@ -304,43 +302,35 @@ static int render_device(lm_mesh* m, int count, int W, int H, const float* Ks, c
         for (int k = 0; k < 9; ++k) { hv[i].K[k] = Ks[9 * i + k]; hv[i].R[k] = Rs[9 * i + k]; }
         for (int k = 0; k < 3; ++k) hv[i].t[k] = ts[3 * i + k];
     }
-    auto ensure = [&](void** p, size_t& cap, size_t bytes) -> int {
-        if (bytes <= cap) return LM_OK;
-        if (*p) (void)hipFree(*p);
-        *p = nullptr; cap = 0;
-        HIP_TRY(hipMalloc(p, bytes));
-        cap = bytes;
-        return LM_OK;
-    };
     const int smax = want_rgb ? ssaa : 1;
     int rc;
-    if ((rc = ensure((void**)&m->d_views, m->cap_views, nview * sizeof(ViewParams)))) return rc;
-    if ((rc = ensure((void**)&m->d_pv, m->cap_pv, nview * m->nv * sizeof(ProjVtx)))) return rc;
-    if ((rc = ensure((void**)&m->d_zbuf, m->cap_zbuf, nview * W * H * smax * smax * sizeof(unsigned long long)))) return rc;
-    if (want_depth && (rc = ensure((void**)&m->d_depth, m->cap_depth, nview * W * H * sizeof(uint16_t)))) return rc;
-    if (want_rgb && (rc = ensure((void**)&m->d_rgb, m->cap_rgb, nview * W * H * 3))) return rc;
+    if ((rc = m->d_views.ensure(nview))) return rc;
+    if ((rc = m->d_pv.ensure(nview * m->nv))) return rc;
+    if ((rc = m->d_zbuf.ensure(nview * W * H * smax * smax))) return rc;
+    if (want_depth && (rc = m->d_depth.ensure(nview * W * H))) return rc;
+    if (want_rgb && (rc = m->d_rgb.ensure(nview * W * H * 3))) return rc;
     if (want_rgb && shade && shade->view_surf) {
-        if ((rc = ensure((void**)&m->d_view_surf, m->cap_view_surf, nview * sizeof(uint32_t)))) return rc;
-        HIP_TRY(hipMemcpyAsync(m->d_view_surf, shade->view_surf, nview * sizeof(uint32_t), hipMemcpyHostToDevice, m->s));
+        if ((rc = m->d_view_surf.ensure(nview))) return rc;
+        HIP_TRY(hipMemcpyAsync(m->d_view_surf.p, shade->view_surf, nview * sizeof(uint32_t), hipMemcpyHostToDevice, m->s));
     }
-    HIP_TRY(hipMemcpyAsync(m->d_views, hv.data(), nview * sizeof(ViewParams), hipMemcpyHostToDevice, m->s));
+    HIP_TRY(hipMemcpyAsync(m->d_views.p, hv.data(), nview * sizeof(ViewParams), hipMemcpyHostToDevice, m->s));
     HIP_TRY(hipStreamSynchronize(m->s));                              // hv is a local
-    MeshDev M{m->d_v, m->d_n, m->d_c, m->d_f, m->nv, m->nf};
+    MeshDev M{m->d_v.p, m->d_n.p, m->d_c.p, m->d_f.p, m->nv, m->nf};
     if (want_depth) {                                                 // the driver renders depth at the native resolution (:206-209)
-        launch_project(M, m->d_views, count, 1, m->d_pv, m->s);
-        launch_raster(M, m->d_pv, count, W, H, clip_near, clip_far, m->d_zbuf, m->s);
-        launch_resolve_depth(m->d_zbuf, count, W, H, m->d_depth, m->s);
+        launch_project(M, m->d_views.p, count, 1, m->d_pv.p, m->s);
+        launch_raster(M, m->d_pv.p, count, W, H, clip_near, clip_far, m->d_zbuf.p, m->s);
+        launch_resolve_depth(m->d_zbuf.p, count, W, H, m->d_depth.p, m->s);
     }
     if (want_rgb) {                                                   // and colour at ssaa x, box-filtered (:212-216)
-        launch_project(M, m->d_views, count, ssaa, m->d_pv, m->s);
-        launch_raster(M, m->d_pv, count, W * ssaa, H * ssaa, clip_near, clip_far, m->d_zbuf, m->s);
-        if (!shade) launch_resolve_rgb(M, m->d_pv, m->d_views, m->d_zbuf, count, W, H, ssaa, ambient, m->d_rgb, m->s);
+        launch_project(M, m->d_views.p, count, ssaa, m->d_pv.p, m->s);
+        launch_raster(M, m->d_pv.p, count, W * ssaa, H * ssaa, clip_near, clip_far, m->d_zbuf.p, m->s);
+        if (!shade) launch_resolve_rgb(M, m->d_pv.p, m->d_views.p, m->d_zbuf.p, count, W, H, ssaa, ambient, m->d_rgb.p, m->s);
         else {
             ShadeParams sp{};
-            if (shade->use_texture) { sp.uv = m->d_uv; sp.tex = m->d_tex; sp.tex_w = m->tex_w; sp.tex_h = m->tex_h; }
-            sp.view_surf = shade->view_surf ? m->d_view_surf : nullptr;
+            if (shade->use_texture) { sp.uv = m->d_uv.p; sp.tex = m->d_tex.p; sp.tex_w = m->tex_w; sp.tex_h = m->tex_h; }
+            sp.view_surf = shade->view_surf ? m->d_view_surf.p : nullptr;
             sp.surf = shade->surf; sp.has_surf = shade->has_surf; sp.bg = shade->bg; sp.ambient = ambient; sp.flat = shade->flat;
-            launch_resolve_shaded(M, m->d_pv, m->d_views, m->d_zbuf, count, W, H, ssaa, sp, m->d_rgb, m->s);
+            launch_resolve_shaded(M, m->d_pv.p, m->d_views.p, m->d_zbuf.p, count, W, H, ssaa, sp, m->d_rgb.p, m->s);
         }
     }
     HIP_TRY(hipGetLastError());
@@ -354,7 +344,7 @@ int lm_mesh_render_device(lm_mesh* m, int count, int W, int H, const float* Ks, 
 }
 int lm_mesh_render_device_shaded(lm_mesh* m, int count, int W, int H, const float* Ks, const float* Rs, const float* ts, const lm_shade_opts& o,
                                  bool want_depth, bool want_rgb) {
-    if (o.use_texture && (!m || !m->d_uv || !m->d_tex)) return lm_set_error(LM_ERR_INVALID, "texture requested but none attached");
+    if (o.use_texture && (!m || !m->d_uv.p || !m->d_tex.p)) return lm_set_error(LM_ERR_INVALID, "texture requested but none attached");
     return render_device(m, count, W, H, Ks, Rs, ts, o.clip_near, o.clip_far, o.ambient, o.ssaa, want_depth, want_rgb, &o);
 }
 
@@ -370,8 +360,8 @@ extern "C" int lm_mesh_render(lm_mesh* m, int count, int width, int height, cons
                                        ambient, ssaa, depth_out != nullptr, rgb_out != nullptr);
         if (rc) return rc;
         const size_t npx = (size_t)width * height;
-        if (depth_out) HIP_TRY(hipMemcpyAsync(depth_out + (size_t)c0 * npx, m->d_depth, (size_t)n * npx * sizeof(uint16_t), hipMemcpyDeviceToHost, m->s));
-        if (rgb_out) HIP_TRY(hipMemcpyAsync(rgb_out + (size_t)c0 * npx * 3, m->d_rgb, (size_t)n * npx * 3, hipMemcpyDeviceToHost, m->s));
+        if (depth_out) HIP_TRY(hipMemcpyAsync(depth_out + (size_t)c0 * npx, m->d_depth.p, (size_t)n * npx * sizeof(uint16_t), hipMemcpyDeviceToHost, m->s));
+        if (rgb_out) HIP_TRY(hipMemcpyAsync(rgb_out + (size_t)c0 * npx * 3, m->d_rgb.p, (size_t)n * npx * 3, hipMemcpyDeviceToHost, m->s));
         HIP_TRY(hipStreamSynchronize(m->s));
     }
     return LM_OK;
@@ -394,8 +384,8 @@ extern "C" int lm_mesh_render_ex(lm_mesh* m, int count, int width, int height, c
                                           rgb_out != nullptr);
         if (rc) return rc;
         const size_t npx = (size_t)width * height;
-        if (depth_out) HIP_TRY(hipMemcpyAsync(depth_out + (size_t)c0 * npx, m->d_depth, (size_t)n * npx * sizeof(uint16_t), hipMemcpyDeviceToHost, m->s));
-        if (rgb_out) HIP_TRY(hipMemcpyAsync(rgb_out + (size_t)c0 * npx * 3, m->d_rgb, (size_t)n * npx * 3, hipMemcpyDeviceToHost, m->s));
+        if (depth_out) HIP_TRY(hipMemcpyAsync(depth_out + (size_t)c0 * npx, m->d_depth.p, (size_t)n * npx * sizeof(uint16_t), hipMemcpyDeviceToHost, m->s));
+        if (rgb_out) HIP_TRY(hipMemcpyAsync(rgb_out + (size_t)c0 * npx * 3, m->d_rgb.p, (size_t)n * npx * 3, hipMemcpyDeviceToHost, m->s));
         HIP_TRY(hipStreamSynchronize(m->s));
     }
     return LM_OK;
@@ -446,30 +436,22 @@ extern "C" int lm_mesh_overlay(lm_mesh* const* meshes, int count, int width, int
         o.view_surf = surf_colors ? vs.data() : nullptr;
         if ((rc = lm_mesh_render_device_shaded(m, n, width, height, K.data(), R.data(), T.data(), o, true, true))) return rc;
         HIP_TRY(hipStreamSynchronize(m->s));                           // vs is reused; the compose runs on m0's stream
-        for (int k = 0; k < n; ++k) layers[mine[k]] = OverlayLayer{m->d_rgb + (size_t)k * npx * 3, m->d_depth + (size_t)k * npx};
+        for (int k = 0; k < n; ++k) layers[mine[k]] = OverlayLayer{m->d_rgb.p + (size_t)k * npx * 3, m->d_depth.p + (size_t)k * npx};
     }
-    auto ensure = [&](void** p, size_t& cap, size_t bytes) -> int {
-        if (bytes <= cap) return LM_OK;
-        if (*p) (void)hipFree(*p);
-        *p = nullptr; cap = 0;
-        HIP_TRY(hipMalloc(p, bytes));
-        cap = bytes;
-        return LM_OK;
-    };
     int rc;
-    if ((rc = ensure((void**)&m0->d_ov_layers, m0->cap_ov_layers, (size_t)count * sizeof(OverlayLayer)))) return rc;
-    if ((rc = ensure((void**)&m0->d_ov_frame, m0->cap_ov_frame, npx * 3))) return rc;
-    if ((rc = ensure((void**)&m0->d_ov_rgb, m0->cap_ov_rgb, npx * 3))) return rc;
-    if ((rc = ensure((void**)&m0->d_ov_index, m0->cap_ov_index, npx))) return rc;
-    if (scene_depth && (rc = ensure((void**)&m0->d_ov_scene, m0->cap_ov_scene, npx * sizeof(uint16_t)))) return rc;
-    HIP_TRY(hipMemcpyAsync(m0->d_ov_layers, layers.data(), (size_t)count * sizeof(OverlayLayer), hipMemcpyHostToDevice, m0->s));
-    HIP_TRY(hipMemcpyAsync(m0->d_ov_frame, rgb, npx * 3, hipMemcpyHostToDevice, m0->s));
-    if (scene_depth) HIP_TRY(hipMemcpyAsync(m0->d_ov_scene, scene_depth, npx * sizeof(uint16_t), hipMemcpyHostToDevice, m0->s));
-    launch_overlay_compose(m0->d_ov_layers, count, m0->d_ov_frame, scene_depth ? m0->d_ov_scene : nullptr, (int)npx, mode == LM_OVERLAY_NEAREST,
-                           m0->d_ov_rgb, m0->d_ov_index, m0->s);
+    if ((rc = m0->d_ov_layers.ensure(count))) return rc;
+    if ((rc = m0->d_ov_frame.ensure(npx * 3))) return rc;
+    if ((rc = m0->d_ov_rgb.ensure(npx * 3))) return rc;
+    if ((rc = m0->d_ov_index.ensure(npx))) return rc;
+    if (scene_depth && (rc = m0->d_ov_scene.ensure(npx))) return rc;
+    HIP_TRY(hipMemcpyAsync(m0->d_ov_layers.p, layers.data(), (size_t)count * sizeof(OverlayLayer), hipMemcpyHostToDevice, m0->s));
+    HIP_TRY(hipMemcpyAsync(m0->d_ov_frame.p, rgb, npx * 3, hipMemcpyHostToDevice, m0->s));
+    if (scene_depth) HIP_TRY(hipMemcpyAsync(m0->d_ov_scene.p, scene_depth, npx * sizeof(uint16_t), hipMemcpyHostToDevice, m0->s));
+    launch_overlay_compose(m0->d_ov_layers.p, count, m0->d_ov_frame.p, scene_depth ? m0->d_ov_scene.p : nullptr, (int)npx, mode == LM_OVERLAY_NEAREST,
+                           m0->d_ov_rgb.p, m0->d_ov_index.p, m0->s);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(rgb_out, m0->d_ov_rgb, npx * 3, hipMemcpyDeviceToHost, m0->s));
-    HIP_TRY(hipMemcpyAsync(index_out, m0->d_ov_index, npx, hipMemcpyDeviceToHost, m0->s));
+    HIP_TRY(hipMemcpyAsync(rgb_out, m0->d_ov_rgb.p, npx * 3, hipMemcpyDeviceToHost, m0->s));
+    HIP_TRY(hipMemcpyAsync(index_out, m0->d_ov_index.p, npx, hipMemcpyDeviceToHost, m0->s));
     HIP_TRY(hipStreamSynchronize(m0->s));
     return LM_OK;
 }

@@ -1,52 +1,37 @@
 // Private view of lm_mesh shared by render.cpp, detector_bank.cpp and pipeline.cpp (not part of the C ABI).
 #pragma once
 #include "../../include/amd_linemod.h"
+#include "dev_buf.h"
 #include "render_kernels.h"
-
-int lm_set_error(int code, const char* fmt, ...);
-#ifndef HIP_TRY
-#define HIP_TRY(expr)                                                                                         \
-    do {                                                                                                      \
-        hipError_t _e = (expr);                                                                               \
-        if (_e != hipSuccess) return lm_set_error(LM_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), \
-                                                  __FILE__, __LINE__);                                        \
-    } while (0)
-#endif
 
 struct lm_mesh {
     int device = 0;
     int nv = 0, nf = 0;
     hipStream_t s = nullptr;
-    float* d_v = nullptr;
-    float* d_n = nullptr;
-    uint8_t* d_c = nullptr;
-    int32_t* d_f = nullptr;
+    DevBuf<float> d_v, d_n;
+    DevBuf<uint8_t> d_c;
+    DevBuf<int32_t> d_f;
     // render scratch / results of the last call (device)
-    lm::ViewParams* d_views = nullptr;
-    lm::ProjVtx* d_pv = nullptr;
-    unsigned long long* d_zbuf = nullptr;
-    uint16_t* d_depth = nullptr;
-    uint8_t* d_rgb = nullptr;
-    size_t cap_views = 0, cap_pv = 0, cap_zbuf = 0, cap_depth = 0, cap_rgb = 0;
+    DevBuf<lm::ViewParams> d_views;
+    DevBuf<lm::ProjVtx> d_pv;
+    DevBuf<unsigned long long> d_zbuf;
+    DevBuf<uint16_t> d_depth;
+    DevBuf<uint8_t> d_rgb;
     int last_W = 0, last_H = 0, last_count = 0;
-    // pose-error scratch (pose_error.cpp): resident scene depth, pair parameters, per-block partials
-    float* d_scene = nullptr;
-    void* d_pe_pairs = nullptr;
-    void* d_pe_partial = nullptr;
-    size_t cap_scene = 0, cap_pe_pairs = 0, cap_pe_partial = 0;
+    // pose-error scratch (pose_error.cpp): resident scene depth, pair parameters, per-block partials (bytes: each metric casts them to its records)
+    DevBuf<float> d_scene;
+    DevBuf<uint8_t> d_pe_pairs, d_pe_partial;
     // texture (lm_mesh_set_texcoords / lm_mesh_set_texture) and per-view surface colours of the last shaded render
-    float* d_uv = nullptr;                 // [nv][2]
-    uint32_t* d_tex = nullptr;             // [tex_h][tex_w] r | g << 8 | b << 16
+    DevBuf<float> d_uv;                    // [nv][2]
+    DevBuf<uint32_t> d_tex;                // [tex_h][tex_w] r | g << 8 | b << 16
     int tex_w = 0, tex_h = 0;
-    uint32_t* d_view_surf = nullptr;
-    size_t cap_view_surf = 0;
+    DevBuf<uint32_t> d_view_surf;
     // overlay scratch / results (lm_mesh_overlay, held by the first mesh of the call)
-    lm::OverlayLayer* d_ov_layers = nullptr;
-    uint8_t* d_ov_frame = nullptr;
-    uint16_t* d_ov_scene = nullptr;
-    uint8_t* d_ov_rgb = nullptr;
-    int8_t* d_ov_index = nullptr;
-    size_t cap_ov_layers = 0, cap_ov_frame = 0, cap_ov_scene = 0, cap_ov_rgb = 0, cap_ov_index = 0;
+    DevBuf<lm::OverlayLayer> d_ov_layers;
+    DevBuf<uint8_t> d_ov_frame;
+    DevBuf<uint16_t> d_ov_scene;
+    DevBuf<uint8_t> d_ov_rgb;
+    DevBuf<int8_t> d_ov_index;
 };
 
 // Renders `count` views into the mesh's device buffers (d_depth [count][H][W], d_rgb [count][H][W][3]) on m->s; no host copy.

@@ -82,15 +82,6 @@ extern "C" int lm_device_count(void) {
 }
 extern "C" void lm_free(void* p) { free(p); }
 
-int ensure_pinned(lm_detector* d, size_t bytes) {
-    if (bytes <= d->pinned_bytes) return LM_OK;
-    if (d->pinned) (void)hipHostFree(d->pinned);
-    d->pinned = nullptr; d->pinned_bytes = 0;
-    HIP_TRY(hipHostMalloc(&d->pinned, bytes, hipHostMallocDefault));
-    d->pinned_bytes = bytes;
-    return LM_OK;
-}
-
 // NORMAL_LUT plane (normal_lut.i): round(atan2(y-10, x-10)/45deg) mod 8, one-hot (z-independent)
 static void make_normal_lut(uint8_t lut[400]) {
     const double PI = 3.14159265358979323846;
@@ -302,51 +293,18 @@ extern "C" void lm_detector_destroy(lm_detector* d) {
     for (auto& sl : d->slot) { free(sl.prep); sl.prep = nullptr; }
     (void)hipStreamSynchronize(d->stream);
     if (d->mstream) (void)hipStreamSynchronize(d->mstream);
-    d->frame_rgb.release(); d->frame_depth.release(); d->nrm_raw.release(); d->border_src.release();
-    for (int i = 0; i < lm_detector::kSlots; ++i) {
-        if (d->ingest.pinned[i]) (void)hipHostFree(d->ingest.pinned[i]);
-        d->ingest.d_rgb[i].release(); d->ingest.d_src[i].release();
-        if (d->ingest.t0[i]) (void)hipEventDestroy(d->ingest.t0[i]);
-        if (d->ingest.t1[i]) (void)hipEventDestroy(d->ingest.t1[i]);
-    }
-    if (d->ingest.stream) (void)hipStreamDestroy(d->ingest.stream);
-    for (int a = 0; a < lm_detector::kSlots; ++a) { d->lm_arena[a].release(); d->sm_arena[a].release(); }
-    for (int a = 0; a < lm_detector::kSlots; ++a) { d->bits_arena[a].release(); d->cbits_arena[a].release(); d->wbits_arena[a].release(); d->wcbits_arena[a].release(); }
-    for (auto& b : d->slot_rgb) b.release();
-    for (auto& b : d->slot_depth) b.release();
-    for (auto& l : d->lvl) { l.rgb.release(); l.mag.release(); l.ang.release(); l.nrm.release(); l.mask[0].release(); l.mask[1].release(); }
-    d->d_entries.release(); d->d_feat_off.release(); d->d_feat_xy.release(); d->d_feat_word.release(); d->d_run_mask.release(); d->d_work.release();
-    d->d_parts.release(); d->d_part_off.release(); d->d_part_word.release();
-    d->d_cands.release(); d->d_counters.release(); d->d_final.release(); d->d_matches_dev.release(); d->d_hash.release(); d->d_distinct_keys.release(); d->d_tiles.release(); d->d_todo.release(); d->d_work_cls.release(); d->d_work_tid.release();
-    for (int l = 0; l < kMaxLevels; ++l) { d->train.mask[l].release(); d->train.lab[l].release(); d->train.hrun[l].release(); }
-    d->train.user_mask.release();
-    d->slabs.hist.release(); d->slabs.modes.release();
-    d->scaled.probe.release(); d->scaled.table.release(); d->scaled.entries.release(); d->scaled.train.release(); d->scaled.cands.release(); d->scaled.counter.release();
-    for (auto& lv : d->slabs.mask) for (auto& m : lv) m.release();
-    if (d->slabs.h_modes) (void)hipHostFree(d->slabs.h_modes);
-    if (d->slabs.modes_ready) (void)hipEventDestroy(d->slabs.modes_ready);
-    d->train.keys.release(); d->train.counts.release(); d->train.bbox.release(); d->train.out.release();
-    for (auto& sl : d->slot) {
-        if (sl.h_matches) (void)hipHostFree(sl.h_matches);
-        if (sl.h_distinct) (void)hipHostFree(sl.h_distinct);
-        if (sl.h_counters) (void)hipHostFree(sl.h_counters);
-        if (sl.fe_done) (void)hipEventDestroy(sl.fe_done);
-        for (auto& e : sl.ev) if (e) (void)hipEventDestroy(e);
-        if (sl.done) (void)hipEventDestroy(sl.done);
-    }
     if (d->xchg.stream) (void)hipStreamSynchronize(d->xchg.stream);
-    for (int a = 0; a < lm_detector::kSlots; ++a) {
-        d->xchg.d_merged[a].release();
-        d->xchg.d_runs.release();
-        if (d->xchg.h_merged[a]) (void)hipHostFree(d->xchg.h_merged[a]);
-        if (d->xchg.done[a]) (void)hipEventDestroy(d->xchg.done[a]);
+    std::vector<hipEvent_t> events(std::begin(d->ev), std::end(d->ev));
+    for (int i = 0; i < lm_detector::kSlots; ++i) {
+        const lm_detector::Slot& sl = d->slot[i];
+        events.insert(events.end(), {d->ingest.t0[i], d->ingest.t1[i], d->xchg.done[i], sl.done, sl.fe_done});
+        events.insert(events.end(), std::begin(sl.ev), std::end(sl.ev));
     }
-    if (d->xchg.stream) (void)hipStreamDestroy(d->xchg.stream);
-    if (d->pinned) (void)hipHostFree(d->pinned);
-    for (auto& ev : d->ev) if (ev) (void)hipEventDestroy(ev);
-    if (d->stream) (void)hipStreamDestroy(d->stream);
-    if (d->mstream) (void)hipStreamDestroy(d->mstream);
-    delete d;
+    events.push_back(d->slabs.modes_ready);
+    hipStream_t streams[] = {d->ingest.stream, d->xchg.stream, d->stream, d->mstream};
+    delete d;                                                         // every DevBuf and PinBuf: device selected, streams idle and still alive
+    for (hipEvent_t e : events) if (e) (void)hipEventDestroy(e);
+    for (hipStream_t s : streams) if (s) (void)hipStreamDestroy(s);
 }
 
 extern "C" int lm_detector_max_in_flight(void) { return lm_detector::kSlots; }

@@ -34,11 +34,11 @@ static size_t canonical_list_of(const lm_detector::Slot& sl, const Candidate* sr
 static void prepare_list_job(lm_detector::Slot* sl) {
     int state = 2;
     sl->prep = nullptr; sl->prep_n = 0;
-    const unsigned long long* hc = sl->h_counters;
-    if (sl->num_work > 0 && hc[0] <= sl->cand_cap && hc[0] <= sl->match_cap && hc[1] <= hc[0]) {
+    const unsigned long long* hc = sl->h_counters.p;
+    if (sl->num_work > 0 && hc[0] <= sl->cand_cap && hc[0] <= sl->h_matches.cap && hc[1] <= hc[0]) {
         const auto t0 = std::chrono::steady_clock::now();
         ListClock lc{};
-        sl->prep_n = canonical_list_of(*sl, sl->h_distinct, hc[1], (size_t)hc[1], true, true, &sl->prep, &lc);
+        sl->prep_n = canonical_list_of(*sl, sl->h_distinct.p, hc[1], (size_t)hc[1], true, true, &sl->prep, &lc);
         sl->prep_collect_ms = (float)(1e3 * seconds_between(t0, lc.converted)); sl->prep_merge_ms = (float)(1e3 * seconds_between(lc.converted, lc.merged));
         if (sl->prep) state = 1;
     }
@@ -90,10 +90,10 @@ static void post_list_jobs(lm_detector* d, const lm_detector::Slot& sl, int slot
 // The frame's candidate count, published by the last block of its k_dedupe (candidates, distinct, alive, key overflow, tiles, evaluations,
 // bytes).  Returns 1 when a buffer overflowed: never drop silently — the capacity grows and the caller reruns the frame.
 static int read_counters(lm_detector* d, const lm_detector::Slot& sl, int slot_index, uint64_t* ncand_out) {
-    const uint64_t ncand = sl.num_work > 0 ? sl.h_counters[0] : 0;
+    const uint64_t ncand = sl.num_work > 0 ? sl.h_counters.p[0] : 0;
     *ncand_out = ncand;
     if (ncand > 0xFFFFFFF0ull) return lm_set_error(LM_ERR_INVALID, "too many coarse candidates (%llu)", (unsigned long long)ncand);
-    if (ncand > sl.cand_cap || ncand > sl.match_cap) {
+    if (ncand > sl.cand_cap || ncand > sl.h_matches.cap) {
         d->cand_cap = std::max<uint32_t>(d->cand_cap, (uint32_t)(ncand + ncand / 4 + 1024));
         d->ingest.used[slot_index] = false;
         return 1;
@@ -105,7 +105,7 @@ static int read_counters(lm_detector* d, const lm_detector::Slot& sl, int slot_i
 // *nm_out: the records alive before std::unique.
 static int fill_timings(lm_detector* d, lm_detector::Slot& sl, int slot_index, int sort_unique, uint64_t ncand, lm_timings* tm_out, uint64_t* nm_out) {
     const lm_detector::Slot& lead = d->slot[sl.leader];
-    const unsigned long long* hc = sl.h_counters;
+    const unsigned long long* hc = sl.h_counters.p;
     lm_timings tm{};
     tm.h2d_ms = sl.h2d_ms; tm.templates = sl.num_work; tm.coarse_bytes = sl.coarse_bytes;
     if (d->ingest.used[slot_index]) {   // streamed frame: its H2D ran on the copy stream
@@ -115,9 +115,9 @@ static int fill_timings(lm_detector* d, lm_detector::Slot& sl, int slot_index, i
     }
     const uint64_t evals = sl.num_work > 0 ? hc[5] : 0, lbytes = sl.num_work > 0 ? hc[6] : 0;
     uint64_t nm = 0;
-    const Candidate* hm = sl.h_matches;
+    const Candidate* hm = sl.h_matches.p;
     if (sl.num_work > 0 && ncand > 0 && (sort_unique == 0 || sort_unique == 3 || d->reference_order))   // the raw per-candidate records, for the callers that want them
-        HIP_TRY(hipMemcpy(sl.h_matches, sl.matches_dev, (size_t)ncand * sizeof(Candidate), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(sl.h_matches.p, sl.matches_dev, (size_t)ncand * sizeof(Candidate), hipMemcpyDeviceToHost));
     if (sl.num_work == 0) nm = 0;
     else if (sort_unique == 0) { for (uint64_t i = 0; i < ncand; ++i) nm += hm[i].work >= 0; }
     else nm = hc[2];                                   // counted on the device by k_dedupe: no pass over the raw records
@@ -147,14 +147,14 @@ static int build_list(const lm_detector::Slot& sl, int sort_unique, uint64_t nca
     if (sort_unique == 3) {
         std::vector<Candidate> coarse((size_t)ncand);                            // from the buffer the frame was submitted with: d->cand_cap may have grown since
         if (ncand) HIP_TRY(hipMemcpy(coarse.data(), sl.cands, (size_t)ncand * sizeof(Candidate), hipMemcpyDeviceToHost));
-        *out = reference_order_list(sl.h_matches, coarse.data(), ncand, (size_t)nm, *sl.work_cls, *sl.work_tid, n_out, clock);
+        *out = reference_order_list(sl.h_matches.p, coarse.data(), ncand, (size_t)nm, *sl.work_cls, *sl.work_tid, n_out, clock);
     } else {
         const bool use_distinct = sort_unique != 0 && sl.num_work > 0;
-        const uint64_t nd = use_distinct ? sl.h_counters[1] : 0;
+        const uint64_t nd = use_distinct ? sl.h_counters.p[1] : 0;
         if (use_distinct && (nd > ncand || nd > nm || nm > ncand))
             return lm_set_error(LM_ERR_HIP, "duplicate removal out of step with the refinement (%llu distinct of %llu alive, %llu candidates)",
                                 (unsigned long long)nd, (unsigned long long)nm, (unsigned long long)ncand);
-        *n_out = canonical_list_of(sl, use_distinct ? sl.h_distinct : sl.h_matches, use_distinct ? nd : ncand, use_distinct ? (size_t)nd : (size_t)nm,
+        *n_out = canonical_list_of(sl, use_distinct ? sl.h_distinct.p : sl.h_matches.p, use_distinct ? nd : ncand, use_distinct ? (size_t)nd : (size_t)nm,
                                    sort_unique == 1, use_distinct, out, clock);
     }
     if (!*out) return lm_set_error(LM_ERR_INVALID, "out of host memory");
@@ -238,7 +238,7 @@ extern "C" int64_t lm_detector_read_candidates(lm_detector* d, uint64_t frame_no
     const lm_detector::Slot& sl = d->slot[si];
     if (sl.cand_cap != d->buf_cand_cap || sl.cands != d->d_cands.p + (size_t)d->buf_cand_cap * si)
         return lm_set_error(LM_ERR_INVALID, "the candidate buffers have been replaced since frame %llu", (unsigned long long)frame_no);
-    const int64_t produced = sl.num_work > 0 ? (int64_t)(sl.h_counters[0] & kCandMask) : 0;
+    const int64_t produced = sl.num_work > 0 ? (int64_t)(sl.h_counters.p[0] & kCandMask) : 0;
     const int64_t n = std::min<int64_t>(std::min<int64_t>(produced, (int64_t)sl.cand_cap), capacity);
     if (dst && n > 0) {
         HIP_TRY(hipSetDevice(d->device));

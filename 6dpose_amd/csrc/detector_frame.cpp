@@ -134,8 +134,8 @@ int upload_frame(lm_detector* d, const uint8_t* rgb, const uint16_t* depth, int 
     const bool m0 = masks && masks[0], m1 = masks && d->nmod == 2 && masks[1];
     const size_t nc = d->use[0] ? n * d->cch : 0, nd = d->use[1] ? n * 2 : 0;     // only the sources of the set are staged and uploaded
     size_t bytes = nc + nd + (m0 ? n : 0) + (m1 ? n : 0);
-    if ((rc = ensure_pinned(d, bytes))) return rc;
-    uint8_t* st = (uint8_t*)d->pinned;
+    if ((rc = d->pinned.ensure(bytes))) return rc;
+    uint8_t* st = d->pinned.p;
     if (nc) memcpy(st, rgb, nc);
     if (nd) memcpy(st + nc, depth, nd);
     BorderStage bs{};
@@ -241,9 +241,9 @@ extern "C" int lm_detector_store_frame(lm_detector* d, int slot, const uint8_t* 
     if (nca && (rc = d->slot_rgb[slot].ensure(nca))) return rc;
     if (nda && (rc = d->slot_depth[slot].ensure(nda))) return rc;
     // staged through the detector's pinned buffer like every other upload (a pageable hipMemcpy stages internally, chunk by chunk)
-    if ((rc = ensure_pinned(d, nc + nd * 2))) return rc;
+    if ((rc = d->pinned.ensure(nc + nd * 2))) return rc;
     HIP_TRY(hipStreamSynchronize(d->stream));                              // the staging buffer is shared with upload_frame
-    uint8_t* st = (uint8_t*)d->pinned;
+    uint8_t* st = d->pinned.p;
     if (nc) memcpy(st, rgb, nc);
     if (nd) memcpy(st + nc, depth, nd * 2);
     if (bordered) {                                                        // the source as it is, then k_frame_border into the slot

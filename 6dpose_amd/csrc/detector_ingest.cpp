@@ -17,14 +17,8 @@ static int ingest_entry(lm_detector* d, int r, size_t n, size_t nsrc) {   // pix
     // cross PCIe —, the device entry the front end reads keeps the aligned size.
     g.src_depth_off = d->use[0] ? (nsrc * d->cch + 15) & ~(size_t)15 : 0;
     const size_t src_bytes = g.src_depth_off + (d->use[1] ? nsrc * 2 : 0);
-    if (g.pinned_bytes[r] < src_bytes) {
-        if (g.pinned[r]) (void)hipHostFree(g.pinned[r]);
-        g.pinned[r] = nullptr; g.pinned_bytes[r] = 0;
-        HIP_TRY(hipHostMalloc(&g.pinned[r], src_bytes, hipHostMallocDefault));
-        g.pinned_bytes[r] = src_bytes;
-    }
     int rc;
-    if ((rc = g.d_rgb[r].ensure(bytes))) return rc;
+    if ((rc = g.pinned[r].ensure(src_bytes)) || (rc = g.d_rgb[r].ensure(bytes))) return rc;
     if (nsrc != n && (rc = g.d_src[r].ensure(src_bytes + 16))) return rc;   // (+16: k_frame_border fetches the aligned dwords around a unit)
     g.d_depth[r] = d->use[1] ? reinterpret_cast<uint16_t*>(g.d_rgb[r].p + g.depth_off) : nullptr;
     return LM_OK;
@@ -59,8 +53,8 @@ extern "C" int lm_detector_ingest_buffer(lm_detector* d, int width, int height, 
     *rgb = nullptr; *depth = nullptr;
     int r, rc = ingest_begin(d, width, height, &r);
     if (rc) return rc;
-    if (d->use[0]) *rgb = (uint8_t*)d->ingest.pinned[r];             // (null stays for a modality outside the set)
-    if (d->use[1]) *depth = (uint16_t*)((uint8_t*)d->ingest.pinned[r] + d->ingest.src_depth_off);
+    if (d->use[0]) *rgb = d->ingest.pinned[r].p;                      // (null stays for a modality outside the set)
+    if (d->use[1]) *depth = (uint16_t*)(d->ingest.pinned[r].p + d->ingest.src_depth_off);
     return LM_OK;
 }
 
@@ -73,7 +67,7 @@ extern "C" int lm_detector_submit_frame(lm_detector* d, const uint8_t* rgb, cons
     if (rc) return rc;
     const size_t n = (size_t)width * height;
     lm_detector::Ingest& g = d->ingest;
-    uint8_t* st = (uint8_t*)g.pinned[r];
+    uint8_t* st = g.pinned[r].p;
     const auto tp0 = std::chrono::steady_clock::now();
     const size_t nc = d->use[0] ? n * d->cch : 0, nd = d->use[1] ? n * 2 : 0;
     const bool bordered = width != d->fW || height != d->fH;     // the source is not aligned: the entry holds it as it is, k_frame_border (enqueue_border) writes the frame the front end reads

@@ -103,8 +103,7 @@ struct lm_detector {
     std::vector<DevBuf<uint8_t>> slot_rgb;      // frames parked in HBM (lm_detector_store_frame)
     std::vector<DevBuf<uint16_t>> slot_depth;
     std::vector<int> slot_w, slot_h;
-    void* pinned = nullptr;          // staging for H2D frame and D2H results
-    size_t pinned_bytes = 0;
+    PinBuf<uint8_t> pinned;          // staging for H2D frame and D2H results
     float last_h2d_ms = 0.f;
 
     // bank on device
@@ -148,10 +147,9 @@ struct lm_detector {
     // Result slots: the refinement kernel of a later frame writes into one pinned buffer while the host
     // collects an earlier frame from another (lm_detector_submit / lm_detector_collect).
     struct Slot {
-        Candidate* h_matches = nullptr;             // pinned: the raw records, copied from matches_dev when a collect asks for them
-        Candidate* h_distinct = nullptr;            // pinned: the same without exact duplicates (k_dedupe), unordered
-        uint32_t match_cap = 0;
-        unsigned long long* h_counters = nullptr;   // pinned: [0] candidate count, [1] distinct records, [2] records alive, [8..] 2 words of statistics per refinement block
+        PinBuf<Candidate> h_matches;                // the raw records, copied from matches_dev when a collect asks for them
+        PinBuf<Candidate> h_distinct;               // the same without exact duplicates (k_dedupe), unordered; as many as h_matches
+        PinBuf<unsigned long long> h_counters;      // [0] candidate count, [1] distinct records, [2] records alive, [8..] 2 words of statistics per refinement block
         // A BATCH of consecutive slots is launched together (one front end / coarse / refinement / duplicate-removal launch for all
         // its frames); the events below are those of the batch's first slot (`leader`).
         int leader = -1, batch_n = 1;               // first slot of the batch this frame was launched with, frames in that batch
@@ -232,7 +230,7 @@ struct lm_detector {
     // quantised maps of lvl[] are those of the resident frame already, so the front end of a lone frame only builds its response memories.
     struct Slabs {
         DevBuf<uint32_t> hist, modes;               // kDepthMaxBins counts; kDepthModeWords words of mode records
-        uint32_t* h_modes = nullptr;                // pinned copy of the mode records
+        PinBuf<uint32_t> h_modes;                   // copy of the mode records
         hipEvent_t modes_ready = nullptr;
         DevBuf<uint8_t> mask[kMaxLevels][3];        // [level][0 / 1: slab & user mask of that kind, 2: the slab alone]
         const uint8_t* mask_of[kMaxLevels][2] = {};
@@ -297,8 +295,7 @@ struct lm_detector {
     // and the front end reads it there.  An entry is free again when its frame was collected.
     struct Ingest {
         hipStream_t stream = nullptr;
-        void* pinned[kSlots] = {};
-        size_t pinned_bytes[kSlots] = {};
+        PinBuf<uint8_t> pinned[kSlots];
         DevBuf<uint8_t> d_rgb[kSlots];                 // colour image, then (16-byte aligned) the depth image: ONE upload per frame, the pinned entry has the same layout
         uint16_t* d_depth[kSlots] = {};                // = d_rgb + depth_off
         size_t depth_off = 0;
@@ -315,8 +312,7 @@ struct lm_detector {
         hipStream_t stream = nullptr;               // created with the detector; also runs the duplicate removal of pipelined frames
         DevBuf<int32_t> d_merged[kSlots];
         DevBuf<ulonglong2> d_runs;                  // scratch of the per-rank sort
-        int32_t* h_merged[kSlots] = {};             // pinned
-        size_t h_words[kSlots] = {};
+        PinBuf<int32_t> h_merged[kSlots];
         hipEvent_t done[kSlots] = {};
         int state[kSlots] = {};                     // 0 idle, 1 packed, 2 merged (result on its way to h_merged)
         int cap[kSlots] = {}, world[kSlots] = {};
@@ -340,7 +336,6 @@ struct lm_detector {
 
 
 // detector.cpp
-int ensure_pinned(lm_detector* d, size_t bytes);
 int lm_need_both(const lm_detector* d, const char* what);   // LM_OK for the default set, else LM_ERR_INVALID "<what> needs both modalities"
 extern const char* const kModalityName[2];                  // "ColorGradient", "DepthNormal"
 

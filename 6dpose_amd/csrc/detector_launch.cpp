@@ -4,21 +4,6 @@
 // goes out is decided by the launch-timing model (launch_model.h); the results come back through detector_collect.cpp.
 #include "detector_internal.h"
 
-static int ensure_slot_buffers(lm_detector* d, lm_detector::Slot& sl, uint32_t match_cap) {
-    if (!sl.h_counters)
-        HIP_TRY(hipHostMalloc((void**)&sl.h_counters, 8 * sizeof(unsigned long long), hipHostMallocDefault));
-    if (match_cap > sl.match_cap) {
-        if (sl.h_matches) (void)hipHostFree(sl.h_matches);
-        sl.h_matches = nullptr; sl.match_cap = 0;
-        HIP_TRY(hipHostMalloc((void**)&sl.h_matches, (size_t)match_cap * sizeof(Candidate), hipHostMallocDefault));
-        if (sl.h_distinct) (void)hipHostFree(sl.h_distinct);
-        sl.h_distinct = nullptr;
-        HIP_TRY(hipHostMalloc((void**)&sl.h_distinct, (size_t)match_cap * sizeof(Candidate), hipHostMallocDefault));
-        sl.match_cap = match_cap;
-    }
-    return LM_OK;
-}
-
 static int sync_all_streams(lm_detector* d) {
     HIP_TRY(hipStreamSynchronize(d->stream)); HIP_TRY(hipStreamSynchronize(d->mstream));
     if (d->xchg.stream) HIP_TRY(hipStreamSynchronize(d->xchg.stream));
@@ -98,8 +83,8 @@ static int frame_slot(lm_detector* d, int si, bool tiled, uint32_t tile_cap, Fra
     F.distinct_keys = d->d_distinct_keys.p + (size_t)cc * si;
     F.final_dev = d->d_final.p + 8 * (size_t)si;
     F.matches = nullptr;                                  // (k_local no longer stores the raw records into host memory: 16-byte PCIe writes per candidate)
-    HIP_TRY(hipHostGetDevicePointer((void**)&F.distinct, sl.h_distinct, 0));
-    HIP_TRY(hipHostGetDevicePointer((void**)&F.final_host, sl.h_counters, 0));
+    HIP_TRY(hipHostGetDevicePointer((void**)&F.distinct, sl.h_distinct.p, 0));
+    HIP_TRY(hipHostGetDevicePointer((void**)&F.final_host, sl.h_counters.p, 0));
     *out = F;
     return LM_OK;
 }
@@ -157,7 +142,7 @@ int slot_begin(lm_detector* d, float threshold, const char* const* class_ids, in
     }
     const int si = (int)(d->n_submitted % K);
     lm_detector::Slot& sl = d->slot[si];
-    if ((rc = ensure_slot_buffers(d, sl, std::max<uint32_t>(sl.match_cap, d->buf_cand_cap)))) return rc;
+    if ((rc = sl.h_counters.ensure(8)) || (rc = sl.h_matches.ensure(d->buf_cand_cap)) || (rc = sl.h_distinct.ensure(d->buf_cand_cap))) return rc;
     sl.t0 = std::chrono::steady_clock::now();
     sl.threshold = threshold; sl.num_work = num_work; sl.coarse_bytes = d->work_coarse_bytes; sl.h2d_ms = d->last_h2d_ms;
     sl.work_cls = d->work_cls; sl.work_tid = d->work_tid;
@@ -220,7 +205,7 @@ static int batch_begin(lm_detector* d, Batch& B) {
     B.cbits = B.cwide || B.parts || cbits_active(d, B.num_work);
     B.tiled = !B.bits && tiles_wanted(d) && B.num_work > 0 && tile_plan_possible(d->geom);
     B.tile_cap = d->buf_cand_cap / 2;
-    B.cap = std::min<uint32_t>(lead.match_cap, d->buf_cand_cap);
+    B.cap = std::min<uint32_t>((uint32_t)lead.h_matches.cap, d->buf_cand_cap);
     B.s = d->mstream;
     B.fb.nb = B.nb;
     B.bank = BankDev{d->d_entries.p, d->d_feat_off.p, d->d_feat_word.p, d->d_run_mask.p, d->d_feat_xy.p, d->d_work.p};

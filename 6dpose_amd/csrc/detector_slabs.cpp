@@ -37,7 +37,7 @@ static int enqueue_modes(lm_detector* d, const lm_depth_mode_options& o, int nbi
     lm_detector::Slabs& S = d->slabs;
     int rc;
     if ((rc = S.hist.ensure(kDepthMaxBins)) || (rc = S.modes.ensure(kDepthModeWords))) return rc;
-    if (!S.h_modes) HIP_TRY(hipHostMalloc((void**)&S.h_modes, kDepthModeWords * sizeof(uint32_t), hipHostMallocDefault));
+    if ((rc = S.h_modes.ensure(kDepthModeWords))) return rc;
     if (!S.modes_ready) HIP_TRY(hipEventCreateWithFlags(&S.modes_ready, hipEventDisableTiming));
     HIP_TRY(hipMemsetAsync(S.hist.p, 0, (size_t)nbins * sizeof(uint32_t), d->stream));
     DepthHistArgs a{};
@@ -47,14 +47,14 @@ static int enqueue_modes(lm_detector* d, const lm_depth_mode_options& o, int nbi
     a.hist = S.hist.p;
     HIP_TRY(launch_depth_hist(a, d->stream));
     HIP_TRY(launch_depth_nms(S.hist.p, nbins, o.near_mm, o.bin_mm, o.window, (uint32_t)o.min_pixels, o.max_modes, S.modes.p, d->stream));
-    HIP_TRY(hipMemcpyAsync(S.h_modes, S.modes.p, kDepthModeWords * sizeof(uint32_t), hipMemcpyDeviceToHost, d->stream));
+    HIP_TRY(hipMemcpyAsync(S.h_modes.p, S.modes.p, kDepthModeWords * sizeof(uint32_t), hipMemcpyDeviceToHost, d->stream));
     HIP_TRY(hipEventRecord(S.modes_ready, d->stream));
     return LM_OK;
 }
 
 static int wait_modes(lm_detector* d, int max_modes, lm_depth_mode* out, int* n) {
     HIP_TRY(hipEventSynchronize(d->slabs.modes_ready));
-    const uint32_t* w = d->slabs.h_modes;
+    const uint32_t* w = d->slabs.h_modes.p;
     *n = (int)std::min<uint32_t>(w[0], (uint32_t)max_modes);
     for (int k = 0; k < *n; ++k) { out[k].bin = (int32_t)w[4 + 3 * k]; out[k].depth_mm = (int32_t)w[5 + 3 * k]; out[k].pixels = w[6 + 3 * k]; }
     return LM_OK;

@@ -103,16 +103,10 @@ extern "C" int lm_detector_exchange_merge_group_strided(lm_detector* d, uint64_t
         if (d->xchg.state[slot] != 1 || d->xchg.cap[slot] != capacity)
             return lm_set_error(LM_ERR_INVALID, "lm_detector_exchange_pack(capacity %d) has to precede the merge of a frame", capacity);
         int rc = d->xchg.d_merged[slot].ensure(words);                                   // the slot's previous frame was collected: buffers are idle
-        if (rc) return rc;
-        if (d->xchg.h_words[slot] < words) {
-            if (d->xchg.h_merged[slot]) (void)hipHostFree(d->xchg.h_merged[slot]);
-            d->xchg.h_merged[slot] = nullptr; d->xchg.h_words[slot] = 0;
-            HIP_TRY(hipHostMalloc((void**)&d->xchg.h_merged[slot], words * sizeof(int32_t), hipHostMallocDefault));
-            d->xchg.h_words[slot] = words;
-        }
+        if (rc || (rc = d->xchg.h_merged[slot].ensure(words))) return rc;
         G.f[i].recv = (const uint32_t*)((const uint8_t*)recv_blocks + (size_t)i * blk);
         G.f[i].merged = d->xchg.d_merged[slot].p;
-        HIP_TRY(hipHostGetDevicePointer((void**)&G.f[i].host, d->xchg.h_merged[slot], 0));
+        HIP_TRY(hipHostGetDevicePointer((void**)&G.f[i].host, d->xchg.h_merged[slot].p, 0));
     }
     hipStream_t xs = d->xchg.stream;
     launch_exchange_merge_group(G, world, (uint32_t)capacity, xs, (uint32_t)(rank_stride_bytes / 4));   // merge + copy-out to the pinned buffers
@@ -172,7 +166,7 @@ static int exchange_collect(lm_detector* d, lm_match* dst, size_t dst_capacity, 
     d->xchg.state[slot] = 0;
     const int rc = lm_collect_frame(d, -1, nullptr, nullptr);                        // retires the frame (timings, overflow bookkeeping)
     if (rc < 0) return rc;
-    const int32_t* h = d->xchg.h_merged[slot];
+    const int32_t* h = d->xchg.h_merged[slot].p;
     const uint32_t flags = (uint32_t)h[1];
     if (rc == 1 && !(flags & kXchgCandOverflow))
         return lm_set_error(LM_ERR_HIP, "candidate overflow seen by the host but not by the exchange");

@@ -1,6 +1,7 @@
 // Private view of the ICP context shared by pose_refine.cpp and pipeline.cpp (not part of the C ABI).
 #pragma once
 #include "../../include/amd_linemod.h"
+#include "dev_buf.h"
 #include "icp_kernels.h"
 #include <vector>
 
@@ -18,25 +19,33 @@ struct lm_icp {
     int slots = 0;                 // resident model depth images
     int max_count = 0;             // hypotheses the arenas hold
     int last_count = 0, last_flags = 0;
-    uint16_t* d_scene = nullptr;
-    uint16_t* d_models = nullptr;
-    int* d_model_bbox = nullptr;   // [slots][8] bounding box of a resident model depth image (x0, y0, x1, y1, state: 1 = known, -, -, -): worked out at upload (k_icp_model_boxes)
+    DevBuf<uint16_t> d_scene;      // [H][W]
+    DevBuf<uint16_t> d_models;     // [slots][H][W]
+    DevBuf<int> d_model_bbox;      // [slots][8] bounding box of a resident model depth image (x0, y0, x1, y1, state: 1 = known, -, -, -): worked out at upload (k_icp_model_boxes)
     std::vector<uint8_t> slot_boxed;   // host view of the state words: 1 = the slot's box was worked out at upload
-    IcpIn* d_in = nullptr;
-    IcpState* d_st = nullptr;
-    IcpBuffers B{};
-    void* pinned = nullptr;        // staging for images
-    size_t pinned_bytes = 0;
-    IcpIn* h_in = nullptr;         // pinned
-    IcpState* h_st = nullptr;      // pinned: the states uploaded before / read after a run
-    IcpState* h_st2 = nullptr;     // pinned: read-back of lm_icp_run (h_st keeps the initial states for a repeated run)
-    int h_cap = 0;
+    // What max_count hypotheses need, allocated together (lm_icp_ensure_arenas) and dropped together (`ar = {}`): the arenas under the
+    // names and with the layouts of IcpBuffers, the hypothesis tables and their pinned twins.
+    struct Arenas {
+        DevBuf<double> model_pts, scene_pts, src, tgt, tgt_sorted, cov, normals, work, nn_lb, strip_sum, strip_mm, partial;
+        DevBuf<int> tgt_orig, cell_start, prev_nn, strip_cnt;
+        DevBuf<lm::TgtRec> tgt_rec;
+        DevBuf<unsigned short> cell_start16;
+        DevBuf<unsigned long long> strip_pub, keys, xchg;
+        DevBuf<unsigned int> sort_look;
+        DevBuf<IcpIn> in;
+        DevBuf<IcpState> st;
+        PinBuf<IcpIn> h_in;
+        PinBuf<IcpState> h_st;     // the states uploaded before / read after a run
+        PinBuf<IcpState> h_st2;    // read-back of lm_icp_run (h_st keeps the initial states for a repeated run)
+    } ar;
+    PinBuf<uint8_t> pinned;        // staging for images
     int cus = 0;                   // compute units of the device: the grid of k_icp_team
     bool sliced_only = false;      // LM_ICP_SLICED=1: RegistrationICP as one launch per evaluation (k_icp_eval, rounds 1-5), no k_icp_team
     std::vector<int> stage;        // per hypothesis of the last run: the lm::IcpStage that finished it
     lm_icp_options opt = {30, 0, 1e-6, 1e-6};   // ICPConvergenceCriteria (lm_icp_set_options)
     bool run_p2p = false;          // the run in flight: LM_ICP_POINT_TO_POINT
     int next_it = 0;               // the run in flight: first evaluation the sliced launches have not been enqueued for
+    IcpBuffers buffers() const;    // what the kernels take, from the buffers as they are now; the caller sets scene, sK and count (pose_refine.cpp)
 };
 
 

@@ -27,22 +27,15 @@ struct lm_pipeline {
     std::vector<float> view_K, view_R, view_t;    // per slot: 9, 9, 3
     std::vector<int32_t> view_valid;
     std::vector<int32_t> view_wh;                 // per slot: NMS box width, height (-1: the template's size)
-    int32_t* d_view_wh = nullptr;
     bool views_dirty = true;
-    float* d_view_K = nullptr;
-    int32_t* d_view_valid = nullptr;
-    int view_cap = 0;
-    int32_t* d_class_base = nullptr;
-    int class_cap = 0;
-    TopkSel* d_sel = nullptr;
-    int32_t* d_nsel = nullptr;
-    int sel_cap = 0;
-    void* d_scratch = nullptr;
-    size_t scratch_cap = 0;
-    TopkSel* h_sel = nullptr;                     // pinned
-    int32_t* h_nsel = nullptr;                    // pinned
-    int32_t* h_class_base = nullptr;              // pinned
-    int h_cap = 0, h_class_cap = 0;
+    DevBuf<float> d_view_K;                       // the view tables on the device: replaced and uploaded together (ensure_run_buffers)
+    DevBuf<int32_t> d_view_valid, d_view_wh;
+    DevBuf<int32_t> d_class_base;
+    DevBuf<TopkSel> d_sel;
+    DevBuf<int32_t> d_nsel;                       // kept, refused, distinct records, (pad)
+    DevBuf<uint8_t> d_scratch;                    // of launch_topk_nms
+    PinBuf<TopkSel> h_sel;
+    PinBuf<int32_t> h_nsel, h_class_base;
     std::vector<int32_t> class_base_on_device;    // what d_class_base holds (re-uploaded only when it changes)
     hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr;
 };
@@ -75,16 +68,11 @@ extern "C" void lm_pipeline_destroy(lm_pipeline* p) {
     (void)hipSetDevice(p->det->device);
     (void)hipStreamSynchronize(p->det->stream);
     (void)hipStreamSynchronize(p->det->mstream);
-    void* dev[] = {p->d_view_K, p->d_view_valid, p->d_view_wh, p->d_class_base, p->d_sel, p->d_nsel, p->d_scratch};
-    for (void* q : dev) if (q) (void)hipFree(q);
-    p->border_src.release();
-    void* pin[] = {p->h_sel, p->h_nsel, p->h_class_base};
-    for (void* q : pin) if (q) (void)hipHostFree(q);
-    if (p->e0) (void)hipEventDestroy(p->e0);
-    if (p->e1) (void)hipEventDestroy(p->e1);
-    if (p->e2) (void)hipEventDestroy(p->e2);
-    lm_icp_destroy(p->icp);
-    delete p;
+    hipEvent_t ev[] = {p->e0, p->e1, p->e2};
+    lm_icp* icp = p->icp;
+    delete p;                                                     // every buffer: device selected, the detector's streams idle
+    for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+    lm_icp_destroy(icp);
 }
 
 extern "C" int lm_pipeline_set_icp_options(lm_pipeline* p, const lm_icp_options* options) {
@@ -92,13 +80,8 @@ extern "C" int lm_pipeline_set_icp_options(lm_pipeline* p, const lm_icp_options*
     return lm_icp_set_options(p->icp, options);
 }
 
-extern "C" int lm_pipeline_set_views(lm_pipeline* p, const char* class_id, int first_template, int count, const uint16_t* const* depth_ren,
-                                     const float* Ks, const float* Rs, const float* ts, const int32_t* box_wh) {
-    if (!p || !class_id || first_template < 0 || count < 0 || (count && (!depth_ren || !Ks || !Rs || !ts)))
-        return lm_set_error(LM_ERR_INVALID, "null argument");
-    const int nt = lm_detector_num_templates(p->det, class_id);
-    if (nt <= 0) return lm_set_error(LM_ERR_NOT_FOUND, "class '%s' has no templates in the detector", class_id);
-    if (first_template + count > nt) return lm_set_error(LM_ERR_INVALID, "views [%d, %d) exceed the %d templates of class '%s'", first_template, first_template + count, nt, class_id);
+// The view slots of a class of nt templates: a new range behind those handed out (tables grown, slots not valid yet), or the one it has.
+static int claim_views(lm_pipeline* p, const char* class_id, int nt, int* base) {
     auto it = p->views.find(class_id);
     if (it == p->views.end()) {
         lm_pipeline::ClassViews cv;
@@ -111,11 +94,37 @@ extern "C" int lm_pipeline_set_views(lm_pipeline* p, const char* class_id, int f
     } else if (it->second.count != nt) {
         return lm_set_error(LM_ERR_INVALID, "class '%s' changed its template count after views were set", class_id);
     }
+    *base = it->second.base;
+    return LM_OK;
+}
+
+// K, R, t and the NMS box of `count` slots from slot0 on, now valid; the next run uploads the tables.
+static void record_views(lm_pipeline* p, int slot0, int count, const float* Ks, const float* Rs, const float* ts, const int32_t* box_wh) {
+    memcpy(&p->view_K[(size_t)slot0 * 9], Ks, (size_t)count * 9 * sizeof(float));
+    memcpy(&p->view_R[(size_t)slot0 * 9], Rs, (size_t)count * 9 * sizeof(float));
+    memcpy(&p->view_t[(size_t)slot0 * 3], ts, (size_t)count * 3 * sizeof(float));
+    for (int i = 0; i < count; ++i) {
+        p->view_valid[(size_t)slot0 + i] = 1;
+        p->view_wh[2 * ((size_t)slot0 + i)] = box_wh ? box_wh[2 * i] : -1;
+        p->view_wh[2 * ((size_t)slot0 + i) + 1] = box_wh ? box_wh[2 * i + 1] : -1;
+    }
+    p->views_dirty = true;
+}
+
+extern "C" int lm_pipeline_set_views(lm_pipeline* p, const char* class_id, int first_template, int count, const uint16_t* const* depth_ren,
+                                     const float* Ks, const float* Rs, const float* ts, const int32_t* box_wh) {
+    if (!p || !class_id || first_template < 0 || count < 0 || (count && (!depth_ren || !Ks || !Rs || !ts)))
+        return lm_set_error(LM_ERR_INVALID, "null argument");
+    const int nt = lm_detector_num_templates(p->det, class_id);
+    if (nt <= 0) return lm_set_error(LM_ERR_NOT_FOUND, "class '%s' has no templates in the detector", class_id);
+    if (first_template + count > nt) return lm_set_error(LM_ERR_INVALID, "views [%d, %d) exceed the %d templates of class '%s'", first_template, first_template + count, nt, class_id);
+    int base = 0;
+    if (int rc = claim_views(p, class_id, nt, &base)) return rc;
     if (count == 0) return LM_OK;
     HIP_TRY(hipSetDevice(p->det->device));
     HIP_TRY(hipStreamSynchronize(p->det->stream));                 // the slot array may be reallocated: no frame may be in flight
     HIP_TRY(hipStreamSynchronize(p->det->mstream));
-    const int slot0 = it->second.base + first_template;
+    const int slot0 = base + first_template;
     int rc;
     if (p->srcW == p->W && p->srcH == p->H) {
         if ((rc = lm_icp_set_models(p->icp, slot0, count, depth_ren))) return rc;
@@ -132,24 +141,16 @@ extern "C" int lm_pipeline_set_views(lm_pipeline* p, const char* class_id, int f
             BorderStage bs{};
             for (int i = 0; i < n; ++i) {
                 HIP_TRY(hipMemcpyAsync(p->border_src.p + (size_t)i * src_img, depth_ren[c0 + i], src_img, hipMemcpyHostToDevice, p->icp->s));
-                border_job(bs.job[bs.njobs++], p->border_src.p + (size_t)i * src_img, p->icp->d_models + ((size_t)slot0 + c0 + i) * npx, p->srcW, p->srcH, p->W, p->H, 2, false);
+                border_job(bs.job[bs.njobs++], p->border_src.p + (size_t)i * src_img, p->icp->d_models.p + ((size_t)slot0 + c0 + i) * npx, p->srcW, p->srcH, p->W, p->H, 2, false);
             }
             HIP_TRY(launch_frame_border(bs, p->icp->s));
             HIP_TRY(hipStreamSynchronize(p->icp->s));              // the staging buffer serves the next eight
         }
-        HIP_TRY(lm::launch_icp_model_boxes(p->icp->d_models, p->icp->d_model_bbox, slot0, count, p->W, p->H, p->icp->s));   // the boxes of the new images, once (LL.cpp:43-50)
+        HIP_TRY(lm::launch_icp_model_boxes(p->icp->d_models.p, p->icp->d_model_bbox.p, slot0, count, p->W, p->H, p->icp->s));   // the boxes of the new images, once (LL.cpp:43-50)
         for (int i = 0; i < count; ++i) p->icp->slot_boxed[(size_t)slot0 + i] = 1;
     }
     HIP_TRY(hipStreamSynchronize(p->icp->s));
-    memcpy(&p->view_K[(size_t)slot0 * 9], Ks, (size_t)count * 9 * sizeof(float));
-    memcpy(&p->view_R[(size_t)slot0 * 9], Rs, (size_t)count * 9 * sizeof(float));
-    memcpy(&p->view_t[(size_t)slot0 * 3], ts, (size_t)count * 3 * sizeof(float));
-    for (int i = 0; i < count; ++i) {
-        p->view_valid[(size_t)slot0 + i] = 1;
-        p->view_wh[2 * ((size_t)slot0 + i)] = box_wh ? box_wh[2 * i] : -1;
-        p->view_wh[2 * ((size_t)slot0 + i) + 1] = box_wh ? box_wh[2 * i + 1] : -1;
-    }
-    p->views_dirty = true;
+    record_views(p, slot0, count, Ks, Rs, ts, box_wh);
     return LM_OK;
 }
 
@@ -164,23 +165,13 @@ extern "C" int lm_pipeline_set_views_rendered(lm_pipeline* p, lm_mesh* m, const 
     const int nt = lm_detector_num_templates(p->det, class_id);
     if (nt <= 0) return lm_set_error(LM_ERR_NOT_FOUND, "class '%s' has no templates in the detector", class_id);
     if (first_template + count > nt) return lm_set_error(LM_ERR_INVALID, "views [%d, %d) exceed the %d templates of class '%s'", first_template, first_template + count, nt, class_id);
-    auto it = p->views.find(class_id);
-    if (it == p->views.end()) {
-        lm_pipeline::ClassViews cv;
-        cv.base = p->num_views; cv.count = nt;
-        p->num_views += nt;
-        p->view_K.resize((size_t)p->num_views * 9, 0.f); p->view_R.resize((size_t)p->num_views * 9, 0.f);
-        p->view_t.resize((size_t)p->num_views * 3, 0.f); p->view_valid.resize((size_t)p->num_views, 0);
-        p->view_wh.resize((size_t)p->num_views * 2, -1);
-        it = p->views.emplace(class_id, cv).first;
-    } else if (it->second.count != nt) {
-        return lm_set_error(LM_ERR_INVALID, "class '%s' changed its template count after views were set", class_id);
-    }
+    int base = 0;
+    if (int rc = claim_views(p, class_id, nt, &base)) return rc;
     if (count == 0) return LM_OK;
     HIP_TRY(hipSetDevice(p->det->device));
     HIP_TRY(hipStreamSynchronize(p->det->stream));
     HIP_TRY(hipStreamSynchronize(p->det->mstream));
-    const int slot0 = it->second.base + first_template;
+    const int slot0 = base + first_template;
     int rc = lm_icp_ensure_slots(p->icp, slot0 + count);
     if (rc) return rc;
     const size_t npx = (size_t)p->W * p->H;
@@ -190,73 +181,32 @@ extern "C" int lm_pipeline_set_views_rendered(lm_pipeline* p, lm_mesh* m, const 
         if ((rc = lm_mesh_render_device(m, n, p->W, p->H, Ks + 9 * (size_t)c0, Rs + 9 * (size_t)c0, ts + 3 * (size_t)c0, clip_near, clip_far, 0.f,
                                         1, true, false)))
             return rc;
-        HIP_TRY(hipMemcpyAsync(p->icp->d_models + ((size_t)slot0 + c0) * npx, m->d_depth.p, (size_t)n * npx * sizeof(uint16_t),
+        HIP_TRY(hipMemcpyAsync(p->icp->d_models.p + ((size_t)slot0 + c0) * npx, m->d_depth.p, (size_t)n * npx * sizeof(uint16_t),
                                hipMemcpyDeviceToDevice, m->s));
-        HIP_TRY(lm::launch_icp_model_boxes(p->icp->d_models, p->icp->d_model_bbox, slot0 + c0, n, p->W, p->H, m->s));   // the boxes of the new views, once (LL.cpp:43-50)
+        HIP_TRY(lm::launch_icp_model_boxes(p->icp->d_models.p, p->icp->d_model_bbox.p, slot0 + c0, n, p->W, p->H, m->s));   // the boxes of the new views, once (LL.cpp:43-50)
         for (int i = 0; i < n; ++i) p->icp->slot_boxed[(size_t)slot0 + c0 + i] = 1;
         HIP_TRY(hipStreamSynchronize(m->s));
     }
-    memcpy(&p->view_K[(size_t)slot0 * 9], Ks, (size_t)count * 9 * sizeof(float));
-    memcpy(&p->view_R[(size_t)slot0 * 9], Rs, (size_t)count * 9 * sizeof(float));
-    memcpy(&p->view_t[(size_t)slot0 * 3], ts, (size_t)count * 3 * sizeof(float));
-    for (int i = 0; i < count; ++i) {
-        p->view_valid[(size_t)slot0 + i] = 1;
-        p->view_wh[2 * ((size_t)slot0 + i)] = box_wh ? box_wh[2 * i] : -1;
-        p->view_wh[2 * ((size_t)slot0 + i) + 1] = box_wh ? box_wh[2 * i + 1] : -1;
-    }
-    p->views_dirty = true;
+    record_views(p, slot0, count, Ks, Rs, ts, box_wh);
     return LM_OK;
 }
 
 static int ensure_run_buffers(lm_pipeline* p, int top_k, int num_classes) {
-    lm_detector* d = p->det;
-    if (p->views_dirty || p->view_cap < p->num_views) {
-        if (p->view_cap < p->num_views) {
-            if (p->d_view_K) (void)hipFree(p->d_view_K);
-            if (p->d_view_valid) (void)hipFree(p->d_view_valid);
-            if (p->d_view_wh) (void)hipFree(p->d_view_wh);
-            p->d_view_K = nullptr; p->d_view_valid = nullptr; p->d_view_wh = nullptr;
-            p->view_cap = std::max(p->num_views, 1);
-            HIP_TRY(hipMalloc((void**)&p->d_view_K, (size_t)p->view_cap * 9 * sizeof(float)));
-            HIP_TRY(hipMalloc((void**)&p->d_view_valid, (size_t)p->view_cap * sizeof(int32_t)));
-            HIP_TRY(hipMalloc((void**)&p->d_view_wh, (size_t)p->view_cap * 2 * sizeof(int32_t)));
-        }
+    int rc;
+    const size_t views = (size_t)std::max(p->num_views, 1), classes = (size_t)std::max(num_classes, 8);
+    if (p->views_dirty || p->d_view_K.cap < views * 9) {          // new views, or tables about to be replaced: upload them
+        if ((rc = p->d_view_K.ensure(views * 9)) || (rc = p->d_view_valid.ensure(views)) || (rc = p->d_view_wh.ensure(views * 2))) return rc;
         if (p->num_views) {
-            HIP_TRY(hipMemcpy(p->d_view_K, p->view_K.data(), (size_t)p->num_views * 9 * sizeof(float), hipMemcpyHostToDevice));
-            HIP_TRY(hipMemcpy(p->d_view_valid, p->view_valid.data(), (size_t)p->num_views * sizeof(int32_t), hipMemcpyHostToDevice));
-            HIP_TRY(hipMemcpy(p->d_view_wh, p->view_wh.data(), (size_t)p->num_views * 2 * sizeof(int32_t), hipMemcpyHostToDevice));
+            HIP_TRY(hipMemcpy(p->d_view_K.p, p->view_K.data(), (size_t)p->num_views * 9 * sizeof(float), hipMemcpyHostToDevice));
+            HIP_TRY(hipMemcpy(p->d_view_valid.p, p->view_valid.data(), (size_t)p->num_views * sizeof(int32_t), hipMemcpyHostToDevice));
+            HIP_TRY(hipMemcpy(p->d_view_wh.p, p->view_wh.data(), (size_t)p->num_views * 2 * sizeof(int32_t), hipMemcpyHostToDevice));
         }
         p->views_dirty = false;
     }
-    if (top_k > p->sel_cap) {
-        if (p->d_sel) (void)hipFree(p->d_sel);
-        if (p->h_sel) (void)hipHostFree(p->h_sel);
-        p->d_sel = nullptr; p->h_sel = nullptr;
-        HIP_TRY(hipMalloc((void**)&p->d_sel, (size_t)top_k * sizeof(TopkSel)));
-        HIP_TRY(hipHostMalloc((void**)&p->h_sel, (size_t)top_k * sizeof(TopkSel), hipHostMallocDefault));
-        p->sel_cap = top_k;
-    }
-    if (!p->d_nsel) {
-        HIP_TRY(hipMalloc((void**)&p->d_nsel, 4 * sizeof(int32_t)));             // kept, refused, distinct records, (pad)
-        HIP_TRY(hipHostMalloc((void**)&p->h_nsel, 4 * sizeof(int32_t), hipHostMallocDefault));
-    }
-    if (num_classes > p->class_cap) {
-        if (p->d_class_base) (void)hipFree(p->d_class_base);
-        if (p->h_class_base) (void)hipHostFree(p->h_class_base);
-        p->d_class_base = nullptr; p->h_class_base = nullptr;
-        p->class_base_on_device.clear();
-        p->class_cap = std::max(num_classes, 8);
-        HIP_TRY(hipMalloc((void**)&p->d_class_base, (size_t)p->class_cap * sizeof(int32_t)));
-        HIP_TRY(hipHostMalloc((void**)&p->h_class_base, (size_t)p->class_cap * sizeof(int32_t), hipHostMallocDefault));
-    }
-    const size_t need = topk_nms_scratch_bytes(d->cand_cap);
-    if (need > p->scratch_cap) {
-        if (p->d_scratch) (void)hipFree(p->d_scratch);
-        p->d_scratch = nullptr; p->scratch_cap = 0;
-        HIP_TRY(hipMalloc(&p->d_scratch, need));
-        p->scratch_cap = need;
-    }
-    return LM_OK;
+    if ((rc = p->d_sel.ensure((size_t)top_k)) || (rc = p->h_sel.ensure((size_t)top_k)) || (rc = p->d_nsel.ensure(4)) || (rc = p->h_nsel.ensure(4))) return rc;
+    if (p->d_class_base.cap < classes) p->class_base_on_device.clear();   // the table is replaced: the next run uploads it
+    if ((rc = p->d_class_base.ensure(classes)) || (rc = p->h_class_base.ensure(classes))) return rc;
+    return p->d_scratch.ensure(topk_nms_scratch_bytes(p->det->cand_cap));
 }
 
 extern "C" int lm_pipeline_run(lm_pipeline* p, float threshold, const char* const* class_ids, int num_class_ids, const float* scene_K,
@@ -284,28 +234,28 @@ extern "C" int lm_pipeline_run(lm_pipeline* p, float threshold, const char* cons
         if ((rc = ensure_run_buffers(p, top_k, (int)order.size()))) return rc;
         for (size_t i = 0; i < order.size(); ++i) {
             auto it = p->views.find(order[i]);
-            p->h_class_base[i] = it == p->views.end() ? -1 : it->second.base;
+            p->h_class_base.p[i] = it == p->views.end() ? -1 : it->second.base;
         }
         if (!order.empty() && (p->class_base_on_device.size() != order.size() ||
-                               memcmp(p->class_base_on_device.data(), p->h_class_base, order.size() * sizeof(int32_t)) != 0)) {
+                               memcmp(p->class_base_on_device.data(), p->h_class_base.p, order.size() * sizeof(int32_t)) != 0)) {
             // the stream order keeps earlier frames' kernels ahead of this copy; the pinned source is stable until the next change
-            HIP_TRY(hipMemcpyAsync(p->d_class_base, p->h_class_base, order.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
-            p->class_base_on_device.assign(p->h_class_base, p->h_class_base + order.size());
+            HIP_TRY(hipMemcpyAsync(p->d_class_base.p, p->h_class_base.p, order.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
+            p->class_base_on_device.assign(p->h_class_base.p, p->h_class_base.p + order.size());
         }
         HIP_TRY(hipEventRecord(p->e1, s));
         const int slot = (int)((d->n_submitted - 1) % lm_detector::kSlots);          // the frame just submitted
         launch_topk_nms(d->d_matches_dev.p + (size_t)d->buf_cand_cap * slot, d->d_final.p + 8 * (size_t)slot, d->buf_cand_cap, d->d_work.p, d->d_work_cls.p, d->d_work_tid.p, d->d_entries.p,
-                        d->pyramid_levels, p->d_class_base, p->d_view_wh, p->num_views, top_k, nms_iou, p->d_scratch, p->d_sel, p->d_nsel, s);
-        launch_icp_bind(p->d_sel, p->d_nsel, p->d_class_base, p->d_view_K, p->d_view_valid, p->num_views, c->d_in, c->d_st, top_k, s);
+                        d->pyramid_levels, p->d_class_base.p, p->d_view_wh.p, p->num_views, top_k, nms_iou, p->d_scratch.p, p->d_sel.p, p->d_nsel.p, s);
+        launch_icp_bind(p->d_sel.p, p->d_nsel.p, p->d_class_base.p, p->d_view_K.p, p->d_view_valid.p, p->num_views, c->ar.in.p, c->ar.st.p, top_k, s);
         HIP_TRY(hipEventRecord(p->e2, s));
-        IcpBuffers B = c->B;
-        B.scene = d->cur_depth; B.models = c->d_models; B.model_bbox = c->d_model_bbox; B.in = c->d_in; B.st = c->d_st;
+        IcpBuffers B = c->buffers();
+        B.scene = d->cur_depth;
         B.count = top_k;
         memcpy(B.sK, scene_K, sizeof(B.sK));
         // (k_icp_bind only binds views that were uploaded, and both upload paths work out the boxes: 0x100 = no k_icp_bbox)
-        if ((rc = lm_icp_enqueue(c, B, (flags & 0xFF) | 0x100, c->h_st, s))) return rc;
-        HIP_TRY(hipMemcpyAsync(p->h_sel, p->d_sel, (size_t)top_k * sizeof(TopkSel), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(p->h_nsel, p->d_nsel, 3 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        if ((rc = lm_icp_enqueue(c, B, (flags & 0xFF) | 0x100, c->ar.h_st.p, s))) return rc;
+        HIP_TRY(hipMemcpyAsync(p->h_sel.p, p->d_sel.p, (size_t)top_k * sizeof(TopkSel), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(p->h_nsel.p, p->d_nsel.p, 3 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
         HIP_TRY(hipGetLastError());
         rc = lm_collect_frame(d, -1, nullptr, nullptr);          // retires the frame; 1 = candidate buffer overflow, rerun
@@ -314,16 +264,16 @@ extern "C" int lm_pipeline_run(lm_pipeline* p, float threshold, const char* cons
             continue;
         }
         if (rc) return rc;
-        if ((rc = lm_icp_finish(c, B, c->h_st, s))) return rc;
+        if ((rc = lm_icp_finish(c, B, c->ar.h_st.p, s))) return rc;
         break;
     }
-    if (p->h_nsel[1] != 0)
+    if (p->h_nsel.p[1] != 0)
         return lm_set_error(LM_ERR_INVALID, "on-device NMS: a match field exceeds the packed record (template id >= 2^24, class position >= 128 or |x|,|y| >= 32768)");
     c->last_count = top_k; c->last_flags = flags;
-    const int n = p->h_nsel[0];
+    const int n = p->h_nsel.p[0];
     for (int i = 0; i < n; ++i) {
-        const TopkSel& sl = p->h_sel[i];
-        const IcpState& st = c->h_st[i];
+        const TopkSel& sl = p->h_sel.p[i];
+        const IcpState& st = c->ar.h_st.p[i];
         lm_detection& o = out[i];
         memset(&o, 0, sizeof(o));
         o.match.x = sl.x; o.match.y = sl.y; o.match.similarity = sl.similarity;
@@ -335,7 +285,7 @@ extern "C" int lm_pipeline_run(lm_pipeline* p, float threshold, const char* cons
         if (st.status == 3) return lm_set_error(LM_ERR_INVALID, "detection %d: point cloud too large for 64-bit voxel keys", i);
         if (st.status == lm::kIcpStalled) return lm_set_error(LM_ERR_HIP, "detection %d: the point kernels stalled (strips waited a second for each other)", i);
         if (st.status != 0) continue;                             // 1: window leaves the frame (LL.cpp:52-55); 5: no view for the template
-        const int base = p->h_class_base[sl.class_index];
+        const int base = p->h_class_base.p[sl.class_index];
         const size_t v = (size_t)base + sl.template_id;
         lm_icp_compose_result(st, &p->view_R[v * 9], &p->view_t[v * 3], &o.pose);
         o.pose.stage = c->stage[(size_t)i];
@@ -350,9 +300,9 @@ extern "C" int lm_pipeline_run(lm_pipeline* p, float threshold, const char* cons
         tm->coarse_candidates = d->timings.coarse_candidates;
         tm->matches_pre_unique = d->timings.matches_pre_unique;
         int its = 0;
-        for (int i = 0; i < n; ++i) if (c->h_st[i].status == 0) its += c->h_st[i].iterations;
+        for (int i = 0; i < n; ++i) if (c->ar.h_st.p[i].status == 0) its += c->ar.h_st.p[i].iterations;
         tm->icp_iterations = its;
-        tm->nms_records = p->h_nsel[2];
+        tm->nms_records = p->h_nsel.p[2];
     }
     return LM_OK;
 }

@@ -34,111 +34,73 @@ size_t pow2_at_least(size_t n) {
 }
 }  // namespace
 
-namespace {
-
-void free_arenas(lm_icp* c) {
-    void* ptrs[] = {c->B.model_pts, c->B.scene_pts, c->B.src, c->B.tgt, c->B.tgt_sorted, c->B.tgt_orig, c->B.cell_start,
-                    c->B.cov, c->B.normals, c->B.work, c->B.prev_nn, c->B.nn_lb, c->B.partial, c->B.strip_cnt, c->B.strip_sum, c->B.tgt_rec, c->B.cell_start16, c->B.keys, c->B.xchg, c->B.strip_mm, c->B.strip_pub, c->B.sort_look, c->d_in, c->d_st};
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);
-    c->B = IcpBuffers{};
-    c->d_in = nullptr; c->d_st = nullptr;
-    if (c->h_in) (void)hipHostFree(c->h_in);
-    if (c->h_st) (void)hipHostFree(c->h_st);
-    if (c->h_st2) (void)hipHostFree(c->h_st2);
-    c->h_in = nullptr; c->h_st = nullptr; c->h_st2 = nullptr; c->h_cap = 0;
-    c->max_count = 0;
+IcpBuffers lm_icp::buffers() const {
+    IcpBuffers B{};
+    B.models = d_models.p; B.model_bbox = d_model_bbox.p; B.in = ar.in.p; B.st = ar.st.p;
+    B.cap = (size_t)W * H; B.cap2 = pow2_at_least(B.cap);
+    B.model_pts = ar.model_pts.p; B.scene_pts = ar.scene_pts.p; B.src = ar.src.p; B.tgt = ar.tgt.p; B.tgt_sorted = ar.tgt_sorted.p;
+    B.tgt_orig = ar.tgt_orig.p; B.tgt_rec = ar.tgt_rec.p; B.cell_start = ar.cell_start.p; B.cell_start16 = ar.cell_start16.p;
+    B.cov = ar.cov.p; B.normals = ar.normals.p; B.work = ar.work.p; B.prev_nn = ar.prev_nn.p; B.nn_lb = ar.nn_lb.p;
+    B.strip_cnt = ar.strip_cnt.p; B.strip_sum = ar.strip_sum.p; B.strip_pub = ar.strip_pub.p; B.strip_mm = ar.strip_mm.p;
+    B.sort_look = ar.sort_look.p; B.partial = ar.partial.p; B.keys = ar.keys.p; B.xchg = ar.xchg.p;
+    return B;
 }
 
-int ensure_pinned(lm_icp* c, size_t bytes) {
-    if (bytes <= c->pinned_bytes) return LM_OK;
-    if (c->pinned) (void)hipHostFree(c->pinned);
-    c->pinned = nullptr; c->pinned_bytes = 0;
-    HIP_TRY(hipHostMalloc(&c->pinned, bytes, hipHostMallocDefault));
-    c->pinned_bytes = bytes;
-    return LM_OK;
-}
-
-}  // namespace
 int lm_icp_ensure_arenas(lm_icp* c, int count) {
     if (count <= c->max_count) return LM_OK;
     HIP_TRY(hipStreamSynchronize(c->s));
-    free_arenas(c);
-    const int n = std::max(count, 16);
-    const size_t cap = (size_t)c->W * c->H, cap2 = pow2_at_least(cap);
-    const size_t pts = (size_t)n * cap * 3 * sizeof(double);
-    IcpBuffers& B = c->B;
-    B.cap = cap; B.cap2 = cap2;
-    HIP_TRY(hipMalloc((void**)&B.model_pts, pts));
-    HIP_TRY(hipMalloc((void**)&B.scene_pts, pts));
-    HIP_TRY(hipMalloc((void**)&B.src, pts));
-    HIP_TRY(hipMalloc((void**)&B.tgt, pts));
-    HIP_TRY(hipMalloc((void**)&B.tgt_sorted, pts));
-    HIP_TRY(hipMalloc((void**)&B.normals, pts));
-    HIP_TRY(hipMalloc((void**)&B.work, pts));
-    HIP_TRY(hipMalloc((void**)&B.cov, (size_t)n * cap * kIcpCovStride * sizeof(double)));
-    HIP_TRY(hipMalloc((void**)&B.tgt_orig, (size_t)n * cap * sizeof(int)));
-    HIP_TRY(hipMalloc((void**)&B.prev_nn, (size_t)n * cap * sizeof(int)));
-    HIP_TRY(hipMalloc((void**)&B.nn_lb, (size_t)n * cap * sizeof(double)));
-    HIP_TRY(hipMalloc((void**)&B.partial, (size_t)2 * n * kIcpMaxSplit * 32 * sizeof(double)));
-    HIP_TRY(hipMalloc((void**)&B.strip_cnt, (size_t)n * kIcpStrips * 2 * sizeof(int)));
-    HIP_TRY(hipMalloc((void**)&B.strip_sum, (size_t)n * kIcpStrips * 8 * sizeof(double)));
-    HIP_TRY(hipMalloc((void**)&B.strip_pub, (size_t)n * kIcpStrips * sizeof(unsigned long long)));
-    HIP_TRY(hipMemset(B.strip_pub, 0, (size_t)n * kIcpStrips * sizeof(unsigned long long)));                      // (0 = not counted yet; every run leaves them cleared for the next)
-    HIP_TRY(hipMalloc((void**)&B.strip_mm, (size_t)n * kIcpStrips * 12 * sizeof(double)));
-    HIP_TRY(hipMalloc((void**)&B.sort_look, (size_t)n * 2 * lm::kIcpSortGroups * sizeof(unsigned int)));
-    HIP_TRY(hipMalloc((void**)&B.tgt_rec, (size_t)n * cap * sizeof(TgtRec)));
-    HIP_TRY(hipMalloc((void**)&B.cell_start16, (size_t)n * kIcpCells16 * sizeof(unsigned short)));
-    HIP_TRY(hipMalloc((void**)&B.cell_start, (size_t)n * kIcpCells * sizeof(int)));
-    HIP_TRY(hipMalloc((void**)&B.keys, (size_t)n * 2 * cap2 * sizeof(unsigned long long)));
-    HIP_TRY(hipMalloc((void**)&B.xchg, (size_t)2 * n * lm::kIcpMaxSplit * 64 * sizeof(unsigned long long)));
-    HIP_TRY(hipMemset(B.xchg, 0, (size_t)2 * n * lm::kIcpMaxSplit * 64 * sizeof(unsigned long long)));      // tag 0 = never published (runs count from 1)
+    c->ar = lm_icp::Arenas{};                                        // all of them go before the first grows; a failure below leaves max_count 0
+    c->max_count = 0;
+    const size_t n = (size_t)std::max(count, 16), cap = (size_t)c->W * c->H, pts = n * cap * 3;
+    lm_icp::Arenas& a = c->ar;
+    int rc;
+    for (DevBuf<double>* b : {&a.model_pts, &a.scene_pts, &a.src, &a.tgt, &a.tgt_sorted, &a.normals, &a.work})
+        if ((rc = b->ensure(pts))) return rc;
+    if ((rc = a.cov.ensure(n * cap * kIcpCovStride)) || (rc = a.tgt_orig.ensure(n * cap)) || (rc = a.prev_nn.ensure(n * cap)) ||
+        (rc = a.nn_lb.ensure(n * cap)) || (rc = a.partial.ensure(2 * n * kIcpMaxSplit * 32)) || (rc = a.strip_cnt.ensure(n * kIcpStrips * 2)) ||
+        (rc = a.strip_sum.ensure(n * kIcpStrips * 8)) || (rc = a.strip_pub.ensure(n * kIcpStrips)) || (rc = a.strip_mm.ensure(n * kIcpStrips * 12)) ||
+        (rc = a.sort_look.ensure(n * 2 * kIcpSortGroups)) || (rc = a.tgt_rec.ensure(n * cap)) || (rc = a.cell_start16.ensure(n * kIcpCells16)) ||
+        (rc = a.cell_start.ensure(n * kIcpCells)) || (rc = a.keys.ensure(n * 2 * pow2_at_least(cap))) || (rc = a.xchg.ensure(2 * n * kIcpMaxSplit * 64)))
+        return rc;
+    HIP_TRY(hipMemset(a.strip_pub.p, 0, a.strip_pub.cap * sizeof(unsigned long long)));   // (0 = not counted yet; every run leaves them cleared for the next)
+    HIP_TRY(hipMemset(a.xchg.p, 0, a.xchg.cap * sizeof(unsigned long long)));             // tag 0 = never published (runs count from 1)
     HIP_TRY(hipDeviceSynchronize());                                 // (the ICP stream does not wait for the null stream)
-    HIP_TRY(hipMalloc((void**)&c->d_in, (size_t)n * sizeof(IcpIn)));
-    HIP_TRY(hipMalloc((void**)&c->d_st, (size_t)n * sizeof(IcpState)));
-    HIP_TRY(hipHostMalloc((void**)&c->h_in, (size_t)n * sizeof(IcpIn), hipHostMallocDefault));
-    HIP_TRY(hipHostMalloc((void**)&c->h_st, (size_t)n * sizeof(IcpState), hipHostMallocDefault));
-    HIP_TRY(hipHostMalloc((void**)&c->h_st2, (size_t)n * sizeof(IcpState), hipHostMallocDefault));
-    c->h_cap = n;
-    c->max_count = n;
+    if ((rc = a.in.ensure(n)) || (rc = a.st.ensure(n)) || (rc = a.h_in.ensure(n)) || (rc = a.h_st.ensure(n)) || (rc = a.h_st2.ensure(n))) return rc;
+    c->max_count = (int)n;
     return LM_OK;
 }
 
 int lm_icp_set_geometry(lm_icp* c, int W, int H) {
     if (W == c->W && H == c->H) return LM_OK;
     HIP_TRY(hipStreamSynchronize(c->s));
-    free_arenas(c);
-    if (c->d_scene) (void)hipFree(c->d_scene);
-    if (c->d_models) (void)hipFree(c->d_models);
-    if (c->d_model_bbox) (void)hipFree(c->d_model_bbox);
-    c->d_scene = nullptr; c->d_models = nullptr; c->d_model_bbox = nullptr; c->slots = 0; c->have_scene = false;
+    c->ar = lm_icp::Arenas{};
+    c->max_count = 0;
+    c->d_scene.release(); c->d_models.release(); c->d_model_bbox.release();
+    c->slots = 0; c->have_scene = false;
     c->slot_boxed.clear();
     c->W = W; c->H = H;
-    HIP_TRY(hipMalloc((void**)&c->d_scene, (size_t)W * H * sizeof(uint16_t)));
-    return LM_OK;
+    return c->d_scene.ensure((size_t)W * H);
 }
 
+// Grows the slot arrays and keeps what they hold (DevBuf::ensure would not): into buffers of its own, which a failing step frees.
 int lm_icp_ensure_slots(lm_icp* c, int slots) {
     if (slots <= c->slots) return LM_OK;
-    const size_t img = (size_t)c->W * c->H * sizeof(uint16_t);
+    const size_t px = (size_t)c->W * c->H;
     const int n = std::max(slots, std::max(16, c->slots * 2));
-    uint16_t* p = nullptr;
-    HIP_TRY(hipMalloc((void**)&p, (size_t)n * img));
-    if (c->d_models) {
-        HIP_TRY(hipMemcpyAsync(p, c->d_models, (size_t)c->slots * img, hipMemcpyDeviceToDevice, c->s));
+    DevBuf<uint16_t> models;
+    DevBuf<int> boxes;
+    int rc;
+    if ((rc = models.ensure((size_t)n * px))) return rc;
+    if (c->d_models.p) {
+        HIP_TRY(hipMemcpyAsync(models.p, c->d_models.p, (size_t)c->slots * px * sizeof(uint16_t), hipMemcpyDeviceToDevice, c->s));
         HIP_TRY(hipStreamSynchronize(c->s));
-        (void)hipFree(c->d_models);
     }
-    c->d_models = p;
-    int* boxes = nullptr;
-    HIP_TRY(hipMalloc((void**)&boxes, (size_t)n * 8 * sizeof(int)));
-    HIP_TRY(hipMemset(boxes, 0, (size_t)n * 8 * sizeof(int)));
-    if (c->d_model_bbox) {
-        HIP_TRY(hipMemcpy(boxes, c->d_model_bbox, (size_t)c->slots * 8 * sizeof(int), hipMemcpyDeviceToDevice));
-        (void)hipFree(c->d_model_bbox);
-    }
+    c->d_models = std::move(models);
+    if ((rc = boxes.ensure((size_t)n * 8))) return rc;
+    HIP_TRY(hipMemset(boxes.p, 0, (size_t)n * 8 * sizeof(int)));
+    if (c->d_model_bbox.p) HIP_TRY(hipMemcpy(boxes.p, c->d_model_bbox.p, (size_t)c->slots * 8 * sizeof(int), hipMemcpyDeviceToDevice));
     HIP_TRY(hipDeviceSynchronize());
-    c->d_model_bbox = boxes;
+    c->d_model_bbox = std::move(boxes);
     c->slot_boxed.resize((size_t)n, 0);
     c->slots = n;
     return LM_OK;
@@ -198,7 +160,7 @@ int lm_icp_enqueue(lm_icp* c, const IcpBuffers& B, int flags, IcpState* h_st, hi
     if (sliced_first(c)) enqueue_evals(c, B, s);
     else launch_icp_team(B, B.count, kIcpStageTeam, c->cus, kMaxDist, kMaxIter, kRelTol, s);
     HIP_TRY(hipEventRecord(c->e1, s));
-    HIP_TRY(hipMemcpyAsync(h_st, c->d_st, (size_t)B.count * sizeof(IcpState), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(h_st, B.st, (size_t)B.count * sizeof(IcpState), hipMemcpyDeviceToHost, s));
     return LM_OK;
 }
 
@@ -224,7 +186,7 @@ int lm_icp_finish(lm_icp* c, const IcpBuffers& B, IcpState* h_st, hipStream_t s)
             enqueue_evals(c, B, s);
         }
         HIP_TRY(hipEventRecord(c->e1, s));
-        HIP_TRY(hipMemcpyAsync(h_st, c->d_st, (size_t)B.count * sizeof(IcpState), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(h_st, B.st, (size_t)B.count * sizeof(IcpState), hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
         HIP_TRY(hipGetLastError());
     }
@@ -281,15 +243,12 @@ extern "C" void lm_icp_destroy(lm_icp* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     if (c->s) (void)hipStreamSynchronize(c->s);
-    free_arenas(c);
-    if (c->d_scene) (void)hipFree(c->d_scene);
-    if (c->d_models) (void)hipFree(c->d_models);
-    if (c->d_model_bbox) (void)hipFree(c->d_model_bbox);
-    if (c->pinned) (void)hipHostFree(c->pinned);
-    if (c->e0) (void)hipEventDestroy(c->e0);
-    if (c->e1) (void)hipEventDestroy(c->e1);
-    if (c->s) (void)hipStreamDestroy(c->s);
-    delete c;
+    hipStream_t s = c->s;
+    hipEvent_t e0 = c->e0, e1 = c->e1;
+    delete c;                                                         // every buffer: device selected, stream idle and still alive
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+    if (s) (void)hipStreamDestroy(s);
 }
 
 extern "C" int lm_icp_set_scene(lm_icp* c, const uint16_t* scene_depth, int width, int height, const float* scene_K) {
@@ -299,9 +258,9 @@ extern "C" int lm_icp_set_scene(lm_icp* c, const uint16_t* scene_depth, int widt
     if (rc) return rc;
     const size_t img = (size_t)width * height * sizeof(uint16_t);
     HIP_TRY(hipStreamSynchronize(c->s));                            // the staging buffer may still be in flight
-    if ((rc = ensure_pinned(c, img))) return rc;
-    memcpy(c->pinned, scene_depth, img);
-    HIP_TRY(hipMemcpyAsync(c->d_scene, c->pinned, img, hipMemcpyHostToDevice, c->s));
+    if ((rc = c->pinned.ensure(img))) return rc;
+    memcpy(c->pinned.p, scene_depth, img);
+    HIP_TRY(hipMemcpyAsync(c->d_scene.p, c->pinned.p, img, hipMemcpyHostToDevice, c->s));
     memcpy(c->sK, scene_K, sizeof(c->sK));
     c->have_scene = true;
     return LM_OK;
@@ -319,11 +278,11 @@ extern "C" int lm_icp_set_models(lm_icp* c, int first_slot, int count, const uin
     const size_t img = (size_t)c->W * c->H * sizeof(uint16_t);
     HIP_TRY(hipStreamSynchronize(c->s));
     // the scene image may sit at the start of the staging buffer and still be copying: keep it, append after it
-    if ((rc = ensure_pinned(c, img * (size_t)(count + 1)))) return rc;
-    uint8_t* stage = (uint8_t*)c->pinned + img;
+    if ((rc = c->pinned.ensure(img * (size_t)(count + 1)))) return rc;
+    uint8_t* stage = c->pinned.p + img;
     for (int i = 0; i < count; ++i) memcpy(stage + (size_t)i * img, model_depths[i], img);
-    HIP_TRY(hipMemcpyAsync(c->d_models + (size_t)first_slot * c->W * c->H, stage, img * (size_t)count, hipMemcpyHostToDevice, c->s));
-    HIP_TRY(lm::launch_icp_model_boxes(c->d_models, c->d_model_bbox, first_slot, count, c->W, c->H, c->s));   // the boxes of the new images, once (LL.cpp:43-50)
+    HIP_TRY(hipMemcpyAsync(c->d_models.p + (size_t)first_slot * c->W * c->H, stage, img * (size_t)count, hipMemcpyHostToDevice, c->s));
+    HIP_TRY(lm::launch_icp_model_boxes(c->d_models.p, c->d_model_bbox.p, first_slot, count, c->W, c->H, c->s));   // the boxes of the new images, once (LL.cpp:43-50)
     for (int i = 0; i < count; ++i) c->slot_boxed[(size_t)first_slot + i] = 1;
     return LM_OK;
 }
@@ -343,40 +302,40 @@ extern "C" int lm_icp_run(lm_icp* c, int count, const int32_t* model_slots, cons
     int rc = lm_icp_ensure_arenas(c, count);
     if (rc) return rc;
     for (int i = 0; i < count; ++i) {
-        IcpIn& in = c->h_in[i];
+        IcpIn& in = c->ar.h_in.p[i];
         memcpy(in.mK, model_Ks + 9 * i, sizeof(in.mK));
         in.dx = detect_xy[2 * i]; in.dy = detect_xy[2 * i + 1];
         in.model_slot = model_slots ? model_slots[i] : i;
         in.pad = 0;
-        IcpState& st = c->h_st[i];
+        IcpState& st = c->ar.h_st.p[i];
         memset(&st, 0, sizeof(st));
         st.bbox[0] = INT_MAX; st.bbox[1] = INT_MAX; st.bbox[2] = -1; st.bbox[3] = -1;
     }
-    IcpBuffers B = c->B;
-    B.scene = c->d_scene; B.models = c->d_models; B.model_bbox = c->d_model_bbox; B.in = c->d_in; B.st = c->d_st;
+    IcpBuffers B = c->buffers();
+    B.scene = c->d_scene.p;
     B.count = count;
     memcpy(B.sK, c->sK, sizeof(B.sK));
-    HIP_TRY(hipMemcpyAsync(c->d_in, c->h_in, (size_t)count * sizeof(IcpIn), hipMemcpyHostToDevice, c->s));
-    HIP_TRY(hipMemcpyAsync(c->d_st, c->h_st, (size_t)count * sizeof(IcpState), hipMemcpyHostToDevice, c->s));
+    HIP_TRY(hipMemcpyAsync(c->ar.in.p, c->ar.h_in.p, (size_t)count * sizeof(IcpIn), hipMemcpyHostToDevice, c->s));
+    HIP_TRY(hipMemcpyAsync(c->ar.st.p, c->ar.h_st.p, (size_t)count * sizeof(IcpState), hipMemcpyHostToDevice, c->s));
     HIP_TRY(hipEventRecord(c->e0, c->s));
     bool boxed = true;                                               // every slot's box was worked out when its image was uploaded: no k_icp_bbox
     for (int i = 0; i < count; ++i) boxed = boxed && c->slot_boxed[(size_t)(model_slots ? model_slots[i] : i)] != 0;
-    if ((rc = lm_icp_enqueue(c, B, (flags & 0xFF) | (boxed ? 0x100 : 0), c->h_st2, c->s))) return rc;
+    if ((rc = lm_icp_enqueue(c, B, (flags & 0xFF) | (boxed ? 0x100 : 0), c->ar.h_st2.p, c->s))) return rc;
     HIP_TRY(hipStreamSynchronize(c->s));
     HIP_TRY(hipGetLastError());
-    if ((rc = lm_icp_finish(c, B, c->h_st2, c->s))) return rc;
-    memcpy(c->h_st, c->h_st2, (size_t)count * sizeof(IcpState));
+    if ((rc = lm_icp_finish(c, B, c->ar.h_st2.p, c->s))) return rc;
+    memcpy(c->ar.h_st.p, c->ar.h_st2.p, (size_t)count * sizeof(IcpState));
     c->last_count = count; c->last_flags = flags;
     if (device_ms) (void)hipEventElapsedTime(device_ms, c->e0, c->e1);
     for (int i = 0; i < count; ++i) {
-        const IcpState& st = c->h_st[i];
+        const IcpState& st = c->ar.h_st.p[i];
         if (st.status == 2) return lm_set_error(LM_ERR_INVALID, "model depth image is empty");
         if (st.status == lm::kIcpStalled) return lm_set_error(LM_ERR_HIP, "hypothesis %d: the point kernels stalled (strips waited a second for each other)", i);
         if (st.status == 3)
             return lm_set_error(LM_ERR_INVALID, "hypothesis %d: point cloud too large for 64-bit voxel keys (depth spans tens of metres?)", i);
     }
     for (int i = 0; i < count; ++i) {
-        const IcpState& st = c->h_st[i];
+        const IcpState& st = c->ar.h_st.p[i];
         lm_pose_result& o = results[i];
         memset(&o, 0, sizeof(o));
         if (st.status == 1) { o.residual = -1.f; continue; }        // LL.cpp:52-55
@@ -389,21 +348,21 @@ extern "C" int lm_icp_run(lm_icp* c, int count, const int32_t* model_slots, cons
 extern "C" int64_t lm_icp_read_debug(lm_icp* c, int hypothesis, int kind, double* dst, int64_t capacity) {
     if (!c || hypothesis < 0 || hypothesis >= c->last_count) return lm_set_error(LM_ERR_INVALID, "no such hypothesis in the last run");
     if (hipSetDevice(c->device) != hipSuccess) return lm_set_error(LM_ERR_HIP, "hipSetDevice failed");
-    const IcpState& st = c->h_st[hypothesis];
-    const size_t off = (size_t)hypothesis * c->B.cap;
+    const IcpState& st = c->ar.h_st.p[hypothesis];
+    const size_t off = (size_t)hypothesis * c->W * c->H;
     const bool scene_mode = (c->last_flags & LM_ICP_SCENE_FROM_SCENE) != 0;
     std::vector<double> tmp;
     int64_t n = 0;
     switch (kind) {
         case 0: {   // source cloud
             n = (int64_t)st.n_src * 3; tmp.resize((size_t)n);
-            if (n && hipMemcpy(tmp.data(), c->B.src + off * 3, (size_t)n * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
+            if (n && hipMemcpy(tmp.data(), c->ar.src.p + off * 3, (size_t)n * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
                 return lm_set_error(LM_ERR_HIP, "read-back failed");
             break;
         }
         case 1: {   // target cloud, original (voxel) order
             n = (int64_t)st.n_tgt * 3; tmp.resize((size_t)n);
-            if (n && hipMemcpy(tmp.data(), (scene_mode ? c->B.tgt : c->B.src) + off * 3, (size_t)n * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
+            if (n && hipMemcpy(tmp.data(), (scene_mode ? c->ar.tgt.p : c->ar.src.p) + off * 3, (size_t)n * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
                 return lm_set_error(LM_ERR_HIP, "read-back failed");
             break;
         }
@@ -411,8 +370,8 @@ extern "C" int64_t lm_icp_read_debug(lm_icp* c, int hypothesis, int kind, double
             n = (int64_t)st.n_tgt * 3; tmp.resize((size_t)n);
             std::vector<double> sorted((size_t)n);
             std::vector<int> orig((size_t)st.n_tgt);
-            if (n && (hipMemcpy(sorted.data(), c->B.normals + off * 3, (size_t)n * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess ||
-                      hipMemcpy(orig.data(), c->B.tgt_orig + off, (size_t)st.n_tgt * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess))
+            if (n && (hipMemcpy(sorted.data(), c->ar.normals.p + off * 3, (size_t)n * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess ||
+                      hipMemcpy(orig.data(), c->ar.tgt_orig.p + off, (size_t)st.n_tgt * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess))
                 return lm_set_error(LM_ERR_HIP, "read-back failed");
             for (int p = 0; p < st.n_tgt; ++p)
                 for (int k = 0; k < 3; ++k) tmp[(size_t)orig[p] * 3 + k] = sorted[(size_t)p * 3 + k];
@@ -441,14 +400,14 @@ extern "C" int64_t lm_icp_read_debug(lm_icp* c, int hypothesis, int kind, double
         }
         case 5: {   // cumulants of the k nearest neighbours per sorted target position [n_tgt][kIcpCovStride]
             n = (int64_t)st.n_tgt * kIcpCovStride; tmp.resize((size_t)n);
-            if (n && hipMemcpy(tmp.data(), c->B.cov + off * kIcpCovStride, (size_t)n * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
+            if (n && hipMemcpy(tmp.data(), c->ar.cov.p + off * kIcpCovStride, (size_t)n * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
                 return lm_set_error(LM_ERR_HIP, "read-back failed");
             break;
         }
         case 6: {   // original (voxel-order) index of the target point at every sorted position [n_tgt]: the row order of kind 5
             n = (int64_t)st.n_tgt; tmp.resize((size_t)n);
             std::vector<int> orig((size_t)n);
-            if (n && hipMemcpy(orig.data(), c->B.tgt_orig + off, (size_t)n * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess)
+            if (n && hipMemcpy(orig.data(), c->ar.tgt_orig.p + off, (size_t)n * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess)
                 return lm_set_error(LM_ERR_HIP, "read-back failed");
             for (int64_t p = 0; p < n; ++p) tmp[(size_t)p] = (double)orig[(size_t)p];
             break;
@@ -456,7 +415,7 @@ extern "C" int64_t lm_icp_read_debug(lm_icp* c, int hypothesis, int kind, double
         case 4: {   // the slices' partial sums of the last two evaluations, [2][kIcpMaxSplit][32] (slots 29..31: shader cycles of the slice)
             n = 2 * kIcpMaxSplit * 32; tmp.resize((size_t)n);
             for (int par = 0; par < 2; ++par)
-                if (hipMemcpy(tmp.data() + (size_t)par * kIcpMaxSplit * 32, c->B.partial + (((size_t)par * c->last_count + hypothesis) * kIcpMaxSplit) * 32,
+                if (hipMemcpy(tmp.data() + (size_t)par * kIcpMaxSplit * 32, c->ar.partial.p + (((size_t)par * c->last_count + hypothesis) * kIcpMaxSplit) * 32,
                               (size_t)kIcpMaxSplit * 32 * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
                     return lm_set_error(LM_ERR_HIP, "read-back failed");
             break;

@@ -1,6 +1,7 @@
-"""Who owns device memory (csrc/dev_buf.h) in the mesh family: lm_mesh, its pose-error scratch and lm_pso (`-m gpu`).
+"""Who owns device and pinned host memory (csrc/dev_buf.h): lm_mesh, its pose-error scratch, lm_pso, lm_icp, lm_pipeline and the
+detector's staging buffer, ingest ring and result slots (`-m gpu`).
 
-DevBuf<T> alone is checked by the stand-alone program tests/cpp/dev_buf_cases.cpp, built here next to the header it tests.
+DevBuf<T> and PinBuf<T> alone are checked by the stand-alone program tests/cpp/dev_buf_cases.cpp, built here next to the header it tests.
 
 The grow-and-reuse tests make ONE context serve a small call, then a larger call under which every scratch buffer of that path has to be
 replaced by a larger one, then the small call again, and compare each answer with the same call on a context that has served nothing else.
@@ -16,6 +17,7 @@ import pytest
 
 import pso_cases as pc
 import pso_edge_cases as ec
+import synth
 from synth import icosphere
 
 pytestmark = pytest.mark.gpu
@@ -35,7 +37,8 @@ def lm():
 
 def test_dev_buf_alone(lm, tmp_path):
     """ensure(0) allocates nothing; ensure(m <= n) keeps pointer and cap; growth gives cap == n; release() twice; both moves leave the
-    source {nullptr, 0}; a std::vector<DevBuf> that reallocates keeps every pointer and what was written through it."""
+    source {nullptr, 0}; a std::vector<DevBuf> that reallocates keeps every pointer and what was written through it.  The same for
+    PinBuf, written and read through the host pointer."""
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     exe = str(tmp_path / "dev_buf_cases")
     subprocess.check_call([hipcc, "-O3", "-std=c++17", "-ffp-contract=off", "--offload-arch=gfx950", "-Wall", "-Werror", "-I",
@@ -192,3 +195,174 @@ def test_pso_edge_scene_grows_and_reuses(lm):
     grow_and_reuse(lambda: lm.PsoContext(0), call(1, (72, 60)), call(3, (pc.W, pc.H)))
     d2, _ = call(3, (pc.W, pc.H))(lm.PsoContext(0))
     assert np.array_equal(d2, ec.scene_d2())
+
+
+# ---- lm_icp ------------------------------------------------------------------------------------------------------------------
+DBG3_NO_CLOCKS = list(range(0, 25)) + list(range(33, 39)) + [47, 48] + list(range(65, 73))   # kind 3 without clk, knn_clk, vox_clk, sort_clk
+
+
+def icp_scene(seed, n_models, W, H):
+    """n_models rendered-object stand-ins on a W x H frame, the scene = the first one 3 mm further away and a pixel to the right, and a
+    camera with its principal point in the middle of the frame."""
+    models = [synth.synth_model_depth(seed + s, W, H) for s in range(n_models)]
+    scene = np.roll(np.where(models[0] > 0, models[0] + 3, 0).astype(np.uint16), 1, axis=1)
+    K = np.array([572.4114, 0, W / 2, 0, 573.57043, H / 2, 0, 0, 1], np.float32).reshape(3, 3)
+    return models, scene, K
+
+
+def icp_run(ctx, models, K, slots):
+    """One hypothesis per entry of slots, each a pixel or two off its model's corner: R, t, iterations and stage of every hypothesis, and
+    of the last one the source and target clouds, the state words that are no clocks and the cumulants of the normals."""
+    n = len(slots)
+    xy = []
+    for h, s in enumerate(slots):
+        ys, xs = np.nonzero(models[s])
+        xy.append((int(xs.min()) + h % 3 - 1 + h // 6, int(ys.min()) + h % 2))
+    Ks = np.tile(K.reshape(1, 9), (n, 1)); Rs = np.tile(np.eye(3, dtype=np.float32).reshape(1, 9), (n, 1))
+    ts = np.array([[0.5 * h, -0.25 * h, 1000 + h] for h in range(n)], np.float32)
+    res, _ = ctx.run(Ks, Rs, ts, xy, model_slots=slots)
+    assert all(r["residual"] >= 0 and r["iterations"] > 0 and r["n_source"] > 1000 for r in res)   # every window inside the frame: registered (a residual of -1 says it was not)
+    return ([(r["R"], r["t"], r["iterations"], r["stage"]) for r in res],
+            [ctx.read_debug(n - 1, 0), ctx.read_debug(n - 1, 1), ctx.read_debug(n - 1, 3)[DBG3_NO_CLOCKS], ctx.read_debug(n - 1, 5)])
+
+
+def icp_context(lm, models, scene, K):
+    ctx = lm.IcpContext(device=0, scene_from_scene=True)
+    ctx.set_scene(scene, K)
+    ctx.set_models(models)
+    return ctx
+
+
+def test_icp_grows_and_reuses(lm):
+    """160 x 120.  3 models in slots 0-2 and 3 hypotheses; then models up to slot 19, past the 16 slots the first upload made room for,
+    and 18 hypotheses, past the 16 the arenas were sized for, on slots 0-2 and 17-19: the used context uploads only slots 3-19, so what it
+    answers for 0-2 comes from the images and boxes that the growth of the slot arrays carried over.  Then both again."""
+    W, H = 160, 120
+    models, scene, K = icp_scene(300, 20, W, H)
+    small, large = [0, 1, 2], [0, 1, 2, 17, 18, 19] * 3
+    want_small = icp_run(icp_context(lm, models[:3], scene, K), models, K, small)
+    want_large = icp_run(icp_context(lm, models, scene, K), models, K, large)
+    used = icp_context(lm, models[:3], scene, K)
+    assert same(icp_run(used, models, K, small), want_small), "first call"
+    used.set_models(models[3:], first_slot=3)
+    assert same(icp_run(used, models, K, large), want_large), "the call under which the slot arrays and every arena grow"
+    assert same(icp_run(used, models, K, small), want_small), "the small call again, in the grown buffers"
+    assert same(icp_run(used, models, K, large), want_large), "and the large one, now without growth"
+    assert len(want_large[1][0]) > 100 and len(want_large[1][3]) > 100                    # the clouds compared are there
+
+
+def test_icp_changes_geometry(lm):
+    """One context at 160 x 120, at 320 x 240 with other models, and at 160 x 120 again: a new frame size drops the arenas, the slots
+    and the scene, so a run before the models are uploaded again is refused — its slots are not resident —, and after the upload the
+    context answers what a fresh one does."""
+    used = lm.IcpContext(device=0, scene_from_scene=True)
+    for W, H, seed in ((160, 120, 340), (320, 240, 350), (160, 120, 340)):
+        models, scene, K = icp_scene(seed, 3, W, H)
+        used.set_scene(scene, K)
+        with pytest.raises(RuntimeError, match="model slot 0 of hypothesis 0 is not resident"):
+            icp_run(used, models, K, [0])
+        used.set_models(models)
+        assert same(icp_run(used, models, K, [0, 1, 2]), icp_run(icp_context(lm, models, scene, K), models, K, [0, 1, 2])), (W, H)
+
+
+# ---- lm_pipeline -------------------------------------------------------------------------------------------------------------
+PIPE_W, PIPE_H, PIPE_T, PIPE_NF, PIPE_THR = 320, 240, [4, 8], (64, 32), 70.0
+PIPE_CLASSES = ["n%d" % i for i in range(9)]
+PIPE_K = np.array([286.2057, 0, 162.63055, 0, 286.785215, 121.024495, 0, 0, 1], np.float32).reshape(3, 3)
+
+
+@pytest.fixture(scope="module")
+def pipe_scene():
+    """A 320 x 240 frame and nine classes of five templates planted in it, each at places of its own well inside the frame (the window of
+    a detection there stays in it, so its pose is refined); the first two with few labels changed, so that their matches score highest
+    and lead the NMS.  Per template a view: one of two rendered-object stand-ins, a pose near 1 m."""
+    import linemod_oracle as lo
+    rgb, dep = synth.make_frame(21, PIPE_W, PIPE_H, n_poly=16)
+    pyr = lo.OracleDetector(PIPE_NF[0], PIPE_T).quantize_pyramid(rgb, dep)
+    banks = {}
+    for i, c in enumerate(PIPE_CLASSES):
+        windows = [(40 + 36 * k + 4 * i, 36 + 22 * k + 2 * (i % 4), 56, 60) for k in range(5)]
+        banks[c] = synth.make_planted_bank(100 + i, 5, [(p[0], p[1]) for p in pyr], PIPE_T, PIPE_NF, label_noise=0.02 if i < 2 else 0.12, windows=windows)
+    shapes = [synth.synth_model_depth(200 + k, PIPE_W, PIPE_H) for k in range(2)]
+    rng = np.random.default_rng(5)
+    views = {c: [(shapes[(t + i) % 2], PIPE_K, np.eye(3, dtype=np.float32), np.array([rng.uniform(-5, 5), rng.uniform(-5, 5), 1000 + rng.uniform(-20, 20)], np.float32))
+                 for t in range(5)] for i, c in enumerate(PIPE_CLASSES)}
+    return dict(frame=[rgb, dep], banks=banks, views=views)
+
+
+def pipeline(lm, sc):
+    det = lm.Detector(PIPE_NF[0], PIPE_T, device=0)
+    for c in PIPE_CLASSES:
+        det.addClassPacked(c, *sc["banks"][c])
+    return det, lm.Pipeline(det, PIPE_W, PIPE_H, scene_from_scene=True)
+
+
+def pipe_views(pipe, sc, c):
+    v = sc["views"][c]
+    pipe.set_views(c, [x[0] for x in v], [x[1] for x in v], [x[2] for x in v], [x[3] for x in v])
+
+
+def pipe_run(det, pipe, sc, class_ids, top_k):
+    det.setFrame(sc["frame"])
+    return pipe.run(PIPE_THR, class_ids, PIPE_K, top_k=top_k, nms_iou=0.5)[0]
+
+
+def test_pipeline_grows_and_reuses(lm, pipe_scene):
+    """One pipeline: class n0 alone with top_k 2; top_k 8 (the selection and its pinned copy grow); the views of a second class (the view
+    tables are replaced and uploaded again); nine class ids, past the eight the class table starts with, and top_k 18, past the 16
+    hypotheses the ICP arenas were sized for; the first call again.  Each against a fresh pipeline on a fresh detector with the same
+    bank and the views set so far."""
+    sc = pipe_scene
+
+    def fresh(classes_with_views, class_ids, top_k):
+        det, pipe = pipeline(lm, sc)
+        for c in classes_with_views:
+            pipe_views(pipe, sc, c)
+        got = pipe_run(det, pipe, sc, class_ids, top_k)
+        pipe.close()
+        return got
+    det, used = pipeline(lm, sc)
+    pipe_views(used, sc, "n0")
+    first = fresh(["n0"], ["n0"], 2)
+    assert len(first) == 2
+    assert same(pipe_run(det, used, sc, ["n0"], 2), first), "first call"
+    assert same(pipe_run(det, used, sc, ["n0"], 8), fresh(["n0"], ["n0"], 8)), "top_k 8"
+    pipe_views(used, sc, "n1")
+    assert same(pipe_run(det, used, sc, ["n0", "n1"], 8), fresh(["n0", "n1"], ["n0", "n1"], 8)), "a second class's views"
+    large = fresh(["n0", "n1"], PIPE_CLASSES, 18)
+    assert same(pipe_run(det, used, sc, PIPE_CLASSES, 18), large), "nine class ids, top_k 18"
+    assert len(large) > 8 and any(r["status"] == 0 and r["iterations"] > 0 for r in large)    # the comparison is not one of empty lists
+    assert len({r["class_index"] for r in large}) > 2
+    assert same(pipe_run(det, used, sc, ["n0"], 2), first), "the first call again, in the grown buffers"
+    assert same(pipe_run(det, used, sc, PIPE_CLASSES, 18), large), "and the large one, now without growth"
+    used.close()
+
+
+# ---- lm_detector: the staging buffer, the ingest ring and the result slots ---------------------------------------------------------
+def test_detector_frames_grow_and_shrink(lm):
+    """One detector matches a 320 x 240 frame, a 640 x 480 frame and the first again, each through matchArray (the staging buffer) and
+    as two frames in flight through submitFrame / collect (the ingest ring's pinned entries, the result slots): the lists are those of a
+    fresh detector with the same bank."""
+    import linemod_oracle as lo
+    T, nf = [4, 8], (64, 32)
+    frames = [synth.make_frame(3, 320, 240, n_poly=16), synth.make_frame(4, 640, 480)]
+    banks = {}
+    for c, (rgb, dep) in zip(("small", "large"), frames):
+        pyr = lo.OracleDetector(nf[0], T).quantize_pyramid(rgb, dep)
+        banks[c] = synth.make_planted_bank(11, 24, [(p[0], p[1]) for p in pyr], T, nfeat=nf)
+
+    def detector():
+        det = lm.Detector(nf[0], T, device=0)
+        for c in banks:
+            det.addClassPacked(c, *banks[c])
+        return det
+
+    def lists(det, frame):
+        got = [det.matchArray(list(frame), 70.0, ["small", "large"])]
+        det.submitFrame(list(frame), 70.0, ["small", "large"]); det.submitFrame(list(frame), 70.0, ["small", "large"])
+        return got + [det.collect(), det.collect()]
+    used = detector()
+    for name, frame in (("small", frames[0]), ("large", frames[1]), ("small again", frames[0]), ("large again", frames[1])):
+        got, want = lists(used, frame), lists(detector(), frame)
+        assert len(want[0]) > 0 and want[1].tobytes() == want[0].tobytes() == want[2].tobytes(), name
+        assert all(g.dtype == w.dtype and g.tobytes() == w.tobytes() for g, w in zip(got, want)), name

@@ -101,6 +101,7 @@ int setup_geometry(lm_detector* d, int W, int H, bool check_match_preconditions)
         if (d->use[0] && (rc = b.ang.ensure(n))) return rc;
         if (d->use[1] && (rc = b.nrm.ensure(n))) return rc;
     }
+    if (d->fW != W || d->fH != H) d->quantised = false;      // the maps of the old size are gone
     d->geom = g;
     d->fW = W; d->fH = H;
     return LM_OK;
@@ -210,6 +211,7 @@ int run_frontend_training(lm_detector* d) {
         if (d->use[0] && l + 1 < L) fe_job_pyrdown(st.job[st.njobs++], src, d->lvl[l + 1].rgb.p, b.W, b.H, d->cch);           // LL.cpp:557-581
         launch_fe_stage(st, s);
     }
+    d->quantised = true;
     HIP_TRY(hipGetLastError());
     return LM_OK;
 }

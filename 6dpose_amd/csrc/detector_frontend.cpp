@@ -63,6 +63,7 @@ int run_frontend_batch(lm_detector* d, int first, int nb, hipStream_t s, bool di
     }
     build_lm_jobs(L - 1);
     flush();
+    if (stages & kFeQuantise) d->quantised = true;
     if (!(stages & kFeMemories)) { HIP_TRY(hipGetLastError()); return LM_OK; }
     if (direct_low || direct_top) {                      // the bit planes of every frame in one launch
         st.njobs = 0;

@@ -93,6 +93,7 @@ struct lm_detector {
     DevBuf<uint8_t> lm_arena[kSlots], sm_arena[kSlots];   // linear memories per result slot: the front end of frame k+1 writes one set
                                                 // while the matching kernels of frame k read the other
     int last_arena = 0;                         // set written by the most recent front end (lm_detector_read_stage)
+    bool quantised = false;                     // a front end has written lvl[]'s quantised maps at the current frame size (lm_pso_set_scene_from_detector)
 
     LevelBufs lvl[kMaxLevels];                  // front-end intermediates of frame 0 of a batch (and of addTemplate, read_stage)
     LevelBufs lvl_x[kMaxBatch - 1][kMaxLevels]; // ... of frames 1.. of a batch (allocated on first use)

@@ -1,5 +1,6 @@
 // lm_pso — pose refinement by particle swarm over rendered depth (kernels and the rule: pso.hip), and over the
-// scene's edges for cameras without depth (§5.3.1; pso_edges.hip): the same swarm with k_pso_edge_cost in k_pso_cost's place.
+// scene's edges for cameras without depth (§5.3.1; pso_edges.hip): the same swarm with k_pso_edge_cost in k_pso_cost's place, or with
+// k_pso_orient_cost against the scene's quantised orientations (§5.3.2; pso_orient.hip).
 // A call enqueues, on the context's own stream, k_pso_init and then per generation k_pso_views, k_project, k_raster,
 // k_pso_cost and k_pso_step; nothing is read back before the copy of the results.  The swarm renders into scratch of its
 // own (projected vertices, z-buffer): the mesh is only read, so lm_mesh_render returns what it did before.
@@ -9,6 +10,7 @@
 #include <algorithm>
 #include <vector>
 
+#include "detector_internal.h"
 #include "pso_kernels.h"
 #include "render_internal.h"
 
@@ -27,6 +29,12 @@ struct lm_pso {
     DevBuf<uint16_t> d_d2;
     int eW = 0, eH = 0, eM = 0;
     double eK[9] = {0};
+    // the oriented scene (lm_pso_set_scene_orientations, lm_pso_set_scene_from_detector): the map Q, per channel its row distances and D2_j,
+    // and the nine planes DD2; a frame and K of its own
+    DevBuf<uint8_t> d_q, d_og;
+    DevBuf<uint16_t> d_od2, d_dd2;
+    int oW = 0, oH = 0, oM = 0, oP = 0;
+    double oK[9] = {0};
     // swarm state, render scratch and the record of the last run
     DevBuf<PsoHyp> d_hyp;
     DevBuf<ViewParams> d_views;
@@ -136,11 +144,84 @@ extern "C" int64_t lm_pso_read_edge_distance(lm_pso* c, uint16_t* dst, int64_t c
     return size;
 }
 
-// The body of lm_pso_run and lm_pso_run_edges.  edge_step < 0: the depth cost against the scene depth; >= 0: the edge cost against D2
-// with that edge_step_mm, tau in pixels, the frame and K of the edge scene.
+// What lm_pso_set_scene_orientations and lm_pso_set_scene_from_detector share: the arguments' checks, and the transforms of the map in d_q.
+static int check_orient_args(const double* K, int max_dist, int orient_penalty) {
+    if (max_dist < 1 || max_dist > 255) return lm_set_error(LM_ERR_INVALID, "max_dist must be in 1..255 (got %d)", max_dist);
+    if (orient_penalty < 0 || orient_penalty > 4096) return lm_set_error(LM_ERR_INVALID, "orient_penalty must be in 0..4096 (got %d)", orient_penalty);
+    for (int k = 0; k < 9; ++k)
+        if (!isfinite(K[k])) return lm_set_error(LM_ERR_INVALID, "K is not finite");
+    return LM_OK;
+}
+static int ensure_orient(lm_pso* c, size_t n) {
+    int rc;
+    if ((rc = c->d_q.ensure(n))) return rc;
+    if ((rc = c->d_og.ensure(8 * n))) return rc;
+    if ((rc = c->d_od2.ensure(8 * n))) return rc;
+    return c->d_dd2.ensure(9 * n);
+}
+static int orient_transforms(lm_pso* c, int width, int height, const double* K, int max_dist, int orient_penalty) {
+    launch_edt_orient(c->d_q.p, width, height, max_dist, orient_penalty, c->d_og.p, c->d_od2.p, c->d_dd2.p, c->s);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(c->s));
+    c->oW = width; c->oH = height; c->oM = max_dist; c->oP = orient_penalty;
+    memcpy(c->oK, K, sizeof(c->oK));
+    return LM_OK;
+}
+
+extern "C" int lm_pso_set_scene_orientations(lm_pso* c, const uint8_t* Q, int width, int height, const double* K, int max_dist, int orient_penalty) {
+    if (!c || !Q || !K) return lm_set_error(LM_ERR_INVALID, "null argument");
+    if (width <= 0 || height <= 0 || width > 16384 || height > 16384) return lm_set_error(LM_ERR_INVALID, "unsupported frame size %dx%d", width, height);
+    if (int rc = check_orient_args(K, max_dist, orient_penalty)) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->s));
+    const size_t n = (size_t)width * height;
+    c->oW = c->oH = 0;                                                    // until DD2 stands
+    if (int rc = ensure_orient(c, n)) return rc;
+    HIP_TRY(hipMemcpyAsync(c->d_q.p, Q, n, hipMemcpyHostToDevice, c->s));
+    return orient_transforms(c, width, height, K, max_dist, orient_penalty);      // synchronises: `Q` is the caller's again
+}
+
+// The device hand-over: the detector's quantised colour map of `level` (lvl[level].ang, what lm_detector_read_stage(level, 0) reads) is
+// copied device to device on the context's stream once the detector's streams are idle; no byte of it crosses PCIe.
+extern "C" int lm_pso_set_scene_from_detector(lm_pso* c, lm_detector* det, int level, const double* K, int max_dist, int orient_penalty) {
+    if (!c || !det || !K) return lm_set_error(LM_ERR_INVALID, "null argument");
+    if (int rc = check_orient_args(K, max_dist, orient_penalty)) return rc;
+    if (det->device != c->device) return lm_set_error(LM_ERR_INVALID, "the detector lives on device %d, the context on %d", det->device, c->device);
+    if (!det->use[0]) return lm_set_error(LM_ERR_INVALID, "the detector's modality set has no ColorGradient: it quantises no orientations");
+    if (level < 0 || level >= det->pyramid_levels) return lm_set_error(LM_ERR_INVALID, "level %d out of range (the detector has %d)", level, det->pyramid_levels);
+    if (det->n_submitted != det->n_collected) return lm_set_error(LM_ERR_INVALID, "the detector has frames in flight: collect them first");
+    if (!det->quantised) return lm_set_error(LM_ERR_INVALID, "no front end has run on the detector: match a frame first");
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->s));
+    HIP_TRY(hipStreamSynchronize(det->stream));                           // the front end that wrote the map, on either stream
+    HIP_TRY(hipStreamSynchronize(det->mstream));
+    const LevelBufs& b = det->lvl[level];
+    if (b.W <= 0 || b.H <= 0 || b.W > 16384 || b.H > 16384) return lm_set_error(LM_ERR_INVALID, "unsupported frame size %dx%d", b.W, b.H);
+    const size_t n = (size_t)b.W * b.H;
+    c->oW = c->oH = 0;
+    if (int rc = ensure_orient(c, n)) return rc;
+    HIP_TRY(hipMemcpyAsync(c->d_q.p, b.ang.p, n, hipMemcpyDeviceToDevice, c->s));
+    return orient_transforms(c, b.W, b.H, K, max_dist, orient_penalty);
+}
+
+extern "C" int64_t lm_pso_read_orient_distance(lm_pso* c, int plane, uint16_t* dst, int64_t capacity) {
+    if (!c) return lm_set_error(LM_ERR_INVALID, "null argument");
+    if (c->oW <= 0) return lm_set_error(LM_ERR_INVALID, "no scene orientations set (lm_pso_set_scene_orientations)");
+    if (plane < 0 || plane > 8) return lm_set_error(LM_ERR_INVALID, "plane must be in 0..8 (got %d)", plane);
+    const int64_t size = (int64_t)c->oW * c->oH;
+    if (!dst || capacity <= 0) return size;
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipMemcpy(dst, c->d_dd2.p + (size_t)plane * size, (size_t)std::min<int64_t>(capacity, size) * sizeof(uint16_t), hipMemcpyDeviceToHost));
+    return size;
+}
+
+// The body of lm_pso_run, lm_pso_run_edges and lm_pso_run_oriented.  kCostDepth: the depth cost against the scene depth; kCostEdges: the
+// edge cost against D2 with edge_step (mm), tau in pixels, the frame and K of the edge scene; kCostOriented: the same against the nine
+// planes DD2 of the oriented scene.
+enum { kCostDepth = 0, kCostEdges = 1, kCostOriented = 2 };
 static int run_swarm(lm_pso* c, lm_mesh* mesh, int count, const double* Rs, const double* ts, const int32_t* windows_xy, int w, int h,
-                     const lm_pso_options* options, int edge_step, lm_pso_result* results, float* device_ms) {
-    const bool edges = edge_step >= 0;
+                     const lm_pso_options* options, int mode, int edge_step, lm_pso_result* results, float* device_ms) {
+    const bool edges = mode == kCostEdges, oriented = mode == kCostOriented;
     if (!c || !mesh || !Rs || !ts || !windows_xy || !results) return lm_set_error(LM_ERR_INVALID, "null argument");
     lm_pso_options o;
     if (options) {
@@ -161,9 +242,11 @@ static int run_swarm(lm_pso* c, lm_mesh* mesh, int count, const double* Rs, cons
     if (!isfinite(o.clip_near) || !isfinite(o.clip_far)) return lm_set_error(LM_ERR_INVALID, "the clip planes must be finite");
     if (mesh->nf <= 0 || mesh->nv <= 0) return lm_set_error(LM_ERR_INVALID, "the mesh has no faces");
     if (mesh->device != c->device) return lm_set_error(LM_ERR_INVALID, "the mesh lives on device %d, the context on %d", mesh->device, c->device);
-    if (!edges && (!c->d_scene.p || c->W <= 0)) return lm_set_error(LM_ERR_INVALID, "no scene depth set (lm_pso_set_scene)");
+    if (mode == kCostDepth && (!c->d_scene.p || c->W <= 0)) return lm_set_error(LM_ERR_INVALID, "no scene depth set (lm_pso_set_scene)");
     if (edges && c->eW <= 0) return lm_set_error(LM_ERR_INVALID, "no scene edges set (lm_pso_set_scene_edges)");
     if (edges && o.tau > c->eM) return lm_set_error(LM_ERR_INVALID, "tau must be <= max_dist for the edge cost (got %d > %d)", o.tau, c->eM);
+    if (oriented && c->oW <= 0) return lm_set_error(LM_ERR_INVALID, "no scene orientations set (lm_pso_set_scene_orientations)");
+    if (oriented && o.tau > c->oM) return lm_set_error(LM_ERR_INVALID, "tau must be <= max_dist for the oriented cost (got %d > %d)", o.tau, c->oM);
     for (size_t k = 0; k < (size_t)count * 9; ++k)
         if (!isfinite(Rs[k])) return lm_set_error(LM_ERR_INVALID, "a hypothesis' R is not finite");
     for (size_t k = 0; k < (size_t)count * 3; ++k)
@@ -174,12 +257,12 @@ static int run_swarm(lm_pso* c, lm_mesh* mesh, int count, const double* Rs, cons
     HIP_TRY(hipStreamSynchronize(c->s));                                  // h_hyp / h_res of an earlier call that failed half way
 
     PsoParams prm{};
-    memcpy(prm.K, edges ? c->eK : c->K, sizeof(prm.K));
+    memcpy(prm.K, oriented ? c->oK : edges ? c->eK : c->K, sizeof(prm.K));
     for (int d = 0; d < 3; ++d) { prm.range[d] = o.trans_range_mm; prm.range[3 + d] = o.rot_range; }
     prm.inertia = o.inertia; prm.c1 = o.c1; prm.c2 = o.c2; prm.seed = o.seed;
     prm.G = o.generations;
     prm.P = prm.G == 0 ? 1 : o.particles;                                 // evaluate-only: the given pose alone
-    prm.w = w; prm.h = h; prm.W = edges ? c->eW : c->W; prm.H = edges ? c->eH : c->H; prm.tau = o.tau; prm.cover_pixels = o.cover_pixels;
+    prm.w = w; prm.h = h; prm.W = oriented ? c->oW : edges ? c->eW : c->W; prm.H = oriented ? c->oH : edges ? c->eH : c->H; prm.tau = o.tau; prm.cover_pixels = o.cover_pixels;
     const int H = count, P = prm.P, G = prm.G;
     const size_t HP = (size_t)H * P, npx = (size_t)w * h, gen = (size_t)G + 1;
 
@@ -219,7 +302,8 @@ static int run_swarm(lm_pso* c, lm_mesh* mesh, int count, const double* Rs, cons
         launch_pso_views(prm, H, c->d_hyp.p, st.x, c->d_views.p, c->s);
         launch_project(M, c->d_views.p, (int)HP, 1, c->d_pv.p, c->s);
         launch_raster(M, c->d_pv.p, (int)HP, w, h, o.clip_near, o.clip_far, c->d_zbuf.p, c->s);
-        if (edges) launch_pso_edge_cost(prm, H, edge_step, c->d_hyp.p, c->d_zbuf.p, c->d_d2.p, st.sum, st.n_r, c->s);
+        if (oriented) launch_pso_orient_cost(prm, H, edge_step, c->d_hyp.p, c->d_zbuf.p, c->d_dd2.p, st.sum, st.n_r, c->s);
+        else if (edges) launch_pso_edge_cost(prm, H, edge_step, c->d_hyp.p, c->d_zbuf.p, c->d_d2.p, st.sum, st.n_r, c->s);
         else launch_pso_cost(prm, H, c->d_hyp.p, c->d_zbuf.p, c->d_scene.p, st.sum, st.n_r, c->s);
         launch_pso_step(prm, H, g, c->d_hyp.p, st, c->s);
     }
@@ -242,13 +326,19 @@ static int run_swarm(lm_pso* c, lm_mesh* mesh, int count, const double* Rs, cons
 
 extern "C" int lm_pso_run(lm_pso* c, lm_mesh* mesh, int count, const double* Rs, const double* ts, const int32_t* windows_xy, int w, int h,
                           const lm_pso_options* options, lm_pso_result* results, float* device_ms) {
-    return run_swarm(c, mesh, count, Rs, ts, windows_xy, w, h, options, -1, results, device_ms);
+    return run_swarm(c, mesh, count, Rs, ts, windows_xy, w, h, options, kCostDepth, 0, results, device_ms);
 }
 
 extern "C" int lm_pso_run_edges(lm_pso* c, lm_mesh* mesh, int count, const double* Rs, const double* ts, const int32_t* windows_xy, int w, int h,
                                 const lm_pso_options* options, int edge_step_mm, lm_pso_result* results, float* device_ms) {
     if (edge_step_mm < 0 || edge_step_mm > 65535) return lm_set_error(LM_ERR_INVALID, "edge_step_mm must be in 0..65535 (got %d)", edge_step_mm);
-    return run_swarm(c, mesh, count, Rs, ts, windows_xy, w, h, options, edge_step_mm, results, device_ms);
+    return run_swarm(c, mesh, count, Rs, ts, windows_xy, w, h, options, kCostEdges, edge_step_mm, results, device_ms);
+}
+
+extern "C" int lm_pso_run_oriented(lm_pso* c, lm_mesh* mesh, int count, const double* Rs, const double* ts, const int32_t* windows_xy, int w, int h,
+                                   const lm_pso_options* options, int edge_step_mm, lm_pso_result* results, float* device_ms) {
+    if (edge_step_mm < 0 || edge_step_mm > 65535) return lm_set_error(LM_ERR_INVALID, "edge_step_mm must be in 0..65535 (got %d)", edge_step_mm);
+    return run_swarm(c, mesh, count, Rs, ts, windows_xy, w, h, options, kCostOriented, edge_step_mm, results, device_ms);
 }
 
 extern "C" int64_t lm_pso_read_debug(lm_pso* c, int hypothesis, int kind, double* dst, int64_t capacity) {

@@ -37,10 +37,10 @@ from lm_detector import (DEFAULT_SCALES, Comm, Detector, Match, NMSBoxes, Templa
                          nms_norms, rgb_to_grey, scale_q10, scaled_box, scaled_features, scaled_options)
 from lm_icp import (ICP_ESTIMATIONS, IcpContext, Pipeline, _icp_flags, _icp_options, _pose_dict, evaluate_registration, poseRefine,
                     pose_refine_batch)
-from lm_pso import PSO_DEBUG_KINDS, PsoContext, derive_windows, pso_options, pso_refine, pso_refine_edges
+from lm_pso import PSO_DEBUG_KINDS, PsoContext, derive_windows, pso_options, pso_refine, pso_refine_edges, pso_refine_oriented
 from lm_render import OVERLAY_MODES, SHADINGS, Mesh, _colour, add_templates_rendered, render_options
 from lm_pose_error import (POSE_METRICS, POSE_METRICS_SYM, _pose_batch, _scene_mm, bop19_thresholds, gt_stats, match_poses, pose_errors,
                            recall, symmetry_transforms)
 
 __all__ = ["Detector", "Match", "poseRefine", "IcpContext", "Pipeline", "Mesh", "Template", "library_path", "load_library", "nms",
-           "pose_errors", "gt_stats", "symmetry_transforms", "match_poses", "recall", "bop19_thresholds", "PsoContext", "pso_refine", "pso_refine_edges"]
+           "pose_errors", "gt_stats", "symmetry_transforms", "match_poses", "recall", "bop19_thresholds", "PsoContext", "pso_refine", "pso_refine_edges", "pso_refine_oriented"]

@@ -286,6 +286,10 @@ PROTOTYPES = {
     "lm_pso_set_scene_edges": (I, [P, P, I, I, P, I]),
     "lm_pso_read_edge_distance": (I64, [P, P, I64]),
     "lm_pso_run_edges": (I, [P, P, I, P, P, P, I, I, PPSOO, I, ctypes.POINTER(_CPsoResult), ctypes.POINTER(F)]),
+    "lm_pso_set_scene_orientations": (I, [P, P, I, I, P, I, I]),
+    "lm_pso_set_scene_from_detector": (I, [P, P, I, P, I, I]),
+    "lm_pso_read_orient_distance": (I64, [P, I, P, I64]),
+    "lm_pso_run_oriented": (I, [P, P, I, P, P, P, I, I, PPSOO, I, ctypes.POINTER(_CPsoResult), ctypes.POINTER(F)]),
 }
 
 

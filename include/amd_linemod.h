@@ -833,6 +833,34 @@ int64_t lm_pso_read_edge_distance(lm_pso *c, uint16_t *dst, int64_t capacity);
  * edge_step_mm outside 0..65535. */
 int lm_pso_run_edges(lm_pso *c, lm_mesh *mesh, int count, const double *Rs, const double *ts, const int32_t *windows_xy /*[count][2]*/,
                      int w, int h, const lm_pso_options *options, int edge_step_mm, lm_pso_result *results, float *device_ms);
+/* ---- the edge cost with orientations: directional chamfer matching (Liu et al., Fast Directional Chamfer Matching) -------
+ * The scene is Q (uint8 [height][width]) with a camera K of its own: bit k (0..7) of a pixel set = an edge of orientation
+ * bin k there, LINE-MOD's quantised colour gradients (what lm_detector_read_stage(level, 0) reads); several bits may be set,
+ * 0 = no edge.  lm_pso_set_scene_orientations uploads it and computes, once, nine planes DD2 [9][height][width] uint16.  With
+ * D2_j the truncated squared distance of lm_pso_set_scene_edges to the pixels with bit j, P = orient_penalty (0..4096 px^2
+ * per bin^2; 16 — one bin off costs as much as 4 px — is a choice, not a measurement) and d(k, j) = min(|k - j|, 8 - |k - j|):
+ * DD2[k] = min(max_dist^2, min over j of D2_j + P d(k, j)^2), k = 0..7, the squared distance in (x, y, sqrt(P) bin) to the
+ * nearest oriented edge; DD2[8] = min over j of D2_j, what lm_pso_set_scene_edges computes for Q != 0.  The oriented scene
+ * is independent of the depth scene and of the edge scene of the same context.  LM_ERR_INVALID: max_dist outside 1..255,
+ * orient_penalty outside 0..4096. */
+int lm_pso_set_scene_orientations(lm_pso *c, const uint8_t *Q, int width, int height, const double *K, int max_dist,
+                                  int orient_penalty);
+/* The same from the detector's last front end, on the device: the quantised colour map of pyramid `level` is copied device to
+ * device once the detector's streams are idle, then transformed; no byte of it crosses PCIe.  The frame is that level's
+ * (the aligned size >> level), K the camera of that level.  LM_ERR_INVALID in addition: frames in flight on the detector,
+ * no front end has run on it, its modality set has no ColorGradient, it lives on another device than the context. */
+int lm_pso_set_scene_from_detector(lm_pso *c, lm_detector *det, int level, const double *K, int max_dist, int orient_penalty);
+/* Test/diagnostic read-back of one plane (0..8) of DD2.  Copies min(capacity, width x height) values, returns width x height. */
+int64_t lm_pso_read_orient_distance(lm_pso *c, int plane, uint16_t *dst, int64_t capacity);
+/* lm_pso_run_edges against the oriented scene.  The contour pixels are lm_pso_run_edges' own.  For a contour pixel of depth r,
+ * o(n) = 1 for each of its 8 neighbours n that lies inside the window and has n == 0 or, with edge_step_mm > 0,
+ * n - r > edge_step_mm, else 0; (gx, gy) are the 3 x 3 Sobel sums of o, y downwards, and the pixel's bin is
+ * k = round(atan2(gy, gx) in degrees mod 360 * 16 / 360) & 7, the front end's own quantisation, from an exact table.  The pixel
+ * adds min(DD2[k], tau^2) at its place in the frame, DD2[8] where gx == gy == 0, tau^2 outside the frame; everything else is
+ * lm_pso_run_edges'.  The rule is stated in numpy by tests/pso_orient_ref.py and followed bit for bit; with orient_penalty 0
+ * a call returns what lm_pso_run_edges returns on Q != 0.  LM_ERR_INVALID in addition: no orientations set, tau > max_dist. */
+int lm_pso_run_oriented(lm_pso *c, lm_mesh *mesh, int count, const double *Rs, const double *ts, const int32_t *windows_xy /*[count][2]*/,
+                        int w, int h, const lm_pso_options *options, int edge_step_mm, lm_pso_result *results, float *device_ms);
 
 #ifdef __cplusplus
 }

@@ -28,6 +28,14 @@ int lm_set_error(int code, const char* fmt, ...) {
     g_err = buf;
     return code;
 }
+int lm_open_device(int device) {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+        return lm_set_error(LM_ERR_NO_DEVICE, "no HIP device visible; libamdlinemod has no CPU fallback");
+    if (device < 0 || device >= ndev) return lm_set_error(LM_ERR_INVALID, "device %d out of range", device);
+    HIP_TRY(hipSetDevice(device));
+    return LM_OK;
+}
 extern "C" const char* lm_last_error(void) { return g_err.c_str(); }
 extern "C" const char* lm_version(void) { return "amd-linemod 0.1 (gfx950)"; }
 // Binds the calling thread to the CPUs next to `device` (its PCI function's local_cpulist in sysfs): pinned staging buffers are then
@@ -185,6 +193,22 @@ extern "C" int lm_rgb_to_grey(int device, const uint8_t* rgb, int64_t pixels, ui
     return e == hipSuccess ? LM_OK : lm_set_error(LM_ERR_HIP, "lm_rgb_to_grey: %s", hipGetErrorString(e));
 }
 
+// The events a detector owns from its creation on (those of exchange.cpp and detector_slabs.cpp come with their first use); the ingest
+// ring's only beside its stream.  Returns the step that failed (lm_last_error: the HIP call), or null.
+static const char* create_events(lm_detector* d) {
+    if (d->ingest_stream)
+        for (int i = 0; i < lm_detector::kSlots; ++i)
+            if (d->ingest.t0[i].ensure() || d->ingest.t1[i].ensure()) return "the ingest ring's timing events";
+    for (auto& ev : d->ev)
+        if (ev.ensure()) return "the frame events";
+    for (auto& sl : d->slot) {
+        for (auto& e : sl.ev)
+            if (e.ensure(hipEventDisableSystemFence)) return "a slot's timing events";   // timing only: nobody synchronises on them, and a default record costs the queue a cache write-back + invalidate (5-6 us between two kernels; sl.done keeps the fence)
+        if (sl.done.ensure(hipEventDisableTiming) || sl.fe_done.ensure(hipEventDisableTiming)) return "a slot's done / fe_done events";
+    }
+    return nullptr;
+}
+
 extern "C" int lm_detector_create_modalities(int num_features, const int* T, int num_levels, int device, const char* const* modalities,
                                              int num_modalities, lm_detector** out) {
     if (!out) return lm_set_error(LM_ERR_INVALID, "out is null");
@@ -244,25 +268,18 @@ extern "C" int lm_detector_create_modalities(int num_features, const int* T, int
     int prio[4] = {prio_greatest, prio_greatest, prio_least, 0};
     if (const char* pe = getenv("LM_STREAM_PRIO"))
         for (int i = 0; i < 4 && pe[i]; ++i) prio[i] = pe[i] == '1' ? prio_least : (pe[i] == '2' ? prio_greatest : 0);
-    bool streams_ok = hipSetDevice(device) == hipSuccess;
-    if (streams_ok)
-        streams_ok = hipStreamCreateWithPriority(&d->stream, hipStreamNonBlocking, prio[0]) == hipSuccess &&
-                     hipStreamCreateWithPriority(&d->mstream, hipStreamNonBlocking, prio[2]) == hipSuccess &&
-                     hipStreamCreateWithPriority(&d->xchg.stream, hipStreamNonBlocking, prio[3]) == hipSuccess;
-    if (!streams_ok) {
+    if (hipSetDevice(device) != hipSuccess || d->stream.ensure(hipStreamNonBlocking, prio[0]) || d->mstream.ensure(hipStreamNonBlocking, prio[2]) ||
+        d->xchg_stream.ensure(hipStreamNonBlocking, prio[3])) {
         delete d;
         return lm_set_error(LM_ERR_NO_DEVICE, "cannot initialise HIP device %d", device);
     }
     // the copy stream of the live-stream ingest too, now: every stream of the detector takes its hardware queue before anything created
-    // later (torch, RCCL) does
-    if (hipStreamCreateWithFlags(&d->ingest.stream, hipStreamNonBlocking) == hipSuccess)
-        for (int i = 0; i < lm_detector::kSlots; ++i) { (void)hipEventCreate(&d->ingest.t0[i]); (void)hipEventCreate(&d->ingest.t1[i]); }
-    else d->ingest.stream = nullptr;
-    for (auto& ev : d->ev) (void)hipEventCreate(&ev);
-    for (auto& sl : d->slot) {
-        for (auto& e : sl.ev) (void)hipEventCreateWithFlags(&e, hipEventDisableSystemFence);   // timing only: nobody synchronises on them, and a default record costs the queue a cache write-back + invalidate (5-6 us between two kernels; sl.done keeps the fence)
-        (void)hipEventCreateWithFlags(&sl.done, hipEventDisableTiming);
-        (void)hipEventCreateWithFlags(&sl.fe_done, hipEventDisableTiming);
+    // later (torch, RCCL) does.  The one creation that may fail: the first streamed frame tries again (ingest_entry).
+    (void)d->ingest_stream.ensure(hipStreamNonBlocking);
+    if (const char* step = create_events(d)) {
+        const std::string why = lm_last_error();
+        delete d;
+        return lm_set_error(LM_ERR_HIP, "lm_detector_create: %s: %s", step, why.c_str());
     }
     d->work_cls = std::make_shared<std::vector<int32_t>>();
     d->work_tid = std::make_shared<std::vector<int32_t>>();
@@ -293,18 +310,8 @@ extern "C" void lm_detector_destroy(lm_detector* d) {
     for (auto& sl : d->slot) { free(sl.prep); sl.prep = nullptr; }
     (void)hipStreamSynchronize(d->stream);
     if (d->mstream) (void)hipStreamSynchronize(d->mstream);
-    if (d->xchg.stream) (void)hipStreamSynchronize(d->xchg.stream);
-    std::vector<hipEvent_t> events(std::begin(d->ev), std::end(d->ev));
-    for (int i = 0; i < lm_detector::kSlots; ++i) {
-        const lm_detector::Slot& sl = d->slot[i];
-        events.insert(events.end(), {d->ingest.t0[i], d->ingest.t1[i], d->xchg.done[i], sl.done, sl.fe_done});
-        events.insert(events.end(), std::begin(sl.ev), std::end(sl.ev));
-    }
-    events.push_back(d->slabs.modes_ready);
-    hipStream_t streams[] = {d->ingest.stream, d->xchg.stream, d->stream, d->mstream};
-    delete d;                                                         // every DevBuf and PinBuf: device selected, streams idle and still alive
-    for (hipEvent_t e : events) if (e) (void)hipEventDestroy(e);
-    for (hipStream_t s : streams) if (s) (void)hipStreamDestroy(s);
+    if (d->xchg_stream) (void)hipStreamSynchronize(d->xchg_stream);
+    delete d;                                                         // every buffer and event, then the streams (detector_internal.h): device selected, streams idle
 }
 
 extern "C" int lm_detector_max_in_flight(void) { return lm_detector::kSlots; }

@@ -794,7 +794,7 @@ int build_work(lm_detector* d, const char* const* class_ids, int num_class_ids) 
     // frames in flight still read the device-resident work list: let them finish before it is replaced
     if (d->n_submitted != d->n_collected) {
         HIP_TRY(hipStreamSynchronize(d->mstream));
-        if (d->xchg.stream) HIP_TRY(hipStreamSynchronize(d->xchg.stream));
+        if (d->xchg_stream) HIP_TRY(hipStreamSynchronize(d->xchg_stream));
     }
     int rc = d->d_work.ensure(std::max<size_t>(1, d->work_pyr.size()));
     if (rc) return rc;

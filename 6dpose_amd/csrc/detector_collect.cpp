@@ -184,7 +184,7 @@ int lm_collect_frame(lm_detector* d, int sort_unique, lm_match** out, size_t* n_
     sl.pending = false;
     d->launch.frame_done(d->n_collected);              // this frame's batch and everything before it are done
     if (d->xchg.state[slot_index] != 0) {               // exchange work of this frame may still read the slot's buffers
-        HIP_TRY(hipStreamSynchronize(d->xchg.stream));
+        HIP_TRY(hipStreamSynchronize(d->xchg_stream));
         d->xchg.state[slot_index] = 0;
     }
     ++d->n_collected;

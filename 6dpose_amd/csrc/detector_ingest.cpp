@@ -7,17 +7,16 @@
 
 static int ingest_entry(lm_detector* d, int r, size_t n, size_t nsrc) {   // pixels of the aligned frame and of the source
     lm_detector::Ingest& g = d->ingest;
-    if (!g.stream) {
-        HIP_TRY(hipStreamCreateWithFlags(&g.stream, hipStreamNonBlocking));
-        for (int i = 0; i < lm_detector::kSlots; ++i) { HIP_TRY(hipEventCreate(&g.t0[i])); HIP_TRY(hipEventCreate(&g.t1[i])); }
-    }
+    int rc = d->ingest_stream.ensure(hipStreamNonBlocking);          // all three kept where lm_detector_create made them; a call that fails part-way is continued by the next
+    if (!rc) rc = g.t0[r].ensure();
+    if (!rc) rc = g.t1[r].ensure();
+    if (rc) return rc;
     g.depth_off = d->use[0] ? (n * d->cch + 15) & ~(size_t)15 : 0;       // the depth image behind the colour image, 16-byte aligned (host entry and device entry alike);
     const size_t bytes = g.depth_off + (d->use[1] ? n * 2 : 0);     // a detector with one modality keeps (and uploads) only that modality's image
     // A source that is not aligned: the pinned entry (and its copy on the device, d_src) has the same layout at the SOURCE size — only those bytes
     // cross PCIe —, the device entry the front end reads keeps the aligned size.
     g.src_depth_off = d->use[0] ? (nsrc * d->cch + 15) & ~(size_t)15 : 0;
     const size_t src_bytes = g.src_depth_off + (d->use[1] ? nsrc * 2 : 0);
-    int rc;
     if ((rc = g.pinned[r].ensure(src_bytes)) || (rc = g.d_rgb[r].ensure(bytes))) return rc;
     if (nsrc != n && (rc = g.d_src[r].ensure(src_bytes + 16))) return rc;   // (+16: k_frame_border fetches the aligned dwords around a unit)
     g.d_depth[r] = d->use[1] ? reinterpret_cast<uint16_t*>(g.d_rgb[r].p + g.depth_off) : nullptr;
@@ -75,17 +74,17 @@ extern "C" int lm_detector_submit_frame(lm_detector* d, const uint8_t* rgb, cons
     staged_copy(d, st, rgb, nc, st + g.src_depth_off, (const uint8_t*)depth, nd);  // zero-copy when the caller filled lm_detector_ingest_buffer's pointers
     const auto tp1 = std::chrono::steady_clock::now();
     if (g.reader[r]) {                                            // a resident re-match of the entry's previous frame may still read it (another slot's front end)
-        HIP_TRY(hipStreamWaitEvent(g.stream, g.reader[r], 0));
+        HIP_TRY(hipStreamWaitEvent(d->ingest_stream, g.reader[r], 0));
         g.reader[r] = nullptr;
     }
-    HIP_TRY(hipEventRecord(g.t0[r], g.stream));
+    HIP_TRY(hipEventRecord(g.t0[r], d->ingest_stream));
     if (copy_2d) {
         const size_t cw = (size_t)std::min(width, d->fW), ch = (size_t)std::min(height, d->fH);
-        if (nc) HIP_TRY(hipMemcpy2DAsync(g.d_rgb[r].p, (size_t)d->fW * d->cch, st, (size_t)width * d->cch, cw * d->cch, ch, hipMemcpyHostToDevice, g.stream));
-        if (nd) HIP_TRY(hipMemcpy2DAsync(g.d_depth[r], (size_t)d->fW * 2, st + g.src_depth_off, (size_t)width * 2, cw * 2, ch, hipMemcpyHostToDevice, g.stream));
+        if (nc) HIP_TRY(hipMemcpy2DAsync(g.d_rgb[r].p, (size_t)d->fW * d->cch, st, (size_t)width * d->cch, cw * d->cch, ch, hipMemcpyHostToDevice, d->ingest_stream));
+        if (nd) HIP_TRY(hipMemcpy2DAsync(g.d_depth[r], (size_t)d->fW * 2, st + g.src_depth_off, (size_t)width * 2, cw * 2, ch, hipMemcpyHostToDevice, d->ingest_stream));
     } else
-    HIP_TRY(hipMemcpyAsync(bordered ? g.d_src[r].p : g.d_rgb[r].p, st, g.src_depth_off + nd, hipMemcpyHostToDevice, g.stream));   // colour + depth: one copy (two cost the copy engine a second set-up: 0.061 -> ~0.05 ms, and the host a call)
-    HIP_TRY(hipEventRecord(g.t1[r], g.stream));                   // the batch's front end waits for it (lm_launch_pending)
+    HIP_TRY(hipMemcpyAsync(bordered ? g.d_src[r].p : g.d_rgb[r].p, st, g.src_depth_off + nd, hipMemcpyHostToDevice, d->ingest_stream));   // colour + depth: one copy (two cost the copy engine a second set-up: 0.061 -> ~0.05 ms, and the host a call)
+    HIP_TRY(hipEventRecord(g.t1[r], d->ingest_stream));                   // the batch's front end waits for it (lm_launch_pending)
     const uint8_t* const in_rgb = d->use[0] ? g.d_rgb[r].p : nullptr;
     d->cur_rgb = in_rgb; d->cur_depth = g.d_depth[r];
     d->have_mask[0] = d->have_mask[1] = false;

@@ -49,6 +49,17 @@ struct LevelPtrs {
 };
 
 struct lm_detector {
+    // device.  The four streams come first, before every event and every DevBuf / PinBuf of the detector (dev_buf.h: members die in
+    // reverse order, so the buffers are freed and the events destroyed while all four streams still exist), and in the order in which
+    // lm_detector_create creates them.
+    int device = 0;
+    DevStream stream;                   // frame upload / select + front end (and addTemplate)
+    DevStream mstream;                  // refinement (a lone frame: all three matching kernels; + the pipeline's NMS / ICP): frame k, while `stream` prepares frame k+1
+    DevStream xchg_stream;              // multi-GPU exchange (exchange.cpp); also runs the duplicate removal of pipelined frames
+    DevStream ingest_stream;            // copy stream of the live-stream ingest; created with the detector, or by the first streamed frame if that failed
+    DevEvent ev[8];
+    int shard_rank = 0, shard_world = 1;
+
     // parameters (LL.cpp:1663-1692 + modality defaults :645-650, :968-974)
     int num_features = 63;
     std::vector<int> T_at_level{5, 8};
@@ -72,13 +83,6 @@ struct lm_detector {
     // crosses PCIe; the ALIGNED size (fW x fH, geom) is that of the frame buffers, the arenas, the parked frames and lm_detector_read_stage.
     int border = kBorderStrict;
     DevBuf<uint8_t> border_src;         // the uploaded sources (and masks) of a blocking upload whose size is not aligned: k_frame_border reads them
-
-    // device
-    int device = 0;
-    hipStream_t stream = nullptr;       // frame upload / select + front end (and addTemplate)
-    hipStream_t mstream = nullptr;      // refinement (a lone frame: all three matching kernels; + the pipeline's NMS / ICP): frame k, while `stream` prepares frame k+1
-    hipEvent_t ev[8] = {};
-    int shard_rank = 0, shard_world = 1;
 
     // frame
     int fW = 0, fH = 0;
@@ -167,9 +171,9 @@ struct lm_detector {
         lm_match* prep = nullptr;
         size_t prep_n = 0;
         float prep_collect_ms = 0.f, prep_merge_ms = 0.f;
-        hipEvent_t ev[6] = {};                      // stage timing: front end 0 -> 1, coarse 1 -> 3, refinement 3 -> 4 (2 and 5: not recorded since round 5)
-        hipEvent_t done = nullptr;                  // recorded after the batch's last kernel: the only event the host waits on
-        hipEvent_t fe_done = nullptr;               // front end of this slot finished (eager, on `stream`): `mstream` waits for it
+        DevEvent ev[6];                             // stage timing: front end 0 -> 1, coarse 1 -> 3, refinement 3 -> 4 (2 and 5: not recorded since round 5)
+        DevEvent done;                              // recorded after the batch's last kernel: the only event the host waits on
+        DevEvent fe_done;                           // front end of this slot finished (eager, on `stream`): `mstream` waits for it
         bool pending = false;
         float threshold = 0.f, h2d_ms = 0.f;
         int num_work = 0;
@@ -207,7 +211,7 @@ struct lm_detector {
     bool fe_keep_top = false;                       // lm_detector_set_direct_bits(d, 2)
     int fe_top_mode = 0;                            // lm_detector_set_direct_bits(d, 4 / 8): which writer of the pair stream (fe_job_top_bits)
     bool fe_bytes_low = true, fe_bytes_top = true;  // did the last front end write the byte planes of the levels below the top / of the top level (read_stage builds them on demand otherwise)
-    hipEvent_t resident_reader = nullptr;           // front end (event of its batch) that reads the resident frame buffers: lm_detector_select_frame's copy waits for it
+    hipEvent_t resident_reader = nullptr;           // front end (event of its batch) that reads the resident frame buffers: lm_detector_select_frame's copy waits for it (not owned: a slot's fe_done)
     // frame b of a batch (its intermediates: level_bufs), level l, result slot `arena` (whose frame decides the masks)
     LevelPtrs level_ptrs(int b, int l, int arena) {
         const LevelBufs& q = level_bufs(b, l);
@@ -232,7 +236,7 @@ struct lm_detector {
     struct Slabs {
         DevBuf<uint32_t> hist, modes;               // kDepthMaxBins counts; kDepthModeWords words of mode records
         PinBuf<uint32_t> h_modes;                   // copy of the mode records
-        hipEvent_t modes_ready = nullptr;
+        DevEvent modes_ready;                       // created by the first pass (enqueue_modes)
         DevBuf<uint8_t> mask[kMaxLevels][3];        // [level][0 / 1: slab & user mask of that kind, 2: the slab alone]
         const uint8_t* mask_of[kMaxLevels][2] = {};
         bool mask_on = false, quantised = false;
@@ -295,26 +299,24 @@ struct lm_detector {
     // dedicated copy stream — the H2D of frame k+1 runs beside the front end of frame k and the matching kernels of k-1 —
     // and the front end reads it there.  An entry is free again when its frame was collected.
     struct Ingest {
-        hipStream_t stream = nullptr;
         PinBuf<uint8_t> pinned[kSlots];
         DevBuf<uint8_t> d_rgb[kSlots];                 // colour image, then (16-byte aligned) the depth image: ONE upload per frame, the pinned entry has the same layout
         uint16_t* d_depth[kSlots] = {};                // = d_rgb + depth_off
         size_t depth_off = 0;
         size_t src_depth_off = 0;                      // the same in an entry of the source size (the pinned entry and d_src; == depth_off for an aligned source)
         DevBuf<uint8_t> d_src[kSlots];                 // the frame at its source size, where that is not aligned: the upload goes here and k_frame_border writes d_rgb / d_depth
-        hipEvent_t t0[kSlots] = {}, t1[kSlots] = {};   // timing of the H2D (copy stream)
+        DevEvent t0[kSlots], t1[kSlots];               // timing of the H2D (copy stream); created with ingest_stream
         bool used[kSlots] = {};                        // the slot's frame came in through the ring (lm_timings.h2d_ms from t0/t1)
-        hipEvent_t reader[kSlots] = {};                // front end (of another slot: a resident re-match of the streamed frame) that still reads the entry
+        hipEvent_t reader[kSlots] = {};                // front end (of another slot: a resident re-match of the streamed frame) that still reads the entry (not owned: a slot's fe_done)
     } ingest;
 
-    // multi-GPU exchange on the device (exchange.cpp): its own stream, so that the sort of frame k's records, the caller's
+    // multi-GPU exchange on the device (exchange.cpp): its own stream (xchg_stream), so that the sort of frame k's records, the caller's
     // RCCL all-gather and the merge run beside the matching kernels of frame k+1
     struct Exchange {
-        hipStream_t stream = nullptr;               // created with the detector; also runs the duplicate removal of pipelined frames
         DevBuf<int32_t> d_merged[kSlots];
         DevBuf<ulonglong2> d_runs;                  // scratch of the per-rank sort
         PinBuf<int32_t> h_merged[kSlots];
-        hipEvent_t done[kSlots] = {};
+        DevEvent done[kSlots];                      // created by the first exchange (ensure_exchange)
         int state[kSlots] = {};                     // 0 idle, 1 packed, 2 merged (result on its way to h_merged)
         int cap[kSlots] = {}, world[kSlots] = {};
         int done_slot[kSlots] = {};                 // the slot whose `done` event covers this frame's group

@@ -6,7 +6,7 @@
 
 static int sync_all_streams(lm_detector* d) {
     HIP_TRY(hipStreamSynchronize(d->stream)); HIP_TRY(hipStreamSynchronize(d->mstream));
-    if (d->xchg.stream) HIP_TRY(hipStreamSynchronize(d->xchg.stream));
+    if (d->xchg_stream) HIP_TRY(hipStreamSynchronize(d->xchg_stream));
     return LM_OK;
 }
 
@@ -181,7 +181,7 @@ struct Batch {
     bool parts;                               // ... under the part rule (match_parts.hip): bits / cbits are set as well
     bool direct_low, direct_top, top_ored;    // the front end writes the bit planes below the top / of the top level itself; ... by OR-ing into a zeroed pair stream
     uint32_t tile_cap, cap;
-    hipStream_t s;                            // every kernel of a batch on the matching stream (one queue; the end of a stage is the start of the next)
+    hipStream_t s;                            // (not owned: the detector's) every kernel of a batch on the matching stream (one queue; the end of a stage is the start of the next)
     FrameBatch fb, fb_rest;                   // fb_rest: for k_local's per-candidate path on what k_local_bits leaves (todo = 1)
     BitsBatch bb;
     TopBits tb;
@@ -327,7 +327,7 @@ static int record_front_end(lm_detector* d, const Batch& B) {
         if (d->slot[B.slot(b)].ring < 0) d->resident_reader = lead.fe_done;
     for (int b = 0; b < B.nb; ++b) {                          // a resident re-match of a streamed frame reads its ring entry: the entry's next upload waits for this front end
         const lm_detector::Slot& sl = d->slot[B.slot(b)];
-        if (sl.ring < 0 && d->ingest.stream)
+        if (sl.ring < 0 && d->ingest_stream)
             for (int r = 0; r < lm_detector::kSlots; ++r)
                 if (d->ingest.d_rgb[r].p && (sl.in_rgb ? sl.in_rgb == d->ingest.d_rgb[r].p : (const void*)sl.in_depth == (const void*)d->ingest.d_rgb[r].p)) d->ingest.reader[r] = lead.fe_done;   // (a depth-only entry starts with the depth image)
     }

@@ -38,7 +38,7 @@ static int enqueue_modes(lm_detector* d, const lm_depth_mode_options& o, int nbi
     int rc;
     if ((rc = S.hist.ensure(kDepthMaxBins)) || (rc = S.modes.ensure(kDepthModeWords))) return rc;
     if ((rc = S.h_modes.ensure(kDepthModeWords))) return rc;
-    if (!S.modes_ready) HIP_TRY(hipEventCreateWithFlags(&S.modes_ready, hipEventDisableTiming));
+    if ((rc = S.modes_ready.ensure(hipEventDisableTiming))) return rc;
     HIP_TRY(hipMemsetAsync(S.hist.p, 0, (size_t)nbins * sizeof(uint32_t), d->stream));
     DepthHistArgs a{};
     a.depth = d->cur_depth; a.W = d->fW; a.H = d->fH; a.pitch = d->fW;

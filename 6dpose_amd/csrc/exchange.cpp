@@ -21,8 +21,8 @@ using namespace lm;
 static_assert(sizeof(lm_match) == 20, "lm_match is five 32-bit fields");
 
 static int ensure_exchange(lm_detector* d) {
-    if (d->xchg.done[0]) return LM_OK;                                               // the stream itself is created with the detector
-    for (int a = 0; a < lm_detector::kSlots; ++a) HIP_TRY(hipEventCreateWithFlags(&d->xchg.done[a], hipEventDisableTiming));
+    for (auto& e : d->xchg.done)                                                     // the stream itself is created with the detector
+        if (int rc = e.ensure(hipEventDisableTiming)) return rc;
     return LM_OK;
 }
 
@@ -33,7 +33,7 @@ static bool valid_capacity(int capacity) {
 extern "C" void* lm_detector_exchange_stream(lm_detector* d) {
     if (!d) { lm_set_error(LM_ERR_INVALID, "null detector"); return nullptr; }
     if (hipSetDevice(d->device) != hipSuccess || ensure_exchange(d) != LM_OK) return nullptr;
-    return (void*)d->xchg.stream;
+    return (void*)d->xchg_stream;
 }
 
 extern "C" int lm_exchange_max_capacity(void) { return (int)kXchgMaxCapacity; }
@@ -61,7 +61,7 @@ extern "C" int lm_detector_exchange_pack_group(lm_detector* d, uint64_t first, i
     if (rc) return rc;
     if ((rc = d->xchg.d_runs.ensure((size_t)kXchgMaxCapacity * kMaxBatch))) return rc;
     const size_t blk = lm_exchange_block_bytes(capacity);
-    hipStream_t xs = d->xchg.stream;
+    hipStream_t xs = d->xchg_stream;
     XchgGroup G{};
     G.n = n;
     int last_leader = -1;
@@ -108,7 +108,7 @@ extern "C" int lm_detector_exchange_merge_group_strided(lm_detector* d, uint64_t
         G.f[i].merged = d->xchg.d_merged[slot].p;
         HIP_TRY(hipHostGetDevicePointer((void**)&G.f[i].host, d->xchg.h_merged[slot].p, 0));
     }
-    hipStream_t xs = d->xchg.stream;
+    hipStream_t xs = d->xchg_stream;
     launch_exchange_merge_group(G, world, (uint32_t)capacity, xs, (uint32_t)(rank_stride_bytes / 4));   // merge + copy-out to the pinned buffers
     HIP_TRY(hipGetLastError());
     for (int i = 0; i < n; ++i) {

@@ -11,8 +11,8 @@ using lm::IcpState;
 
 struct lm_icp {
     int device = 0;
-    hipStream_t s = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
+    DevStream s;                   // first: every event and buffer below dies before it (dev_buf.h)
+    DevEvent e0, e1;
     int W = 0, H = 0;
     bool have_scene = false;
     float sK[9] = {0};

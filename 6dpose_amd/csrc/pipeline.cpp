@@ -37,7 +37,7 @@ struct lm_pipeline {
     PinBuf<TopkSel> h_sel;
     PinBuf<int32_t> h_nsel, h_class_base;
     std::vector<int32_t> class_base_on_device;    // what d_class_base holds (re-uploaded only when it changes)
-    hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr;
+    DevEvent e0, e1, e2;                          // (no stream of its own: the pipeline runs on the detector's and the ICP context's, which both outlive it)
 };
 
 extern "C" int lm_pipeline_create(lm_detector* det, int width, int height, lm_pipeline** out) {
@@ -53,7 +53,7 @@ extern "C" int lm_pipeline_create(lm_detector* det, int width, int height, lm_pi
     rc = lm_icp_create(det->device, &p->icp);
     if (!rc) rc = lm_icp_set_geometry(p->icp, p->W, p->H);
     if (rc) { if (p->icp) lm_icp_destroy(p->icp); delete p; return rc; }
-    if (hipEventCreate(&p->e0) != hipSuccess || hipEventCreate(&p->e1) != hipSuccess || hipEventCreate(&p->e2) != hipSuccess) {
+    if (p->e0.ensure() || p->e1.ensure() || p->e2.ensure()) {
         lm_icp_destroy(p->icp); delete p;
         return lm_set_error(LM_ERR_HIP, "could not create the pipeline events");
     }
@@ -68,10 +68,8 @@ extern "C" void lm_pipeline_destroy(lm_pipeline* p) {
     (void)hipSetDevice(p->det->device);
     (void)hipStreamSynchronize(p->det->stream);
     (void)hipStreamSynchronize(p->det->mstream);
-    hipEvent_t ev[] = {p->e0, p->e1, p->e2};
     lm_icp* icp = p->icp;
-    delete p;                                                     // every buffer: device selected, the detector's streams idle
-    for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+    delete p;                                                     // the events and every buffer: device selected, the detector's streams idle
     lm_icp_destroy(icp);
 }
 

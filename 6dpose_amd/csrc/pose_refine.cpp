@@ -195,20 +195,15 @@ int lm_icp_finish(lm_icp* c, const IcpBuffers& B, IcpState* h_st, hipStream_t s)
 extern "C" int lm_icp_create(int device, lm_icp** out) {
     if (!out) return lm_set_error(LM_ERR_INVALID, "null argument");
     *out = nullptr;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return lm_set_error(LM_ERR_NO_DEVICE, "no HIP device visible; libamdlinemod has no CPU fallback");
-    if (device < 0 || device >= ndev) return lm_set_error(LM_ERR_INVALID, "device %d out of range", device);
-    HIP_TRY(hipSetDevice(device));
+    if (int rc = lm_open_device(device)) return rc;
     int cus = 0;
     HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
     lm_icp* c = new lm_icp();
     c->device = device;
     c->cus = cus;
     if (const char* e = getenv("LM_ICP_SLICED")) c->sliced_only = e[0] && e[0] != '0';
-    if (hipStreamCreateWithFlags(&c->s, hipStreamNonBlocking) != hipSuccess || hipEventCreate(&c->e0) != hipSuccess ||
-        hipEventCreate(&c->e1) != hipSuccess) {
-        delete c;
+    if (c->s.ensure(hipStreamNonBlocking) || c->e0.ensure() || c->e1.ensure()) {
+        delete c;                                                         // (releases what was created)
         return lm_set_error(LM_ERR_HIP, "could not create the ICP stream / events");
     }
     *out = c;
@@ -243,12 +238,7 @@ extern "C" void lm_icp_destroy(lm_icp* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     if (c->s) (void)hipStreamSynchronize(c->s);
-    hipStream_t s = c->s;
-    hipEvent_t e0 = c->e0, e1 = c->e1;
-    delete c;                                                         // every buffer: device selected, stream idle and still alive
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    if (s) (void)hipStreamDestroy(s);
+    delete c;                                                         // every buffer, the events, then the stream: device selected, stream idle
 }
 
 extern "C" int lm_icp_set_scene(lm_icp* c, const uint16_t* scene_depth, int width, int height, const float* scene_K) {

@@ -18,8 +18,8 @@ using namespace lm;
 
 struct lm_pso {
     int device = 0;
-    hipStream_t s = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    DevStream s;                          // first: every event and buffer below dies before it (dev_buf.h)
+    DevEvent ev0, ev1;
     // the scene
     DevBuf<uint16_t> d_scene;
     int W = 0, H = 0;
@@ -67,15 +67,10 @@ extern "C" void lm_pso_options_init(lm_pso_options* o) {
 extern "C" int lm_pso_create(int device, lm_pso** out) {
     if (!out) return lm_set_error(LM_ERR_INVALID, "null argument");
     *out = nullptr;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return lm_set_error(LM_ERR_NO_DEVICE, "no HIP device visible; libamdlinemod has no CPU fallback");
-    if (device < 0 || device >= ndev) return lm_set_error(LM_ERR_INVALID, "device %d out of range", device);
-    HIP_TRY(hipSetDevice(device));
+    if (int rc = lm_open_device(device)) return rc;
     lm_pso* c = new lm_pso();
     c->device = device;
-    if (hipStreamCreateWithFlags(&c->s, hipStreamNonBlocking) != hipSuccess || hipEventCreate(&c->ev0) != hipSuccess ||
-        hipEventCreate(&c->ev1) != hipSuccess) {
+    if (c->s.ensure(hipStreamNonBlocking) || c->ev0.ensure() || c->ev1.ensure()) {
         lm_pso_destroy(c);
         return lm_set_error(LM_ERR_HIP, "stream / event creation failed");
     }
@@ -87,12 +82,7 @@ extern "C" void lm_pso_destroy(lm_pso* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     if (c->s) (void)hipStreamSynchronize(c->s);
-    hipStream_t s = c->s;
-    hipEvent_t ev0 = c->ev0, ev1 = c->ev1;
-    delete c;                                                             // every buffer: device selected, stream idle and still alive
-    if (ev0) (void)hipEventDestroy(ev0);
-    if (ev1) (void)hipEventDestroy(ev1);
-    if (s) (void)hipStreamDestroy(s);
+    delete c;                                                             // every buffer, the events, then the stream: device selected, stream idle
 }
 
 extern "C" int lm_pso_set_scene(lm_pso* c, const uint16_t* scene_depth, int width, int height, const double* K) {

@@ -21,11 +21,7 @@ extern "C" int lm_mesh_create(int device, const float* vertices, const float* no
     *out = nullptr;
     for (int i = 0; i < 3 * nf; ++i)
         if (faces[i] < 0 || faces[i] >= nv) return lm_set_error(LM_ERR_INVALID, "face index %d out of range", faces[i]);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return lm_set_error(LM_ERR_NO_DEVICE, "no HIP device visible; libamdlinemod has no CPU fallback");
-    if (device < 0 || device >= ndev) return lm_set_error(LM_ERR_INVALID, "device %d out of range", device);
-    HIP_TRY(hipSetDevice(device));
+    if (int rc = lm_open_device(device)) return rc;
     lm_mesh* m = new lm_mesh();
     m->device = device; m->nv = nv; m->nf = nf;
     auto upload = [](auto& buf, const auto* src, size_t n) -> int {
@@ -34,7 +30,7 @@ extern "C" int lm_mesh_create(int device, const float* vertices, const float* no
         HIP_TRY(hipMemcpy(buf.p, src, n * sizeof(*src), hipMemcpyHostToDevice));
         return LM_OK;
     };
-    int rc = hipStreamCreateWithFlags(&m->s, hipStreamNonBlocking) == hipSuccess ? LM_OK : lm_set_error(LM_ERR_HIP, "hipStreamCreate failed");
+    int rc = m->s.ensure(hipStreamNonBlocking);
     if (!rc) rc = upload(m->d_v, vertices, (size_t)nv * 3);
     if (!rc) rc = upload(m->d_f, faces, (size_t)nf * 3);
     if (!rc && normals) rc = upload(m->d_n, normals, (size_t)nv * 3);
@@ -48,9 +44,7 @@ extern "C" void lm_mesh_destroy(lm_mesh* m) {
     if (!m) return;
     (void)hipSetDevice(m->device);
     if (m->s) (void)hipStreamSynchronize(m->s);
-    hipStream_t s = m->s;
-    delete m;                                                         // every buffer: device selected, stream idle and still alive
-    if (s) (void)hipStreamDestroy(s);
+    delete m;                                                         // every buffer, then the stream: device selected, stream idle
 }
 
 extern "C" int lm_mesh_counts(const lm_mesh* m, int* nv, int* nf) {

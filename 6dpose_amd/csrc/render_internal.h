@@ -7,7 +7,7 @@
 struct lm_mesh {
     int device = 0;
     int nv = 0, nf = 0;
-    hipStream_t s = nullptr;
+    DevStream s;                           // before every buffer below: they die first (dev_buf.h)
     DevBuf<float> d_v, d_n;
     DevBuf<uint8_t> d_c;
     DevBuf<int32_t> d_f;

@@ -1,13 +1,17 @@
 """Who owns device and pinned host memory (csrc/dev_buf.h): lm_mesh, its pose-error scratch, lm_pso, lm_icp, lm_pipeline and the
 detector's staging buffer, ingest ring and result slots (`-m gpu`).
 
-DevBuf<T> and PinBuf<T> alone are checked by the stand-alone program tests/cpp/dev_buf_cases.cpp, built here next to the header it tests.
+DevBuf<T> and PinBuf<T> alone are checked by the stand-alone program tests/cpp/dev_buf_cases.cpp, built here next to the header it tests;
+DevStream and DevEvent, which own every stream and event of the same contexts, by tests/cpp/dev_handle_cases.cpp.  The lifecycle tests at
+the end open and close every context several times in one process, close a detector with frames in flight and after its lazily created
+handles have been made, and compare what the next context answers with what the first one did.
 
 The grow-and-reuse tests make ONE context serve a small call, then a larger call under which every scratch buffer of that path has to be
 replaced by a larger one, then the small call again, and compare each answer with the same call on a context that has served nothing else.
 A buffer that kept its old capacity, its old pointer in a kernel argument, or a stale capacity after it was replaced shows as a difference
 (or as a fault).  The comparisons are exact: these paths use integer atomics and sums in a fixed order, and two fresh contexts agree bit for
 bit."""
+import ctypes
 import os
 import shutil
 import subprocess
@@ -35,17 +39,30 @@ def lm():
     return mod
 
 
+def run_alone(name, tmp_path):
+    """Builds tests/cpp/<name>.cpp next to the header it tests, with the library's flags and -Werror, and runs it."""
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    exe = str(tmp_path / name)
+    subprocess.check_call([hipcc, "-O3", "-std=c++17", "-ffp-contract=off", "--offload-arch=gfx950", "-Wall", "-Werror", "-I",
+                           os.path.join(ROOT, "6dpose_amd", "csrc"), "-x", "hip", os.path.join(ROOT, "tests", "cpp", name + ".cpp"), "-o", exe],
+                          timeout=600)
+    r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=120)
+    assert r.returncode == 0 and b"ok:" in r.stdout, r.stdout.decode()[-2000:]
+
+
 def test_dev_buf_alone(lm, tmp_path):
     """ensure(0) allocates nothing; ensure(m <= n) keeps pointer and cap; growth gives cap == n; release() twice; both moves leave the
     source {nullptr, 0}; a std::vector<DevBuf> that reallocates keeps every pointer and what was written through it.  The same for
     PinBuf, written and read through the host pointer."""
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    exe = str(tmp_path / "dev_buf_cases")
-    subprocess.check_call([hipcc, "-O3", "-std=c++17", "-ffp-contract=off", "--offload-arch=gfx950", "-Wall", "-Werror", "-I",
-                           os.path.join(ROOT, "6dpose_amd", "csrc"), "-x", "hip", os.path.join(ROOT, "tests", "cpp", "dev_buf_cases.cpp"), "-o", exe],
-                          timeout=600)
-    r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=120)
-    assert r.returncode == 0 and b"ok:" in r.stdout, r.stdout.decode()[-2000:]
+    run_alone("dev_buf_cases", tmp_path)
+
+
+def test_dev_handles_alone(lm, tmp_path):
+    """DevStream and DevEvent: no copies, nothrow moves; a default-constructed handle is null; ensure() creates one and a second ensure()
+    keeps it; release() twice; both moves leave the source null; a std::vector<DevEvent> that reallocates keeps every handle.  A stream
+    of each creation form takes a 256-byte memset and has the priority it was created with; two default events time the memset; an
+    event of each of the three flag kinds is recorded, waited on from a second stream and synchronised."""
+    run_alone("dev_handle_cases", tmp_path)
 
 
 # ---- the shared scene: the 80-triangle icosphere of radius 40 mm, about 400 mm from the camera ----------------------------------
@@ -366,3 +383,128 @@ def test_detector_frames_grow_and_shrink(lm):
         got, want = lists(used, frame), lists(detector(), frame)
         assert len(want[0]) > 0 and want[1].tobytes() == want[0].tobytes() == want[2].tobytes(), name
         assert all(g.dtype == w.dtype and g.tobytes() == w.tobytes() for g, w in zip(got, want)), name
+
+
+# ---- lifecycles: every stream and event is created with its context and dies with it (DevStream / DevEvent) -----------------------------
+LIFE_W, LIFE_H, LIFE_T, LIFE_NF, LIFE_THR = 64, 48, [2, 2], (32, 16), 70.0
+LIFE_MODES = dict(min_pixels=200)                                                          # of the 3072 pixels of the frame
+
+
+def close(ctx):
+    """Destroys the context now: its close(), or for the detector, which has none, what dropping the last reference runs."""
+    ctx.close() if hasattr(ctx, "close") else ctx.__del__()
+
+
+@pytest.fixture(scope="module")
+def life_scene(lm):
+    """A 64 x 48 frame, four templates planted where the refinement reaches them (T = 2: a border of 16 pixels), and what a detector that
+    has done nothing else answers: the records of the frame, and its depth-slab pass."""
+    import linemod_oracle as lo
+    rgb, dep = synth.make_frame(3, LIFE_W, LIFE_H, n_poly=6)
+    pyr = lo.OracleDetector(LIFE_NF[0], LIFE_T).quantize_pyramid(rgb, dep)
+    windows = [(18 + 2 * k, 16 + 2 * (k % 2), 24, 14) for k in range(4)]
+    bank = synth.make_planted_bank(11, 4, [(p[0], p[1]) for p in pyr], LIFE_T, nfeat=LIFE_NF, label_noise=0.05, windows=windows)
+    sc = dict(frame=[rgb, dep], bank=bank)
+    det = life_detector(lm, sc)
+    sc["records"] = det.matchArray(sc["frame"], LIFE_THR, ["obj"])
+    sc["slabs"] = det.matchSlabs(sc["frame"], LIFE_THR, ["obj"], **LIFE_MODES)
+    close(det)
+    assert len(sc["records"]) > 0 and len(set(sc["records"]["template_id"])) == 4           # the comparisons are not ones of empty lists
+    assert sc["slabs"][1][0]["depth_mm"] is not None and len(sc["slabs"][0]) > 0           # at least one mode, and records under its slab
+    return sc
+
+
+def life_detector(lm, sc):
+    det = lm.Detector(LIFE_NF[0], LIFE_T, device=0)
+    det.addClassPacked("obj", *sc["bank"])
+    det.setClassDepthRange("obj", 300, 4000)
+    return det
+
+
+def life_case(lm, kind, life_scene, pipe_scene):
+    """(open, call, close) of one kind of context: open() gives what close() takes, call() one small call on it."""
+    if kind == "detector":
+        return (lambda: life_detector(lm, life_scene)), (lambda d: d.matchArray(life_scene["frame"], LIFE_THR, ["obj"])), close
+    if kind == "mesh":
+        Rs, ts = poses(2, 11)
+        return (lambda: full_mesh(lm)), (lambda m: m.render((32, 24), cam(32, 24), Rs, ts, clip_near=100.0, clip_far=2000.0, ssaa=1)), close
+    if kind == "pso":
+        mesh = lm.Mesh(*pc.mesh())
+
+        def run(ctx):
+            ctx.set_scene(pc.scene()[:60, :72], pc.K)
+            return swarm(ctx, mesh, 1, (32, 32), particles=8, generations=2)
+        return (lambda: lm.PsoContext(0)), run, close
+    if kind == "icp":
+        models, scene, K = icp_scene(300, 1, 160, 120)
+        return (lambda: icp_context(lm, models, scene, K)), (lambda c: icp_run(c, models, K, [0])), close
+
+    def open_pipeline():
+        det, pipe = pipeline(lm, pipe_scene)
+        pipe_views(pipe, pipe_scene, "n0")
+        return det, pipe
+
+    def close_pipeline(both):
+        close(both[1])                                                                     # the pipeline, then the detector it was made on
+        close(both[0])
+    return open_pipeline, (lambda both: pipe_run(both[0], both[1], pipe_scene, ["n0"], 2)), close_pipeline
+
+
+@pytest.mark.parametrize("kind", ["detector", "mesh", "pso", "icp", "pipeline"])
+def test_context_opens_and_closes_three_times(lm, life_scene, pipe_scene, kind):
+    """Created and closed three times in one process: once without having run anything, twice after one small call, whose answer is both
+    times the same, bit for bit.  The pipeline is closed before its detector."""
+    make, call, shut = life_case(lm, kind, life_scene, pipe_scene)
+    shut(make())
+    answers = []
+    for _ in range(2):
+        ctx = make()
+        answers.append(call(ctx))
+        shut(ctx)
+    assert same(answers[1], answers[0])
+    if kind == "detector":
+        assert same(answers[0], life_scene["records"])
+    if kind == "pipeline":
+        assert len(answers[0]) == 2
+
+
+def test_detector_closes_with_frames_in_flight(lm, life_scene):
+    """Two streamed frames launched and never collected, a third still waiting for its batch: destroying the detector launches and flushes
+    them.  The next detector in the process matches the frame to the same records."""
+    sc = life_scene
+    det = life_detector(lm, sc)
+    det.setBatch(2); det.setBatchQueue(0)                                                  # a batch goes out when it is full, not before
+    for _ in range(3):
+        det.submitFrame(sc["frame"], LIFE_THR, ["obj"])
+    assert (det.framesSubmitted(), det.framesLaunched(), det.framesCollected()) == (3, 2, 0)
+    close(det)
+    det = life_detector(lm, sc)
+    assert same(det.matchArray(sc["frame"], LIFE_THR, ["obj"]), sc["records"])
+    close(det)
+
+
+def test_detector_closes_after_its_lazy_handles(lm, life_scene):
+    """A detector that has been through every site that creates a handle on first use — a frame streamed through the ingest ring (its copy
+    stream and timing events are made with the detector, or there), a depth-slab pass (modes_ready) and one exchange group of world 1,
+    packed and merged in place (the exchange's done events) — answers what a fresh detector does, and so does the next one after it."""
+    sc = life_scene
+    det = life_detector(lm, sc)
+    det.submitFrame(sc["frame"], LIFE_THR, ["obj"])
+    assert same(det.collect(), sc["records"]), "ingest ring"
+    assert same(det.matchSlabs(sc["frame"], LIFE_THR, ["obj"], **LIFE_MODES), sc["slabs"]), "depth slabs"
+    lib = lm.load_library()                                                                # (its handle also resolves the HIP runtime it is bound to)
+    block, nbytes = ctypes.c_void_p(), ctypes.c_size_t(lib.lm_exchange_block_bytes(256))
+    assert lib.hipMalloc(ctypes.byref(block), nbytes) == 0 and lib.hipMemset(block, 0, nbytes) == 0 and lib.hipDeviceSynchronize() == 0
+    try:
+        first = det.framesSubmitted()
+        det.submit(LIFE_THR, ["obj"]); det.flush()
+        det.exchangePackGroup(first, 1, block.value, 256)
+        det.exchangeMergeGroup(first, 1, block.value, 1, 256)
+        got, failed = det.exchangeCollect()
+        assert failed == 0 and same(got, sc["records"]), "exchange of world 1"
+        close(det)
+    finally:
+        lib.hipFree(block)
+    det = life_detector(lm, sc)
+    assert same(det.matchArray(sc["frame"], LIFE_THR, ["obj"]), sc["records"])
+    close(det)

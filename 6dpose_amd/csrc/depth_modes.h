@@ -18,13 +18,13 @@ struct DepthHistArgs {
     uint32_t* hist;                           // [nbins], zero before the launch
 };
 // hist[b] += pixels of bin b: per-workgroup counts in LDS, one atomic add per non-empty bin and workgroup.  Any W, H, pitch and alignment.
-hipError_t launch_depth_hist(const DepthHistArgs& a, hipStream_t s);
+[[nodiscard]] hipError_t launch_depth_hist(const DepthHistArgs& a, hipStream_t s);
 
 // One workgroup: bin b is a mode iff hist[b] >= min_pixels, hist[b] > hist[j] for j in [b - window, b) and hist[b] >= hist[j] for j in
 // (b, b + window] (bins outside [0, nbins) do not exist); out = the max_modes modes with the most pixels, ties towards the smaller bin,
 // in that order, as kDepthModeWords words.
-hipError_t launch_depth_nms(const uint32_t* hist, int nbins, int near_mm, int bin_mm, int window, uint32_t min_pixels, int max_modes,
-                            uint32_t* out, hipStream_t s);
+[[nodiscard]] hipError_t launch_depth_nms(const uint32_t* hist, int nbins, int near_mm, int bin_mm, int window, uint32_t min_pixels, int max_modes,
+                                          uint32_t* out, hipStream_t s);
 
 // out[k][i] = (depth[i] != 0 && lo <= depth[i] <= hi && (!user[k] || user[k][i])) ? 255 : 0 for the n_out outputs; n pixels, a multiple of 8,
 // every pointer 16-byte (depth) / 8-byte (masks) aligned.
@@ -36,6 +36,6 @@ struct SlabMaskArgs {
     const uint8_t* user[3];
     uint8_t* out[3];
 };
-hipError_t launch_slab_mask(const SlabMaskArgs& a, hipStream_t s);
+[[nodiscard]] hipError_t launch_slab_mask(const SlabMaskArgs& a, hipStream_t s);
 
 }  // namespace lm

@@ -3,6 +3,7 @@
 // counts, and so the modes, do not depend on the order the workgroups arrive in.
 #include <algorithm>
 
+#include "launch.h"
 #include "depth_modes.h"
 
 namespace lm {
@@ -53,8 +54,7 @@ hipError_t launch_depth_hist(const DepthHistArgs& a, hipStream_t s) {
     const uint32_t upr = ((uint32_t)k.W + 7u) / 8u;
     const uint32_t units = upr * (uint32_t)k.H;
     const uint32_t blocks = std::min<uint32_t>((units + 255u) / 256u, 512u);
-    hipLaunchKernelGGL(k_depth_hist, dim3(blocks), dim3(256), 0, s, k, units, upr);
-    return hipGetLastError();
+    return lm_launch(k_depth_hist, dim3(blocks), dim3(256), 0, s, k, units, upr);
 }
 
 // Thread t owns bins t, t + 256, ...: a bit per owned bin says "a mode, not selected yet"; a selection round is a maximum over the
@@ -109,8 +109,7 @@ __global__ __launch_bounds__(256) void k_depth_nms(const uint32_t* hist, int nbi
 hipError_t launch_depth_nms(const uint32_t* hist, int nbins, int near_mm, int bin_mm, int window, uint32_t min_pixels, int max_modes,
                             uint32_t* out, hipStream_t s) {
     if (nbins < 1 || nbins > kDepthMaxBins || max_modes < 1 || max_modes > kDepthMaxModes || window < 0 || min_pixels < 1u) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_depth_nms, dim3(1), dim3(256), 0, s, hist, nbins, near_mm, bin_mm, std::min(window, nbins), min_pixels, max_modes, out);
-    return hipGetLastError();
+    return lm_launch(k_depth_nms, dim3(1), dim3(256), 0, s, hist, nbins, near_mm, bin_mm, std::min(window, nbins), min_pixels, max_modes, out);
 }
 
 // Eight pixels per thread: one dwordx4 of depths in, one dwordx2 per output mask out.
@@ -140,8 +139,7 @@ hipError_t launch_slab_mask(const SlabMaskArgs& a, hipStream_t s) {
     if (a.n == 0 || a.n % 8u || a.n_out < 1 || a.n_out > 3 || ((uintptr_t)a.depth & 15u)) return hipErrorInvalidValue;
     for (int o = 0; o < a.n_out; ++o)
         if (!a.out[o] || ((uintptr_t)a.out[o] & 7u) || ((uintptr_t)a.user[o] & 7u)) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_slab_mask, dim3((a.n / 8u + 255u) / 256u), dim3(256), 0, s, a);
-    return hipGetLastError();
+    return lm_launch(k_slab_mask, dim3((a.n / 8u + 255u) / 256u), dim3(256), 0, s, a);
 }
 
 }  // namespace lm

@@ -45,7 +45,7 @@ extern "C" int lm_bind_thread_near_device(int device, char* cpulist_out, size_t 
     if (cpulist_out && cap) cpulist_out[0] = 0;
     char bdf[64] = {0};
     if (hipDeviceGetPCIBusId(bdf, (int)sizeof(bdf), device) != hipSuccess) {
-        (void)hipGetLastError();
+        (void)hipGetLastError();                              // the refusal above (an invalid device): not left for the caller's next check
         return lm_set_error(LM_ERR_NO_DEVICE, "no PCI bus id for device %d", device);
     }
     for (char* c = bdf; *c; ++c) *c = (char)tolower(*c);
@@ -185,7 +185,7 @@ extern "C" int lm_rgb_to_grey(int device, const uint8_t* rgb, int64_t pixels, ui
     hipError_t e = hipSuccess;
     if (!rc) {
         e = hipMemcpy(in.p, rgb, (size_t)pixels * 3, hipMemcpyHostToDevice);
-        if (e == hipSuccess) { launch_rgb_to_grey(in.p, out.p, (size_t)pixels, nullptr); e = hipGetLastError(); }
+        if (e == hipSuccess) e = launch_rgb_to_grey(in.p, out.p, (size_t)pixels, nullptr);
         if (e == hipSuccess) e = hipMemcpy(grey, out.p, (size_t)pixels, hipMemcpyDeviceToHost);   // (synchronises with the null stream)
     }
     in.release(); out.release();
@@ -297,7 +297,10 @@ extern "C" int lm_detector_create_modalities(int num_features, const int* T, int
     }
     uint8_t lut[400];
     make_normal_lut(lut);
-    upload_normal_lut(lut);
+    if (const hipError_t e = upload_normal_lut(lut); e != hipSuccess) {
+        delete d;
+        return lm_set_error(LM_ERR_HIP, "lm_detector_create: upload_normal_lut: %s", hipGetErrorString(e));
+    }
     *out = d;
     return LM_OK;
 }

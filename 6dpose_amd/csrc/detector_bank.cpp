@@ -141,11 +141,9 @@ static int add_template_device(lm_detector* d, const uint8_t* mask, int width, i
     HIP_TRY(hipMemsetAsync(T.counts.p, 0, (size_t)L * 16 * sizeof(uint32_t), s));
     HIP_TRY(hipMemsetAsync(T.bbox.p, 0x80, 4 * sizeof(int32_t), s));
     const int mods = (d->use[0] ? 1 : 0) | (d->use[1] ? 2 : 0);
-    launch_train_prep(d->frame_depth.p, T.user_mask.p, g, d->strong_threshold * d->strong_threshold, d->extract_threshold, T.keys.p, kTrainCap, T.counts.p,
-                      T.bbox.p, s, mods);
-    if (launch_train_select(T.keys.p, T.counts.p, g, kTrainCap, d->num_features, nf_cap, 1, T.out.p, s, mods))
-        return lm_set_error(LM_ERR_HIP, "cannot reserve LDS for the selection kernel");
-    HIP_TRY(hipGetLastError());
+    HIP_TRY(launch_train_prep(d->frame_depth.p, T.user_mask.p, g, d->strong_threshold * d->strong_threshold, d->extract_threshold, T.keys.p, kTrainCap, T.counts.p,
+                              T.bbox.p, s, mods));
+    HIP_TRY(launch_train_select(T.keys.p, T.counts.p, g, kTrainCap, d->num_features, nf_cap, 1, T.out.p, s, mods));   // (or the kernel's LDS cannot be reserved)
     std::vector<int32_t> h_out((size_t)L * 2 * out_words);
     HIP_TRY(hipMemcpyAsync(h_out.data(), T.out.p, h_out.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
@@ -191,7 +189,7 @@ extern "C" int lm_detector_add_template(lm_detector* d, const uint8_t* rgb, cons
 // The rasteriser's colour image of a view into the detector's frame buffer: as it is, or — a grey detector — through the fixed-point RGB2GRAY of
 // k_rgb_to_grey (what lm_rgb_to_grey gives a caller who trains from colour photographs), without leaving the device.
 static int rendered_colour_to_frame(lm_detector* d, const uint8_t* view_rgb, size_t npx, hipStream_t s) {
-    if (d->cch == 1) { launch_rgb_to_grey(view_rgb, d->frame_rgb.p, npx, s); HIP_TRY(hipGetLastError()); }
+    if (d->cch == 1) HIP_TRY(launch_rgb_to_grey(view_rgb, d->frame_rgb.p, npx, s));
     else HIP_TRY(hipMemcpyAsync(d->frame_rgb.p, view_rgb, npx * 3, hipMemcpyDeviceToDevice, s));
     return LM_OK;
 }
@@ -279,12 +277,10 @@ static int add_templates_rendered(lm_detector* d, lm_mesh* m, const char* class_
             if (d->use[0] && (rc = rendered_colour_to_frame(d, m->d_rgb.p + (size_t)i * npx * 3, npx, s))) return rc;
             if (d->use[1]) HIP_TRY(hipMemcpyAsync(d->frame_depth.p, view_depth, npx * 2, hipMemcpyDeviceToDevice, s));
             if ((rc = run_frontend_training(d))) return rc;
-            launch_train_prep(d->use[1] ? d->frame_depth.p : view_depth, nullptr, g, strong_sq, d->extract_threshold, T.keys.p + keys_view * i, kTrainCap,
-                              T.counts.p + counts_view * i, T.bbox.p + 4 * (size_t)i, s, mods);
+            HIP_TRY(launch_train_prep(d->use[1] ? d->frame_depth.p : view_depth, nullptr, g, strong_sq, d->extract_threshold, T.keys.p + keys_view * i, kTrainCap,
+                                      T.counts.p + counts_view * i, T.bbox.p + 4 * (size_t)i, s, mods));
         }
-        if (launch_train_select(T.keys.p, T.counts.p, g, kTrainCap, d->num_features, nf_cap, n, T.out.p, s, mods))
-            return lm_set_error(LM_ERR_HIP, "cannot reserve LDS for the selection kernel");
-        HIP_TRY(hipGetLastError());
+        HIP_TRY(launch_train_select(T.keys.p, T.counts.p, g, kTrainCap, d->num_features, nf_cap, n, T.out.p, s, mods));   // (or the kernel's LDS cannot be reserved)
         h_out.resize((size_t)n * L * 2 * out_words);
         h_bbox.resize(4 * (size_t)n);
         HIP_TRY(hipMemcpyAsync(h_out.data(), T.out.p, h_out.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));

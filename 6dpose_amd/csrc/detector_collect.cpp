@@ -64,7 +64,7 @@ static int model_before_wait(lm_detector* d, const lm_detector::Slot& sl, Launch
     *w = d->launch.before_wait(d->n_collected, sl.leader);
     if (!w->batch_head) return LM_OK;
     w->blocked = hipEventQuery(d->slot[sl.leader].done) == hipErrorNotReady;
-    (void)hipGetLastError();
+    (void)hipGetLastError();                              // hipErrorNotReady is not an error
     if (w->blocked && d->launch.due_before_wait(d->pend_n, d->n_collected)) return lm_launch_pending(d);
     return LM_OK;
 }
@@ -133,7 +133,7 @@ static int fill_timings(lm_detector* d, lm_detector::Slot& sl, int slot_index, i
         hipEventElapsedTime(&tm.coarse_ms, lead.ev[1], lead.ev[3]) != hipSuccess ||
         hipEventElapsedTime(&tm.local_ms, lead.ev[3], lead.ev[4]) != hipSuccess ||
         hipEventElapsedTime(&tm.total_ms, lead.ev[0], lead.ev[4]) != hipSuccess) {
-        (void)hipGetLastError();
+        (void)hipGetLastError();                          // an event that was never recorded (hipErrorInvalidHandle / NotReady): no timings, not an error
         tm.frontend_ms = tm.coarse_ms = tm.local_ms = tm.d2h_ms = tm.total_ms = 0.f;
     }
     *tm_out = tm; *nm_out = nm;
@@ -188,7 +188,6 @@ int lm_collect_frame(lm_detector* d, int sort_unique, lm_match** out, size_t* n_
         d->xchg.state[slot_index] = 0;
     }
     ++d->n_collected;
-    HIP_TRY(hipGetLastError());
     uint64_t ncand = 0, nm = 0;
     lm_timings tm{};
     if ((rc = read_counters(d, sl, slot_index, &ncand)) || (rc = fill_timings(d, sl, slot_index, sort_unique, ncand, &tm, &nm))) {

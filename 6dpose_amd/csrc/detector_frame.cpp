@@ -176,7 +176,7 @@ int upload_frame(lm_detector* d, const uint8_t* rgb, const uint16_t* depth, int 
             FeStage st{};                                   // one launch per level: level l reads level l - 1
             st.njobs = 1;
             fe_job_nn_down2(st.job[0], a.mask[m].p, b.mask[m].p, a.W, a.H);
-            launch_fe_stage(st, d->stream);
+            HIP_TRY(launch_fe_stage(st, d->stream));
         }
     }
     HIP_TRY(hipEventRecord(d->ev[7], d->stream));
@@ -209,10 +209,9 @@ int run_frontend_training(lm_detector* d) {
             else fe_job_nn_down2(st.job[st.njobs++], d->lvl[l - 1].nrm.p, b.nrm.p, d->lvl[l - 1].W, d->lvl[l - 1].H); // LL.cpp:857-880
         }
         if (d->use[0] && l + 1 < L) fe_job_pyrdown(st.job[st.njobs++], src, d->lvl[l + 1].rgb.p, b.W, b.H, d->cch);           // LL.cpp:557-581
-        launch_fe_stage(st, s);
+        HIP_TRY(launch_fe_stage(st, s));
     }
     d->quantised = true;
-    HIP_TRY(hipGetLastError());
     return LM_OK;
 }
 
@@ -338,7 +337,7 @@ extern "C" int64_t lm_detector_read_stage(lm_detector* d, int level, int kind, u
             st.resp = d->resp;
             st.njobs = 1;
             fe_job_build_lm(st.job[0], P.quant, P.mask, P.lm, P.strips, b.W, b.H, lv.T, d->mod_kind[0], d->nmod);
-            launch_fe_stage(st, d->stream);
+            HIP_TRY(launch_fe_stage(st, d->stream));
             (void)hipStreamSynchronize(d->stream);
         }
         hipError_t e = hipMemcpy(dst, src, (size_t)std::min(size, capacity), hipMemcpyDeviceToHost);

@@ -29,16 +29,17 @@ int run_frontend_batch(lm_detector* d, int first, int nb, hipStream_t s, bool di
     const int m0 = d->mod_kind[0], nm = d->nmod;         // the modality set: the quantising chains and the writers' slices of the set only
     FeStage st{};
     st.resp = d->resp;                                   // the detector's response table: every writer of response memories takes it from the launch
-    auto flush = [&]() { if (st.njobs) { LM_CLOCK("launch_fe_stage"); launch_fe_stage(st, s); } st.njobs = 0; };
-    auto room = [&](int jobs) { if (st.njobs + jobs > kFeMaxJobs) flush(); };
-    auto build_lm_jobs = [&](int l) {                        // linear memories of level l of every frame (its quantised maps are complete)
-        if (!(stages & kFeMemories)) return;
-        if (l < L - 1 ? direct_low : direct_top) return;    // bit planes only: fe_bits_jobs below
+    auto flush = [&]() -> int { if (st.njobs) { LM_CLOCK("launch_fe_stage"); HIP_TRY(launch_fe_stage(st, s)); } st.njobs = 0; return LM_OK; };
+    auto room = [&](int jobs) { return st.njobs + jobs > kFeMaxJobs ? flush() : LM_OK; };
+    auto build_lm_jobs = [&](int l) -> int {                 // linear memories of level l of every frame (its quantised maps are complete)
+        if (!(stages & kFeMemories)) return LM_OK;
+        if (l < L - 1 ? direct_low : direct_top) return LM_OK;   // bit planes only: fe_bits_jobs below
         for (int b = 0; b < nb; ++b) {
             const LevelPtrs P = d->level_ptrs(b, l, (first + b) % lm_detector::kSlots);
-            room(1);
+            if (int e = room(1)) return e;
             fe_job_build_lm(st.job[st.njobs++], P.quant, P.mask, P.lm, P.strips, d->lvl[l].W, d->lvl[l].H, d->geom.lv[l].T, m0, nm);
         }
+        return LM_OK;
     };
     // Launch l quantises level l of every frame and — beside it, they only need level l - 1 — builds the linear memories of level
     // l - 1; a last launch builds those of the top level.  (The memories of level 0 are 3/4 of that work: they no longer wait for
@@ -49,7 +50,7 @@ int run_frontend_batch(lm_detector* d, int first, int nb, hipStream_t s, bool di
             const lm_detector::Slot& sl = d->slot[(first + b) % lm_detector::kSlots];
             LevelBufs& B = d->level_bufs(b, l);
             const uint8_t* src = l == 0 ? sl.in_rgb : B.rgb.p;
-            room(3);
+            if ((rc = room(3))) return rc;
             if (d->use[0]) fe_job_colour(st.job[st.njobs++], src, nullptr /* magnitudes: addTemplate only */, B.ang.p, B.W, B.H, thr_sq, d->cch);      // LL.cpp:367-504
             if (d->use[1]) {
                 if (l == 0) fe_job_normals(st.job[st.njobs++], sl.in_depth, b == 0 ? d->nrm_raw.p : d->nrm_raw_x[b - 1].p, B.nrm.p, B.W, B.H,
@@ -58,32 +59,30 @@ int run_frontend_batch(lm_detector* d, int first, int nb, hipStream_t s, bool di
             }
             if (d->use[0] && l + 1 < L) fe_job_pyrdown(st.job[st.njobs++], src, d->level_bufs(b, l + 1).rgb.p, B.W, B.H, d->cch);                     // LL.cpp:557-581
         }
-        if (l > 0) build_lm_jobs(l - 1);
-        flush();
+        if (l > 0 && (rc = build_lm_jobs(l - 1))) return rc;
+        if ((rc = flush())) return rc;
     }
-    build_lm_jobs(L - 1);
-    flush();
+    if ((rc = build_lm_jobs(L - 1)) || (rc = flush())) return rc;
     if (stages & kFeQuantise) d->quantised = true;
-    if (!(stages & kFeMemories)) { HIP_TRY(hipGetLastError()); return LM_OK; }
+    if (!(stages & kFeMemories)) return LM_OK;
     if (direct_low || direct_top) {                      // the bit planes of every frame in one launch
         st.njobs = 0;
-        auto flush_bits = [&]() { if (st.njobs) { LM_CLOCK("launch_fe_bits"); launch_fe_bits(st, s); } st.njobs = 0; };
+        auto flush_bits = [&]() -> int { if (st.njobs) { LM_CLOCK("launch_fe_bits"); HIP_TRY(launch_fe_bits(st, s)); } st.njobs = 0; return LM_OK; };
         for (int b = 0; b < nb; ++b) {
             for (int l = 0; l < L; ++l) {
                 const bool top = l == L - 1;
                 if (top ? !direct_top : !direct_low) continue;
                 const LevelPtrs P = d->level_ptrs(b, l, (first + b) % lm_detector::kSlots);
                 const int W = d->lvl[l].W, H = d->lvl[l].H, T = d->geom.lv[l].T;
-                if (st.njobs + 1 > kFeMaxJobs) flush_bits();
+                if (st.njobs + 1 > kFeMaxJobs && (rc = flush_bits())) return rc;
                 if (top) fe_job_top_bits(st.job[st.njobs++], P.quant, P.mask, P.top_stream, P.bit0, W, H, T, d->fe_top_mode, m0, nm);
                 else fe_job_bits_rows(st.job[st.njobs++], P.quant, P.mask, P.bits, W, H, T, d->fe_top_mode == 0, m0, nm);
             }
         }
-        flush_bits();
+        if ((rc = flush_bits())) return rc;
     }
     d->fe_bytes_low = !direct_low; d->fe_bytes_top = !direct_top;
     d->last_arena = first;                               // read_stage: the maps of level_bufs(0, .) belong to the batch's first frame
-    HIP_TRY(hipGetLastError());
     return LM_OK;
 }
 

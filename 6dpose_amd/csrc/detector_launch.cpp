@@ -283,7 +283,7 @@ static int ensure_wide_arenas(lm_detector* d, const Batch& B) {
 }
 
 // The tables of the bit-plane kernels (BitsBatch, TopBits), and the bit planes themselves where the front end left byte planes.
-static void pack_bit_planes(lm_detector* d, Batch& B) {
+static int pack_bit_planes(lm_detector* d, Batch& B) {
     B.fb_rest = B.fb;
     if (B.bits) {
         for (int b = 0; b < B.nb; ++b) {
@@ -294,10 +294,10 @@ static void pack_bit_planes(lm_detector* d, Batch& B) {
         }
         if (B.wide) {
             for (int b = 0; b < B.nb; ++b) B.wb.set1[b] = d->wbits_arena[B.slot(b)].p;
-            for (int l = 0; l + 1 < d->geom.levels; ++l) launch_pack_wide(B.bb, B.wb, B.nb, d->geom.lv[l], B.s);
+            for (int l = 0; l + 1 < d->geom.levels; ++l) HIP_TRY(launch_pack_wide(B.bb, B.wb, B.nb, d->geom.lv[l], B.s));
         } else
         if (!B.direct_low)
-            for (int l = 0; l + 1 < d->geom.levels; ++l) launch_pack_bits(B.bb, B.nb, d->geom.lv[l], B.s);
+            for (int l = 0; l + 1 < d->geom.levels; ++l) HIP_TRY(launch_pack_bits(B.bb, B.nb, d->geom.lv[l], B.s));
     }
     if (B.cbits) {
         for (int b = 0; b < B.nb; ++b) {
@@ -309,10 +309,11 @@ static void pack_bit_planes(lm_detector* d, Batch& B) {
         if (B.top_ored && !d->fe_keep_top) B.bb.top_clear_units = (d->cbits_npairs * 8u + 15u) / 16u;
         if (B.cwide) {
             for (int b = 0; b < B.nb; ++b) B.wt.set1[b] = d->wcbits_arena[B.slot(b)].p;
-            launch_pack_top_wide(B.tb, B.wt, B.nb, d->cbits_byte0, d->cbits_npairs, B.s);
+            HIP_TRY(launch_pack_top_wide(B.tb, B.wt, B.nb, d->cbits_byte0, d->cbits_npairs, B.s));
         } else
-        if (!B.direct_top) launch_pack_top(B.tb, B.nb, d->cbits_byte0, d->cbits_npairs, B.s);
+        if (!B.direct_top) HIP_TRY(launch_pack_top(B.tb, B.nb, d->cbits_byte0, d->cbits_npairs, B.s));
     }
+    return LM_OK;
 }
 
 // One queue for the whole batch: the end of a stage IS the start of the next — one timing record between two kernels instead of two or
@@ -337,10 +338,10 @@ static int record_front_end(lm_detector* d, const Batch& B) {
 static int enqueue_coarse(lm_detector* d, const Batch& B) {
     // the counters are zero on entry (reset by the slots' previous k_dedupe)
     { LM_CLOCK("launch_coarse");
-    if (B.cwide) launch_coarse_wide(B.fb, B.tb, B.wt, d->geom, B.bank, B.num_work, B.threshold, d->buf_cand_cap, d->cbits_byte0, d->cbits_max_nf, B.s);
-    else if (B.parts) { launch_coarse_parts(B.fb, B.tb, d->geom, B.bank, B.pd, B.num_work, B.threshold, d->buf_cand_cap, d->cbits_byte0, d->cbits_max_nf, d->resp_low_weight, B.s); d->coarse_batched = false; }
-    else if (B.cbits) d->coarse_batched = launch_coarse_bits(B.fb, B.tb, d->geom, B.bank, B.num_work, B.threshold, d->buf_cand_cap, d->cbits_byte0, d->cbits_max_nf, d->resp_low_weight, B.s, d->coarse_batch);
-    else launch_coarse(B.fb, d->geom, B.bank, B.num_work, B.threshold, d->buf_cand_cap, B.tile_cap, B.s);
+    if (B.cwide) HIP_TRY(launch_coarse_wide(B.fb, B.tb, B.wt, d->geom, B.bank, B.num_work, B.threshold, d->buf_cand_cap, d->cbits_byte0, d->cbits_max_nf, B.s));
+    else if (B.parts) { d->coarse_batched = false; HIP_TRY(launch_coarse_parts(B.fb, B.tb, d->geom, B.bank, B.pd, B.num_work, B.threshold, d->buf_cand_cap, d->cbits_byte0, d->cbits_max_nf, d->resp_low_weight, B.s)); }
+    else if (B.cbits) HIP_TRY(launch_coarse_bits(B.fb, B.tb, d->geom, B.bank, B.num_work, B.threshold, d->buf_cand_cap, d->cbits_byte0, d->cbits_max_nf, d->resp_low_weight, B.s, &d->coarse_batched, d->coarse_batch));
+    else HIP_TRY(launch_coarse(B.fb, d->geom, B.bank, B.num_work, B.threshold, d->buf_cand_cap, B.tile_cap, B.s));
     }
     HIP_TRY(hipEventRecord(d->slot[B.first].ev[3], B.s));
     return LM_OK;
@@ -353,17 +354,17 @@ static int enqueue_match(lm_detector* d, const Batch& B) {
     const uint32_t dedupe_slots = (uint32_t)dedupe_table_slots(d->buf_cand_cap);
     if (B.bits) {
         { LM_CLOCK("launch_local_bits");
-        if (B.wide) launch_local_wide(B.fb, B.bb, B.wb, d->geom, B.bank, d->buf_cand_cap, B.threshold, B.cap, dedupe_slots, bits_grid(d), d->bits_max_nf, B.s);
-        else if (B.parts) launch_local_parts(B.fb, B.bb, d->geom, B.bank, B.pd, d->buf_cand_cap, B.threshold, B.cap, dedupe_slots, bits_grid(d), d->bits_max_nf, d->resp_low_weight, B.s);
-        else launch_local_bits(B.fb, B.bb, d->geom, B.bank, d->buf_cand_cap, B.threshold, B.cap, dedupe_slots, bits_grid(d), d->bits_max_nf, d->resp_low_weight, B.s); }
+        if (B.wide) HIP_TRY(launch_local_wide(B.fb, B.bb, B.wb, d->geom, B.bank, d->buf_cand_cap, B.threshold, B.cap, dedupe_slots, bits_grid(d), d->bits_max_nf, B.s));
+        else if (B.parts) HIP_TRY(launch_local_parts(B.fb, B.bb, d->geom, B.bank, B.pd, d->buf_cand_cap, B.threshold, B.cap, dedupe_slots, bits_grid(d), d->bits_max_nf, d->resp_low_weight, B.s));
+        else HIP_TRY(launch_local_bits(B.fb, B.bb, d->geom, B.bank, d->buf_cand_cap, B.threshold, B.cap, dedupe_slots, bits_grid(d), d->bits_max_nf, d->resp_low_weight, B.s)); }
         if (B.bb.top_clear_units)     // the pair streams this launch zeroes again are clean for their slots' next frames
             for (int b = 0; b < B.nb; ++b)
                 if (B.bb.top_clear[b]) d->cbits_clean[B.slot(b)] = true;
         if (!d->bits_all_in)          // candidates whose windows leave their planes (marked in todo): k_local's per-candidate path
-            launch_local(B.fb_rest, d->geom, B.bank, d->buf_cand_cap, B.threshold, B.cap, dedupe_slots, B.tile_cap, d->num_cus * 2, B.s);
+            HIP_TRY(launch_local(B.fb_rest, d->geom, B.bank, d->buf_cand_cap, B.threshold, B.cap, dedupe_slots, B.tile_cap, d->num_cus * 2, B.s));
     } else
     if (B.num_work > 0)
-        launch_local(B.fb, d->geom, B.bank, d->buf_cand_cap, B.threshold, B.cap, dedupe_slots, B.tile_cap, local_grid(d, B.nb), B.s);
+        HIP_TRY(launch_local(B.fb, d->geom, B.bank, d->buf_cand_cap, B.threshold, B.cap, dedupe_slots, B.tile_cap, local_grid(d, B.nb), B.s));
     HIP_TRY(hipEventRecord(d->slot[B.first].ev[4], B.s));
     return LM_OK;
 }
@@ -377,7 +378,7 @@ static int enqueue_dedupe(lm_detector* d, const Batch& B) {
                                                         : std::max(64, std::min(d->num_cus * 2, (int)((d->ncand_hint + 255) / 256)));
     if (B.num_work > 0) {
         LM_CLOCK("launch_dedupe");
-        launch_dedupe(B.fb, d->buf_cand_cap, dedupe_table_slots(d->buf_cand_cap), d->d_work_cls.p, d->d_work_tid.p, dedupe_blocks, B.s);
+        HIP_TRY(launch_dedupe(B.fb, d->buf_cand_cap, dedupe_table_slots(d->buf_cand_cap), d->d_work_cls.p, d->d_work_tid.p, dedupe_blocks, B.s));
     }
     else
         for (int b = 0; b < B.nb; ++b) HIP_TRY(hipMemsetAsync(B.fb.f[b].final_dev, 0, 8 * sizeof(unsigned long long), B.s));   // nothing searched: no records for NMS / exchange
@@ -410,7 +411,7 @@ int lm_launch_pending(lm_detector* d) {
     }
     const int stages = d->slabs.quantised && B.nb == 1 ? kFeMemories : kFeQuantise | kFeMemories;
     { LM_CLOCK("step front end"); if ((rc = run_frontend_batch(d, B.first, B.nb, B.s, B.direct_low, B.direct_top, stages))) return rc; }
-    { LM_CLOCK("step bits tables+ev1"); pack_bit_planes(d, B); if ((rc = record_front_end(d, B))) return rc; }
+    { LM_CLOCK("step bits tables+ev1"); if ((rc = pack_bit_planes(d, B)) || (rc = record_front_end(d, B))) return rc; }
     { LM_CLOCK("step coarse"); if ((rc = enqueue_coarse(d, B))) return rc; }
     { LM_CLOCK("step refine"); if ((rc = enqueue_match(d, B))) return rc; }
     { LM_CLOCK("step dedupe+done"); if ((rc = enqueue_dedupe(d, B))) return rc; }

@@ -124,9 +124,8 @@ static int write_slab_masks(lm_detector* d, int lo, int hi) {
         FeStage st{};
         for (int o = 0; o < a.n_out; ++o)
             fe_job_nn_down2(st.job[st.njobs++], S.mask[l - 1][buf[o]].p, S.mask[l][buf[o]].p, d->lvl[l - 1].W, d->lvl[l - 1].H);
-        launch_fe_stage(st, d->stream);
+        HIP_TRY(launch_fe_stage(st, d->stream));
     }
-    HIP_TRY(hipGetLastError());
     for (int l = 0; l < L; ++l)
         for (int m = 0; m < 2; ++m) S.mask_of[l][m] = which[m] >= 0 ? S.mask[l][which[m]].p : nullptr;
     return LM_OK;

@@ -75,8 +75,7 @@ extern "C" int lm_detector_exchange_pack_group(lm_detector* d, uint64_t first, i
         G.f[i].runs = d->xchg.d_runs.p + (size_t)kXchgMaxCapacity * i;
         G.f[i].block = (uint32_t*)((uint8_t*)send_blocks + (size_t)i * blk);
     }
-    launch_exchange_pack_group(G, d->buf_cand_cap, (uint32_t)capacity, xs);
-    HIP_TRY(hipGetLastError());
+    HIP_TRY(launch_exchange_pack_group(G, d->buf_cand_cap, (uint32_t)capacity, xs));
     for (int i = 0; i < n; ++i) {
         const int slot = (int)((first + (uint64_t)i) % lm_detector::kSlots);
         d->xchg.state[slot] = 1;
@@ -109,8 +108,7 @@ extern "C" int lm_detector_exchange_merge_group_strided(lm_detector* d, uint64_t
         HIP_TRY(hipHostGetDevicePointer((void**)&G.f[i].host, d->xchg.h_merged[slot].p, 0));
     }
     hipStream_t xs = d->xchg_stream;
-    launch_exchange_merge_group(G, world, (uint32_t)capacity, xs, (uint32_t)(rank_stride_bytes / 4));   // merge + copy-out to the pinned buffers
-    HIP_TRY(hipGetLastError());
+    HIP_TRY(launch_exchange_merge_group(G, world, (uint32_t)capacity, xs, (uint32_t)(rank_stride_bytes / 4)));   // merge + copy-out to the pinned buffers
     for (int i = 0; i < n; ++i) {
         // the group's completion on EVERY member slot's own event (a record is cheap): with one event on the first slot, that slot's next
         // frame — 16 frames on — re-recorded it while the later members of this group were still uncollected, and their collect then waited

@@ -16,6 +16,7 @@
 // std::unique exactly when its predecessor in the merged order agrees on (x, y, similarity, class) (Match::operator==,
 // LL.h:243-246); the predecessor is the largest of the per-run predecessors, which the same searches deliver, so no pass
 // over the merged list is needed.  The host only skips the marked records while copying out.
+#include "launch.h"
 #include "lm_kernels.h"
 
 namespace lm {
@@ -209,11 +210,11 @@ k_exchange_merge(XchgGroup G, int W, uint32_t cap, uint32_t block_words) {
     o[4] = (int32_t)(uint32_t)(key.x & 0xFFFFFFFFu);
 }
 
-void launch_exchange_pack_group(const XchgGroup& G, uint32_t cand_cap, uint32_t cap, hipStream_t s) {
-    if (G.n <= 0) return;
+hipError_t launch_exchange_pack_group(const XchgGroup& G, uint32_t cand_cap, uint32_t cap, hipStream_t s) {
+    if (G.n <= 0) return hipSuccess;
     const dim3 grid((cap + kWG - 1) / kWG, G.n);
-    hipLaunchKernelGGL(k_exchange_sort256, grid, dim3(kWG), 0, s, G, cand_cap, cap);
-    hipLaunchKernelGGL(k_exchange_merge256, grid, dim3(kWG), 0, s, G, cand_cap, cap);
+    LAUNCH_TRY(lm_launch(k_exchange_sort256, grid, dim3(kWG), 0, s, G, cand_cap, cap));
+    return lm_launch(k_exchange_merge256, grid, dim3(kWG), 0, s, G, cand_cap, cap);
 }
 
 // The merged list of every frame of the group into its pinned host buffer: header + the records actually there (16-byte stores).  A
@@ -231,11 +232,11 @@ k_exchange_copyout(XchgGroup G) {
     for (uint32_t i = blockIdx.x * kWG + threadIdx.x; i < quads; i += gridDim.x * kWG) d4[i] = s4[i];
 }
 
-void launch_exchange_merge_group(const XchgGroup& G, int world, uint32_t cap, hipStream_t s, uint32_t rank_stride_words) {
-    if (G.n <= 0) return;
+hipError_t launch_exchange_merge_group(const XchgGroup& G, int world, uint32_t cap, hipStream_t s, uint32_t rank_stride_words) {
+    if (G.n <= 0) return hipSuccess;
     const uint32_t block_words = rank_stride_words ? rank_stride_words : 4 + cap * 4;   // distance between the blocks of consecutive ranks
-    hipLaunchKernelGGL(k_exchange_merge, dim3((cap + kWG - 1) / kWG, world, G.n), dim3(kWG), 0, s, G, world, cap, block_words);
-    if (G.f[0].host) hipLaunchKernelGGL(k_exchange_copyout, dim3(16, G.n), dim3(kWG), 0, s, G);
+    LAUNCH_TRY(lm_launch(k_exchange_merge, dim3((cap + kWG - 1) / kWG, world, G.n), dim3(kWG), 0, s, G, world, cap, block_words));
+    return G.f[0].host ? lm_launch(k_exchange_copyout, dim3(16, G.n), dim3(kWG), 0, s, G) : hipSuccess;
 }
 
 }  // namespace lm

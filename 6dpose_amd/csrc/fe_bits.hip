@@ -8,6 +8,7 @@
 //   k_fe_bits                                             the one kernel of all of these: k_fe_stage's job table and persistent walk
 //   fe_bits_rows_possible, fe_job_bits_rows, fe_top_bits_kind, fe_job_top_bits, launch_fe_bits
 // What it shares with fe_quant.hip is fe_device.h.
+#include "launch.h"
 #include "fe_device.h"
 #include "knobs.h"
 
@@ -437,18 +438,19 @@ void fe_job_top_bits(FeJob& j, const uint8_t* const quant[2], const uint8_t* con
         j.kind = kFeTopBitsAligned; j.gx = (T * T * npos + 255) / 256; j.gy = 1; j.m_np = div_magic((uint32_t)npos);
     }
 }
-static void launch_bits_jobs(FeStage& st, hipStream_t s) {
+static hipError_t launch_bits_jobs(FeStage& st, hipStream_t s) {
     const int total = fe_prepare(st);
-    if (total > 0) hipLaunchKernelGGL(k_fe_bits, dim3(std::min(total, fe_cus() * 8)), dim3(256), 0, s, st, total);
+    return total > 0 ? lm_launch(k_fe_bits, dim3(std::min(total, fe_cus() * 8)), dim3(256), 0, s, st, total) : hipSuccess;
 }
-void launch_fe_bits(FeStage& st, hipStream_t s) {
+hipError_t launch_fe_bits(FeStage& st, hipStream_t s) {
     if (!knobs().fe_bits_split) return launch_bits_jobs(st, s);
     for (int kind : {kFeBitsRows, kFeTopBits}) {          // LM_FE_BITS_SPLIT=1 (measurements): the strip-record jobs and the pair-stream jobs as two launches
         FeStage part{};
         part.resp = st.resp;
         for (int i = 0; i < st.njobs; ++i) if ((st.job[i].kind == kFeBitsRows || st.job[i].kind == kFeBitsRowsTile) == (kind == kFeBitsRows)) part.job[part.njobs++] = st.job[i];
-        launch_bits_jobs(part, s);
+        LAUNCH_TRY(launch_bits_jobs(part, s));
     }
+    return hipSuccess;
 }
 
 }  // namespace lm

@@ -15,6 +15,7 @@
 // output element with coalesced stores.  Parity-critical float steps use the *_rn intrinsics so
 // that no FMA contraction or reassociation can occur (the reference is x86-64 SSE2 scalar float,
 // OpenCV semantics per SURVEY Appendix A).
+#include "launch.h"
 #include "fe_device.h"
 #include "knobs.h"
 
@@ -22,8 +23,8 @@ namespace lm {
 
 __constant__ uint8_t c_normal_lut[400];   // NORMAL_LUT[.][y][x] (z-independent), normal_lut.i
 
-void upload_normal_lut(const uint8_t lut400[400]) {
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(c_normal_lut), lut400, 400);
+hipError_t upload_normal_lut(const uint8_t lut400[400]) {
+    return hipMemcpyToSymbol(HIP_SYMBOL(c_normal_lut), lut400, 400);
 }
 
 static __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
@@ -362,8 +363,8 @@ __global__ void __launch_bounds__(256) k_rgb_to_grey(const uint8_t* __restrict__
     const uint8_t* p = rgb + 3 * i;
     grey[i] = (uint8_t)((4899u * p[0] + 9617u * p[1] + 1868u * p[2] + 8192u) >> 14);
 }
-void launch_rgb_to_grey(const uint8_t* rgb, uint8_t* grey, size_t pixels, hipStream_t s) {
-    if (pixels) hipLaunchKernelGGL(k_rgb_to_grey, dim3((unsigned)((pixels + 255) / 256)), dim3(256), 0, s, rgb, grey, pixels);
+hipError_t launch_rgb_to_grey(const uint8_t* rgb, uint8_t* grey, size_t pixels, hipStream_t s) {
+    return pixels ? lm_launch(k_rgb_to_grey, dim3((unsigned)((pixels + 255) / 256)), dim3(256), 0, s, rgb, grey, pixels) : hipSuccess;
 }
 
 // ---- quantizedNormals (LL.cpp:729-817; Appendix A.7) + cv::medianBlur(5) (LL.cpp:818), replicate border ----------
@@ -677,15 +678,14 @@ void fe_job_build_lm(FeJob& j, const uint8_t* const quant[2], const uint8_t* con
     j.gx = (j.Wd * j.Hd + 255) / 256;
     for (int z = 0; z < nm; ++z) j.lm[z] = LmJob{quant[m0 + z], mask[m0 + z], lm[m0 + z], strips[m0 + z]};
 }
-void launch_fe_stage(FeStage& st, hipStream_t s) {
+hipError_t launch_fe_stage(FeStage& st, hipStream_t s) {
     const int total = fe_prepare(st);
-    if (total <= 0) return;
+    if (total <= 0) return hipSuccess;
     const int per_cu = knobs().fe_wgs_per_cu;
     const int grid = per_cu > 0 ? std::min(total, fe_cus() * per_cu) : total;
     bool grey = false;                                               // the grey kinds come from a detector with colour_channels = 1, which never adds the RGB ones
     for (int i = 0; i < st.njobs; ++i) grey = grey || st.job[i].kind == kFeColourGrey || st.job[i].kind == kFePyrDownGrey;
-    if (grey) hipLaunchKernelGGL(k_fe_stage<1>, dim3(grid), dim3(256), 0, s, st, total);
-    else hipLaunchKernelGGL(k_fe_stage<3>, dim3(grid), dim3(256), 0, s, st, total);
+    return lm_launch(grey ? k_fe_stage<1> : k_fe_stage<3>, dim3(grid), dim3(256), 0, s, st, total);
 }
 
 }  // namespace lm

@@ -77,7 +77,7 @@ inline void border_job(BorderJob& j, const void* src, void* dst, int W, int H, i
     j.first = 0; j.units = 0;
 }
 // dst must be 16-byte aligned and Wa * Ha a multiple of 16 (every aligned geometry is); src may start at any byte.
-hipError_t launch_frame_border(BorderStage& st, hipStream_t s);
+[[nodiscard]] hipError_t launch_frame_border(BorderStage& st, hipStream_t s);
 #endif
 
 }  // namespace lm

@@ -7,6 +7,7 @@
 // one or two per row) is 16 consecutive source bytes; they start at any byte offset (W odd, colour rows of 3 W bytes, the depth image
 // behind a colour image of odd size), so they are fetched as the aligned dwords that cover them and shifted into place.  The other units
 // — across a row end, in the margins — are put together byte by byte.
+#include "launch.h"
 #include "frame_border.h"
 
 namespace lm {
@@ -66,8 +67,7 @@ hipError_t launch_frame_border(BorderStage& st, hipStream_t s) {
         total += j.units;
     }
     if (!total) return hipSuccess;
-    hipLaunchKernelGGL(k_frame_border, dim3((total + 255u) / 256u), dim3(256), 0, s, st, total);
-    return hipGetLastError();
+    return lm_launch(k_frame_border, dim3((total + 255u) / 256u), dim3(256), 0, s, st, total);
 }
 
 }  // namespace lm

@@ -19,6 +19,7 @@
 // oracle/linemod_oracle.py).  All arithmetic is double like Open3D's (f64 VALU; nothing here is a dense contraction, so no MFMA).
 #include <limits.h>
 
+#include "launch.h"
 #include "icp_device.h"
 #include "icp_kernels.h"
 #include "knobs.h"
@@ -1459,20 +1460,20 @@ k_icp_normals(IcpBuffers B) {
     }
 }
 
-void launch_icp_prepare(const IcpBuffers& B, int count, int W, int H, int flags, double voxel, int knn, hipStream_t s) {
-    if (count <= 0) return;
+hipError_t launch_icp_prepare(const IcpBuffers& B, int count, int W, int H, int flags, double voxel, int knn, hipStream_t s) {
+    if (count <= 0) return hipSuccess;
     const Knobs& kn = knobs();
     const int scene_mode = flags & 1;
-    launch_icp_clouds(B, count, W, H, flags, s);
+    LAUNCH_TRY(launch_icp_clouds(B, count, W, H, flags, s));
     // voxel down-sampling and the search grid by kIcpSortGroups workgroups per cloud; the one-workgroup kernels behind them take what those
     // left (IcpState::vox_done / grid_done) and cost ~2 us when there is nothing
-    if (kn.icp_wide_sort) hipLaunchKernelGGL(k_icp_voxel_wide, dim3(kIcpSortGroups, count, scene_mode ? 2 : 1), dim3(kWG), 0, s, B, flags, voxel);
-    hipLaunchKernelGGL(k_icp_voxel, dim3(count, scene_mode ? 2 : 1), dim3(kWG), 0, s, B, flags, voxel);
-    if (kn.icp_wide_sort) hipLaunchKernelGGL(k_icp_grid_wide, dim3(kIcpSortGroups, count), dim3(kWG), 0, s, B, flags);
-    hipLaunchKernelGGL(k_icp_grid, dim3(count), dim3(kWG), 0, s, B, flags);
-    hipLaunchKernelGGL(k_icp_knn, dim3(kn.knn_blocks > 0 ? kn.knn_blocks : (count <= 32 ? 64 : 32), count), dim3(kKnnWG), 0, s, B, knn);
-    hipLaunchKernelGGL(k_icp_knn_far, dim3(kKnnFarBlocks, count), dim3(512), 0, s, B, knn);
-    if (!(flags & 2)) hipLaunchKernelGGL(k_icp_normals, dim3(count <= 32 ? 64 : 16, count), dim3(256), 0, s, B);   // (point-to-point reads no normals)
+    if (kn.icp_wide_sort) LAUNCH_TRY(lm_launch(k_icp_voxel_wide, dim3(kIcpSortGroups, count, scene_mode ? 2 : 1), dim3(kWG), 0, s, B, flags, voxel));
+    LAUNCH_TRY(lm_launch(k_icp_voxel, dim3(count, scene_mode ? 2 : 1), dim3(kWG), 0, s, B, flags, voxel));
+    if (kn.icp_wide_sort) LAUNCH_TRY(lm_launch(k_icp_grid_wide, dim3(kIcpSortGroups, count), dim3(kWG), 0, s, B, flags));
+    LAUNCH_TRY(lm_launch(k_icp_grid, dim3(count), dim3(kWG), 0, s, B, flags));
+    LAUNCH_TRY(lm_launch(k_icp_knn, dim3(kn.knn_blocks > 0 ? kn.knn_blocks : (count <= 32 ? 64 : 32), count), dim3(kKnnWG), 0, s, B, knn));
+    LAUNCH_TRY(lm_launch(k_icp_knn_far, dim3(kKnnFarBlocks, count), dim3(512), 0, s, B, knn));
+    return flags & 2 ? hipSuccess : lm_launch(k_icp_normals, dim3(count <= 32 ? 64 : 16, count), dim3(256), 0, s, B);   // (point-to-point reads no normals)
 }
 
 }  // namespace lm

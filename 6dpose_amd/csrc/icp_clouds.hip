@@ -11,6 +11,7 @@
 // oracle/linemod_oracle.py).  All arithmetic is double like Open3D's (f64 VALU; nothing here is a dense contraction, so no MFMA).
 #include <limits.h>
 
+#include "launch.h"
 #include "icp_device.h"
 #include "icp_kernels.h"
 #include "knobs.h"
@@ -120,10 +121,8 @@ k_icp_model_boxes(const uint16_t* __restrict__ models, int* __restrict__ model_b
 
 hipError_t launch_icp_model_boxes(const uint16_t* models, int* model_bbox, int first_slot, int count, int W, int H, hipStream_t s) {
     if (count <= 0) return hipSuccess;
-    const hipError_t e = hipMemsetAsync(model_bbox + (size_t)first_slot * 8, 0, (size_t)count * 8 * sizeof(int), s);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_icp_model_boxes, dim3(32, count), dim3(256), 0, s, models, model_bbox, first_slot, W, H);
-    return hipGetLastError();
+    LAUNCH_TRY(hipMemsetAsync(model_bbox + (size_t)first_slot * 8, 0, (size_t)count * 8 * sizeof(int), s));
+    return lm_launch(k_icp_model_boxes, dim3(32, count), dim3(256), 0, s, models, model_bbox, first_slot, W, H);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -497,21 +496,18 @@ __global__ void k_icp_bind(const TopkSel* __restrict__ sel, const int32_t* __res
     S.status = status;
 }
 
-void launch_icp_bind(const TopkSel* sel, const int32_t* nsel_status, const int32_t* class_base, const float* view_K,
+hipError_t launch_icp_bind(const TopkSel* sel, const int32_t* nsel_status, const int32_t* class_base, const float* view_K,
                      const int32_t* view_valid, int num_views, IcpIn* in, IcpState* st, int top_k, hipStream_t s) {
-    if (top_k <= 0) return;
-    hipLaunchKernelGGL(k_icp_bind, dim3((top_k + 63) / 64), dim3(64), 0, s, sel, nsel_status, class_base, view_K, view_valid, num_views, in, st,
-                       top_k);
+    if (top_k <= 0) return hipSuccess;
+    return lm_launch(k_icp_bind, dim3((top_k + 63) / 64), dim3(64), 0, s, sel, nsel_status, class_base, view_K, view_valid, num_views, in, st, top_k);
 }
 
-void launch_icp_clouds(const IcpBuffers& B, int count, int W, int H, int flags, hipStream_t s) {
+hipError_t launch_icp_clouds(const IcpBuffers& B, int count, int W, int H, int flags, hipStream_t s) {
     const Knobs& kn = knobs();
-    if (!(flags & 0x100) || !kn.icp_wide_sort) hipLaunchKernelGGL(k_icp_bbox, dim3(32, count), dim3(256), 0, s, B, W, H);   // (0x100: every slot's box is in model_bbox)
-    if (kn.icp_wide_sort) hipLaunchKernelGGL(k_icp_points_fused, dim3(kIcpStrips, count), dim3(kPtsWG), 0, s, B, W, H, flags);
-    else {
-        hipLaunchKernelGGL(k_icp_points<false>, dim3(kIcpStrips, count), dim3(kPtsWG), 0, s, B, W, H, flags);
-        hipLaunchKernelGGL(k_icp_points<true>, dim3(kIcpStrips, count), dim3(kPtsWG), 0, s, B, W, H, flags);
-    }
+    if (!(flags & 0x100) || !kn.icp_wide_sort) LAUNCH_TRY(lm_launch(k_icp_bbox, dim3(32, count), dim3(256), 0, s, B, W, H));   // (0x100: every slot's box is in model_bbox)
+    if (kn.icp_wide_sort) return lm_launch(k_icp_points_fused, dim3(kIcpStrips, count), dim3(kPtsWG), 0, s, B, W, H, flags);
+    LAUNCH_TRY(lm_launch(k_icp_points<false>, dim3(kIcpStrips, count), dim3(kPtsWG), 0, s, B, W, H, flags));
+    return lm_launch(k_icp_points<true>, dim3(kIcpStrips, count), dim3(kPtsWG), 0, s, B, W, H, flags);
 }
 
 }  // namespace lm

@@ -86,6 +86,6 @@ static __device__ __forceinline__ double wave_reduce32(double (&v)[32], int lane
 }
 
 // The first launches of launch_icp_prepare: box, dilated mask and back-projection of every hypothesis (icp_clouds.hip)
-void launch_icp_clouds(const IcpBuffers& B, int count, int W, int H, int flags, hipStream_t s);
+[[nodiscard]] hipError_t launch_icp_clouds(const IcpBuffers& B, int count, int W, int H, int flags, hipStream_t s);
 
 }  // namespace lm

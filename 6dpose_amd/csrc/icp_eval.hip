@@ -11,6 +11,7 @@
 // oracle/linemod_oracle.py).  All arithmetic is double like Open3D's (f64 VALU; nothing here is a dense contraction, so no MFMA).
 #include <limits.h>
 
+#include "launch.h"
 #include "icp_device.h"
 #include "icp_kabsch.h"
 #include "icp_kernels.h"
@@ -548,9 +549,9 @@ static int icp_slices(int count, int it) {
     return it < kIcpFineFrom || kn.icp_splits > 0 ? splits : kIcpMaxSplit;
 }
 
-void launch_icp_evals(const IcpBuffers& B, int count, int it_from, int it_to, bool p2p, double max_dist, int max_iter, double rel_fit, double rel_rmse,
+hipError_t launch_icp_evals(const IcpBuffers& B, int count, int it_from, int it_to, bool p2p, double max_dist, int max_iter, double rel_fit, double rel_rmse,
                       hipStream_t s) {
-    if (count <= 0) return;
+    if (count <= 0) return hipSuccess;
     const Knobs& kn = knobs();
 #ifdef LM_DIAG
     if (kn.icp_maxiter_diag >= 0) max_iter = kn.icp_maxiter_diag;            // diagnostics only (profiles/): stop after a few evaluations
@@ -559,10 +560,11 @@ void launch_icp_evals(const IcpBuffers& B, int count, int it_from, int it_to, bo
     for (int it = it_from; it <= it_to; ++it) {
         // lanes per searching point: at most 8 while every point searches (the first evaluations: more lanes only multiply the
         // set-up), 16 afterwards (few searches left: their latency is what counts) — measured, profiles/r02_icp_experiments.txt
-        hipLaunchKernelGGL(p2p ? k_icp_eval<true> : k_icp_eval<false>, dim3(icp_slices(count, it), count), dim3(kSearchWG), 0, s, B, it,
-                           it > 0 ? icp_slices(count, it - 1) : 1, it < kIcpFineFrom ? kn.icp_maxshift : kn.icp_maxshift_late, max_dist, max_iter,
-                           rel_fit, rel_rmse);
+        LAUNCH_TRY(lm_launch(p2p ? k_icp_eval<true> : k_icp_eval<false>, dim3(icp_slices(count, it), count), dim3(kSearchWG), 0, s, B, it,
+                             it > 0 ? icp_slices(count, it - 1) : 1, it < kIcpFineFrom ? kn.icp_maxshift : kn.icp_maxshift_late, max_dist, max_iter,
+                             rel_fit, rel_rmse));
     }
+    return hipSuccess;
 }
 
 }  // namespace lm

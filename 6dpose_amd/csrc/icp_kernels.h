@@ -99,19 +99,19 @@ struct IcpBuffers {
 };
 
 struct TopkSel;
-void launch_icp_bind(const TopkSel* sel, const int32_t* nsel_status, const int32_t* class_base, const float* view_K,
-                     const int32_t* view_valid, int num_views, IcpIn* in, IcpState* st, int top_k, hipStream_t s);
+[[nodiscard]] hipError_t launch_icp_bind(const TopkSel* sel, const int32_t* nsel_status, const int32_t* class_base, const float* view_K,
+                                         const int32_t* view_valid, int num_views, IcpIn* in, IcpState* st, int top_k, hipStream_t s);
 // The preparation of the clouds (box, dilated mask, back-projection, voxel down-sampling, search grid, kNN normals); bit 0x100 of flags:
 // every model slot the hypotheses use had its box worked out at upload (launch_icp_model_boxes); bit 2 (LM_ICP_POINT_TO_POINT): no
 // k_icp_normals, nothing reads them (k_icp_knn still runs: k_icp_eval certifies correspondences by the separation it writes).
 // RegistrationICP comes after it.
-void launch_icp_prepare(const IcpBuffers& B, int count, int W, int H, int flags, double voxel, int knn, hipStream_t s);
-hipError_t launch_icp_model_boxes(const uint16_t* models, int* model_bbox, int first_slot, int count, int W, int H, hipStream_t s);
+[[nodiscard]] hipError_t launch_icp_prepare(const IcpBuffers& B, int count, int W, int H, int flags, double voxel, int knn, hipStream_t s);
+[[nodiscard]] hipError_t launch_icp_model_boxes(const uint16_t* models, int* model_bbox, int first_slot, int count, int W, int H, hipStream_t s);
 // The sliced launches of evaluations [it_from, it_to] (k_icp_eval); a hypothesis they finish gets stop == 1.  p2p: the point-to-point
 // build (TransformationEstimationPointToPoint).  rel_fit / rel_rmse: ICPConvergenceCriteria relative_fitness_ / relative_rmse_;
 // max_iter == 0 is EvaluateRegistration (evaluation 0, finished by the prologue of launch 1 without an update).
-void launch_icp_evals(const IcpBuffers& B, int count, int it_from, int it_to, bool p2p, double max_dist, int max_iter, double rel_fit,
-                      double rel_rmse, hipStream_t s);
+[[nodiscard]] hipError_t launch_icp_evals(const IcpBuffers& B, int count, int it_from, int it_to, bool p2p, double max_dist, int max_iter, double rel_fit,
+                                          double rel_rmse, hipStream_t s);
 
 // The stage of the ICP ladder that finished a hypothesis (lm_pose_result::stage); 0: not registered (status != 0).
 enum IcpStage { kIcpStageNone = 0, kIcpStageTeam = 1, kIcpStageLarge = 2, kIcpStageSliced = 3 };
@@ -120,6 +120,6 @@ enum IcpStage { kIcpStageNone = 0, kIcpStageTeam = 1, kIcpStageLarge = 2, kIcpSt
 // A hypothesis the launch cannot hold comes back with stop == 0; one it finishes carries the run tag of its launch in stop (>= 2).
 // cus: compute units of the device the stream belongs to.  Point-to-plane at the default criteria only (one rel_tol for both tests): the
 // driver sends everything else to the sliced launches.
-void launch_icp_team(const IcpBuffers& B, int count, IcpStage stage, int cus, double max_dist, int max_iter, double rel_tol, hipStream_t s);
+[[nodiscard]] hipError_t launch_icp_team(const IcpBuffers& B, int count, IcpStage stage, int cus, double max_dist, int max_iter, double rel_tol, hipStream_t s);
 
 }  // namespace lm

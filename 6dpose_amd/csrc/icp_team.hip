@@ -9,6 +9,7 @@
 
 #include <atomic>
 
+#include "launch.h"
 #include "icp_device.h"
 #include "icp_kernels.h"
 #include "knobs.h"
@@ -991,8 +992,8 @@ k_icp_team(IcpBuffers B, unsigned int run, int shift_floor, double max_dist, int
 // to 64 hypotheses — where the kernel deals the workgroups out by cloud size and a member holds more than 704 points only when the batch
 // has more than ~170k source points — the first stage launches builds 1 and 2 only; the driver tries kIcpStageLarge (4 and 8) on what is
 // left before it goes to the sliced launches.
-void launch_icp_team(const IcpBuffers& B, int count, IcpStage stage, int cus, double max_dist, int max_iter, double rel_tol, hipStream_t s) {
-    if (count <= 0) return;
+hipError_t launch_icp_team(const IcpBuffers& B, int count, IcpStage stage, int cus, double max_dist, int max_iter, double rel_tol, hipStream_t s) {
+    if (count <= 0) return hipSuccess;
     const Knobs& kn = knobs();
 #ifdef LM_DIAG
     if (kn.icp_maxiter_diag >= 0) max_iter = kn.icp_maxiter_diag;
@@ -1012,7 +1013,7 @@ void launch_icp_team(const IcpBuffers& B, int count, IcpStage stage, int cus, do
     auto launch = [&](void (*kernel)(IcpBuffers, unsigned int, int, double, int, double, int, int), int allow) {
         unsigned int run;
         do run = (runs.fetch_add(1) + 1) & 0x3FFFFFFu; while (run < 2);
-        hipLaunchKernelGGL(kernel, grid, dim3(kSoloWG), 0, s, B, run, kn.icp_maxshift, max_dist, max_iter, rel_tol, allow, kn.icp_team_min_points);
+        return lm_launch(kernel, grid, dim3(kSoloWG), 0, s, B, run, kn.icp_maxshift, max_dist, max_iter, rel_tol, allow, kn.icp_team_min_points);
     };
     // A SECOND LAUNCH for a cramped batch (dealt grids): most hypotheses of a batch converge within a couple of evaluations and their
     // workgroups then idle while the ones that go on for all 30 keep the team they were dealt at the start (the pipeline's 16 detections: 12
@@ -1024,11 +1025,12 @@ void launch_icp_team(const IcpBuffers& B, int count, IcpStage stage, int cus, do
     const int relaunch = dealt && !large && kn.icp_builds == 0 ? kn.icp_relaunch : 0;
     for (int ph = 0; ph <= relaunch; ++ph) {
         const int allow = ph < relaunch ? kn.icp_cut_index * (ph + 1) * (ph + 1) : 0, b = ph == 0 ? builds : 2;   // (cut indices 3, 12, 27 ...)
-        if (b & 1) launch(k_icp_team<1, false>, allow);
-        if (b & 2) launch(k_icp_team<1, true>, allow);
-        if (b & 4) launch(k_icp_team<2, true>, allow);
-        if (b & 8) launch(k_icp_team<5, true>, allow);
+        if (b & 1) LAUNCH_TRY(launch(k_icp_team<1, false>, allow));
+        if (b & 2) LAUNCH_TRY(launch(k_icp_team<1, true>, allow));
+        if (b & 4) LAUNCH_TRY(launch(k_icp_team<2, true>, allow));
+        if (b & 8) LAUNCH_TRY(launch(k_icp_team<5, true>, allow));
     }
+    return hipSuccess;
 }
 
 }  // namespace lm

@@ -24,7 +24,7 @@ inline int resp_low_weight(const uint8_t r[5]) { const uint32_t p = resp_pack(r)
 inline bool resp_two_planes(const uint8_t r[5]) { const uint32_t kl = (resp_pack(r) >> 24) & 7u; return kl == 4 || r[kl + 1] == 0; }          // nothing non-zero beyond the second value
 
 // ---- front end (fe_quant.hip, fe_bits.hip): reference A1-A7, LL.cpp:350-505, 557-581, 729-880, 1026-1243 ----
-void upload_normal_lut(const uint8_t lut400[400]);
+[[nodiscard]] hipError_t upload_normal_lut(const uint8_t lut400[400]);
 
 // Every job of the front end goes through one job table: several independent jobs in one launch (fe_quant.hip, k_fe_stage).
 // The jobs: the colour chain (blur7 + sobel_quant + hysteresis) and the normal chain (normals + median5) as tiled passes, the pyramid
@@ -68,10 +68,10 @@ void fe_job_bits_rows(FeJob& j, const uint8_t* const quant[2], const uint8_t* co
 // mode: 0 = the cheapest writer the geometry allows (pixel tiles -> whole dwords per wave -> OR-ed ballots), 1 = the OR-ing writer, 2 = no tiles (tests)
 void fe_job_top_bits(FeJob& j, const uint8_t* const quant[2], const uint8_t* const mask[2], uint8_t* stream, const uint32_t bit0[2], int W, int H, int T, int mode, int m0 = 0, int nm = 2);
 int fe_top_bits_kind(int W, int H, int T, const uint32_t bit0[2], int mode, int m0 = 0, int nm = 2);   // kFeTopBitsTile / kFeTopBitsAligned / kFeTopBits (the only one that needs a zeroed stream)
-void launch_fe_stage(FeStage& st, hipStream_t s);
-void launch_fe_bits(FeStage& st, hipStream_t s);      // a launch of bit-plane jobs only (fe_job_bits_rows, fe_job_top_bits)
+[[nodiscard]] hipError_t launch_fe_stage(FeStage& st, hipStream_t s);
+[[nodiscard]] hipError_t launch_fe_bits(FeStage& st, hipStream_t s);      // a launch of bit-plane jobs only (fe_job_bits_rows, fe_job_top_bits)
 // grey[i] = (4899 R + 9617 G + 1868 B + 8192) >> 14 of pixel i of an interleaved R G B image (training a grey detector from renders, lm_rgb_to_grey)
-void launch_rgb_to_grey(const uint8_t* rgb, uint8_t* grey, size_t pixels, hipStream_t s);
+[[nodiscard]] hipError_t launch_rgb_to_grey(const uint8_t* rgb, uint8_t* grey, size_t pixels, hipStream_t s);
 
 // ---- matching (match_bytes.hip, match_bits.hip): reference A8-A11, LL.cpp:1284-1428, 1788-1941 ----
 struct LevelGeom {        // one pyramid level of the current frame
@@ -157,20 +157,20 @@ struct FrameBatch {
 struct BitsBatch { const uint8_t* strips[kMaxBatch]; uint8_t* bits[kMaxBatch];
                    uint8_t* top_clear[kMaxBatch]; uint32_t top_clear_units; };   // != 0: k_local_bits zeroes 16 x units bytes of every frame's pair stream (the front end ORs the next frame into it)
 constexpr int kBitsSmallMax = 511;            // features per template entry the 9-bit counters hold; larger entries (<= 16383) take the 14-bit instantiation
-void launch_pack_bits(const BitsBatch& B, int nb, const LevelGeom& lv, hipStream_t s);      // bytes {0, a, 4} -> {is a, is 4}, any a in 1..3
+[[nodiscard]] hipError_t launch_pack_bits(const BitsBatch& B, int nb, const LevelGeom& lv, hipStream_t s);      // bytes {0, a, 4} -> {is a, is 4}, any a in 1..3
 // Every level below the top: todo[ci] = 1 for the candidates it leaves to launch_local's per-candidate path (windows leaving their planes);
 // max_features = the largest nf of the bank's entries below the top level.
-void launch_local_bits(const FrameBatch& fb, const BitsBatch& B, const FrameGeom& g, const BankDev& bank, uint32_t cand_cap, float threshold,
-                       uint32_t cap, uint32_t dedupe_cap_slots, int grid_blocks, int max_features, int low_weight /* a: the sum is a n_a + 4 n_4 */, hipStream_t s);
+[[nodiscard]] hipError_t launch_local_bits(const FrameBatch& fb, const BitsBatch& B, const FrameGeom& g, const BankDev& bank, uint32_t cand_cap, float threshold,
+                                           uint32_t cap, uint32_t dedupe_cap_slots, int grid_blocks, int max_features, int low_weight /* a: the sum is a n_a + 4 n_4 */, hipStream_t s);
 // Coarse pass on bit planes: per frame of a batch the flat arena and the pair stream of bytes [byte0, byte0 + 32 npairs) of it (the top
 // level's blocks of both modalities with their zero tails): launch_pack_top packs it from the bytes, the front end writes it directly when
 // nothing reads the top level's bytes (fe_bits.hip, top_bits_body: the stream must be zero before).
 struct TopBits { const uint8_t* lm[kMaxBatch]; uint8_t* bits[kMaxBatch]; };
-void launch_pack_top(const TopBits& B, int nb, uint32_t byte0, uint32_t npairs, hipStream_t s);
+[[nodiscard]] hipError_t launch_pack_top(const TopBits& B, int nb, uint32_t byte0, uint32_t npairs, hipStream_t s);
 // candidates only (no tiles); max_features = the largest nf of the bank's top-level entries.  Two kernels: k_coarse_bits (a wave = one template on
 // one frame) and k_coarse_bits_batch (the frames of a batch share a template's waves).  batch_mode: < 0 = the batched
 // kernel when the batch has two frames or more and it issues fewer waves per template, 0 = never, > 0 = wherever a frame fits a workgroup (tests,
-// A/B runs).  Returns whether the batched kernel was launched.  Candidates, counters and the order of a template's hits inside a frame are the same.
+// A/B runs).  *batched: whether the batched kernel was chosen.  Candidates, counters and the order of a template's hits inside a frame are the same.
 struct CoarseBatchPlan {
     int L;                       // lanes per frame = ceil(positions / 32)
     int groups, fpg;             // the batch's frames in `groups` of up to `fpg`: a group's lanes fit one workgroup
@@ -178,8 +178,8 @@ struct CoarseBatchPlan {
     int waves, waves_per_frame_kernel;   // waves per template over the batch: this plan / k_coarse_bits
 };
 bool coarse_batch_plan(int nb, int npos, CoarseBatchPlan* p);   // false: a frame does not fit a workgroup (more than 32768 positions)
-bool launch_coarse_bits(const FrameBatch& fb, const TopBits& B, const FrameGeom& g, const BankDev& bank, int num_work, float threshold, uint32_t cap, uint32_t byte0, int max_features, int low_weight, hipStream_t s,
-                        int batch_mode = -1);
+[[nodiscard]] hipError_t launch_coarse_bits(const FrameBatch& fb, const TopBits& B, const FrameGeom& g, const BankDev& bank, int num_work, float threshold, uint32_t cap, uint32_t byte0, int max_features, int low_weight, hipStream_t s,
+                                            bool* batched, int batch_mode = -1);
 // Wide bit planes (match_wide.hip): tables with three or four distinct non-zero values.  A response v = 0..4 is three
 // binary digits.  Set 0 lives in the arenas above with their layout: bit 2c of a strip record = v & 1 of cell c, bit 2c + 1 = (v == 4); the
 // pair stream's low dword = v & 1, its high dword = (v == 4).  Set 1 — a second arena of the same layout and size per frame — holds (v >> 1) & 1
@@ -187,13 +187,13 @@ bool launch_coarse_bits(const FrameBatch& fb, const TopBits& B, const FrameGeom&
 // travel in a struct of their own: the argument blocks of k_local_bits, k_coarse_bits and k_pack_* stay what they are.)
 struct WidePlanes { uint8_t* set1[kMaxBatch]; };
 constexpr int kWideMaxFeatures = 16383;       // features per template entry the wide kernels' counters hold (9 bits up to kBitsSmallMax, 14 beyond)
-void launch_pack_wide(const BitsBatch& B, const WidePlanes& P, int nb, const LevelGeom& lv, hipStream_t s);           // bytes 0..4 -> both sets of strip records
-void launch_pack_top_wide(const TopBits& B, const WidePlanes& P, int nb, uint32_t byte0, uint32_t npairs, hipStream_t s);   // ... of the pair stream
+[[nodiscard]] hipError_t launch_pack_wide(const BitsBatch& B, const WidePlanes& P, int nb, const LevelGeom& lv, hipStream_t s);           // bytes 0..4 -> both sets of strip records
+[[nodiscard]] hipError_t launch_pack_top_wide(const TopBits& B, const WidePlanes& P, int nb, uint32_t byte0, uint32_t npairs, hipStream_t s);   // ... of the pair stream
 // as launch_local_bits / launch_coarse_bits (todo, candidates only, max_features), for any response table
-void launch_local_wide(const FrameBatch& fb, const BitsBatch& B, const WidePlanes& P, const FrameGeom& g, const BankDev& bank, uint32_t cand_cap, float threshold,
-                       uint32_t cap, uint32_t dedupe_cap_slots, int grid_blocks, int max_features, hipStream_t s);
-void launch_coarse_wide(const FrameBatch& fb, const TopBits& B, const WidePlanes& P, const FrameGeom& g, const BankDev& bank, int num_work, float threshold, uint32_t cap,
-                        uint32_t byte0, int max_features, hipStream_t s);
+[[nodiscard]] hipError_t launch_local_wide(const FrameBatch& fb, const BitsBatch& B, const WidePlanes& P, const FrameGeom& g, const BankDev& bank, uint32_t cand_cap, float threshold,
+                                           uint32_t cap, uint32_t dedupe_cap_slots, int grid_blocks, int max_features, hipStream_t s);
+[[nodiscard]] hipError_t launch_coarse_wide(const FrameBatch& fb, const TopBits& B, const WidePlanes& P, const FrameGeom& g, const BankDev& bank, int num_work, float threshold, uint32_t cap,
+                                            uint32_t byte0, int max_features, hipStream_t s);
 // Part-based matching (match_parts.hip): a template entry is cut into 4 quadrants — a feature at (x, y) belongs to part
 // (2 x >= width) + 2 (2 y >= height), both modalities pooled — and a position is accepted when at least min_parts eligible parts pass the threshold
 // on their own; the score stays the holistic one.  Per entry (indexed like TemplEntry) the part table, and part-ordered copies of the feature
@@ -208,16 +208,16 @@ struct PartEntry {
 };
 struct PartsDev { const PartEntry* table; const int32_t* feat_off; const uint32_t* feat_word; int min_parts; };
 // as launch_coarse_bits (k_coarse_bits's grid: a wave per template, (templates / 4, frames)) and launch_local_bits, under the part rule; threshold >= 0
-void launch_coarse_parts(const FrameBatch& fb, const TopBits& B, const FrameGeom& g, const BankDev& bank, const PartsDev& parts, int num_work, float threshold, uint32_t cap,
-                         uint32_t byte0, int max_features, int low_weight, hipStream_t s);
-void launch_local_parts(const FrameBatch& fb, const BitsBatch& B, const FrameGeom& g, const BankDev& bank, const PartsDev& parts, uint32_t cand_cap, float threshold,
-                        uint32_t cap, uint32_t dedupe_cap_slots, int grid_blocks, int max_features, int low_weight, hipStream_t s);
+[[nodiscard]] hipError_t launch_coarse_parts(const FrameBatch& fb, const TopBits& B, const FrameGeom& g, const BankDev& bank, const PartsDev& parts, int num_work, float threshold, uint32_t cap,
+                                             uint32_t byte0, int max_features, int low_weight, hipStream_t s);
+[[nodiscard]] hipError_t launch_local_parts(const FrameBatch& fb, const BitsBatch& B, const FrameGeom& g, const BankDev& bank, const PartsDev& parts, uint32_t cand_cap, float threshold,
+                                            uint32_t cap, uint32_t dedupe_cap_slots, int grid_blocks, int max_features, int low_weight, hipStream_t s);
 bool tile_plan_possible(const FrameGeom& g);
 size_t coarse_plan_lds_bytes(int Wd, int Hd);
 // Per frame of the batch: counters[0] = number of candidates produced (may exceed cap: nothing is written past cap); with tiles
 // (and a geometry tile_plan_possible accepts) also counters[0] >> kCandBits = number of tiles, todo[slot] = 1 for the candidates
 // no tile serves.  Grid (workgroups of templates, frames).
-void launch_coarse(const FrameBatch& fb, const FrameGeom& g, const BankDev& bank, int num_work, float threshold, uint32_t cap, uint32_t tile_cap, hipStream_t s);
+[[nodiscard]] hipError_t launch_coarse(const FrameBatch& fb, const FrameGeom& g, const BankDev& bank, int num_work, float threshold, uint32_t cap, uint32_t tile_cap, hipStream_t s);
 // Persistent grid: waves stride over the tiles of all frames of the batch, then over their candidates (counts read on the device).
 // matches_dev[ci] = refined candidate ci (work = -1: dropped).  Also empties the part of every frame's hash table k_dedupe will use.
 // Per feature of a level below the top ONE word, feat_word = base0 | cls: base0 = byte offset (a multiple of 16) inside the strip
@@ -229,7 +229,7 @@ void launch_coarse(const FrameBatch& fb, const FrameGeom& g, const BankDev& bank
 // run_mask[f / 8] bit (f % 8): feature f starts a new class run (class change, or 62 features of one class: the packed-byte sums hold
 // 63 x 4).  Runs have even length and start at even indices (the per-candidate path loads same-class pairs).
 constexpr int kRunMax = 62;
-void launch_local(const FrameBatch& fb, const FrameGeom& g, const BankDev& bank, uint32_t cand_cap, float threshold, uint32_t cap, uint32_t dedupe_cap_slots, uint32_t tile_cap, int grid_blocks, hipStream_t s);
+[[nodiscard]] hipError_t launch_local(const FrameBatch& fb, const FrameGeom& g, const BankDev& bank, uint32_t cand_cap, float threshold, uint32_t cap, uint32_t dedupe_cap_slots, uint32_t tile_cap, int grid_blocks, hipStream_t s);
 // slots of k_dedupe's open-addressing table used for n records (power of two, >= 2n, <= cap_slots = dedupe_table_slots(cand_cap)):
 // k_local empties exactly these, k_dedupe hashes into exactly these
 __host__ __device__ inline uint32_t dedupe_slots_for(uint32_t n, uint32_t cap_slots) {
@@ -250,18 +250,18 @@ struct TopkSel {          // one kept detection
 // the canonical match list of the frame (sorted + adjacent-unique as Detector::match returns it), stopped
 // after top_k kept boxes.  matches_dev / counters as written by launch_local; scratch: topk_nms_scratch_bytes(cap).
 // sel[0..*nsel) in keep order; status: 0 ok, 1 field overflow (template id >= 2^24, class >= 128, |x|,|y| >= 2^15).
-void launch_topk_nms(const Candidate* matches_dev, const unsigned long long* counters, uint32_t cap, const int32_t* work_pyramids,
-                     const int32_t* work_cls, const int32_t* work_tid, const TemplEntry* entries, int levels,
-                     const int32_t* class_base /*class position -> first view slot, may be null*/,
-                     const int32_t* view_wh /*[views][2] box override, -1 = template size, may be null*/, int num_views, int top_k,
-                     double iou_thresh, void* scratch, TopkSel* sel, int32_t* nsel_status, hipStream_t s);
+[[nodiscard]] hipError_t launch_topk_nms(const Candidate* matches_dev, const unsigned long long* counters, uint32_t cap, const int32_t* work_pyramids,
+                                         const int32_t* work_cls, const int32_t* work_tid, const TemplEntry* entries, int levels,
+                                         const int32_t* class_base /*class position -> first view slot, may be null*/,
+                                         const int32_t* view_wh /*[views][2] box override, -1 = template size, may be null*/, int num_views, int top_k,
+                                         double iou_thresh, void* scratch, TopkSel* sel, int32_t* nsel_status, hipStream_t s);
 size_t topk_nms_scratch_bytes(uint32_t cap);
 // Exact-duplicate removal of the refined records of every frame of a batch (nms.hip), grid (blocks, frames): counters[1] / [2]
 // receive the distinct / alive counts; `distinct` (pinned host memory) the surviving records, unordered.  The last block of a frame
 // to finish publishes its counts — final_dev[0..3] (HBM: on-device NMS, exchange) and final_host[0..6] (pinned) — and zeroes the
 // frame's working counters for the slot's next frame, so that no memset / copy node surrounds the matching kernels.
-void launch_dedupe(const FrameBatch& fb, uint32_t cap, size_t table_slots, const int32_t* work_cls, const int32_t* work_tid, int blocks,
-                   hipStream_t s);
+[[nodiscard]] hipError_t launch_dedupe(const FrameBatch& fb, uint32_t cap, size_t table_slots, const int32_t* work_cls, const int32_t* work_tid, int blocks,
+                                       hipStream_t s);
 size_t dedupe_table_slots(uint32_t cap);
 
 // ---- template extraction on the device (train.hip; LL.cpp:589-643, 888-966, 279-318) ----
@@ -279,11 +279,12 @@ struct TrainGeom {                            // the maps of the view being prep
 };
 // keys_view: [levels][2][cap] sort keys / (distance, position, label) records; counts_view: [levels][16]; bbox_view: [4] = {max(-x), max(-y), max(x), max(y)}
 // user_mask (W0 x H0, nonzero = object) replaces depth > 0 when given
-void launch_train_prep(const uint16_t* depth, const uint8_t* user_mask, const TrainGeom& g, float strong_sq, int extract_threshold, unsigned long long* keys_view,
-                       uint32_t cap, uint32_t* counts_view, int32_t* bbox_view, hipStream_t s, int mods = 3);   // mods: bit 0 colour, bit 1 normals — the detector's modality set
+[[nodiscard]] hipError_t launch_train_prep(const uint16_t* depth, const uint8_t* user_mask, const TrainGeom& g, float strong_sq, int extract_threshold, unsigned long long* keys_view,
+                                           uint32_t cap, uint32_t* counts_view, int32_t* bbox_view, hipStream_t s, int mods = 3);   // mods: bit 0 colour, bit 1 normals — the detector's modality set
 // out: [views][levels][2][4 + 3 * nf_cap]: status (1 ok, 0 too few candidates, 2 leave it to the host path), count, -, -, then x, y, label
-int launch_train_select(const unsigned long long* keys, const uint32_t* counts, const TrainGeom& g, uint32_t cap, int num_features, int nf_cap,
-                        int views, int32_t* out, hipStream_t s, int mods = 3);
+// (the result is also the status of reserving the kernel's LDS, cap keys: refused, nothing is launched)
+[[nodiscard]] hipError_t launch_train_select(const unsigned long long* keys, const uint32_t* counts, const TrainGeom& g, uint32_t cap, int num_features, int nf_cap,
+                                             int views, int32_t* out, hipStream_t s, int mods = 3);
 
 // ---- multi-GPU exchange of match records (exchange.hip) ----
 // Block a rank contributes to the all-gather: 4 header words {count, flags, capacity, 0} + capacity 128-bit keys (a sorted run).
@@ -313,9 +314,9 @@ struct XchgFrame {
 };
 struct XchgGroup { int n; int pad; XchgFrame f[kMaxBatch]; };
 // counters: [0] coarse candidates, [1] distinct records, [3] != 0: a record did not fit the key (all written by the matching stream)
-void launch_exchange_pack_group(const XchgGroup& G, uint32_t cand_cap, uint32_t cap, hipStream_t s);
+[[nodiscard]] hipError_t launch_exchange_pack_group(const XchgGroup& G, uint32_t cand_cap, uint32_t cap, hipStream_t s);
 // rank_stride_words: distance between consecutive ranks' blocks (0 = packed: one block per rank; a gathered group of frames has the blocks of
 // all its frames between two ranks)
-void launch_exchange_merge_group(const XchgGroup& G, int world, uint32_t cap, hipStream_t s, uint32_t rank_stride_words = 0);
+[[nodiscard]] hipError_t launch_exchange_merge_group(const XchgGroup& G, int world, uint32_t cap, hipStream_t s, uint32_t rank_stride_words = 0);
 
 }  // namespace lm

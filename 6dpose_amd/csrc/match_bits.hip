@@ -5,6 +5,7 @@
 // it shares with match_wide.hip's kernels (template head, hit test and emission of the coarse pass; window, arg-max, update and epilogue of
 // the refinement; the packers' indexing) are in match_planes.h, the bit-sliced adders in match_device.h.  The byte kernels are in
 // match_bytes.hip; data layout and bank: match_bytes.hip.
+#include "launch.h"
 #include "match_planes.h"
 #include <algorithm>
 #include <type_traits>
@@ -160,15 +161,16 @@ k_local_bits(FrameBatch fb, BitsBatch B, FrameGeom g, const TemplEntry* __restri
     local_flush_stats(fb, s_acc);
 }
 
-void launch_pack_bits(const BitsBatch& B, int nb, const LevelGeom& lv, hipStream_t s) {
+hipError_t launch_pack_bits(const BitsBatch& B, int nb, const LevelGeom& lv, hipStream_t s) {
     const uint32_t records = (uint32_t)(2 * 8 * lv.T * lv.T) * (uint32_t)lv.NS * (uint32_t)lv.Hd;
-    hipLaunchKernelGGL(k_pack_bits, dim3((records + 255) / 256, nb), dim3(256), 0, s, B, lv.sm_off[0], records, lv.NS, lv.Hd);
+    if (records == 0 || nb <= 0) return hipSuccess;   // an empty level / batch: nothing to pack
+    return lm_launch(k_pack_bits, dim3((records + 255) / 256, nb), dim3(256), 0, s, B, lv.sm_off[0], records, lv.NS, lv.Hd);
 }
-void launch_local_bits(const FrameBatch& fb, const BitsBatch& B, const FrameGeom& g, const BankDev& bank, uint32_t cand_cap, float threshold,
+hipError_t launch_local_bits(const FrameBatch& fb, const BitsBatch& B, const FrameGeom& g, const BankDev& bank, uint32_t cand_cap, float threshold,
                        uint32_t cap, uint32_t dedupe_cap_slots, int grid_blocks, int max_features, int low_weight, hipStream_t s) {
-    with_bits_instance<4, 4>(max_features, low_weight, [&](auto hi, auto waves, auto a) {
-        hipLaunchKernelGGL((k_local_bits<hi(), waves(), a()>), dim3(grid_blocks), dim3(256), 0, s, fb, B, g, bank.entries, bank.feat_word, bank.work, cand_cap, threshold, cap,
-                           dedupe_cap_slots);
+    return with_bits_instance<4, 4>(max_features, low_weight, [&](auto hi, auto waves, auto a) {
+        return lm_launch(k_local_bits<hi(), waves(), a()>, dim3(grid_blocks), dim3(256), 0, s, fb, B, g, bank.entries, bank.feat_word, bank.work, cand_cap, threshold, cap,
+                         dedupe_cap_slots);
     });
 }
 
@@ -350,8 +352,9 @@ k_coarse_bits_batch(FrameBatch fb, TopBits B, LevelGeom lv, int level, int level
     }
 }
 
-void launch_pack_top(const TopBits& B, int nb, uint32_t byte0, uint32_t npairs, hipStream_t s) {
-    hipLaunchKernelGGL(k_pack_top, dim3((npairs + 255) / 256, nb), dim3(256), 0, s, B, byte0, npairs);
+hipError_t launch_pack_top(const TopBits& B, int nb, uint32_t byte0, uint32_t npairs, hipStream_t s) {
+    if (npairs == 0 || nb <= 0) return hipSuccess;   // an empty pair stream / batch: nothing to pack
+    return lm_launch(k_pack_top, dim3((npairs + 255) / 256, nb), dim3(256), 0, s, B, byte0, npairs);
 }
 bool coarse_batch_plan(int nb, int npos, CoarseBatchPlan* p) {
     const int lanes_max = 64 * kCoarseBatchWaves;
@@ -370,22 +373,22 @@ bool coarse_batch_plan(int nb, int npos, CoarseBatchPlan* p) {
     p->waves_per_frame_kernel = nb * ((p->L + 63) / 64);
     return true;
 }
-bool launch_coarse_bits(const FrameBatch& fb, const TopBits& B, const FrameGeom& g, const BankDev& bank, int num_work, float threshold, uint32_t cap, uint32_t byte0, int max_features, int low_weight, hipStream_t s,
-                        int batch_mode) {
-    if (num_work <= 0 || fb.nb <= 0) return false;
+hipError_t launch_coarse_bits(const FrameBatch& fb, const TopBits& B, const FrameGeom& g, const BankDev& bank, int num_work, float threshold, uint32_t cap, uint32_t byte0, int max_features, int low_weight, hipStream_t s,
+                              bool* batched_out, int batch_mode) {
+    *batched_out = false;
+    if (num_work <= 0 || fb.nb <= 0) return hipSuccess;
     const int level = g.levels - 1;
     CoarseBatchPlan p;
     const bool can = coarse_batch_plan(fb.nb, g.lv[level].Wd * g.lv[level].Hd, &p);
     const bool batched = can && (batch_mode > 0 || (batch_mode < 0 && fb.nb >= 2 && p.waves < p.waves_per_frame_kernel));
-    with_bits_instance<6, 5>(max_features, low_weight, [&](auto hi, auto waves, auto a) {
+    *batched_out = batched;
+    return with_bits_instance<6, 5>(max_features, low_weight, [&](auto hi, auto waves, auto a) {
         if (batched)
-            hipLaunchKernelGGL((k_coarse_bits_batch<hi(), waves(), a()>), dim3((num_work + p.tpw - 1) / p.tpw, p.groups), dim3(64 * p.tpw * p.Wg), 0, s, fb, B, g.lv[level], level,
-                               g.levels, bank.entries, bank.feat_off, bank.work, num_work, threshold, cap, byte0, p.L, p.fpg, p.Wg);
-        else
-            hipLaunchKernelGGL((k_coarse_bits<hi(), waves(), a()>), dim3((num_work + 3) / 4, fb.nb), dim3(256), 0, s, fb, B, g.lv[level], level, g.levels, bank.entries,
-                               bank.feat_off, bank.work, num_work, threshold, cap, byte0);
+            return lm_launch(k_coarse_bits_batch<hi(), waves(), a()>, dim3((num_work + p.tpw - 1) / p.tpw, p.groups), dim3(64 * p.tpw * p.Wg), 0, s, fb, B, g.lv[level], level,
+                             g.levels, bank.entries, bank.feat_off, bank.work, num_work, threshold, cap, byte0, p.L, p.fpg, p.Wg);
+        return lm_launch(k_coarse_bits<hi(), waves(), a()>, dim3((num_work + 3) / 4, fb.nb), dim3(256), 0, s, fb, B, g.lv[level], level, g.levels, bank.entries,
+                         bank.feat_off, bank.work, num_work, threshold, cap, byte0);
     });
-    return batched;
 }
 
 }  // namespace lm

@@ -19,6 +19,7 @@
 //             read on the slow path of the refinement (bounds test of LL.cpp:1394).
 #include <algorithm>
 
+#include "launch.h"
 #include "knobs.h"
 #include "match_device.h"
 
@@ -417,8 +418,8 @@ size_t coarse_plan_lds_bytes(int Wd, int Hd) {                 // per template o
     return (npos + nw + 4 * (size_t)kMaxTilesPerTemplate + kPlanHits) * sizeof(uint32_t);   // scores | hit bitmap | tile records | hit list
 }
 
-void launch_coarse(const FrameBatch& fb, const FrameGeom& g, const BankDev& bank, int num_work, float threshold, uint32_t cap, uint32_t tile_cap, hipStream_t s) {
-    if (num_work <= 0 || fb.nb <= 0) return;
+hipError_t launch_coarse(const FrameBatch& fb, const FrameGeom& g, const BankDev& bank, int num_work, float threshold, uint32_t cap, uint32_t tile_cap, hipStream_t s) {
+    if (num_work <= 0 || fb.nb <= 0) return hipSuccess;
     const TileRec* tiles = fb.f[0].tiles;                      // tiles are planned for all frames of a batch or for none
     const uint8_t* todo = fb.f[0].todo;
     const int level = g.levels - 1;
@@ -452,8 +453,8 @@ void launch_coarse(const FrameBatch& fb, const FrameGeom& g, const BankDev& bank
         group = std::max(1, std::min(std::min(4, std::max(1, max_group)), std::min(16 / waves, (int)((64 * 1024 - 256) / per))));
         lds = per * group + (4 * (size_t)group + 4) * sizeof(uint32_t);
     }
-    hipLaunchKernelGGL(k_coarse, dim3((num_work + group - 1) / group, fb.nb), dim3(group * waves * 64), lds, s, fb, lv, level, g.levels, bank.entries,
-                       bank.feat_off, bank.work, num_work, waves, cpw, threshold, cap, plan);
+    return lm_launch(k_coarse, dim3((num_work + group - 1) / group, fb.nb), dim3(group * waves * 64), lds, s, fb, lv, level, g.levels, bank.entries,
+                     bank.feat_off, bank.work, num_work, waves, cpw, threshold, cap, plan);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -880,14 +881,14 @@ k_local(FrameBatch fb, FrameGeom g, const TemplEntry* __restrict__ entries, cons
     }
 }
 
-void launch_local(const FrameBatch& fb, const FrameGeom& g, const BankDev& bank, uint32_t cand_cap, float threshold, uint32_t cap, uint32_t dedupe_cap_slots, uint32_t tile_cap, int grid_blocks, hipStream_t s) {
-    if (grid_blocks <= 0 || fb.nb <= 0) return;
+hipError_t launch_local(const FrameBatch& fb, const FrameGeom& g, const BankDev& bank, uint32_t cand_cap, float threshold, uint32_t cap, uint32_t dedupe_cap_slots, uint32_t tile_cap, int grid_blocks, hipStream_t s) {
+    if (grid_blocks <= 0 || fb.nb <= 0) return hipSuccess;
     int dbg = 0;
 #ifdef LM_DIAG
     dbg = knobs().local_dbg;                                    // timing experiments (wrong results): 1 = tiles only, 2 = singles only
 #endif
-    hipLaunchKernelGGL(k_local, dim3(grid_blocks), dim3(256), 0, s, fb, g, bank.entries, bank.feat_off, bank.feat_word, bank.run_mask, bank.feat_xy, bank.work, cand_cap,
-                       threshold, cap, dedupe_cap_slots, tile_cap, dbg);
+    return lm_launch(k_local, dim3(grid_blocks), dim3(256), 0, s, fb, g, bank.entries, bank.feat_off, bank.feat_word, bank.run_mask, bank.feat_xy, bank.work, cand_cap,
+                     threshold, cap, dedupe_cap_slots, tile_cap, dbg);
 }
 
 }  // namespace lm

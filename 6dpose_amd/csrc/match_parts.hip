@@ -6,6 +6,7 @@
 // 3-bit bit-sliced pass count, and a ripple add of S_p into the holistic sum S.  A lane keeps one part's counters, S and three words, not
 // four sets of counters.  Positions, slot order, window, arg-max (on S) and scores (of S) are the holistic kernels': the stages of
 // match_planes.h.  The rule itself is stated in tests/part_match_ref.py.
+#include "launch.h"
 #include "match_planes.h"
 
 namespace lm {
@@ -217,20 +218,20 @@ k_local_parts(FrameBatch fb, BitsBatch B, FrameGeom g, const TemplEntry* __restr
     local_flush_stats(fb, s_acc);
 }
 
-void launch_coarse_parts(const FrameBatch& fb, const TopBits& B, const FrameGeom& g, const BankDev& bank, const PartsDev& parts, int num_work, float threshold, uint32_t cap,
+hipError_t launch_coarse_parts(const FrameBatch& fb, const TopBits& B, const FrameGeom& g, const BankDev& bank, const PartsDev& parts, int num_work, float threshold, uint32_t cap,
                          uint32_t byte0, int max_features, int low_weight, hipStream_t s) {
-    if (num_work <= 0 || fb.nb <= 0) return;
+    if (num_work <= 0 || fb.nb <= 0) return hipSuccess;
     const int level = g.levels - 1;
-    with_bits_instance<5, 4>(max_features, low_weight, [&](auto hi, auto waves, auto a) {
-        hipLaunchKernelGGL((k_coarse_parts<hi(), waves(), a()>), dim3((num_work + 3) / 4, fb.nb), dim3(256), 0, s, fb, B, g.lv[level], level, g.levels, bank.entries, parts.table,
-                           parts.feat_off, bank.work, num_work, threshold, parts.min_parts, cap, byte0);
+    return with_bits_instance<5, 4>(max_features, low_weight, [&](auto hi, auto waves, auto a) {
+        return lm_launch(k_coarse_parts<hi(), waves(), a()>, dim3((num_work + 3) / 4, fb.nb), dim3(256), 0, s, fb, B, g.lv[level], level, g.levels, bank.entries, parts.table,
+                         parts.feat_off, bank.work, num_work, threshold, parts.min_parts, cap, byte0);
     });
 }
-void launch_local_parts(const FrameBatch& fb, const BitsBatch& B, const FrameGeom& g, const BankDev& bank, const PartsDev& parts, uint32_t cand_cap, float threshold,
+hipError_t launch_local_parts(const FrameBatch& fb, const BitsBatch& B, const FrameGeom& g, const BankDev& bank, const PartsDev& parts, uint32_t cand_cap, float threshold,
                         uint32_t cap, uint32_t dedupe_cap_slots, int grid_blocks, int max_features, int low_weight, hipStream_t s) {
-    with_bits_instance<4, 3>(max_features, low_weight, [&](auto hi, auto waves, auto a) {   // (14-bit counters + the holistic sum: 3 waves per SIMD keep them in registers)
-        hipLaunchKernelGGL((k_local_parts<hi(), waves(), a()>), dim3(grid_blocks), dim3(256), 0, s, fb, B, g, bank.entries, parts.table, parts.feat_word, bank.work, cand_cap, threshold,
-                           parts.min_parts, cap, dedupe_cap_slots);
+    return with_bits_instance<4, 3>(max_features, low_weight, [&](auto hi, auto waves, auto a) {   // (14-bit counters + the holistic sum: 3 waves per SIMD keep them in registers)
+        return lm_launch(k_local_parts<hi(), waves(), a()>, dim3(grid_blocks), dim3(256), 0, s, fb, B, g, bank.entries, parts.table, parts.feat_word, bank.work, cand_cap, threshold,
+                         parts.min_parts, cap, dedupe_cap_slots);
     });
 }
 

@@ -321,16 +321,16 @@ static __device__ __forceinline__ size_t strip_cells(const uint8_t* strips, uint
 
 // The instantiation for a bank and a table, for every two-plane kernel: counters of 9 bits (kHi = 5) for entries of up to kBitsSmallMax features, of
 // 14 (kHi = 10) beyond, each at the waves per SIMD the kernel declares for it; kA = the table's low weight.  launch(kHi, kWaves, kA) receives them
-// as std::integral_constants, i.e. as template arguments.
+// as std::integral_constants, i.e. as template arguments, and its status is the result.
 template <int kWavesSmall, int kWavesBig, class Launch>
-static void with_bits_instance(int max_features, int low_weight, Launch launch) {
+[[nodiscard]] static hipError_t with_bits_instance(int max_features, int low_weight, Launch launch) {
     auto with_a = [&](auto a) {
-        if (max_features > kBitsSmallMax) launch(std::integral_constant<int, 10>(), std::integral_constant<int, kWavesBig>(), a);
-        else launch(std::integral_constant<int, 5>(), std::integral_constant<int, kWavesSmall>(), a);
+        if (max_features > kBitsSmallMax) return launch(std::integral_constant<int, 10>(), std::integral_constant<int, kWavesBig>(), a);
+        return launch(std::integral_constant<int, 5>(), std::integral_constant<int, kWavesSmall>(), a);
     };
-    if (low_weight == 2) with_a(std::integral_constant<int, 2>());
-    else if (low_weight == 3) with_a(std::integral_constant<int, 3>());
-    else with_a(std::integral_constant<int, 1>());
+    if (low_weight == 2) return with_a(std::integral_constant<int, 2>());
+    if (low_weight == 3) return with_a(std::integral_constant<int, 3>());
+    return with_a(std::integral_constant<int, 1>());
 }
 
 }  // namespace lm

@@ -7,6 +7,7 @@
 // top per launch: the 16 x 16 window of the carried k).  The byte linear memories are those of the front end (fe_job_build_lm), whatever the
 // response table.  A cell outside the level reads 0: no wrap into the next row or memory (the one departure from the reference's reads).
 // Integers throughout; the only float is the score.  The rule itself is stated in tests/scaled_match_ref.py.
+#include "launch.h"
 #include "match_device.h"
 #include "scaled_kernels.h"
 
@@ -52,8 +53,7 @@ __global__ void __launch_bounds__(256) k_depth_probe(const uint16_t* __restrict_
 
 hipError_t launch_depth_probe(const uint16_t* depth, int W, int H, int probe, uint16_t* out, hipStream_t s) {
     if (probe < 0 || probe > kScaledMaxProbe || W < 1 || H < 1) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_depth_probe, dim3((W + kPW - 1) / kPW, (H + kPH - 1) / kPH), dim3(256), 0, s, depth, W, H, probe, out);
-    return hipGetLastError();
+    return lm_launch(k_depth_probe, dim3((W + kPW - 1) / kPW, (H + kPH - 1) / kPH), dim3(256), 0, s, depth, W, H, probe, out);
 }
 
 // ---- Coarse pass: one workgroup per work item, its K-row table in LDS, a lane = a cell of the top level.  The lane reads the probe value under
@@ -118,9 +118,8 @@ hipError_t launch_coarse_scaled(const uint8_t* lm_arena, const uint16_t* probe_m
         const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_coarse_scaled), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
         if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL(k_coarse_scaled, dim3(num_work), dim3(256), std::max<size_t>(lds_bytes, 8), s, lm_arena, probe_map, W0, H0, top, levels, entries, table,
-                       ladder, train_depth, threshold, cands, counter, cap);
-    return hipGetLastError();
+    return lm_launch(k_coarse_scaled, dim3(num_work), dim3(256), std::max<size_t>(lds_bytes, 8), s, lm_arena, probe_map, W0, H0, top, levels, entries, table,
+                     ladder, train_depth, threshold, cands, counter, cap);
 }
 
 // ---- Refinement of one level: a wave per candidate, lane = window row lane / 4, columns 4 (lane % 4) .. + 3 (four positions per lane, four
@@ -171,8 +170,7 @@ k_local_scaled(const uint8_t* __restrict__ lm, LevelGeom lv, int level, int leve
 hipError_t launch_local_scaled(const uint8_t* lm_arena, LevelGeom lv, int level, int levels, const ScaledEntry* entries, const ScaledFeat* table, int K,
                                float threshold, ScaledCand* cands, uint32_t n, hipStream_t s) {
     if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_local_scaled, dim3((n + 3) / 4), dim3(256), 0, s, lm_arena, lv, level, levels, entries, table, K, threshold, cands, n);
-    return hipGetLastError();
+    return lm_launch(k_local_scaled, dim3((n + 3) / 4), dim3(256), 0, s, lm_arena, lv, level, levels, entries, table, K, threshold, cands, n);
 }
 
 }  // namespace lm

@@ -6,6 +6,7 @@
 // a position is c0 + 2 c1 + 4 c2 with c_i = the number of features whose digit i is set there: three bit-sliced counters instead of two.
 // k_pack_wide / k_local_wide: strip records of the levels below the top; k_pack_top_wide / k_coarse_wide: pair stream of the top level.  The
 // front end writes the byte planes for such tables and these kernels pack them (the front end's own bit-plane writers know two planes).
+#include "launch.h"
 #include "match_planes.h"
 
 namespace lm {
@@ -150,16 +151,15 @@ k_local_wide(FrameBatch fb, BitsBatch B, WidePlanes P, FrameGeom g, const TemplE
     local_flush_stats(fb, s_acc);
 }
 
-void launch_pack_wide(const BitsBatch& B, const WidePlanes& P, int nb, const LevelGeom& lv, hipStream_t s) {
+hipError_t launch_pack_wide(const BitsBatch& B, const WidePlanes& P, int nb, const LevelGeom& lv, hipStream_t s) {
     const uint32_t records = (uint32_t)(2 * 8 * lv.T * lv.T) * (uint32_t)lv.NS * (uint32_t)lv.Hd;
-    hipLaunchKernelGGL(k_pack_wide, dim3((records + 255) / 256, nb), dim3(256), 0, s, B, P, lv.sm_off[0], records, lv.NS, lv.Hd);
+    if (records == 0 || nb <= 0) return hipSuccess;   // an empty level / batch: nothing to pack
+    return lm_launch(k_pack_wide, dim3((records + 255) / 256, nb), dim3(256), 0, s, B, P, lv.sm_off[0], records, lv.NS, lv.Hd);
 }
-void launch_local_wide(const FrameBatch& fb, const BitsBatch& B, const WidePlanes& P, const FrameGeom& g, const BankDev& bank, uint32_t cand_cap, float threshold,
+hipError_t launch_local_wide(const FrameBatch& fb, const BitsBatch& B, const WidePlanes& P, const FrameGeom& g, const BankDev& bank, uint32_t cand_cap, float threshold,
                        uint32_t cap, uint32_t dedupe_cap_slots, int grid_blocks, int max_features, hipStream_t s) {
-#define LM_LAUNCH_LOCAL_WIDE(HI, WAVES, FLY) \
-    hipLaunchKernelGGL((k_local_wide<HI, WAVES, FLY>), dim3(grid_blocks), dim3(256), 0, s, fb, B, P, g, bank.entries, bank.feat_word, bank.work, cand_cap, threshold, cap, dedupe_cap_slots)
-    if (max_features > kBitsSmallMax) LM_LAUNCH_LOCAL_WIDE(10, 3, 4); else LM_LAUNCH_LOCAL_WIDE(5, 4, 2);   // 158 / 126 VGPRs, no spills (5, 4, 4 spills one)
-#undef LM_LAUNCH_LOCAL_WIDE
+    const auto kernel = max_features > kBitsSmallMax ? k_local_wide<10, 3, 4> : k_local_wide<5, 4, 2>;   // 158 / 126 VGPRs, no spills (5, 4, 4 spills one)
+    return lm_launch(kernel, dim3(grid_blocks), dim3(256), 0, s, fb, B, P, g, bank.entries, bank.feat_word, bank.work, cand_cap, threshold, cap, dedupe_cap_slots);
 }
 
 // ---- Coarse pass on two pair streams: k_coarse_bits's scheme — a wave per template, a lane = 32 consecutive positions, a feature's load =
@@ -248,18 +248,17 @@ k_coarse_wide(FrameBatch fb, TopBits B, WidePlanes P, LevelGeom lv, int level, i
     }
 }
 
-void launch_pack_top_wide(const TopBits& B, const WidePlanes& P, int nb, uint32_t byte0, uint32_t npairs, hipStream_t s) {
-    hipLaunchKernelGGL(k_pack_top_wide, dim3((npairs + 255) / 256, nb), dim3(256), 0, s, B, P, byte0, npairs);
+hipError_t launch_pack_top_wide(const TopBits& B, const WidePlanes& P, int nb, uint32_t byte0, uint32_t npairs, hipStream_t s) {
+    if (npairs == 0 || nb <= 0) return hipSuccess;   // an empty pair stream / batch: nothing to pack
+    return lm_launch(k_pack_top_wide, dim3((npairs + 255) / 256, nb), dim3(256), 0, s, B, P, byte0, npairs);
 }
-void launch_coarse_wide(const FrameBatch& fb, const TopBits& B, const WidePlanes& P, const FrameGeom& g, const BankDev& bank, int num_work, float threshold, uint32_t cap,
+hipError_t launch_coarse_wide(const FrameBatch& fb, const TopBits& B, const WidePlanes& P, const FrameGeom& g, const BankDev& bank, int num_work, float threshold, uint32_t cap,
                         uint32_t byte0, int max_features, hipStream_t s) {
-    if (num_work <= 0 || fb.nb <= 0) return;
+    if (num_work <= 0 || fb.nb <= 0) return hipSuccess;
     const int level = g.levels - 1;
-#define LM_LAUNCH_COARSE_WIDE(HI, WAVES, FLY) \
-    hipLaunchKernelGGL((k_coarse_wide<HI, WAVES, FLY>), dim3((num_work + 3) / 4, fb.nb), dim3(256), 0, s, fb, B, P, g.lv[level], level, g.levels, bank.entries, bank.feat_off, \
-                       bank.work, num_work, threshold, cap, byte0)
-    if (max_features > kBitsSmallMax) LM_LAUNCH_COARSE_WIDE(10, 4, 2); else LM_LAUNCH_COARSE_WIDE(5, 5, 2);   // 109 / 89 VGPRs
-#undef LM_LAUNCH_COARSE_WIDE
+    const auto kernel = max_features > kBitsSmallMax ? k_coarse_wide<10, 4, 2> : k_coarse_wide<5, 5, 2>;   // 109 / 89 VGPRs
+    return lm_launch(kernel, dim3((num_work + 3) / 4, fb.nb), dim3(256), 0, s, fb, B, P, g.lv[level], level, g.levels, bank.entries, bank.feat_off, bank.work, num_work,
+                     threshold, cap, byte0);
 }
 
 }  // namespace lm

@@ -14,6 +14,7 @@
 // One 1024-thread workgroup.  Records identical in every field (several coarse candidates of a template refined
 // to one position) are dropped first with a hash; the distinct ones (a few thousand) live in LDS.  A round =
 // arg-max of the live records, predecessor test, suppression: three passes over LDS.
+#include "launch.h"
 #include "lm_kernels.h"
 
 namespace lm {
@@ -263,7 +264,7 @@ k_topk_nms(int top_k, double thresh, int4* __restrict__ rec, const uint32_t* __r
     if (tid == 0) { nsel_status[0] = kept; nsel_status[1] = 0; nsel_status[2] = m; }
 }
 
-void launch_topk_nms(const Candidate* matches_dev, const unsigned long long* counters, uint32_t cap, const int32_t* work_pyramids,
+hipError_t launch_topk_nms(const Candidate* matches_dev, const unsigned long long* counters, uint32_t cap, const int32_t* work_pyramids,
                      const int32_t* work_cls, const int32_t* work_tid, const TemplEntry* entries, int levels,
                      const int32_t* class_base, const int32_t* view_wh, int num_views, int top_k,
                      double iou_thresh, void* scratch, TopkSel* sel, int32_t* nsel_status, hipStream_t s) {
@@ -273,10 +274,10 @@ void launch_topk_nms(const Candidate* matches_dev, const unsigned long long* cou
     while (tsz < 2 * (size_t)cap) tsz <<= 1;
     unsigned long long* table = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(scratch) + (size_t)cap * 16);
     uint32_t* ctr = reinterpret_cast<uint32_t*>(table + tsz);
-    (void)hipMemsetAsync(table, 0xFF, tsz * sizeof(unsigned long long) + 16, s);
-    hipLaunchKernelGGL(k_nms_pack, dim3(64), dim3(256), 0, s, matches_dev, counters, cap, work_pyramids, work_cls, work_tid, entries, levels, class_base,
-                       view_wh, num_views, reinterpret_cast<int4*>(scratch), table, (uint32_t)(tsz - 1), ctr);
-    hipLaunchKernelGGL(k_topk_nms, dim3(1), dim3(kNmsWG), 0, s, top_k, iou_thresh, reinterpret_cast<int4*>(scratch), ctr, sel, nsel_status);
+    LAUNCH_TRY(hipMemsetAsync(table, 0xFF, tsz * sizeof(unsigned long long) + 16, s));
+    LAUNCH_TRY(lm_launch(k_nms_pack, dim3(64), dim3(256), 0, s, matches_dev, counters, cap, work_pyramids, work_cls, work_tid, entries, levels, class_base,
+                         view_wh, num_views, reinterpret_cast<int4*>(scratch), table, (uint32_t)(tsz - 1), ctr));
+    return lm_launch(k_topk_nms, dim3(1), dim3(kNmsWG), 0, s, top_k, iou_thresh, reinterpret_cast<int4*>(scratch), ctr, sel, nsel_status);
 }
 
 // Records identical in every field — several coarse candidates of one template refined to the same position — are
@@ -362,10 +363,10 @@ k_dedupe(FrameBatch fb, uint32_t cap, uint32_t table_mask /*allocated slots - 1*
     }
 }
 
-void launch_dedupe(const FrameBatch& fb, uint32_t cap, size_t table_slots, const int32_t* work_cls, const int32_t* work_tid, int blocks,
+hipError_t launch_dedupe(const FrameBatch& fb, uint32_t cap, size_t table_slots, const int32_t* work_cls, const int32_t* work_tid, int blocks,
                    hipStream_t s) {
-    if (fb.nb <= 0 || blocks <= 0) return;
-    hipLaunchKernelGGL(k_dedupe, dim3(blocks, fb.nb), dim3(256), 0, s, fb, cap, (uint32_t)(table_slots - 1), work_cls, work_tid);
+    if (fb.nb <= 0 || blocks <= 0) return hipSuccess;
+    return lm_launch(k_dedupe, dim3(blocks, fb.nb), dim3(256), 0, s, fb, cap, (uint32_t)(table_slots - 1), work_cls, work_tid);
 }
 
 size_t dedupe_table_slots(uint32_t cap) {

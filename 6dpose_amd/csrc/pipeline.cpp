@@ -242,9 +242,9 @@ extern "C" int lm_pipeline_run(lm_pipeline* p, float threshold, const char* cons
         }
         HIP_TRY(hipEventRecord(p->e1, s));
         const int slot = (int)((d->n_submitted - 1) % lm_detector::kSlots);          // the frame just submitted
-        launch_topk_nms(d->d_matches_dev.p + (size_t)d->buf_cand_cap * slot, d->d_final.p + 8 * (size_t)slot, d->buf_cand_cap, d->d_work.p, d->d_work_cls.p, d->d_work_tid.p, d->d_entries.p,
-                        d->pyramid_levels, p->d_class_base.p, p->d_view_wh.p, p->num_views, top_k, nms_iou, p->d_scratch.p, p->d_sel.p, p->d_nsel.p, s);
-        launch_icp_bind(p->d_sel.p, p->d_nsel.p, p->d_class_base.p, p->d_view_K.p, p->d_view_valid.p, p->num_views, c->ar.in.p, c->ar.st.p, top_k, s);
+        HIP_TRY(launch_topk_nms(d->d_matches_dev.p + (size_t)d->buf_cand_cap * slot, d->d_final.p + 8 * (size_t)slot, d->buf_cand_cap, d->d_work.p, d->d_work_cls.p, d->d_work_tid.p,
+                                d->d_entries.p, d->pyramid_levels, p->d_class_base.p, p->d_view_wh.p, p->num_views, top_k, nms_iou, p->d_scratch.p, p->d_sel.p, p->d_nsel.p, s));
+        HIP_TRY(launch_icp_bind(p->d_sel.p, p->d_nsel.p, p->d_class_base.p, p->d_view_K.p, p->d_view_valid.p, p->num_views, c->ar.in.p, c->ar.st.p, top_k, s));
         HIP_TRY(hipEventRecord(p->e2, s));
         IcpBuffers B = c->buffers();
         B.scene = d->cur_depth;
@@ -255,7 +255,6 @@ extern "C" int lm_pipeline_run(lm_pipeline* p, float threshold, const char* cons
         HIP_TRY(hipMemcpyAsync(p->h_sel.p, p->d_sel.p, (size_t)top_k * sizeof(TopkSel), hipMemcpyDeviceToHost, s));
         HIP_TRY(hipMemcpyAsync(p->h_nsel.p, p->d_nsel.p, 3 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
-        HIP_TRY(hipGetLastError());
         rc = lm_collect_frame(d, -1, nullptr, nullptr);          // retires the frame; 1 = candidate buffer overflow, rerun
         if (rc == 1) {
             if (++overflows >= 3) return lm_set_error(LM_ERR_INVALID, "candidate buffer kept overflowing");

@@ -102,8 +102,7 @@ int run_pts(lm_mesh* m, const std::vector<PtsPair>& pairs, int mode, std::vector
         if ((rc = m->d_pe_pairs.ensure((size_t)np * sizeof(PtsPair)))) return rc;
         if ((rc = m->d_pe_partial.ensure((size_t)np * chunks * sizeof(PtsPartial)))) return rc;
         HIP_TRY(hipMemcpyAsync(m->d_pe_pairs.p, pairs.data() + p0, (size_t)np * sizeof(PtsPair), hipMemcpyHostToDevice, m->s));
-        launch_pose_pts(m->d_v.p, m->nv, (const PtsPair*)m->d_pe_pairs.p, np, mode, (PtsPartial*)m->d_pe_partial.p, m->s);
-        HIP_TRY(hipGetLastError());
+        HIP_TRY(launch_pose_pts(m->d_v.p, m->nv, (const PtsPair*)m->d_pe_pairs.p, np, mode, (PtsPartial*)m->d_pe_partial.p, m->s));
         part.resize((size_t)np * chunks);
         HIP_TRY(hipMemcpyAsync(part.data(), m->d_pe_partial.p, part.size() * sizeof(PtsPartial), hipMemcpyDeviceToHost, m->s));
         HIP_TRY(hipStreamSynchronize(m->s));
@@ -227,9 +226,8 @@ extern "C" int lm_mesh_pose_errors(lm_mesh* m, int n_est, const double* R_est, c
                     return rc;
                 const size_t np = (size_t)ng * ne;
                 if ((rc = m->d_pe_partial.ensure(np * nblk * sizeof(VsdPartial)))) return rc;
-                launch_vsd(m->d_zbuf.p, 0, ng, ng, ne, want_vsd ? m->d_scene.p : nullptr, width, height, cam, (float)delta, 1.0 / tau, tau,
-                           (VsdPartial*)m->d_pe_partial.p, m->s);
-                HIP_TRY(hipGetLastError());
+                HIP_TRY(launch_vsd(m->d_zbuf.p, 0, ng, ng, ne, want_vsd ? m->d_scene.p : nullptr, width, height, cam, (float)delta, 1.0 / tau, tau,
+                                   (VsdPartial*)m->d_pe_partial.p, m->s));
                 part.resize(np * nblk);
                 HIP_TRY(hipMemcpyAsync(part.data(), m->d_pe_partial.p, part.size() * sizeof(VsdPartial), hipMemcpyDeviceToHost, m->s));
                 HIP_TRY(hipStreamSynchronize(m->s));
@@ -318,8 +316,7 @@ extern "C" int lm_mesh_pose_errors_sym(lm_mesh* m, int n_est, const double* R_es
         double* d_out = d_partial + np * per_pair;
         HIP_TRY(hipMemcpyAsync(d_xf, xf.data(), xf_bytes, hipMemcpyHostToDevice, m->s));   // again after ensure() may have moved the buffer
         HIP_TRY(hipMemcpyAsync(d_pairs, pairs.data(), np * sizeof(SymPair), hipMemcpyHostToDevice, m->s));
-        launch_pose_sym(m->d_v.p, m->nv, d_pairs, (int)np, d_xf, n_sym, cam, mssd, mspd, d_partial, d_out, m->s);
-        HIP_TRY(hipGetLastError());
+        HIP_TRY(launch_pose_sym(m->d_v.p, m->nv, d_pairs, (int)np, d_xf, n_sym, cam, mssd, mspd, d_partial, d_out, m->s));
         res.resize(np * nm);
         HIP_TRY(hipMemcpyAsync(res.data(), d_out, res.size() * sizeof(double), hipMemcpyDeviceToHost, m->s));
         HIP_TRY(hipStreamSynchronize(m->s));
@@ -352,8 +349,7 @@ extern "C" int lm_mesh_gt_stats(lm_mesh* m, int n_gt, const double* R_gt, const 
         if ((rc = render_views(m, width, height, K, R_gt + 9 * (size_t)g0, t_gt + 3 * (size_t)g0, ng, nullptr, nullptr, 0, clip_near, clip_far)))
             return rc;
         if ((rc = m->d_pe_partial.ensure((size_t)ng * nblk * sizeof(GtPartial)))) return rc;
-        launch_gt_stats(m->d_zbuf.p, ng, m->d_scene.p, width, height, cam, (float)delta, (GtPartial*)m->d_pe_partial.p, m->s);
-        HIP_TRY(hipGetLastError());
+        HIP_TRY(launch_gt_stats(m->d_zbuf.p, ng, m->d_scene.p, width, height, cam, (float)delta, (GtPartial*)m->d_pe_partial.p, m->s));
         part.resize((size_t)ng * nblk);
         HIP_TRY(hipMemcpyAsync(part.data(), m->d_pe_partial.p, part.size() * sizeof(GtPartial), hipMemcpyDeviceToHost, m->s));
         HIP_TRY(hipStreamSynchronize(m->s));

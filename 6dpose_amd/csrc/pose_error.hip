@@ -15,6 +15,7 @@
 // Every partial is reduced inside the block by a fixed LDS tree and written per block; the host sums the blocks in
 // order, so repeated calls are bit-identical (no floating-point atomics).  -ffp-contract=off (Makefile) keeps the f64
 // pixel expressions unfused; the f32 distance of the search uses explicit fmaf.
+#include "launch.h"
 #include "pose_error_kernels.h"
 
 namespace lm {
@@ -111,12 +112,12 @@ __global__ __launch_bounds__(kPtsThreads) void k_pose_pts(const float* __restric
     if (tid == 0) partial[(size_t)pair * gridDim.x + chunk] = PtsPartial{red_a[0], red_b[0]};
 }
 
-void launch_pose_pts(const float* v, int nv, const PtsPair* pairs, int npairs, int mode, PtsPartial* partial, hipStream_t s) {
-    if (nv <= 0 || npairs <= 0) return;
+hipError_t launch_pose_pts(const float* v, int nv, const PtsPair* pairs, int npairs, int mode, PtsPartial* partial, hipStream_t s) {
+    if (nv <= 0 || npairs <= 0) return hipSuccess;
     const dim3 grid((nv + kPtsChunk - 1) / kPtsChunk, npairs);
-    if (mode == kPtsAddOnly) hipLaunchKernelGGL(k_pose_pts<kPtsAddOnly>, grid, dim3(kPtsThreads), 0, s, v, nv, pairs, partial);
-    else if (mode == kPtsAdi) hipLaunchKernelGGL(k_pose_pts<kPtsAdi>, grid, dim3(kPtsThreads), 0, s, v, nv, pairs, partial);
-    else hipLaunchKernelGGL(k_pose_pts<kPtsDiameter>, grid, dim3(kPtsThreads), 0, s, v, nv, pairs, partial);
+    if (mode == kPtsAddOnly) return lm_launch(k_pose_pts<kPtsAddOnly>, grid, dim3(kPtsThreads), 0, s, v, nv, pairs, partial);
+    if (mode == kPtsAdi) return lm_launch(k_pose_pts<kPtsAdi>, grid, dim3(kPtsThreads), 0, s, v, nv, pairs, partial);
+    return lm_launch(k_pose_pts<kPtsDiameter>, grid, dim3(kPtsThreads), 0, s, v, nv, pairs, partial);
 }
 
 // ---- symmetry-aware maxima (MSSD, MSPD) -------------------------------------------------------------------------
@@ -239,16 +240,16 @@ __global__ __launch_bounds__(kSymThreads) void k_pose_sym_min(const double* __re
     }
 }
 
-void launch_pose_sym(const float* v, int nv, const SymPair* pairs, int npairs, const SymXf* xf, int n_sym, SymCam cam, bool mssd, bool mspd,
+hipError_t launch_pose_sym(const float* v, int nv, const SymPair* pairs, int npairs, const SymXf* xf, int n_sym, SymCam cam, bool mssd, bool mspd,
                      double* partial, double* out, hipStream_t s) {
-    if (nv <= 0 || npairs <= 0 || n_sym <= 0 || !(mssd || mspd)) return;
+    if (nv <= 0 || npairs <= 0 || n_sym <= 0 || !(mssd || mspd)) return hipSuccess;
     const int chunks = sym_chunks(nv);
     const dim3 grid(chunks, npairs), block(kSymThreads);
-    if (mssd && mspd) hipLaunchKernelGGL((k_pose_sym<true, true>), grid, block, 0, s, v, nv, pairs, xf, n_sym, cam, partial);
-    else if (mssd) hipLaunchKernelGGL((k_pose_sym<true, false>), grid, block, 0, s, v, nv, pairs, xf, n_sym, cam, partial);
-    else hipLaunchKernelGGL((k_pose_sym<false, true>), grid, block, 0, s, v, nv, pairs, xf, n_sym, cam, partial);
+    if (mssd && mspd) LAUNCH_TRY(lm_launch(k_pose_sym<true, true>, grid, block, 0, s, v, nv, pairs, xf, n_sym, cam, partial));
+    else if (mssd) LAUNCH_TRY(lm_launch(k_pose_sym<true, false>, grid, block, 0, s, v, nv, pairs, xf, n_sym, cam, partial));
+    else LAUNCH_TRY(lm_launch(k_pose_sym<false, true>, grid, block, 0, s, v, nv, pairs, xf, n_sym, cam, partial));
     const int nm = (mssd ? 1 : 0) + (mspd ? 1 : 0);
-    hipLaunchKernelGGL(k_pose_sym_min, dim3(npairs * nm), block, 0, s, (const double*)partial, chunks, nm, n_sym, out);
+    return lm_launch(k_pose_sym_min, dim3(npairs * nm), block, 0, s, (const double*)partial, chunks, nm, n_sym, out);
 }
 
 // ---- pixel passes -----------------------------------------------------------------------------------------------
@@ -351,18 +352,18 @@ __global__ __launch_bounds__(kPixThreads) void k_gt_stats(const unsigned long lo
             GtPartial{(unsigned)red[0][0], (unsigned)red[1][0], (unsigned)red[2][0], 0u, red[3][0], red[4][0], red[5][0], red[6][0]};
 }
 
-void launch_vsd(const unsigned long long* zbuf, int gt_view0, int n_gt, int est_view0, int n_est, const float* scene, int W, int H,
+hipError_t launch_vsd(const unsigned long long* zbuf, int gt_view0, int n_gt, int est_view0, int n_est, const float* scene, int W, int H,
                 PixCam cam, float delta, double tau_inv, double tau, VsdPartial* partial, hipStream_t s) {
-    if (n_gt <= 0 || n_est <= 0) return;
+    if (n_gt <= 0 || n_est <= 0) return hipSuccess;
     const int npx = W * H;
-    hipLaunchKernelGGL(k_vsd, dim3(pix_blocks(npx), n_gt * n_est), dim3(kPixThreads), 0, s, zbuf, gt_view0, est_view0, n_est, scene, W, npx, cam,
-                       delta, tau_inv, tau, partial);
+    return lm_launch(k_vsd, dim3(pix_blocks(npx), n_gt * n_est), dim3(kPixThreads), 0, s, zbuf, gt_view0, est_view0, n_est, scene, W, npx, cam,
+                     delta, tau_inv, tau, partial);
 }
-void launch_gt_stats(const unsigned long long* zbuf, int n_gt, const float* scene, int W, int H, PixCam cam, float delta, GtPartial* partial,
+hipError_t launch_gt_stats(const unsigned long long* zbuf, int n_gt, const float* scene, int W, int H, PixCam cam, float delta, GtPartial* partial,
                      hipStream_t s) {
-    if (n_gt <= 0) return;
+    if (n_gt <= 0) return hipSuccess;
     const int npx = W * H;
-    hipLaunchKernelGGL(k_gt_stats, dim3(pix_blocks(npx), n_gt), dim3(kPixThreads), 0, s, zbuf, scene, W, npx, cam, delta, partial);
+    return lm_launch(k_gt_stats, dim3(pix_blocks(npx), n_gt), dim3(kPixThreads), 0, s, zbuf, scene, W, npx, cam, delta, partial);
 }
 
 }  // namespace lm

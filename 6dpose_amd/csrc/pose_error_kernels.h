@@ -21,7 +21,7 @@ struct PtsPartial {
 enum PtsMode { kPtsAddOnly = 0, kPtsAdi = 1, kPtsDiameter = 2 };
 constexpr int kPtsThreads = 256, kPtsPer = 1, kPtsChunk = kPtsThreads * kPtsPer, kPtsTile = 1024;
 
-void launch_pose_pts(const float* v, int nv, const PtsPair* pairs, int npairs, int mode, PtsPartial* partial, hipStream_t s);
+[[nodiscard]] hipError_t launch_pose_pts(const float* v, int nv, const PtsPair* pairs, int npairs, int mode, PtsPartial* partial, hipStream_t s);
 
 // Symmetry-aware maxima (MSSD, MSPD).  One composed GT-side transform per (GT, symmetry): A = R_g R_s, b = R_g t_s + t_g
 // (f64, host), stored [g][s]; a pair names its GT and carries the estimate's pose.
@@ -42,8 +42,8 @@ constexpr int kSymFlight = 4;   // symmetries evaluated per lane before the wave
 // partial: f64 [npairs][chunks][nm][n_sym], the largest SQUARED distance of the chunk's vertices, chunks = sym_chunks(nv).
 // out: f64 [npairs][nm] = sqrt(min over s of max over chunks).
 inline int sym_chunks(int nv) { return (nv + kSymThreads - 1) / kSymThreads; }
-void launch_pose_sym(const float* v, int nv, const SymPair* pairs, int npairs, const SymXf* xf, int n_sym, SymCam cam, bool mssd, bool mspd,
-                     double* partial, double* out, hipStream_t s);
+[[nodiscard]] hipError_t launch_pose_sym(const float* v, int nv, const SymPair* pairs, int npairs, const SymXf* xf, int n_sym, SymCam cam, bool mssd, bool mspd,
+                                         double* partial, double* out, hipStream_t s);
 
 // Per (pair, block) counts of the pixel pass.  VSD: union / inter of the visibility masks and the step cost count;
 // COU: inter / union of the rendered masks.  tl: the block's tlinear cost sum (f64, fixed order).
@@ -65,9 +65,9 @@ int pix_blocks(int npx);  // blocks per pair / GT of the pixel passes (a functio
 // zbuf: [views][H][W] keys of the rasteriser (float32 eye depth in the high 32 bits, ~0 = background).
 // Pair p = (gi, ei) reads view gt_view0 + gi and est_view0 + ei, gi = p / n_est, ei = p % n_est.
 // scene == nullptr: COU counts only.
-void launch_vsd(const unsigned long long* zbuf, int gt_view0, int n_gt, int est_view0, int n_est, const float* scene, int W, int H,
-                PixCam cam, float delta, double tau_inv, double tau, VsdPartial* partial, hipStream_t s);
-void launch_gt_stats(const unsigned long long* zbuf, int n_gt, const float* scene, int W, int H, PixCam cam, float delta, GtPartial* partial,
-                     hipStream_t s);
+[[nodiscard]] hipError_t launch_vsd(const unsigned long long* zbuf, int gt_view0, int n_gt, int est_view0, int n_est, const float* scene, int W, int H,
+                                    PixCam cam, float delta, double tau_inv, double tau, VsdPartial* partial, hipStream_t s);
+[[nodiscard]] hipError_t launch_gt_stats(const unsigned long long* zbuf, int n_gt, const float* scene, int W, int H, PixCam cam, float delta, GtPartial* partial,
+                                         hipStream_t s);
 
 }  // namespace lm

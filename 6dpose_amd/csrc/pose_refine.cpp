@@ -145,20 +145,21 @@ bool sliced_first(const lm_icp* c) {
 }
 
 // the next evaluations of the sliced launches, at most kEvalChunk of them, up to the prologue that finishes evaluation max_iteration
-void enqueue_evals(lm_icp* c, const IcpBuffers& B, hipStream_t s) {
+int enqueue_evals(lm_icp* c, const IcpBuffers& B, hipStream_t s) {
     const int last = c->opt.max_iteration + 1;
     const int to = last - c->next_it < kEvalChunk ? last : c->next_it + kEvalChunk - 1;
-    launch_icp_evals(B, B.count, c->next_it, to, c->run_p2p, kMaxDist, c->opt.max_iteration, c->opt.relative_fitness, c->opt.relative_rmse, s);
+    HIP_TRY(launch_icp_evals(B, B.count, c->next_it, to, c->run_p2p, kMaxDist, c->opt.max_iteration, c->opt.relative_fitness, c->opt.relative_rmse, s));
     c->next_it = to + 1;
+    return LM_OK;
 }
 }  // namespace
 
 int lm_icp_enqueue(lm_icp* c, const IcpBuffers& B, int flags, IcpState* h_st, hipStream_t s) {
     c->run_p2p = (flags & LM_ICP_POINT_TO_POINT) != 0;
     c->next_it = 0;
-    launch_icp_prepare(B, B.count, c->W, c->H, flags, kVoxel, kKnn, s);
-    if (sliced_first(c)) enqueue_evals(c, B, s);
-    else launch_icp_team(B, B.count, kIcpStageTeam, c->cus, kMaxDist, kMaxIter, kRelTol, s);
+    HIP_TRY(launch_icp_prepare(B, B.count, c->W, c->H, flags, kVoxel, kKnn, s));
+    if (sliced_first(c)) { if (int rc = enqueue_evals(c, B, s)) return rc; }
+    else HIP_TRY(launch_icp_team(B, B.count, kIcpStageTeam, c->cus, kMaxDist, kMaxIter, kRelTol, s));
     HIP_TRY(hipEventRecord(c->e1, s));
     HIP_TRY(hipMemcpyAsync(h_st, B.st, (size_t)B.count * sizeof(IcpState), hipMemcpyDeviceToHost, s));
     return LM_OK;
@@ -179,16 +180,15 @@ int lm_icp_finish(lm_icp* c, const IcpBuffers& B, IcpState* h_st, hipStream_t s)
         // (more than kEvalChunk evaluations asked for: the next chunk)
         if (stage == kIcpStageSliced && c->next_it > c->opt.max_iteration + 1) return lm_set_error(LM_ERR_HIP, "ICP: a hypothesis was left unfinished");
         if (stage == kIcpStageTeam) {
-            launch_icp_team(B, B.count, kIcpStageLarge, c->cus, kMaxDist, kMaxIter, kRelTol, s);
+            HIP_TRY(launch_icp_team(B, B.count, kIcpStageLarge, c->cus, kMaxDist, kMaxIter, kRelTol, s));
             stage = kIcpStageLarge;
         } else {
             stage = kIcpStageSliced;
-            enqueue_evals(c, B, s);
+            if (int rc = enqueue_evals(c, B, s)) return rc;
         }
         HIP_TRY(hipEventRecord(c->e1, s));
         HIP_TRY(hipMemcpyAsync(h_st, B.st, (size_t)B.count * sizeof(IcpState), hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
-        HIP_TRY(hipGetLastError());
     }
 }
 
@@ -312,7 +312,6 @@ extern "C" int lm_icp_run(lm_icp* c, int count, const int32_t* model_slots, cons
     for (int i = 0; i < count; ++i) boxed = boxed && c->slot_boxed[(size_t)(model_slots ? model_slots[i] : i)] != 0;
     if ((rc = lm_icp_enqueue(c, B, (flags & 0xFF) | (boxed ? 0x100 : 0), c->ar.h_st2.p, c->s))) return rc;
     HIP_TRY(hipStreamSynchronize(c->s));
-    HIP_TRY(hipGetLastError());
     if ((rc = lm_icp_finish(c, B, c->ar.h_st2.p, c->s))) return rc;
     memcpy(c->ar.h_st.p, c->ar.h_st2.p, (size_t)count * sizeof(IcpState));
     c->last_count = count; c->last_flags = flags;

@@ -116,8 +116,7 @@ extern "C" int lm_pso_set_scene_edges(lm_pso* c, const uint8_t* edges, int width
     if ((rc = c->d_g.ensure(n))) return rc;
     if ((rc = c->d_d2.ensure(n))) return rc;
     HIP_TRY(hipMemcpyAsync(c->d_edges.p, edges, n, hipMemcpyHostToDevice, c->s));
-    launch_edt(c->d_edges.p, width, height, max_dist, c->d_g.p, c->d_d2.p, c->s);
-    HIP_TRY(hipGetLastError());
+    HIP_TRY(launch_edt(c->d_edges.p, width, height, max_dist, c->d_g.p, c->d_d2.p, c->s));
     HIP_TRY(hipStreamSynchronize(c->s));                                  // `edges` is the caller's again
     c->eW = width; c->eH = height; c->eM = max_dist;
     memcpy(c->eK, K, sizeof(c->eK));
@@ -150,8 +149,7 @@ static int ensure_orient(lm_pso* c, size_t n) {
     return c->d_dd2.ensure(9 * n);
 }
 static int orient_transforms(lm_pso* c, int width, int height, const double* K, int max_dist, int orient_penalty) {
-    launch_edt_orient(c->d_q.p, width, height, max_dist, orient_penalty, c->d_og.p, c->d_od2.p, c->d_dd2.p, c->s);
-    HIP_TRY(hipGetLastError());
+    HIP_TRY(launch_edt_orient(c->d_q.p, width, height, max_dist, orient_penalty, c->d_og.p, c->d_od2.p, c->d_dd2.p, c->s));
     HIP_TRY(hipStreamSynchronize(c->s));
     c->oW = width; c->oH = height; c->oM = max_dist; c->oP = orient_penalty;
     memcpy(c->oK, K, sizeof(c->oK));
@@ -287,17 +285,16 @@ static int run_swarm(lm_pso* c, lm_mesh* mesh, int count, const double* Rs, cons
     MeshDev M{mesh->d_v.p, mesh->d_n.p, mesh->d_c.p, mesh->d_f.p, mesh->nv, mesh->nf};
     HIP_TRY(hipEventRecord(c->ev0, c->s));
     HIP_TRY(hipMemcpyAsync(c->d_hyp.p, c->h_hyp.data(), H * sizeof(PsoHyp), hipMemcpyHostToDevice, c->s));
-    launch_pso_init(prm, H, st, c->s);
+    HIP_TRY(launch_pso_init(prm, H, st, c->s));
     for (int g = 0; g <= G; ++g) {
-        launch_pso_views(prm, H, c->d_hyp.p, st.x, c->d_views.p, c->s);
-        launch_project(M, c->d_views.p, (int)HP, 1, c->d_pv.p, c->s);
-        launch_raster(M, c->d_pv.p, (int)HP, w, h, o.clip_near, o.clip_far, c->d_zbuf.p, c->s);
-        if (oriented) launch_pso_orient_cost(prm, H, edge_step, c->d_hyp.p, c->d_zbuf.p, c->d_dd2.p, st.sum, st.n_r, c->s);
-        else if (edges) launch_pso_edge_cost(prm, H, edge_step, c->d_hyp.p, c->d_zbuf.p, c->d_d2.p, st.sum, st.n_r, c->s);
-        else launch_pso_cost(prm, H, c->d_hyp.p, c->d_zbuf.p, c->d_scene.p, st.sum, st.n_r, c->s);
-        launch_pso_step(prm, H, g, c->d_hyp.p, st, c->s);
+        HIP_TRY(launch_pso_views(prm, H, c->d_hyp.p, st.x, c->d_views.p, c->s));
+        HIP_TRY(launch_project(M, c->d_views.p, (int)HP, 1, c->d_pv.p, c->s));
+        HIP_TRY(launch_raster(M, c->d_pv.p, (int)HP, w, h, o.clip_near, o.clip_far, c->d_zbuf.p, c->s));
+        if (oriented) HIP_TRY(launch_pso_orient_cost(prm, H, edge_step, c->d_hyp.p, c->d_zbuf.p, c->d_dd2.p, st.sum, st.n_r, c->s));
+        else if (edges) HIP_TRY(launch_pso_edge_cost(prm, H, edge_step, c->d_hyp.p, c->d_zbuf.p, c->d_d2.p, st.sum, st.n_r, c->s));
+        else HIP_TRY(launch_pso_cost(prm, H, c->d_hyp.p, c->d_zbuf.p, c->d_scene.p, st.sum, st.n_r, c->s));
+        HIP_TRY(launch_pso_step(prm, H, g, c->d_hyp.p, st, c->s));
     }
-    HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(c->h_res.data(), st.result, H * sizeof(PsoResultDev), hipMemcpyDeviceToHost, c->s));
     HIP_TRY(hipEventRecord(c->ev1, c->s));
     HIP_TRY(hipStreamSynchronize(c->s));

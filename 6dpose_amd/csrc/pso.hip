@@ -10,6 +10,7 @@
 //   random numbers: the splitmix64 finaliser of seed + 0x9E3779B97F4A7C15 (1 + counter), counter = ((g P + p) 6 + d) 2 + draw;
 //   g = 0 draws the initial positions, generation g >= 1 draws u1 (draw 0) and u2 (draw 1).  No state, the same for every hypothesis.
 // The z-buffer: launch_raster clears it before every generation (its hipMemsetAsync), so k_pso_cost only reads it.
+#include "launch.h"
 #include "pso_kernels.h"
 
 namespace lm {
@@ -214,20 +215,20 @@ __global__ __launch_bounds__(256) void k_pso_step(PsoParams prm, int g, const Ps
     }
 }
 
-void launch_pso_init(const PsoParams& p, int H, const PsoState& st, hipStream_t s) {
+hipError_t launch_pso_init(const PsoParams& p, int H, const PsoState& st, hipStream_t s) {
     const int HP = H * p.P;
-    hipLaunchKernelGGL(k_pso_init, dim3((HP + 255) / 256), dim3(256), 0, s, p, HP, st);
+    return lm_launch(k_pso_init, dim3((HP + 255) / 256), dim3(256), 0, s, p, HP, st);
 }
-void launch_pso_views(const PsoParams& p, int H, const PsoHyp* hyp, const double* x, ViewParams* views, hipStream_t s) {
+hipError_t launch_pso_views(const PsoParams& p, int H, const PsoHyp* hyp, const double* x, ViewParams* views, hipStream_t s) {
     const int HP = H * p.P;
-    hipLaunchKernelGGL(k_pso_views, dim3((HP + 255) / 256), dim3(256), 0, s, p, HP, hyp, x, views);
+    return lm_launch(k_pso_views, dim3((HP + 255) / 256), dim3(256), 0, s, p, HP, hyp, x, views);
 }
-void launch_pso_cost(const PsoParams& p, int H, const PsoHyp* hyp, const unsigned long long* zbuf, const uint16_t* scene,
+hipError_t launch_pso_cost(const PsoParams& p, int H, const PsoHyp* hyp, const unsigned long long* zbuf, const uint16_t* scene,
                      unsigned long long* sum, unsigned int* n_r, hipStream_t s) {
-    hipLaunchKernelGGL(k_pso_cost, dim3(H * p.P), dim3(256), 0, s, p, hyp, zbuf, scene, sum, n_r);
+    return lm_launch(k_pso_cost, dim3(H * p.P), dim3(256), 0, s, p, hyp, zbuf, scene, sum, n_r);
 }
-void launch_pso_step(const PsoParams& p, int H, int g, const PsoHyp* hyp, const PsoState& st, hipStream_t s) {
-    hipLaunchKernelGGL(k_pso_step, dim3(H), dim3(256), 0, s, p, g, hyp, st);
+hipError_t launch_pso_step(const PsoParams& p, int H, int g, const PsoHyp* hyp, const PsoState& st, hipStream_t s) {
+    return lm_launch(k_pso_step, dim3(H), dim3(256), 0, s, p, g, hyp, st);
 }
 
 }  // namespace lm

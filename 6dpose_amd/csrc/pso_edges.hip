@@ -8,6 +8,7 @@
 //   sum += min(D2, tau^2) at a contour pixel inside the frame, tau^2 outside; n_c counts the contour pixels.
 // The swarm around it (k_pso_init, k_pso_views, k_project, k_raster, k_pso_step) is pso.hip's, used as it is: k_pso_edge_cost
 // writes (sum, n_c) where k_pso_cost writes (sum, n_r).  The kernels' bodies are pso_edge_device.h's, shared with pso_orient.hip.
+#include "launch.h"
 #include "pso_edge_device.h"
 
 namespace lm {
@@ -24,14 +25,14 @@ __global__ __launch_bounds__(256) void k_pso_edge_cost(PsoParams prm, int edge_s
     pso_contour_cost_body<false>(prm, edge_step, hyp, zbuf, d2, nullptr, sum_out, nr_out);
 }
 
-void launch_edt(const uint8_t* edges, int W, int H, int M, uint8_t* g, uint16_t* d2, hipStream_t s) {
-    hipLaunchKernelGGL(k_edt_rows, dim3((W + kEdtRun - 1) / kEdtRun, H), dim3(256), 0, s, edges, W, H, M, g);
+hipError_t launch_edt(const uint8_t* edges, int W, int H, int M, uint8_t* g, uint16_t* d2, hipStream_t s) {
+    LAUNCH_TRY(lm_launch(k_edt_rows, dim3((W + kEdtRun - 1) / kEdtRun, H), dim3(256), 0, s, edges, W, H, M, g));
     const size_t lds = (size_t)(kEdtRows + 2 * (M - 1)) * kEdtCols;
-    hipLaunchKernelGGL(k_edt_cols, dim3((W + kEdtCols - 1) / kEdtCols, (H + kEdtRows - 1) / kEdtRows), dim3(256), lds, s, g, W, H, M, d2);
+    return lm_launch(k_edt_cols, dim3((W + kEdtCols - 1) / kEdtCols, (H + kEdtRows - 1) / kEdtRows), dim3(256), lds, s, g, W, H, M, d2);
 }
-void launch_pso_edge_cost(const PsoParams& p, int H, int edge_step, const PsoHyp* hyp, const unsigned long long* zbuf, const uint16_t* d2,
+hipError_t launch_pso_edge_cost(const PsoParams& p, int H, int edge_step, const PsoHyp* hyp, const unsigned long long* zbuf, const uint16_t* d2,
                           unsigned long long* sum, unsigned int* n_r, hipStream_t s) {
-    hipLaunchKernelGGL(k_pso_edge_cost, dim3(H * p.P), dim3(256), 0, s, p, edge_step, hyp, zbuf, d2, sum, n_r);
+    return lm_launch(k_pso_edge_cost, dim3(H * p.P), dim3(256), 0, s, p, edge_step, hyp, zbuf, d2, sum, n_r);
 }
 
 }  // namespace lm

@@ -46,23 +46,23 @@ struct PsoState {            // [HP] unless stated
     PsoResultDev* result;    // [H]
 };
 
-void launch_pso_init(const PsoParams& p, int H, const PsoState& st, hipStream_t s);
-void launch_pso_views(const PsoParams& p, int H, const PsoHyp* hyp, const double* x, ViewParams* views, hipStream_t s);
-void launch_pso_cost(const PsoParams& p, int H, const PsoHyp* hyp, const unsigned long long* zbuf, const uint16_t* scene,
-                     unsigned long long* sum, unsigned int* n_r, hipStream_t s);
-void launch_pso_step(const PsoParams& p, int H, int g, const PsoHyp* hyp, const PsoState& st, hipStream_t s);
+[[nodiscard]] hipError_t launch_pso_init(const PsoParams& p, int H, const PsoState& st, hipStream_t s);
+[[nodiscard]] hipError_t launch_pso_views(const PsoParams& p, int H, const PsoHyp* hyp, const double* x, ViewParams* views, hipStream_t s);
+[[nodiscard]] hipError_t launch_pso_cost(const PsoParams& p, int H, const PsoHyp* hyp, const unsigned long long* zbuf, const uint16_t* scene,
+                                         unsigned long long* sum, unsigned int* n_r, hipStream_t s);
+[[nodiscard]] hipError_t launch_pso_step(const PsoParams& p, int H, int g, const PsoHyp* hyp, const PsoState& st, hipStream_t s);
 
 // pso_edges.hip: the edge cost.  launch_edt: k_edt_rows (edges -> g, uint8) and k_edt_cols (g -> d2, uint16), 1 <= M <= 255.
 // launch_pso_edge_cost: p.W, p.H are the edge frame's, p.tau is in pixels (<= M); it writes what launch_pso_cost writes.
-void launch_edt(const uint8_t* edges, int W, int H, int M, uint8_t* g, uint16_t* d2, hipStream_t s);
-void launch_pso_edge_cost(const PsoParams& p, int H, int edge_step, const PsoHyp* hyp, const unsigned long long* zbuf, const uint16_t* d2,
-                          unsigned long long* sum, unsigned int* n_r, hipStream_t s);
+[[nodiscard]] hipError_t launch_edt(const uint8_t* edges, int W, int H, int M, uint8_t* g, uint16_t* d2, hipStream_t s);
+[[nodiscard]] hipError_t launch_pso_edge_cost(const PsoParams& p, int H, int edge_step, const PsoHyp* hyp, const unsigned long long* zbuf, const uint16_t* d2,
+                                              unsigned long long* sum, unsigned int* n_r, hipStream_t s);
 
 // pso_orient.hip: the directional edge cost.  launch_edt_orient: q (bit k = an edge of bin k) -> g [8][H][W] uint8 and
 // d2 [8][H][W] uint16 per channel (k_edt_rows_bits, k_edt_cols_planes), then dd2 [9][H][W] uint16 (k_edt_orient); 1 <= M <= 255, 0 <= P <= 4096.
 // launch_pso_orient_cost: launch_pso_edge_cost with the nine planes dd2 in d2's place.
-void launch_edt_orient(const uint8_t* q, int W, int H, int M, int P, uint8_t* g, uint16_t* d2, uint16_t* dd2, hipStream_t s);
-void launch_pso_orient_cost(const PsoParams& p, int H, int edge_step, const PsoHyp* hyp, const unsigned long long* zbuf, const uint16_t* dd2,
-                            unsigned long long* sum, unsigned int* n_r, hipStream_t s);
+[[nodiscard]] hipError_t launch_edt_orient(const uint8_t* q, int W, int H, int M, int P, uint8_t* g, uint16_t* d2, uint16_t* dd2, hipStream_t s);
+[[nodiscard]] hipError_t launch_pso_orient_cost(const PsoParams& p, int H, int edge_step, const PsoHyp* hyp, const unsigned long long* zbuf, const uint16_t* dd2,
+                                                unsigned long long* sum, unsigned int* n_r, hipStream_t s);
 
 }  // namespace lm

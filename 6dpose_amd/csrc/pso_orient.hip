@@ -9,6 +9,7 @@
 //   sum += min(DD2[k_p], tau^2) at a contour pixel inside the frame, tau^2 outside; n_c counts the contour pixels.
 // The two channel passes are k_edt_rows' and k_edt_cols' bodies (pso_edge_device.h) with the channel as the grid's z, and k_pso_orient_cost
 // is k_pso_edge_cost's body with the plane chosen per contour pixel: one copy of each, instantiated here and in pso_edges.hip.
+#include "launch.h"
 #include "pso_edge_device.h"
 
 namespace lm {
@@ -67,16 +68,16 @@ __global__ __launch_bounds__(256) void k_pso_orient_cost(PsoParams prm, int edge
     pso_contour_cost_body<true>(prm, edge_step, hyp, zbuf, dd2, kBinOf, sum_out, nr_out);
 }
 
-void launch_edt_orient(const uint8_t* q, int W, int H, int M, int P, uint8_t* g, uint16_t* d2, uint16_t* dd2, hipStream_t s) {
-    hipLaunchKernelGGL(k_edt_rows_bits, dim3((W + kEdtRun - 1) / kEdtRun, H, 8), dim3(256), 0, s, q, W, H, M, g);
+hipError_t launch_edt_orient(const uint8_t* q, int W, int H, int M, int P, uint8_t* g, uint16_t* d2, uint16_t* dd2, hipStream_t s) {
+    LAUNCH_TRY(lm_launch(k_edt_rows_bits, dim3((W + kEdtRun - 1) / kEdtRun, H, 8), dim3(256), 0, s, q, W, H, M, g));
     const size_t lds = (size_t)(kEdtRows + 2 * (M - 1)) * kEdtCols;
-    hipLaunchKernelGGL(k_edt_cols_planes, dim3((W + kEdtCols - 1) / kEdtCols, (H + kEdtRows - 1) / kEdtRows, 8), dim3(256), lds, s, g, W, H, M, d2);
+    LAUNCH_TRY(lm_launch(k_edt_cols_planes, dim3((W + kEdtCols - 1) / kEdtCols, (H + kEdtRows - 1) / kEdtRows, 8), dim3(256), lds, s, g, W, H, M, d2));
     const size_t n = (size_t)W * H, blocks = (n + 255) / 256;
-    hipLaunchKernelGGL(k_edt_orient, dim3((unsigned)(blocks < 2048 ? blocks : 2048)), dim3(256), 0, s, d2, n, M, P, dd2);
+    return lm_launch(k_edt_orient, dim3((unsigned)(blocks < 2048 ? blocks : 2048)), dim3(256), 0, s, d2, n, M, P, dd2);
 }
-void launch_pso_orient_cost(const PsoParams& p, int H, int edge_step, const PsoHyp* hyp, const unsigned long long* zbuf, const uint16_t* dd2,
+hipError_t launch_pso_orient_cost(const PsoParams& p, int H, int edge_step, const PsoHyp* hyp, const unsigned long long* zbuf, const uint16_t* dd2,
                             unsigned long long* sum, unsigned int* n_r, hipStream_t s) {
-    hipLaunchKernelGGL(k_pso_orient_cost, dim3(H * p.P), dim3(256), 0, s, p, edge_step, hyp, zbuf, dd2, sum, n_r);
+    return lm_launch(k_pso_orient_cost, dim3(H * p.P), dim3(256), 0, s, p, edge_step, hyp, zbuf, dd2, sum, n_r);
 }
 
 }  // namespace lm

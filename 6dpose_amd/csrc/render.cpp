@@ -311,23 +311,22 @@ static int render_device(lm_mesh* m, int count, int W, int H, const float* Ks, c
     HIP_TRY(hipStreamSynchronize(m->s));                              // hv is a local
     MeshDev M{m->d_v.p, m->d_n.p, m->d_c.p, m->d_f.p, m->nv, m->nf};
     if (want_depth) {                                                 // the driver renders depth at the native resolution (:206-209)
-        launch_project(M, m->d_views.p, count, 1, m->d_pv.p, m->s);
-        launch_raster(M, m->d_pv.p, count, W, H, clip_near, clip_far, m->d_zbuf.p, m->s);
-        launch_resolve_depth(m->d_zbuf.p, count, W, H, m->d_depth.p, m->s);
+        HIP_TRY(launch_project(M, m->d_views.p, count, 1, m->d_pv.p, m->s));
+        HIP_TRY(launch_raster(M, m->d_pv.p, count, W, H, clip_near, clip_far, m->d_zbuf.p, m->s));
+        HIP_TRY(launch_resolve_depth(m->d_zbuf.p, count, W, H, m->d_depth.p, m->s));
     }
     if (want_rgb) {                                                   // and colour at ssaa x, box-filtered (:212-216)
-        launch_project(M, m->d_views.p, count, ssaa, m->d_pv.p, m->s);
-        launch_raster(M, m->d_pv.p, count, W * ssaa, H * ssaa, clip_near, clip_far, m->d_zbuf.p, m->s);
-        if (!shade) launch_resolve_rgb(M, m->d_pv.p, m->d_views.p, m->d_zbuf.p, count, W, H, ssaa, ambient, m->d_rgb.p, m->s);
+        HIP_TRY(launch_project(M, m->d_views.p, count, ssaa, m->d_pv.p, m->s));
+        HIP_TRY(launch_raster(M, m->d_pv.p, count, W * ssaa, H * ssaa, clip_near, clip_far, m->d_zbuf.p, m->s));
+        if (!shade) HIP_TRY(launch_resolve_rgb(M, m->d_pv.p, m->d_views.p, m->d_zbuf.p, count, W, H, ssaa, ambient, m->d_rgb.p, m->s));
         else {
             ShadeParams sp{};
             if (shade->use_texture) { sp.uv = m->d_uv.p; sp.tex = m->d_tex.p; sp.tex_w = m->tex_w; sp.tex_h = m->tex_h; }
             sp.view_surf = shade->view_surf ? m->d_view_surf.p : nullptr;
             sp.surf = shade->surf; sp.has_surf = shade->has_surf; sp.bg = shade->bg; sp.ambient = ambient; sp.flat = shade->flat;
-            launch_resolve_shaded(M, m->d_pv.p, m->d_views.p, m->d_zbuf.p, count, W, H, ssaa, sp, m->d_rgb.p, m->s);
+            HIP_TRY(launch_resolve_shaded(M, m->d_pv.p, m->d_views.p, m->d_zbuf.p, count, W, H, ssaa, sp, m->d_rgb.p, m->s));
         }
     }
-    HIP_TRY(hipGetLastError());
     m->last_W = W; m->last_H = H; m->last_count = count;
     return LM_OK;
 }
@@ -441,9 +440,8 @@ extern "C" int lm_mesh_overlay(lm_mesh* const* meshes, int count, int width, int
     HIP_TRY(hipMemcpyAsync(m0->d_ov_layers.p, layers.data(), (size_t)count * sizeof(OverlayLayer), hipMemcpyHostToDevice, m0->s));
     HIP_TRY(hipMemcpyAsync(m0->d_ov_frame.p, rgb, npx * 3, hipMemcpyHostToDevice, m0->s));
     if (scene_depth) HIP_TRY(hipMemcpyAsync(m0->d_ov_scene.p, scene_depth, npx * sizeof(uint16_t), hipMemcpyHostToDevice, m0->s));
-    launch_overlay_compose(m0->d_ov_layers.p, count, m0->d_ov_frame.p, scene_depth ? m0->d_ov_scene.p : nullptr, (int)npx, mode == LM_OVERLAY_NEAREST,
-                           m0->d_ov_rgb.p, m0->d_ov_index.p, m0->s);
-    HIP_TRY(hipGetLastError());
+    HIP_TRY(launch_overlay_compose(m0->d_ov_layers.p, count, m0->d_ov_frame.p, scene_depth ? m0->d_ov_scene.p : nullptr, (int)npx, mode == LM_OVERLAY_NEAREST,
+                                   m0->d_ov_rgb.p, m0->d_ov_index.p, m0->s));
     HIP_TRY(hipMemcpyAsync(rgb_out, m0->d_ov_rgb.p, npx * 3, hipMemcpyDeviceToHost, m0->s));
     HIP_TRY(hipMemcpyAsync(index_out, m0->d_ov_index.p, npx, hipMemcpyDeviceToHost, m0->s));
     HIP_TRY(hipStreamSynchronize(m0->s));

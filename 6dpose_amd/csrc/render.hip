@@ -18,6 +18,7 @@
 //     (cv2.resize INTER_AREA with an integer factor).
 // One thread per triangle and view for coverage (model triangles are smaller than a pixel at template
 // distances), 64-bit atomicMin on (depth bits | triangle) for the depth test, one thread per pixel to resolve.
+#include "launch.h"
 #include "render_kernels.h"
 
 namespace lm {
@@ -351,40 +352,38 @@ __global__ void k_overlay_compose(const OverlayLayer* __restrict__ layers, int c
     out_index[i] = (int8_t)best;
 }
 
-void launch_project(const MeshDev& M, const ViewParams* views, int count, int scale, ProjVtx* out, hipStream_t s) {
-    if (count <= 0 || M.nv <= 0) return;
-    hipLaunchKernelGGL(k_project, dim3((M.nv + 255) / 256, count), dim3(256), 0, s, M, views, scale, out);
+hipError_t launch_project(const MeshDev& M, const ViewParams* views, int count, int scale, ProjVtx* out, hipStream_t s) {
+    if (count <= 0 || M.nv <= 0) return hipSuccess;
+    return lm_launch(k_project, dim3((M.nv + 255) / 256, count), dim3(256), 0, s, M, views, scale, out);
 }
-void launch_raster(const MeshDev& M, const ProjVtx* pv, int count, int Ws, int Hs, double clip_near, double clip_far,
+hipError_t launch_raster(const MeshDev& M, const ProjVtx* pv, int count, int Ws, int Hs, double clip_near, double clip_far,
                    unsigned long long* zbuf, hipStream_t s) {
-    if (count <= 0 || M.nf <= 0) return;
-    (void)hipMemsetAsync(zbuf, 0xFF, (size_t)count * Ws * Hs * sizeof(unsigned long long), s);
-    hipLaunchKernelGGL(k_raster, dim3((M.nf + 255) / 256, count), dim3(256), 0, s, M, pv, Ws, Hs, clip_near, clip_far, zbuf);
+    if (count <= 0 || M.nf <= 0) return hipSuccess;
+    LAUNCH_TRY(hipMemsetAsync(zbuf, 0xFF, (size_t)count * Ws * Hs * sizeof(unsigned long long), s));
+    return lm_launch(k_raster, dim3((M.nf + 255) / 256, count), dim3(256), 0, s, M, pv, Ws, Hs, clip_near, clip_far, zbuf);
 }
-void launch_resolve_depth(const unsigned long long* zbuf, int count, int W, int H, uint16_t* depth, hipStream_t s) {
-    if (count <= 0) return;
-    hipLaunchKernelGGL(k_resolve_depth, dim3((W * H + 255) / 256, count), dim3(256), 0, s, zbuf, W * H, depth);
+hipError_t launch_resolve_depth(const unsigned long long* zbuf, int count, int W, int H, uint16_t* depth, hipStream_t s) {
+    if (count <= 0) return hipSuccess;
+    return lm_launch(k_resolve_depth, dim3((W * H + 255) / 256, count), dim3(256), 0, s, zbuf, W * H, depth);
 }
-void launch_resolve_rgb(const MeshDev& M, const ProjVtx* pv, const ViewParams* views, const unsigned long long* zbuf, int count, int W, int H,
+hipError_t launch_resolve_rgb(const MeshDev& M, const ProjVtx* pv, const ViewParams* views, const unsigned long long* zbuf, int count, int W, int H,
                         int ssaa, float ambient, uint8_t* rgb, hipStream_t s) {
-    if (count <= 0) return;
-    hipLaunchKernelGGL(k_resolve_rgb, dim3((W + 255) / 256, H, count), dim3(256), 0, s, M, pv, views, zbuf, W, H, ssaa, ambient, rgb);
+    if (count <= 0) return hipSuccess;
+    return lm_launch(k_resolve_rgb, dim3((W + 255) / 256, H, count), dim3(256), 0, s, M, pv, views, zbuf, W, H, ssaa, ambient, rgb);
 }
 
-void launch_resolve_shaded(const MeshDev& M, const ProjVtx* pv, const ViewParams* views, const unsigned long long* zbuf, int count, int W, int H,
+hipError_t launch_resolve_shaded(const MeshDev& M, const ProjVtx* pv, const ViewParams* views, const unsigned long long* zbuf, int count, int W, int H,
                            int ssaa, const ShadeParams& sp, uint8_t* rgb, hipStream_t s) {
-    if (count <= 0) return;
+    if (count <= 0) return hipSuccess;
     const dim3 grid((W + 255) / 256, H, count), block(256);
     const bool tex = sp.tex != nullptr && sp.uv != nullptr;
-    if (sp.flat && tex) hipLaunchKernelGGL((k_resolve_shaded<true, true>), grid, block, 0, s, M, pv, views, zbuf, W, H, ssaa, sp, rgb);
-    else if (sp.flat) hipLaunchKernelGGL((k_resolve_shaded<true, false>), grid, block, 0, s, M, pv, views, zbuf, W, H, ssaa, sp, rgb);
-    else if (tex) hipLaunchKernelGGL((k_resolve_shaded<false, true>), grid, block, 0, s, M, pv, views, zbuf, W, H, ssaa, sp, rgb);
-    else hipLaunchKernelGGL((k_resolve_shaded<false, false>), grid, block, 0, s, M, pv, views, zbuf, W, H, ssaa, sp, rgb);
+    const auto kernel = sp.flat ? (tex ? k_resolve_shaded<true, true> : k_resolve_shaded<true, false>) : (tex ? k_resolve_shaded<false, true> : k_resolve_shaded<false, false>);
+    return lm_launch(kernel, grid, block, 0, s, M, pv, views, zbuf, W, H, ssaa, sp, rgb);
 }
-void launch_overlay_compose(const OverlayLayer* layers, int count, const uint8_t* frame, const uint16_t* scene, int npx, int nearest,
+hipError_t launch_overlay_compose(const OverlayLayer* layers, int count, const uint8_t* frame, const uint16_t* scene, int npx, int nearest,
                             uint8_t* out_rgb, int8_t* out_index, hipStream_t s) {
-    if (npx <= 0) return;
-    hipLaunchKernelGGL(k_overlay_compose, dim3((npx + 255) / 256), dim3(256), 0, s, layers, count, frame, scene, npx, nearest, out_rgb, out_index);
+    if (npx <= 0) return hipSuccess;
+    return lm_launch(k_overlay_compose, dim3((npx + 255) / 256), dim3(256), 0, s, layers, count, frame, scene, npx, nearest, out_rgb, out_index);
 }
 
 }  // namespace lm

@@ -21,12 +21,12 @@ struct ProjVtx {
     int valid, pad;
 };
 
-void launch_project(const MeshDev& M, const ViewParams* views, int count, int scale, ProjVtx* out, hipStream_t s);
-void launch_raster(const MeshDev& M, const ProjVtx* pv, int count, int Ws, int Hs, double clip_near, double clip_far,
-                   unsigned long long* zbuf, hipStream_t s);
-void launch_resolve_depth(const unsigned long long* zbuf, int count, int W, int H, uint16_t* depth, hipStream_t s);
-void launch_resolve_rgb(const MeshDev& M, const ProjVtx* pv, const ViewParams* views, const unsigned long long* zbuf, int count, int W, int H,
-                        int ssaa, float ambient, uint8_t* rgb, hipStream_t s);
+[[nodiscard]] hipError_t launch_project(const MeshDev& M, const ViewParams* views, int count, int scale, ProjVtx* out, hipStream_t s);
+[[nodiscard]] hipError_t launch_raster(const MeshDev& M, const ProjVtx* pv, int count, int Ws, int Hs, double clip_near, double clip_far,
+                                       unsigned long long* zbuf, hipStream_t s);
+[[nodiscard]] hipError_t launch_resolve_depth(const unsigned long long* zbuf, int count, int W, int H, uint16_t* depth, hipStream_t s);
+[[nodiscard]] hipError_t launch_resolve_rgb(const MeshDev& M, const ProjVtx* pv, const ViewParams* views, const unsigned long long* zbuf, int count, int W, int H,
+                                            int ssaa, float ambient, uint8_t* rgb, hipStream_t s);
 
 // The resolve with the options of renderer.render beyond the default (render.hip, "shading options").  Colours are packed
 // r | g << 8 | b << 16, 8 bits each.
@@ -41,15 +41,15 @@ struct ShadeParams {
     float ambient;
     int flat;                   // 0: phong (interpolated vertex normals), 1: flat (face normal turned to the camera)
 };
-void launch_resolve_shaded(const MeshDev& M, const ProjVtx* pv, const ViewParams* views, const unsigned long long* zbuf, int count, int W, int H,
-                           int ssaa, const ShadeParams& sp, uint8_t* rgb, hipStream_t s);
+[[nodiscard]] hipError_t launch_resolve_shaded(const MeshDev& M, const ProjVtx* pv, const ViewParams* views, const unsigned long long* zbuf, int count, int W, int H,
+                                               int ssaa, const ShadeParams& sp, uint8_t* rgb, hipStream_t s);
 
 // Pose overlays: layer p of the composition is view p of some mesh's last render (colour and depth at the frame's size).
 struct OverlayLayer {
     const uint8_t* rgb;         // [H][W][3]
     const uint16_t* depth;      // [H][W] mm, 0 = not covered
 };
-void launch_overlay_compose(const OverlayLayer* layers, int count, const uint8_t* frame, const uint16_t* scene, int npx, int nearest,
-                            uint8_t* out_rgb, int8_t* out_index, hipStream_t s);
+[[nodiscard]] hipError_t launch_overlay_compose(const OverlayLayer* layers, int count, const uint8_t* frame, const uint16_t* scene, int npx, int nearest,
+                                                uint8_t* out_rgb, int8_t* out_index, hipStream_t s);
 
 }  // namespace lm

@@ -20,13 +20,13 @@ struct ScaledCand { int32_t x, y; float score; int32_t work, k, depth; };   // w
 struct ScaledLadder { int32_t K, lo, hi; int32_t s[kScaledMaxLadder]; };    // Q10 scales, ascending; bounds lo <= d_train * 1024 / d <= hi
 
 // probe map: out[y * W + x] = the smallest non-zero depth of the (2 probe + 1)^2 window around (x, y) clipped to the frame, 0 if there is none
-hipError_t launch_depth_probe(const uint16_t* depth, int W, int H, int probe, uint16_t* out, hipStream_t s);
+[[nodiscard]] hipError_t launch_depth_probe(const uint16_t* depth, int W, int H, int probe, uint16_t* out, hipStream_t s);
 // One workgroup per work item; counter[0] += candidates (may exceed cap: nothing is written past cap).  lds_bytes = K * (largest nf) * 8.
-hipError_t launch_coarse_scaled(const uint8_t* lm_arena, const uint16_t* probe_map, int W0, int H0, LevelGeom top, int levels, const ScaledEntry* entries,
-                                const ScaledFeat* table, ScaledLadder ladder, const int32_t* train_depth, int num_work, float threshold,
-                                ScaledCand* cands, unsigned int* counter, uint32_t cap, size_t lds_bytes, hipStream_t s);
+[[nodiscard]] hipError_t launch_coarse_scaled(const uint8_t* lm_arena, const uint16_t* probe_map, int W0, int H0, LevelGeom top, int levels, const ScaledEntry* entries,
+                                              const ScaledFeat* table, ScaledLadder ladder, const int32_t* train_depth, int num_work, float threshold,
+                                              ScaledCand* cands, unsigned int* counter, uint32_t cap, size_t lds_bytes, hipStream_t s);
 // Level `level` (below the top) for the n candidates, in place: position, score, work = -1 for a dropped one.
-hipError_t launch_local_scaled(const uint8_t* lm_arena, LevelGeom lv, int level, int levels, const ScaledEntry* entries, const ScaledFeat* table, int K,
-                               float threshold, ScaledCand* cands, uint32_t n, hipStream_t s);
+[[nodiscard]] hipError_t launch_local_scaled(const uint8_t* lm_arena, LevelGeom lv, int level, int levels, const ScaledEntry* entries, const ScaledFeat* table, int K,
+                                             float threshold, ScaledCand* cands, uint32_t n, hipStream_t s);
 
 }  // namespace lm

@@ -16,6 +16,7 @@
 //                  selectScatteredFeatures: candidates in order, 64 at a time — every lane tests its candidate against the
 //                  features chosen so far, the survivors are then accepted first-come, each acceptance knocking out the later
 //                  lanes it is too close to — with the reference's float distance schedule (start value, -1 per pass over the list).
+#include "launch.h"
 #include "lm_kernels.h"
 
 namespace lm {
@@ -265,29 +266,27 @@ k_train_select(const unsigned long long* __restrict__ keys_all, const uint32_t* 
     if (lane == 0) { out[0] = 1; out[1] = ns; }
 }
 
-void launch_train_prep(const uint16_t* depth, const uint8_t* user_mask, const TrainGeom& g, float strong_sq, int extract_threshold, unsigned long long* keys_view,
+hipError_t launch_train_prep(const uint16_t* depth, const uint8_t* user_mask, const TrainGeom& g, float strong_sq, int extract_threshold, unsigned long long* keys_view,
                        uint32_t cap, uint32_t* counts_view, int32_t* bbox_view, hipStream_t s, int mods) {
     const int n0 = g.W[0] * g.H[0];
-    hipLaunchKernelGGL(k_train_mask, dim3((n0 + 255) / 256), dim3(256), 0, s, depth, user_mask, g, bbox_view);
+    LAUNCH_TRY(lm_launch(k_train_mask, dim3((n0 + 255) / 256), dim3(256), 0, s, depth, user_mask, g, bbox_view));
     const dim3 grid((n0 + 255) / 256, g.levels);              // level l uses the first W_l * H_l / 256 blocks of its row
-    if (mods == 1) { hipLaunchKernelGGL(k_train_prep<1>, grid, dim3(256), 0, s, g, strong_sq, keys_view, cap, counts_view); return; }   // colour only: no labels, runs or distances
-    if (mods == 2) hipLaunchKernelGGL(k_train_prep<2>, grid, dim3(256), 0, s, g, strong_sq, keys_view, cap, counts_view);
-    else hipLaunchKernelGGL(k_train_prep<3>, grid, dim3(256), 0, s, g, strong_sq, keys_view, cap, counts_view);
-    hipLaunchKernelGGL(k_train_runs, grid, dim3(256), 0, s, g);
-    hipLaunchKernelGGL(k_train_dt, grid, dim3(256), 0, s, g, extract_threshold < 0 ? 0 : extract_threshold, keys_view, cap, counts_view);
+    if (mods == 1) return lm_launch(k_train_prep<1>, grid, dim3(256), 0, s, g, strong_sq, keys_view, cap, counts_view);   // colour only: no labels, runs or distances
+    LAUNCH_TRY(lm_launch(mods == 2 ? k_train_prep<2> : k_train_prep<3>, grid, dim3(256), 0, s, g, strong_sq, keys_view, cap, counts_view));
+    LAUNCH_TRY(lm_launch(k_train_runs, grid, dim3(256), 0, s, g));
+    return lm_launch(k_train_dt, grid, dim3(256), 0, s, g, extract_threshold < 0 ? 0 : extract_threshold, keys_view, cap, counts_view);
 }
 
-int launch_train_select(const unsigned long long* keys, const uint32_t* counts, const TrainGeom& g, uint32_t cap, int num_features, int nf_cap,
+hipError_t launch_train_select(const unsigned long long* keys, const uint32_t* counts, const TrainGeom& g, uint32_t cap, int num_features, int nf_cap,
                         int views, int32_t* out, hipStream_t s, int mods) {
     static size_t configured = 0;
     const size_t lds = (size_t)cap * sizeof(unsigned long long);
     if (lds > configured) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_train_select), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return -1;
+        LAUNCH_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_train_select), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));   // the LDS cannot be reserved
         configured = lds;
     }
     const int only_mod = mods == 3 ? -1 : mods - 1;
-    hipLaunchKernelGGL(k_train_select, dim3(g.levels * (only_mod < 0 ? 2 : 1), views), dim3(256), lds, s, keys, counts, g, cap, num_features, nf_cap, out, only_mod);
-    return 0;
+    return lm_launch(k_train_select, dim3(g.levels * (only_mod < 0 ? 2 : 1), views), dim3(256), lds, s, keys, counts, g, cap, num_features, nf_cap, out, only_mod);
 }
 
 }  // namespace lm

@@ -89,8 +89,7 @@ int main(int argc, char** argv) {
             G.f[i].runs = d_runs[i];
             G.f[i].block = d_block[i];
         }
-        lm::launch_exchange_pack_group(G, cand_cap, cap, s);
-        HIP_OK(hipGetLastError());
+        HIP_OK(lm::launch_exchange_pack_group(G, cand_cap, cap, s));
         HIP_OK(hipStreamSynchronize(s));
         for (uint32_t i = 0; i < frames; ++i) {
             block.resize(words);

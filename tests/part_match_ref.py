@@ -97,8 +97,12 @@ def local_parts(F, width, height, lms, W, H, T, xs, ys):
     return raw, n
 
 
-def match_parts(bank, lms, sizes, T, threshold, min_parts, min_part_features=8):
-    """Raw records (lo.MATCH_DTYPE, cls = 0) of a packed bank under the part rule; min_parts = 0: the holistic rule."""
+def match_parts(bank, lms, sizes, T, threshold, min_parts, min_part_features=8, cls=0, trace=None):
+    """Raw records (lo.MATCH_DTYPE) of a packed bank under the part rule; min_parts = 0: the holistic rule.  cls: the class column of the
+    records (a multi-class request is this function per class, cls = the class's place in the request).  trace: a list that receives, per
+    template and level from the top down, {"tid", "level", "entered", "left", "pos", "raw", "n", "hit"} — the candidates that entered and left the
+    level, and for those that entered the top-level position index resp. a zero, the part sums [entered][4] there (below the top: at the
+    arg-max position) the parts' feature counts and who left; it observes the rule and takes no part in it."""
     feat, offs, wh = bank
     L = len(T)
     P = (len(offs) - 1) // (2 * L)
@@ -121,6 +125,8 @@ def match_parts(bank, lms, sizes, T, threshold, min_parts, min_part_features=8):
                     passes += score_of(raw[k], n[k]) > thr
             hit = passes >= min_parts
         pos = np.nonzero(hit)[0]                                                        # raster order
+        if trace is not None:
+            trace.append({"tid": p, "level": L - 1, "entered": raw.shape[1], "left": len(pos), "pos": np.arange(raw.shape[1]), "raw": raw.T.copy(), "n": n, "hit": hit.copy()})
         off = Tt // 2 + (Tt % 2 - 1)
         Wd = Wt // Tt
         cx, cy = (pos % Wd) * Tt + off, (pos // Wd) * Tt + off
@@ -150,9 +156,12 @@ def match_parts(bank, lms, sizes, T, threshold, min_parts, min_part_features=8):
                     if n[k] >= min_part_features:
                         passes += score_of(raw[np.arange(len(x)), k, at], n[k]) >= thr
                 keep = passes >= min_parts
+            if trace is not None:
+                trace.append({"tid": p, "level": l, "entered": len(x), "left": int(keep.sum()), "pos": np.zeros(len(x), np.int64),
+                              "raw": raw[np.arange(len(x)), :, np.where(rawmax > 0, best, 0)], "n": n, "hit": keep.copy()})
             cx, cy, sim = cx[keep], cy[keep], sim[keep]
         rec = np.zeros(len(cx), lo.MATCH_DTYPE)
-        rec["x"], rec["y"], rec["sim"], rec["tid"] = cx, cy, sim, p
+        rec["x"], rec["y"], rec["sim"], rec["tid"], rec["cls"] = cx, cy, sim, p, cls
         out.append(rec)
     return np.concatenate(out) if out else np.zeros(0, lo.MATCH_DTYPE)
 

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import linemod_oracle as lo
+import part_match_cases as pc
 import part_match_ref as pm
 import response_table_ref as rt
 import synth
@@ -129,26 +130,7 @@ def test_the_golden_half_occluded_frame(lm):
 
 
 # ---- 4. edges ---------------------------------------------------------------------------------------------------------------------------------
-@functools.lru_cache(maxsize=None)
-def edge_bank(levels):
-    """One bank on G1's frame: a template with all its features in one part; parts of 7, 8, 9, 16 and 17 features (padding); an entry of 600
-    features (the 14-bit counters); a template as wide as the refinement allows, whose position count lies below the map's."""
-    rng = np.random.default_rng(77)
-    feats, whs = [], []
-
-    def entry(per_part, w, h, l):
-        quad = [(0, w // 2, 0, h // 2), ((w + 1) // 2, w + 1, 0, h // 2), (0, w // 2, (h + 1) // 2, h + 1), ((w + 1) // 2, w + 1, (h + 1) // 2, h + 1)]
-        rows = [(int(rng.integers(a, b)), int(rng.integers(c, d)), int(rng.integers(0, 8)), k % 2) for (a, b, c, d), n in zip(quad, per_part) for k in range(n)]
-        for m in range(2):
-            feats.append(np.array([r[:3] for r in rows if r[3] == m], np.int32).reshape(-1, 3)); whs.append((w >> 0, h >> 0))
-
-    shapes = [((40, 0, 0, 0), 60, 48), ((7, 8, 9, 16), 60, 48), ((17, 16, 8, 7), 50, 40), ((150, 150, 150, 150), 64, 48), ((20, 20, 20, 20), 120, 90)]
-    for per_part, w, h in shapes:
-        for l in range(levels):
-            entry(per_part, w >> l, h >> l, l)
-    offs = np.zeros(len(feats) + 1, np.int32)
-    offs[1:] = np.cumsum([len(f) for f in feats])
-    return np.ascontiguousarray(np.concatenate(feats), np.int32), offs, np.array(whs, np.int32).reshape(-1, 2)
+edge_bank = pc.edge_bank              # (the bank of this section lives in part_match_cases.py, which test_gpu_part_match_edges.py shares)
 
 
 @pytest.mark.parametrize("levels", [2, 1])

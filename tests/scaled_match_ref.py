@@ -157,6 +157,17 @@ def match_scaled(bank, lms, sizes, T, threshold, depth0, d_train, scales, lo=Non
     return np.concatenate(out) if out else np.zeros(0, DTYPE)
 
 
+def match_classes(banks, d_train, selection, lms, sizes, T, threshold, depth0, scales, lo=None, hi=None, probe=2, stats=None):
+    """match_scaled once per listed class — `selection` as the caller gives it: unknown names are skipped and keep their position, a repeated
+    name is matched again; an empty selection is every class in the order of its name — with class_index = the position in the list and that
+    class's own training depth; the raw records concatenated.  banks and d_train: name -> packed bank / mm."""
+    out = []
+    for pos, name in enumerate(selection if len(selection) else sorted(banks)):
+        if name in banks:
+            out.append(match_scaled(banks[name], lms, sizes, T, threshold, depth0, d_train[name], scales, lo, hi, probe, cls=pos, stats=stats))
+    return np.concatenate(out) if out else np.zeros(0, DTYPE)
+
+
 def canonical(rec):
     """exact duplicates removed; similarity descending, then class_index, template_id, y, x, scale_index, depth_mm ascending"""
     if len(rec) == 0:
